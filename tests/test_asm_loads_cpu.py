@@ -6,7 +6,6 @@ a loop body is walked with what its own bottom left outstanding (the shape of ev
 Runs without a GPU (hipcc cross-compiles)."""
 import os
 import shutil
-import subprocess
 import sys
 
 import pytest
@@ -43,16 +42,10 @@ def test_a_hazard_across_a_loop_back_edge_is_seen():
 
 
 def test_the_round_4_fault_is_still_found():
-    """the prefetching wavefront's lost loop bound (fuzz case 40501, fixed in 8c2bcc2): the source before the fix fails"""
+    """the prefetching wavefront's lost loop bound (fuzz case 40501, fixed in 8c2bcc2): the source before the fix fails.
+    tests/asm_hazard/before_8c2bcc2/ holds that source as it was in 8c2bcc2^ (accum_mfma.hip and the headers it
+    includes, same layout), so that the check needs no git history"""
     import check_asm_loads
-    import tempfile
-    with tempfile.TemporaryDirectory() as t:
-        for f in ("ngsdist_amd/csrc/accum_mfma.hip", "ngsdist_amd/csrc/ngd_internal.h", "ngsdist_amd/csrc/ngd_shard.h",
-                  "include/ngsdist_amd.h"):
-            r = subprocess.run(["git", "-C", ROOT, "show", "8c2bcc2^:" + f], capture_output=True)
-            if r.returncode != 0:
-                pytest.skip("no git history here (the snapshot on the GPU box has none)")
-            os.makedirs(os.path.dirname(os.path.join(t, f)), exist_ok=True)
-            open(os.path.join(t, f), "wb").write(r.stdout)
-        findings, _ = check_asm_loads.check(os.path.join(t, "ngsdist_amd/csrc/accum_mfma.hip"))
+    findings, _ = check_asm_loads.check(os.path.join(ROOT, "tests", "asm_hazard", "before_8c2bcc2", "ngsdist_amd", "csrc",
+                                                     "accum_mfma.hip"))
     assert findings and any("k_accum_mfma" in f[0] for f in findings)

@@ -347,7 +347,7 @@ def test_bench_line_contract(tmp_path):
     import json
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--n_sites", "4000",
-                        "--steps", "2", "--warmup", "1", "--cpu_sites", "400"], capture_output=True, text=True)
+                        "--steps", "2", "--warmup", "1", "--cpu_sites", "400", "--full"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -365,6 +365,41 @@ def test_bench_line_contract(tmp_path):
     assert d["spot_check"]["max_rel_err_vs_oracle"] < 1e-9
 
 
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline alone (no pipelined region, spot check or CPU baseline), --steps sets
+    the timed steps, and --dump-outputs writes the last step's finished matrix: the same bits in two runs of the same
+    arguments, every cell finite, and the corner pairs equal to the CPU oracle's."""
+    import json
+
+    def line(out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--n_sites", "4000",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    a, b = line(tmp_path / "a"), line(tmp_path / "b")
+    for d in (a, b):
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["metric"] == "pair-distances/sec" and d["dtype"] == "f64"
+        assert d["higher_is_better"] is True and d["unit"] == "pair-distances/s"
+        assert d["full"] is False and d["pipelined"] is None and d["cpu_baseline"] is None and d["spot_check"] is None
+        assert d["outputs"]["files"] == ["dist"]
+    da, db = np.load(tmp_path / "a" / "dist.npy"), np.load(tmp_path / "b" / "dist.npy")
+    assert da.dtype == np.float64 and da.shape == (1, 200 * 199 // 2) and np.isfinite(da).all()
+    assert np.array_equal(da.view(np.uint64), db.view(np.uint64))
+    idx = [0, 1, 100, 199]
+    sub = np.concatenate([O.synth_indmajor(2, 200, 4000, i0=i, n_sub=1) for i in idx])
+    so, co = O.all_pairs(sub)
+    do = O.finish(so, co, 0, 0)
+    k = 0
+    for x in range(len(idx)):
+        for y in range(x + 1, len(idx)):
+            g = da[0, O.n_pairs(200) - O.n_pairs(200 - idx[x]) + (idx[y] - idx[x] - 1)]
+            assert abs(g - do[k]) <= 1e-9 * abs(do[k]), (idx[x], idx[y])
+            k += 1
+
+
 def test_bench_pipelined_tail_and_em_roofline_fields(tmp_path):
     """N = 1: the headline region runs one job at a time (ms_per_step = one job's latency); a second region runs the same
     jobs two deep -- a job's copy-out and host tail on the worker thread beside the next job's kernels (forced here on
@@ -376,7 +411,7 @@ def test_bench_pipelined_tail_and_em_roofline_fields(tmp_path):
     import sys
 
     def line(*args):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1"] + list(args),
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--full"] + list(args),
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

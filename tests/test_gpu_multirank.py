@@ -18,7 +18,7 @@ def _bench(*extra):
     env = dict(os.environ)
     env.pop("RANK", None), env.pop("WORLD_SIZE", None), env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same_device",
-           "--steps", "2", "--warmup", "1", "--no_cpu"] + list(extra)
+           "--steps", "2", "--warmup", "1", "--full", "--no_cpu"] + list(extra)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -74,7 +74,7 @@ def test_two_ranks_pairwise_del_counts_are_reduced():
     out = _bench("--workload", "cfg2", "--pairwise_del", "--miss_frac", "0.1")
     assert out["valid"] is True
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--pairwise_del",
-                          "--miss_frac", "0.1", "--steps", "1", "--warmup", "0", "--no_cpu"], cwd=ROOT,
+                          "--miss_frac", "0.1", "--steps", "1", "--warmup", "0", "--full", "--no_cpu"], cwd=ROOT,
                          capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
     assert json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])["valid"] is True

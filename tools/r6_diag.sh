@@ -17,6 +17,6 @@ head -12 $OUT/hiptrace_emboot/*/*_hip_api_stats.csv
 head -8 $OUT/hiptrace_emboot/*/*_kernel_stats.csv | cut -c1-200
 rocprofv3 --hip-trace --stats --output-format csv -d $OUT/hiptrace_cfg2 -- python3 $ROOT/bench.py --workload cfg2 --steps 200 --warmup 5 --no_cpu > $OUT/hiptrace_cfg2.json 2> $OUT/hiptrace_cfg2.err
 head -14 $OUT/hiptrace_cfg2/*/*_hip_api_stats.csv
-cd $ROOT; python3 bench.py --workload cfg2 --steps 200 --warmup 5 --no_cpu > $OUT/cfg2_plain.json 2>/dev/null; python3 -c "
+cd $ROOT; python3 bench.py --workload cfg2 --steps 200 --warmup 5 --full --no_cpu > $OUT/cfg2_plain.json 2>/dev/null; python3 -c "
 import json; d=json.loads(open('$OUT/cfg2_plain.json').read().strip().splitlines()[-1]); print('cfg2 ms_per_step', d['ms_per_step'], d['roofline']['ms_per_launch'], d['valid'])"
 cat $OUT/finish_timing.txt | tail -6

@@ -16,7 +16,7 @@ mkdir -p "$OUT" "$ROOT/gpurun_out/r6"
 cd "$ROOT"
 line() { # name, bench args...
   local name=$1; shift
-  python3 bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "$name: exit $?"
+  python3 bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "$name: exit $?"
 }
 PART=${1:-lines}
 if [ "$PART" = e2e ]; then

@@ -2,7 +2,7 @@
 """tools/rccl_preflight.py -- what the collectives of a multi-GPU job cost on THIS node, before the job runs.
 
 No multi-GPU node was available to this build (every N > 1 figure in DESIGN.md section 7 is a prediction), so the first
-hardware run has to explain its own scaling curve: `bench.py --gpus N` calls preflight() in every rank process, after
+hardware run has to explain its own scaling curve: `bench.py --gpus N --full` calls preflight() in every rank process, after
 the process group is up and BEFORE the engine is created, and rank 0 prints one JSON line to stderr with
   * the RCCL version and the environment the communicator came up under,
   * all_reduce / reduce_scatter / all_gather of the job's REAL message sizes (the cells of the job: sums as float64,

@@ -8,7 +8,7 @@ run() { # n, args...
   local n=$1; shift
   echo "== N=$n $*"
   timeout -k 10 280 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) \
-    bench.py --gpus $n --backend gloo --same_device --steps 2 --warmup 1 --no_cpu "$@" 2>&1 | grep -E '^\{|Error|error|Traceback' | \
+    bench.py --gpus $n --backend gloo --same_device --steps 2 --warmup 1 --full --no_cpu "$@" 2>&1 | grep -E '^\{|Error|error|Traceback' | \
     python3 -c "
 import sys, json
 for l in sys.stdin:
