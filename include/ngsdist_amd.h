@@ -331,6 +331,10 @@ int ngd_drop_caches(ngd_engine *e);
                                  /* no block map launches only what is left.  Same bits as without it.  For a host whose     */
                                  /* first call after ngd_commit IS that pass (no bootstrap): anything else drops the work.    */
                                  /* MFMA kernel above 384 padded individuals and the table-driven EM kernel; else ignored.    */
+#define NGD_OPT_WIN_PLAN 13       /* [0] ngd_run_windows*: 0 auto (the cheaper plan by estimate), 1 one weighted pass per       */
+                                 /*     window only, 2 the segment-slab plan only (NGD_E_NOMEM if a window cannot fit it)      */
+#define NGD_OPT_WIN_MAX_BYTES 14  /* [0 = 85 % of free device memory, the rule of NGD_OPT_BOOT_MAX_BYTES] budget of one batch   */
+                                 /*     of the segment-slab plan (its partial results, counts and slice weights)              */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -385,6 +389,49 @@ int ngd_last_shader_clock(const ngd_engine *e, double *mhz);
  * of (64 x 64 pair tile, site) visits and of table rounds (16 EM steps of a tile's 128 individuals each) -- the
  * data-dependent part of its operation count (the EM's iteration count, emOptim2.cpp:118-133).  Zero for other kernels. */
 int ngd_last_em_work(const ngd_engine *e, uint64_t *tile_sites, uint64_t *table_rounds);
+
+/* Windows along the genome: one matrix per window [lo, hi) of the engine's sites, each exactly what ngd_run() gives on a
+ * data set that holds only those sites (gen_dist() over an input cut down to the window; --pairwise_del counts, called
+ * genotypes and the EM path alike).  win_lo / win_hi: n_win engine-local ranges, lo < hi <= n_sites, lo non-decreasing;
+ * windows may overlap and nest.  NGD_E_INVALID for anything else, and on an engine that owns a share of the pairs.
+ * Outputs are [n_win][n_pairs] with the meaning of ngd_run() (host memory; ..._device: device pointers of the caller's).
+ * Two plans (NGD_OPT_WIN_PLAN):
+ *  - segment slab (MFMA kernel, engines with both operands resident or the one congruent image): the elementary
+ *    intervals between consecutive window boundaries are the slices of ONE accumulation pass into per-segment partial
+ *    results, then a banded reduction adds each window's segments, in ascending order, for a group of consecutive windows
+ *    per read of their segments; --pairwise_del counts the same way from per-segment popcounts.  Calls whose segments do
+ *    not fit the budget (NGD_OPT_WIN_MAX_BYTES) go in batches of consecutive windows; a segment two batches share is
+ *    computed in both.  One-image engines (single_image = 2) then recompute with the two-operand arithmetic the pairs
+ *    whose sum in some window is below 1e-6 x the window's length (x the pair's count under --pairwise_del);
+ *  - per window (every other kernel, or when cheaper): one weighted pass per window over that window's sites (the pass
+ *    ngd_run_mult() makes with 0/1 multiplicities).
+ * Sums agree with the cut-down data set's ngd_run() to rounding (<= 1e-9 relative), counts exactly. */
+int ngd_run_windows(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, double *sum,
+                    uint64_t *cnt);
+int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, void *d_sum,
+                           void *d_cnt);
+/* ... and the tail of gen_dist() on every window (as ngd_finish() with tot_sites / evol_model: the host's libm, as
+ * ngd_run_job_dist): dist is [n_win][n_pairs] host memory.  NGD_E_MODEL for evol_model > 2 before anything is launched. */
+int ngd_run_windows_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
+                         uint64_t evol_model, double *dist);
+/* What the last ngd_run_windows* call did */
+typedef struct ngd_windows_info {
+  uint64_t segments;       /* slices of the segment-slab plan's accumulation passes, summed over its batches          */
+  uint64_t slab_bytes;     /* bytes of the largest batch's per-segment partial results (sums + counts)               */
+  uint64_t batches;        /* batches of the segment-slab plan                                                        */
+  uint64_t band_launches;  /* banded-reduction launches (sums and counts)                                             */
+  uint64_t windows_by_pass;/* windows served by a weighted pass of their own (the per-window plan)                    */
+  uint64_t fixup_pairs;    /* pairs the one-image fix-up recomputed, summed over the windows it recomputed them in    */
+  double ms;               /* device time of the call (HIP events on the engine's stream)                             */
+} ngd_windows_info;
+int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info);
+/* The window list of --win_size / --win_step (pure host arithmetic): sites [0, n_sites) split into chromosomes --
+ * maximal runs of equal chrom_id (chrom_id == NULL: one sequence); in each chromosome starting at c0 the windows
+ * [c0 + k step, c0 + k step + size) that fit inside it, k = 0, 1, ...  Returns the number of windows and, if lo / hi are
+ * not NULL, writes the first min(count, cap) of them; NGD_E_INVALID for size or step 0 and for a chromosome id that
+ * shows up again after another one (a positions file not grouped by chromosome). */
+int64_t ngd_window_ranges(const uint32_t *chrom_id, uint64_t n_sites, uint64_t size, uint64_t step, uint64_t *lo, uint64_t *hi,
+                          uint64_t cap);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

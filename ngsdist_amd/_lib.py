@@ -55,6 +55,11 @@ class NgdSpillTiming(C.Structure):
                                   "matrix_groups", "contract_launches")]
 
 
+class NgdWindowsInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("segments", "slab_bytes", "batches", "band_launches", "windows_by_pass",
+                                          "fixup_pairs")] + [("ms", C.c_double)]
+
+
 class NgdFixupInfo(C.Structure):
     _fields_ = [("flagged", C.c_uint64), ("recomputed", C.c_uint64), ("skipped", C.c_uint64), ("ms", C.c_double),
                 ("by_pass", C.c_uint64)]
@@ -68,7 +73,8 @@ EXPORTS = [
     "ngd_run_device", "ngd_run_batch", "ngd_run_batch_device", "ngd_run_mult_batch",
     "ngd_run_mult_batch_device", "ngd_run_job", "ngd_run_job_device", "ngd_run_job_dist", "ngd_run_batch_dist", "ngd_run_mult_batch_dist", "ngd_fetch_matrix", "ngd_drop_caches", "ngd_set_option", "ngd_last_timing", "ngd_last_spill_timing", "ngd_last_fixup", "ngd_image_mode", "ngd_last_shader_clock", "ngd_last_em_work", "ngd_finish", "ngd_finish_stream", "ngd_format_matrix", "ngd_taus_seed", "ngd_taus_get",
     "ngd_taus_uniform", "ngd_boot_block_map", "ngd_n_pairs", "ngd_pair_index", "ngd_device_bytes", "ngd_device_memory", "ngd_shard_of_pair", "ngd_shard_map",
-    "ngd_score_congruence",
+    "ngd_score_congruence", "ngd_run_windows", "ngd_run_windows_device", "ngd_run_windows_dist", "ngd_last_windows",
+    "ngd_window_ranges",
 ]
 
 _lib = None
@@ -156,6 +162,12 @@ def load():
     L.ngd_shard_map.restype = None
     L.ngd_score_congruence.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ngd_score_congruence.restype = C.c_int
+    L.ngd_run_windows.argtypes = [vp, u64p, u64p, u64, dp, u64p]
+    L.ngd_run_windows_device.argtypes = [vp, u64p, u64p, u64, vp, vp]
+    L.ngd_run_windows_dist.argtypes = [vp, u64p, u64p, u64, u64, u64, dp]
+    L.ngd_last_windows.argtypes = [vp, C.POINTER(NgdWindowsInfo)]
+    L.ngd_window_ranges.argtypes = [u32p, u64, u64, u64, u64p, u64p, u64]
+    L.ngd_window_ranges.restype = C.c_int64
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(EXACT >= 4 ? 1024 : EXACT == 3 ? 768 : EXACT ? 64 :
     const uint32_t *__restrict__ kgl, const ngd_job *__restrict__ jobs, uint32_t n_tiles /* workgroups per slice */, uint32_t n_ig,
     uint32_t n_pad, uint64_t kg_per_slice, uint64_t n_kg, uint64_t k_per_slice, uint32_t w_slice_stride,
     double *__restrict__ slab, uint32_t n_igv_touch = 0, unsigned long long *__restrict__ clk = nullptr,
-    uint32_t ks0 = 0, uint32_t resume = 0) {
+    uint32_t ks0 = 0, uint32_t resume = 0, const uint64_t *__restrict__ seg = nullptr) {
   // XCD-aware deal: blocks b and b+8 share an XCD (round-robin dispatch; speed only).
   const uint32_t b = blockIdx.x;
   const uint32_t xcd = b & 7u, q = b >> 3;
@@ -111,6 +111,12 @@ __global__ __launch_bounds__(EXACT >= 4 ? 1024 : EXACT == 3 ? 768 : EXACT ? 64 :
     kg0 = ((uint64_t)ks * k_per_slice) >> 2;
     kg1 = ((uint64_t)(ks + 1) * k_per_slice + 3) >> 2;
   }
+  // a slice table (windows along the genome, engine.hip windows_slab): slice ks is the segment whose k-groups are
+  // [seg[5 ks], seg[5 ks + 1]), its 0/1 edge masks from k-group seg[5 ks + 2] of wk on (NGD_SEG_* in ngd_internal.h)
+  if (seg) {
+    kg0 = seg[(uint64_t)ks * NGD_SEG_STRIDE + NGD_SEG_KG0];
+    kg1 = seg[(uint64_t)ks * NGD_SEG_STRIDE + NGD_SEG_KG1];
+  }
   if (kg1 > n_kg) kg1 = n_kg;
   if (TOUCH && toucher) {  // (wave-uniform)
     const uint64_t ks_d = (uint64_t)n_ig * 64;
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(EXACT >= 4 ? 1024 : EXACT == 3 ? 768 : EXACT ? 64 :
   const double *wk_s = wk;  // weight of real k-group kg: wk_s + (kg - wk_kg0) * 4
   uint64_t wk_kg0 = 0;
   if (WEIGHTED && w_slice_stride) {
-    wk_s = wk + (uint64_t)ks * w_slice_stride * 4;
+    wk_s = wk + (seg ? seg[(uint64_t)ks * NGD_SEG_STRIDE + NGD_SEG_WOFF] : (uint64_t)ks * w_slice_stride) * 4;
     wk_kg0 = kg0;
   }
 
@@ -591,18 +597,19 @@ void ngd_launch_accum_mfma(hipStream_t st, const ngd_geom &g, const double *PA, 
                            const double *d_ws /* wk */, const uint32_t *d_kgl, const ngd_job *d_jobs, uint32_t n_wg,
                            int exact_shapes /* 3: n_wg = 1 workgroup of wg_waves wavefronts per slice */, uint32_t wg_waves, uint32_t n_ks, uint64_t kg_per_slice, uint64_t n_kg_eff,
                            uint64_t k_per_slice, uint32_t w_slice_stride, double *slab, unsigned long long *d_clk,
-                           uint32_t ks0, uint32_t resume) {
+                           uint32_t ks0, uint32_t resume, const uint64_t *d_seg) {
   if (!n_wg) return;
+  if (d_seg) k_per_slice = 0;  // (the table holds the slices' ranges; w_slice_stride != 0 says their weights are per slice)
   // EXACT = 3: a prefetching wavefront beside the jobs where a twelfth fits and the slices are plain k-group ranges
   uint32_t touch_igv = 0;
   const uint32_t n_igv = (uint32_t)((g.n_ind + 15) / 16);
   // EXACT = 5 (operands through LDS): plain k-group ranges, at most 16 groups a side and 4 fragments per wavefront;
   // weighted passes and masked slices of the same engine take the register form (EXACT = 4) of the same jobs
-  if (exact_shapes == 5 && (d_ws || d_kgl || k_per_slice || n_igv > 16 || 2 * n_igv > 4 * wg_waves)) exact_shapes = 4;
+  if (exact_shapes == 5 && (d_ws || d_kgl || k_per_slice || d_seg || n_igv > 16 || 2 * n_igv > 4 * wg_waves)) exact_shapes = 4;
   if (exact_shapes == 5) {
     touch_igv = n_igv;
   } else if (((exact_shapes == 3 && wg_waves <= 11) || (exact_shapes == 4 && wg_waves <= 15)) && !d_ws && !d_kgl && !k_per_slice &&
-             n_igv <= 16) {  // (the prefetching wavefront keeps 24 + 2 n_igv loads in flight: the counter holds 63)
+             !d_seg && n_igv <= 16) {  // (the prefetching wavefront keeps 24 + 2 n_igv loads in flight: the counter holds 63)
     touch_igv = n_igv;
     wg_waves += 1;
   }
@@ -612,7 +619,7 @@ void ngd_launch_accum_mfma(hipStream_t st, const ngd_geom &g, const double *PA, 
 #define NGD_MFMA(W, D, P, X)                                                                                    \
   hipLaunchKernelGGL((k_accum_mfma<W, D, P, X>), dim3(n_wg * n_ks), dim3(X >= 3 ? 64 * wg_waves : X ? 64 : 256),       \
                      X == 5 ? 2 * 32 * 64 * sizeof(double) : 0, st, PA, QB, d_ws, d_kgl, d_jobs,                        \
-                     n_wg, g.n_ig, g.n_pad, kg_per_slice, n_kg_eff, k_per_slice, w_slice_stride, slab, touch_igv, d_clk, ks0, resume)
+                     n_wg, g.n_ig, g.n_pad, kg_per_slice, n_kg_eff, k_per_slice, w_slice_stride, slab, touch_igv, d_clk, ks0, resume, d_seg)
   // No in-wave run-ahead (DEPTH 1), 3 wavefronts per SIMD: the third wavefront covers the others' load phases.
   // Measured against a 4-deep register ring at 2 wavefronts per SIMD (56.0 vs 51.0 ms on the same job layout) and
   // against LDS-staged operand panels (tools/experiments/accum_mfma_lds.hip; profiles/r01_cfg3_mfma_*): both lose.

@@ -59,9 +59,14 @@
 #include <ctime>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../../include/ngsdist_amd.h"
+
+// The engine's windowed entry point is referred to weakly: a host linked against an engine without it (a stub) still
+// links, and --win_size then fails with a message.  ngd_window_ranges (host_util.cpp) is always there.
+#pragma weak ngd_run_windows_dist
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
 static const double kInf = 1e15;          // INF, gen_func.hpp:15
@@ -93,6 +98,9 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   int prep = 0;  // 0 auto (device unless genotypes are called), 1 host, 2 device
   unsigned stage_piece = 0, stage_ring = 0, stage_grain = 2, stage_drop = 1;  // --stage (0: the engine's defaults)
   int eager = 1;  // --eager 0|1|2: the full-data pass beside the load where the first engine call is that pass
+  // --win_size / --win_step: one matrix per window of sites along the genome (not in the reference)
+  bool win = false, win_step_set = false;
+  uint64_t win_size = 0, win_step = 0;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -189,6 +197,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"prep", required_argument, nullptr, 1004},
                                  {"stage", required_argument, nullptr, 1009},
                                  {"eager", required_argument, nullptr, 1010},
+                                 {"win_size", required_argument, nullptr, 1011},
+                                 {"win_step", required_argument, nullptr, 1012},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -221,6 +231,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1005: p.same_device = true; break;
       case 1006: p.max_device_bytes = strtoull(optarg, nullptr, 10); break;
       case 1010: p.eager = atoi(optarg); break;
+      case 1011: p.win = true; p.win_size = strtoull(optarg, nullptr, 10); break;
+      case 1012: p.win_step_set = true; p.win_step = strtoull(optarg, nullptr, 10); break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -260,6 +272,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
             p.pairwise_del ? "true" : "false", p.score[4] == 0.5 ? "true" : "false",
             p.evol_model <= 6 ? kModelNames[p.evol_model] : "?", p.indep_geno ? "true" : "false", p.n_boot_rep,
             p.boot_block_size, p.out, p.n_threads, p.verbose, p.seed, kVersion);
+    if (p.win || p.win_step_set)
+      fprintf(stderr, "\twin_size: %lu\n\twin_step: %lu\n\n", p.win_size, p.win_step_set ? p.win_step : p.win_size);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -277,6 +291,14 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
   if (p.n_threads < 1) die(__FUNCTION__, "number of threads cannot be less than 1!");
   if (p.n_gpus < 1) die(__FUNCTION__, "number of GPUs cannot be less than 1!");
   if (p.boot_block_size < 1) die(__FUNCTION__, "bootstrap block size cannot be less than 1!");
+  if (p.win_step_set && !p.win) die(__FUNCTION__, "window step (--win_step) requires a window size (--win_size)!");
+  if (p.win) {
+    if (!p.win_step_set) p.win_step = p.win_size;
+    if (p.win_size < 1) die(__FUNCTION__, "window size (--win_size) cannot be less than 1!");
+    if (p.win_step < 1) die(__FUNCTION__, "window step (--win_step) cannot be less than 1!");
+    if (p.n_boot_rep > 0) die(__FUNCTION__, "windows (--win_size) cannot be combined with bootstrap replicates (--n_boot_rep)!");
+    if (p.n_gpus > 1) die(__FUNCTION__, "windows (--win_size) are computed on one GPU (--n_gpus 1)!");
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1070,7 +1092,11 @@ int main(int argc, char **argv) {
   }
   if (p.verbose >= 4) for (auto &l : labels) fprintf(stderr, "%s\n", l.c_str());
 
-  // positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149
+  // positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149 -- except for the chromosomes
+  // and coordinates of --win_size's windows
+  std::vector<uint32_t> win_chrom;
+  std::vector<std::string> win_pos_txt;
+  std::unordered_map<uint32_t, std::string> win_chr_name;
   if (p.in_pos) {
     if (p.verbose >= 1) fprintf(stderr, "==> Reading positions file\n");
     std::vector<std::string> pos = read_lines(p.in_pos, p.in_pos_header ? 1 : 0);
@@ -1082,6 +1108,33 @@ int main(int argc, char **argv) {
       if (n != n_fields) die("read_split", "invalid number of fields in file!");
     }
     if (pos.size() != p.n_sites || n_fields < 2) die(__FUNCTION__, "invalid POS file!");
+    if (p.win) {  // fields 1 (chromosome) and 2 (position) of every site: the windows' chromosomes and coordinates
+      std::unordered_map<std::string, uint32_t> ids;
+      win_chrom.resize(p.n_sites);
+      win_pos_txt.resize(p.n_sites);
+      for (uint64_t s = 0; s < p.n_sites; s++) {
+        const std::string &l = pos[s];
+        const size_t t1 = l.find('\t'), t2 = l.find('\t', t1 + 1);
+        const std::string chr = l.substr(0, t1);
+        win_chrom[s] = ids.emplace(chr, (uint32_t)ids.size()).first->second;
+        win_pos_txt[s] = l.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
+        if (s == 0 || win_chrom[s] != win_chrom[s - 1]) win_chr_name.emplace(win_chrom[s], chr);
+      }
+    }
+  }
+  // the windows (--win_size / --win_step): the list the Python package makes too (host_util.cpp ngd_window_ranges)
+  std::vector<uint64_t> win_lo, win_hi;
+  if (p.win) {
+    const uint32_t *ids = win_chrom.empty() ? nullptr : win_chrom.data();
+    const int64_t n_win = ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, nullptr, nullptr, 0);
+    if (n_win < 0) die(__FUNCTION__, "positions file not grouped by chromosome!");
+    if (n_win == 0) die(__FUNCTION__, "no window fits the data set (--win_size larger than every chromosome)!");
+    win_lo.resize((size_t)n_win);
+    win_hi.resize((size_t)n_win);
+    ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win_lo.data(), win_hi.data(), (uint64_t)n_win);
+    if (!ngd_run_windows_dist)
+      die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
+    if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
   }
 
   g_phases.mark("args_labels");
@@ -1108,7 +1161,7 @@ int main(int argc, char **argv) {
     // begin with it): on the EM path, where that pass is several times the load, it starts beside the load
     // (NGD_OPT_EAGER_FULL: [measured] cfg 4 2.96 -> 2.78 s end to end; --eager 0 switches it off, --eager 2 also takes it
     // for --indep_geno, where a 46 ms pass beside a 0.5 s load gains nothing measurable)
-    if (p.eager && (!p.indep_geno || p.eager >= 2) && (p.n_boot_rep == 0 || eager_ranges) &&
+    if (p.eager && (!p.indep_geno || p.eager >= 2) && (p.n_boot_rep == 0 || eager_ranges) && !p.win &&
         (rc = ngd_set_option(eng.h, NGD_OPT_EAGER_FULL, 1)))
       die_engine("ngd_set_option", rc);
     if (p.stage_piece && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_PIECE_MIB, p.stage_piece))) die_engine("ngd_set_option", rc);
@@ -1138,6 +1191,8 @@ int main(int argc, char **argv) {
   const uint64_t budget = p.max_device_bytes ? p.max_device_bytes : dev_free / 100 * 85;
   const bool in_parts = p.n_gpus > 1 || fixed + per_site * p.n_sites > budget;
   eager_ranges = in_parts;
+  if (p.win && in_parts)
+    die(__FUNCTION__, "windows (--win_size) need the whole data set on one GPU; it does not fit the device budget!");
 
   if (p.verbose >= 2) fprintf(stderr, "==> Setting seed for random number generator\n");
   uint32_t rng[3];
@@ -1205,9 +1260,10 @@ int main(int argc, char **argv) {
   // and the print block
   auto emit = [&](uint64_t rep, const double *rs, const uint64_t *rc_, const uint64_t *bm, uint64_t n_blocks,
                   const double *ready = nullptr /* the matrix's distances, finished already (beside the matrix before it) */,
-                  int ready_rc = 0) {
+                  int ready_rc = 0, const char *window = nullptr /* --win_size: the window's name; rs, rc_ unused */) {
     if (p.verbose >= 1) {
-      if (rep == 0) fprintf(stderr, "==> Analyzing full dataset...\n");
+      if (window) fprintf(stderr, "==> Window %s ...\n", window);
+      else if (rep == 0) fprintf(stderr, "==> Analyzing full dataset...\n");
       else fprintf(stderr, "==> Bootstrap replicate # %lu ...\n", rep);
     }
     if (p.verbose >= 2) fprintf(stderr, "> Mapping positions...\n");
@@ -1218,7 +1274,7 @@ int main(int argc, char **argv) {
                   b * p.boot_block_size + s, bm[b], bm[b] * p.boot_block_size + s);
     }
     if (p.verbose >= 2) fprintf(stderr, "> Calculating pairwise genetic distances...\n");
-    if (p.verbose >= 3) {  // the per-pair line of ngsDist.cpp:366-367
+    if (p.verbose >= 3 && !window) {  // the per-pair line of ngsDist.cpp:366-367
       uint64_t k = 0;
       for (uint64_t i1 = 0; i1 < p.n_ind; i1++)
         for (uint64_t i2 = i1 + 1; i2 < p.n_ind; i2++, k++)
@@ -1413,6 +1469,41 @@ int main(int argc, char **argv) {
     fprintf(stderr, "> read + prepare + upload: %.3f s (%.2f GB of prepared input resident on the device)\n", t_load,
             (double)p.n_ind * p.n_sites * 24 / 1e9);
 
+  if (p.win) {
+    // ---- windows along the genome: one matrix per window, in window order, a group of windows per engine call (their
+    // distances in ~2 GB of host memory), each window's block formatted and written like the full data set's ----
+    const uint64_t n_win = win_lo.size();
+    const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * std::max<uint64_t>(1, n_comb))));
+    std::vector<double> wd;
+    for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
+      const uint64_t n = std::min(per, n_win - w0);
+      const auto t_c0 = std::chrono::steady_clock::now();
+      wd.resize(n * n_comb);
+      const int rc = ngd_run_windows_dist(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, wd.data());
+      if (rc) die_engine("ngd_run_windows_dist", rc);
+      report_fixup(eng.h, p.verbose);
+      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
+      for (uint64_t k = 0; k < n; k++) {
+        const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
+        emit(w0 + k, nullptr, nullptr, nullptr, 0, &wd[k * n_comb], 0, name.c_str());
+      }
+      writer.wait_idle();  // (the last block's text is written before the next group's call)
+    }
+    // <out>.windows: where each window lies
+    const std::string wpath = std::string(p.out) + ".windows";
+    FILE *wf = fopen(wpath.c_str(), "w");
+    if (!wf) die(__FUNCTION__, "cannot open windows output file!");
+    fprintf(wf, "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
+    for (uint64_t w = 0; w < n_win; w++) {
+      const uint64_t lo = win_lo[w], hi = win_hi[w];
+      if (win_chrom.empty())
+        fprintf(wf, "%lu\t.\t%lu\t%lu\t%lu\t%lu\n", w, lo + 1, hi, lo, hi - lo);
+      else
+        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
+                win_pos_txt[hi - 1].c_str(), lo, hi - lo);
+    }
+    if (fclose(wf) != 0) die(__FUNCTION__, "cannot write windows output file!");
+  } else {
   // Matrices go to the engine in batches: the first batch is the full-data matrix plus the first replicates
   // (ngd_run_job, which lets the engine share work between them), later ones replicates only (ngd_run_batch).
   // The block maps of a batch are drawn up front, in the order rnd_map_data (ngsDist.cpp:416-437) would draw
@@ -1503,6 +1594,7 @@ int main(int argc, char **argv) {
       for (uint64_t r = 0; r < n_in_batch; r++, rep++)
         emit(rep, &sum[r * n_comb], &cnt[r * n_comb], rep > 0 ? &block_maps[(r - (with_full ? 1 : 0)) * n_blocks] : nullptr, n_blocks);
     }
+  }
   }
   g_phases.mark("matrices");
   eng.leave_to_exit = true;

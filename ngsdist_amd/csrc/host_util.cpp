@@ -14,6 +14,7 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/ngsdist_amd.h"
@@ -519,6 +520,34 @@ int ngd_finish_stream(const double *sum, const uint64_t *cnt, uint64_t n_pairs, 
     (wide ? host_pool_wide() : host_pool()).run(parts, share);
   }
   return NGD_OK;
+}
+
+// --win_size / --win_step: per chromosome (a maximal run of equal ids) the windows of `size` sites every `step` sites that
+// fit inside it.  The host and the Python package both call this, so that they agree on the list.
+int64_t ngd_window_ranges(const uint32_t *chrom_id, uint64_t n_sites, uint64_t size, uint64_t step, uint64_t *lo, uint64_t *hi,
+                          uint64_t cap) {
+  if (!size || !step) return NGD_E_INVALID;
+  std::unordered_set<uint32_t> seen;  // ids of the chromosomes met so far (a reappearing one is an error)
+  uint64_t count = 0;
+  for (uint64_t c0 = 0; c0 < n_sites;) {
+    uint64_t c1 = c0 + 1;
+    if (chrom_id) {
+      while (c1 < n_sites && chrom_id[c1] == chrom_id[c0]) c1++;
+      if (!seen.insert(chrom_id[c0]).second) return NGD_E_INVALID;
+    } else {
+      c1 = n_sites;
+    }
+    for (uint64_t s = c0; c1 - s >= size; s += step) {
+      if (lo && hi && count < cap) {
+        lo[count] = s;
+        hi[count] = s + size;
+      }
+      count++;
+      if (step > c1 - s) break;  // (s + step would pass the chromosome's end)
+    }
+    c0 = c1;
+  }
+  return (int64_t)count;
 }
 
 }  // extern "C"

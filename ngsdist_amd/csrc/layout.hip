@@ -281,6 +281,20 @@ __global__ void k_slice_weights(uint32_t n_slices, uint32_t stride, uint64_t k_p
   W[t] = (k >= lo && k < hi) ? d3.v[k % 3] : 0.0;
 }
 
+// Windows along the genome: the weights of segment q (grid.x) -- d3[k % 3] for the contraction indices of its sites
+// [s_lo, s_hi), 0 for those its first and last k-group share with the neighbouring segments and for the run-ahead past
+// them -- written at k-group woff of W (vector stores; a segment's k-groups are disjoint from every other's)
+__global__ void k_seg_weights(const uint64_t *__restrict__ seg, double *__restrict__ W, ngd_d3 d3) {
+  const uint64_t *t = seg + (uint64_t)blockIdx.x * NGD_SEG_STRIDE;
+  const uint64_t kg0 = t[NGD_SEG_KG0], kg1 = t[NGD_SEG_KG1], woff = t[NGD_SEG_WOFF];
+  const uint64_t k_lo = 3 * t[NGD_SEG_SLO], k_hi = 3 * t[NGD_SEG_SHI];
+  const uint64_t n = (kg1 - kg0 + 1 + NGD_KG_TAIL) * 4;
+  for (uint64_t r = blockIdx.y * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.y * blockDim.x) {
+    const uint64_t k = kg0 * 4 + r;
+    W[woff * 4 + r] = (k >= k_lo && k < k_hi) ? d3.v[k % 3] : 0.0;
+  }
+}
+
 // bit-planes of the per-site multiplicity, for weighted valid-site counts
 __global__ void k_planes(const uint32_t *__restrict__ ws, uint64_t n_sites, uint32_t n_words,
                          uint32_t n_planes, unsigned long long *planes) {
@@ -469,4 +483,12 @@ void ngd_launch_planes(hipStream_t st, const uint32_t *d_ws, uint64_t n_sites, u
                        uint32_t n_planes, unsigned long long *d_planes) {
   hipLaunchKernelGGL(k_planes, dim3((n_words + 255) / 256), dim3(256), 0, st, d_ws, n_sites, n_words,
                      n_planes, d_planes);
+}
+
+void ngd_launch_seg_weights(hipStream_t st, const uint64_t *d_seg, uint32_t n_seg, uint64_t max_wkg, const double *d3,
+                            double *d_W) {
+  if (!n_seg) return;
+  const uint64_t want = (max_wkg * 4 + 255) / 256;
+  const uint32_t ny = (uint32_t)(want < 64 ? want : 64);
+  hipLaunchKernelGGL(k_seg_weights, dim3(n_seg, ny ? ny : 1), dim3(256), 0, st, d_seg, d_W, d3_of(d3));
 }

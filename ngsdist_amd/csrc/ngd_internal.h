@@ -128,6 +128,19 @@ void ngd_launch_accum_stream(hipStream_t st, const ngd_geom &g, const double *PI
                              uint64_t n_sites_eff, const ngd_score &score, int pairwise_del,
                              const uint64_t *d_pairs, uint64_t n_owned, double *d_sum);
 
+// Windows along the genome (engine.hip windows_slab): a slice table entry per segment of sites [s_lo, s_hi) --
+// k-groups [kg0, kg1) = [3 s_lo / 4, ceil(3 s_hi / 4)), its 0/1 weights (d3[k % 3] inside the segment, 0 outside) at k-group
+// woff of the weight array, kg1 - kg0 + 1 + NGD_KG_TAIL k-groups of them (the operand pipeline's run-ahead reads past kg1)
+#define NGD_SEG_STRIDE 5
+#define NGD_SEG_KG0 0
+#define NGD_SEG_KG1 1
+#define NGD_SEG_WOFF 2
+#define NGD_SEG_SLO 3
+#define NGD_SEG_SHI 4
+// layout.hip: the weights of every segment of the table (w_total k-groups in all)
+void ngd_launch_seg_weights(hipStream_t st, const uint64_t *d_seg, uint32_t n_seg, uint64_t max_wkg, const double *d3,
+                            double *d_W);
+
 // accum_mfma.hip : FP64 MFMA tiles, split over site slices into slabs
 // d_wk / d_kgl: bootstrap weights per contraction index and the list of k-groups to visit; with a list,
 // kg_per_slice and n_kg_eff count LIST entries.  k_per_slice != 0: slices are k_per_slice contraction indices
@@ -138,7 +151,9 @@ void ngd_launch_accum_mfma(hipStream_t st, const ngd_geom &g, const double *PA, 
                            uint64_t k_per_slice, uint32_t w_slice_stride, double *slab,
                            unsigned long long *d_clk /* [2] or NULL: shader-cycle / constant-rate counter deltas of one wavefront */,
                            uint32_t ks0 = 0 /* the launch covers slices ks0 .. ks0 + n_ks - 1 (multiples of 8) */,
-                           uint32_t resume = 0 /* 1: every block continues from its plane of the slab (a pass in ranges) */);
+                           uint32_t resume = 0 /* 1: every block continues from its plane of the slab (a pass in ranges) */,
+                           const uint64_t *d_seg = nullptr /* slice table [n_ks][NGD_SEG_STRIDE] (windows): each slice's own   */
+                                                           /* k-group range and weight offset; needs d_ws and w_slice_stride != 0 */);
 
 // accum_em.hip : per-site EM, one thread per pair of a 16x16 tile
 void ngd_launch_accum_em(hipStream_t st, const ngd_geom &g, const double *PA, const uint32_t *d_ws,
@@ -265,7 +280,15 @@ void ngd_launch_reduce_c(hipStream_t st, const ngd_geom &g, const uint32_t *C, u
                          uint32_t m_stride, uint32_t n_rep, const ngd_tile *d_tiles, uint32_t n_tiles,
                          unsigned long long *d_cnt, uint32_t chunk = 0);
 void ngd_launch_count_blocks(hipStream_t st, const ngd_geom &g, const unsigned long long *mask, uint64_t block_size,
-                             uint32_t n_blocks, const ngd_tile *d_tiles16, uint32_t n_tiles16, uint32_t *C);
+                             uint32_t n_blocks, const ngd_tile *d_tiles16, uint32_t n_tiles16, uint32_t *C,
+                             const uint64_t *d_seg = nullptr /* windows: block b = segment b of the slice table */);
+// windows along the genome: the banded reduction (k_reduce_band) of per-segment sums (C == NULL) or valid-site counts
+// (slab unused) into [n_win][n_pairs]; d_win[2 w] = first | end segment << 32, d_win[2 w + 1] = window length; a sum
+// launch also writes the length as the count when d_cnt != NULL and notes pairs for the fix-up when fix != NULL
+uint32_t ngd_band_windows();  // windows per group (grid.y)
+void ngd_launch_reduce_band(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C,
+                            const unsigned long long *d_win, uint32_t n_win, const ngd_tile *d_tiles, uint32_t n_tiles,
+                            double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags *fix);
 void ngd_launch_count(hipStream_t st, const ngd_geom &g, const unsigned long long *mask,
                       const unsigned long long *planes, uint32_t n_planes, const ngd_tile *d_tiles,
                       uint32_t n_tiles, unsigned long long *d_cnt);  // owned 128-tiles

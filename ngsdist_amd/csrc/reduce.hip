@@ -5,6 +5,8 @@
 // bootstrap multiplicities entering as bit-planes, (3) bootstrap replicates
 // as weighted reductions of per-block partial (sum, cnt), many replicates per
 // pass over the partials.
+#include <type_traits>
+
 #include "ngd_internal.h"
 
 namespace {
@@ -298,16 +300,19 @@ __global__ __launch_bounds__(256) void k_count(const unsigned long long *__restr
 // Per-block valid-site counts C[b][i][j] = popcount(mask_i & mask_j over the sites of block b): the cnt half
 // of the per-block partials.  Workgroup = 16x16 pairs; grid.y strides over the blocks.  A block is any
 // site range [b*B, (b+1)*B), so its first and last mask words are trimmed.
+// seg != NULL (windows along the genome): block b is the segment [seg[b].s_lo, seg[b].s_hi) of the slice table instead.
 __global__ __launch_bounds__(256) void k_count_blocks(const unsigned long long *__restrict__ mask,
                                                        uint32_t n_words, uint64_t block_size, uint32_t n_blocks,
                                                        const ngd_tile *__restrict__ tiles, uint32_t n_pad,
-                                                       uint64_t n_ind, uint32_t *__restrict__ C) {
+                                                       uint64_t n_ind, uint32_t *__restrict__ C,
+                                                       const uint64_t *__restrict__ seg) {
   __shared__ unsigned long long mi[16][CW + 1], mj[16][CW + 1];
   const uint32_t ig = tiles[blockIdx.x].ti, jg = tiles[blockIdx.x].tj;
   const uint32_t ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
   const uint32_t i = ig * 16 + ty, j = jg * 16 + tx;
   for (uint32_t b = blockIdx.y; b < n_blocks; b += gridDim.y) {
-    const uint64_t s_lo = (uint64_t)b * block_size, s_hi = s_lo + block_size;  // sites [s_lo, s_hi)
+    const uint64_t s_lo = seg ? seg[(uint64_t)b * NGD_SEG_STRIDE + NGD_SEG_SLO] : (uint64_t)b * block_size;  // sites [s_lo, s_hi)
+    const uint64_t s_hi = seg ? seg[(uint64_t)b * NGD_SEG_STRIDE + NGD_SEG_SHI] : s_lo + block_size;
     const uint32_t w_lo = (uint32_t)(s_lo >> 6), w_hi = (uint32_t)((s_hi - 1) >> 6);
     uint32_t cnt = 0;
     for (uint32_t w0 = w_lo; w0 <= w_hi; w0 += CW) {
@@ -331,6 +336,78 @@ __global__ __launch_bounds__(256) void k_count_blocks(const unsigned long long *
       __syncthreads();
     }
     C[((uint64_t)b * n_pad + i) * n_pad + j] = cnt;
+  }
+}
+
+// Windows along the genome (engine.hip windows_slab), the banded reduction: k_reduce_wb's tiling and output order, a group
+// of RB consecutive windows per grid.y.  The group reads the union of its windows' segments ONCE, in ascending order, and
+// adds each to the windows that contain it -- reads scale with the segments, not windows x segments as k_reduce_wb on 0/1
+// weights would.  win[2 w] = first segment | end segment << 32 of window w (segments of the batch), win[2 w + 1] = its
+// length in sites.  CNT = false: slab of per-segment sums -> d_sum, and (d_cnt != NULL, no --pairwise_del) the window's
+// length as every pair's count; single_image = 2 engines note a pair whose sum in any window is below NGD_FIX_MEAN x the
+// window's length.  CNT = true: per-segment valid-site counts (k_count_blocks over the segments) -> d_cnt, exactly.
+template <int RB, bool CNT>
+__global__ __launch_bounds__(128) void k_reduce_band(const void *__restrict__ slab_v, const unsigned long long *__restrict__ win,
+                                                      uint32_t n_win, const ngd_tile *__restrict__ tiles, uint32_t n_pad,
+                                                      uint64_t n_ind, uint64_t n_pairs, double *__restrict__ d_sum,
+                                                      unsigned long long *__restrict__ d_cnt, ngd_fix_flags fix) {
+  typedef typename std::conditional<CNT, uint32_t, double>::type T;
+  typedef typename std::conditional<CNT, unsigned long long, double>::type A;
+  const uint32_t tile = blockIdx.x >> 7, row = blockIdx.x & 127;
+  const uint32_t i = tiles[tile].ti * NGD_TILE + row;
+  const uint32_t j = tiles[tile].tj * NGD_TILE + threadIdx.x;
+  if (!(i < j && j < n_ind)) return;
+  const uint32_t w0 = blockIdx.y * RB;
+  uint32_t f[RB], l[RB];  // the group's windows as segment ranges (uniform across the workgroup)
+  uint32_t a = 0xffffffffu, b = 0;
+#pragma unroll
+  for (int r = 0; r < RB; r++) {
+    const unsigned long long t = w0 + r < n_win ? win[2 * (uint64_t)(w0 + r)] : 0ull;
+    f[r] = (uint32_t)t;
+    l[r] = (uint32_t)(t >> 32);
+    if (f[r] < l[r]) { a = a < f[r] ? a : f[r]; b = b > l[r] ? b : l[r]; }
+  }
+  const uint64_t plane = (uint64_t)n_pad * n_pad;
+  const T *p = reinterpret_cast<const T *>(slab_v) + (uint64_t)i * n_pad + j;
+  A acc[RB];
+#pragma unroll
+  for (int r = 0; r < RB; r++) acc[r] = 0;
+  constexpr int U = 4;  // segments in flight per thread
+  uint32_t s = a;
+  for (; s + U <= b; s += U) {
+    T v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) v[u] = p[(uint64_t)(s + u) * plane];
+#pragma unroll
+    for (int u = 0; u < U; u++)
+#pragma unroll
+      for (int r = 0; r < RB; r++)
+        if (s + u >= f[r] && s + u < l[r]) acc[r] += (A)v[u];  // (a select, never 0 x v: nothing outside a window enters it)
+  }
+  for (; s < b; s++) {
+    const T v = p[(uint64_t)s * plane];
+#pragma unroll
+    for (int r = 0; r < RB; r++)
+      if (s >= f[r] && s < l[r]) acc[r] += (A)v;
+  }
+  const uint64_t idx = ngd_pair_idx(n_ind, i, j);
+  bool small = false;
+#pragma unroll
+  for (int r = 0; r < RB; r++)
+    if (w0 + r < n_win) {
+      const uint64_t o = (uint64_t)(w0 + r) * n_pairs + idx;
+      if (CNT) {
+        d_cnt[o] = (unsigned long long)acc[r];
+      } else {
+        const unsigned long long len = win[2 * (uint64_t)(w0 + r) + 1];
+        d_sum[o] = (double)acc[r];
+        if (d_cnt) d_cnt[o] = len;
+        if (fix.list) small = small || (double)acc[r] < NGD_FIX_MEAN * (double)len;
+      }
+    }
+  if (!CNT && small && !((atomicOr(&fix.seen[idx >> 5], 1u << (idx & 31)) >> (idx & 31)) & 1u)) {
+    const uint32_t slot = atomicAdd(fix.count, 1u);
+    if (slot < fix.cap) fix.list[slot] = ((unsigned long long)i << 32) | j;
   }
 }
 
@@ -405,10 +482,31 @@ void ngd_launch_reduce_c(hipStream_t st, const ngd_geom &g, const uint32_t *C, u
 }
 
 void ngd_launch_count_blocks(hipStream_t st, const ngd_geom &g, const unsigned long long *mask, uint64_t block_size,
-                             uint32_t n_blocks, const ngd_tile *d_tiles16, uint32_t n_tiles16, uint32_t *C) {
+                             uint32_t n_blocks, const ngd_tile *d_tiles16, uint32_t n_tiles16, uint32_t *C, const uint64_t *d_seg) {
   if (!n_tiles16 || !n_blocks) return;
   hipLaunchKernelGGL(k_count_blocks, dim3(n_tiles16, n_blocks < 1024 ? n_blocks : 1024), dim3(256), 0, st, mask,
-                     g.n_words, block_size, n_blocks, d_tiles16, g.n_pad, g.n_ind, C);
+                     g.n_words, block_size, n_blocks, d_tiles16, g.n_pad, g.n_ind, C, d_seg);
+}
+
+uint32_t ngd_band_windows() { return 16; }
+
+void ngd_launch_reduce_band(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C,
+                            const unsigned long long *d_win, uint32_t n_win, const ngd_tile *d_tiles, uint32_t n_tiles,
+                            double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags *fix) {
+  if (!n_tiles || !n_win) return;
+  const uint64_t n_pairs = g.n_ind * (g.n_ind - 1) / 2;
+  const ngd_fix_flags f = fix ? *fix : ngd_fix_flags{nullptr, nullptr, nullptr, 0};
+  for (uint32_t w0 = 0; w0 < n_win; w0 += 16 * 32768) {  // (grid.y holds 65 535)
+    const uint32_t n = n_win - w0 < 16 * 32768 ? n_win - w0 : 16 * 32768;
+    const dim3 grid(n_tiles * NGD_TILE, (n + 15) / 16);
+    if (C)
+      hipLaunchKernelGGL((k_reduce_band<16, true>), grid, dim3(128), 0, st, (const void *)C, d_win + 2 * (uint64_t)w0, n, d_tiles,
+                         g.n_pad, g.n_ind, n_pairs, nullptr, d_cnt + (uint64_t)w0 * n_pairs, f);
+    else
+      hipLaunchKernelGGL((k_reduce_band<16, false>), grid, dim3(128), 0, st, (const void *)slab, d_win + 2 * (uint64_t)w0, n,
+                         d_tiles, g.n_pad, g.n_ind, n_pairs, d_sum + (uint64_t)w0 * n_pairs,
+                         d_cnt ? d_cnt + (uint64_t)w0 * n_pairs : nullptr, f);
+  }
 }
 
 void ngd_launch_fill_cnt(hipStream_t st, const ngd_geom &g, const ngd_tile *d_tiles, uint32_t n_tiles,

@@ -16,7 +16,7 @@ KERNELS = {"auto": 0, "stream": 1, "mfma": 2, "em_faithful": 3, "em_fast": 4, "e
 # NGD_OPT_* of include/ngsdist_amd.h
 OPTIONS = {"boot_partials": 1, "boot_max_bytes": 2, "boot_wg": 3, "boot_unaligned": 4, "em_batch": 5,
            "em_spill": 6, "em_spill_bytes": 7, "single_image_bytes": 8, "fixup_work": 9, "stage_piece_mib": 10,
-           "stage_ring": 11, "eager_full": 12, "debug_forge_job": 100}
+           "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "debug_forge_job": 100}
 
 # parse_args.cpp:25-27
 DEFAULT_SCORE = (0.0, 0.5, 1.0, 0.5, 0.0, 0.5, 1.0, 0.5, 0.0)
@@ -228,6 +228,43 @@ class Engine:
         _check(fn(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model), d.ctypes.data_as(C.POINTER(C.c_double))))
         return d
 
+    @staticmethod
+    def _win_args(lo, hi):
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+        if lo.ndim != 1 or lo.shape != hi.shape:
+            raise ValueError("lo, hi: expected two 1-D arrays of the same length")
+        return lo, hi, lo.ctypes.data_as(C.POINTER(C.c_uint64)), hi.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    def run_windows(self, lo, hi, d_sum_ptr=None, d_cnt_ptr=None):
+        """one matrix per window of sites [lo[w], hi[w]) (ngd_run_windows): -> (sum float64[n_win][n_pairs],
+        cnt uint64[n_win][n_pairs]), each what run() gives on the data set cut down to the window; with device pointers
+        (ngd_run_windows_device) the results go there and None is returned"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        if d_sum_ptr is not None:
+            _check(self._L.ngd_run_windows_device(self._h, lp, hp, lo.size, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr)))
+            return None
+        s = np.empty((lo.size, self.n_pairs), dtype=np.float64)
+        c = np.empty((lo.size, self.n_pairs), dtype=np.uint64)
+        _check(self._L.ngd_run_windows(self._h, lp, hp, lo.size, s.ctypes.data_as(C.POINTER(C.c_double)),
+                                       c.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return s, c
+
+    def run_windows_dist(self, lo, hi, evol_model=1, tot_sites=0):
+        """the windows and the tail of gen_dist() on each (ngd_run_windows_dist): float64[n_win][n_pairs]"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        d = np.empty((lo.size, self.n_pairs), dtype=np.float64)
+        _check(self._L.ngd_run_windows_dist(self._h, lp, hp, lo.size, int(tot_sites), int(evol_model),
+                                            d.ctypes.data_as(C.POINTER(C.c_double))))
+        return d
+
+    def windows_info(self):
+        """what the last windowed call did (ngd_last_windows): segments, slab_bytes, batches, band_launches,
+        windows_by_pass, fixup_pairs, ms"""
+        t = _lib.NgdWindowsInfo()
+        _check(self._L.ngd_last_windows(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_}
+
     def run_job_keep(self, block_maps, block_size=1):
         """ngd_run_job with the matrices left in the engine; fetch_matrix(r) copies them out one at a time"""
         a = np.ascontiguousarray(block_maps, dtype=np.uint64)
@@ -249,7 +286,7 @@ class Engine:
 
     def set_option(self, name, value):
         """plan selection for the replicate loop (ngd_set_option): boot_partials, boot_max_bytes, boot_wg, boot_unaligned,
-        em_batch, em_spill, em_spill_bytes, single_image_bytes, fixup_work"""
+        em_batch, em_spill, em_spill_bytes, single_image_bytes, fixup_work, win_plan, win_max_bytes"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self
 
@@ -309,6 +346,28 @@ def finish(sum_, cnt, tot_sites=0, evol_model=1, out=None):
     _check(L.ngd_finish(s.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_uint64)),
                         s.size, int(tot_sites), int(evol_model), out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+def window_ranges(n_sites, size, step=None, chrom=None):
+    """the window list of --win_size / --win_step (ngd_window_ranges): -> (lo, hi) uint64 arrays.  chrom: one id per site
+    (any hashable values; a chromosome is a maximal run of equal ids and must not come back after another one)."""
+    L = _lib.load()
+    step = size if step is None else step
+    ids = None
+    if chrom is not None:
+        if len(chrom) != n_sites:
+            raise ValueError("chrom: expected one id per site")
+        codes = {}
+        ids = np.fromiter((codes.setdefault(c, len(codes)) for c in chrom), dtype=np.uint32, count=n_sites)
+    idp = ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None
+    n = L.ngd_window_ranges(idp, int(n_sites), int(size), int(step), None, None, 0)
+    if n < 0:
+        raise NgdError(int(n), "window_ranges: size and step must be positive and chromosomes grouped")
+    lo = np.zeros(n, dtype=np.uint64)
+    hi = np.zeros(n, dtype=np.uint64)
+    L.ngd_window_ranges(idp, int(n_sites), int(size), int(step), lo.ctypes.data_as(C.POINTER(C.c_uint64)),
+                        hi.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+    return lo, hi
 
 
 def score_congruence(score):
