@@ -40,8 +40,10 @@ def engine(p, kernel, pairwise_del=False, indep_geno=True, **kw):
     return e
 
 
-def check(e, p, lo, hi, plans=(0, 1, 2), pairwise_del=False, indep_geno=True, exact=False):
-    so, co = oracle_windows(p, lo, hi, pairwise_del, indep_geno)
+def check(e, p, lo, hi, plans=(0, 1, 2), pairwise_del=False, indep_geno=True, exact=False, ref=None, infos=None):
+    """every plan of `plans` against the oracle on each window's sites (ref: its (sums, counts), computed once by the caller);
+    infos: a dict that receives windows_info() per plan"""
+    so, co = oracle_windows(p, lo, hi, pairwise_del, indep_geno) if ref is None else ref
     for plan in plans:
         e.set_option("win_plan", plan)
         s, c = e.run_windows(lo, hi)
@@ -51,6 +53,8 @@ def check(e, p, lo, hi, plans=(0, 1, 2), pairwise_del=False, indep_geno=True, ex
             assert np.array_equal(s, so), "plan %d: called genotypes must be bit-exact" % plan
         assert rel_err(s, so) < RTOL, "plan %d" % plan
         info = e.windows_info()
+        if infos is not None:
+            infos[plan] = info
         if plan == 1:
             assert info["windows_by_pass"] == len(lo) and info["segments"] == 0
         if plan == 2:
