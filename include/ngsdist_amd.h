@@ -173,7 +173,14 @@ int ngd_commit(ngd_engine *e);
  * ngd_stage_submit(), which returns at once: the copy runs on a copy stream of its own, the
  * preparation kernel behind it on the engine's stream, and the next acquire hands out the
  * next buffer of the ring (waiting only for the copy out of THAT buffer, a turn ago).  ngd_upload_raw_sites() is the blocking
- * convenience form.  NGD_E_NAN is reported by ngd_commit() at the latest. */
+ * convenience form.  NGD_E_NAN is reported by ngd_commit() at the latest.
+ *
+ * Upload contract (every path above: ngd_upload_sites, ngd_upload_ind_major, ngd_upload_raw_sites, ngd_stage_*):
+ *   - before a successful ngd_commit(), sites may be written any number of times, by any of the paths, in any order;
+ *   - each site holds the last values written to it, whether it is missing (--pairwise_del) included;
+ *   - after ngd_commit() has returned NGD_E_NAN the engine accepts a fresh upload (then ngd_commit() again);
+ *   - a site that is never written holds unspecified values: writing every site is the caller's responsibility (the
+ *     engine does not track it). */
 typedef struct ngd_prep {
   int32_t in_logscale; /* --log_scale                           */
   int32_t call_geno;   /* --call_geno (or -N / -C)              */

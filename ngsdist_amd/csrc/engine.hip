@@ -1192,6 +1192,13 @@ int ngd_stage_submit(ngd_engine *e, uint64_t s0, uint64_t n, const ngd_prep *pre
   if (n > e->pin_sites || s0 + n > e->g.n_sites || s0 + n < s0)
     return fail(NGD_E_INVALID, "ngd_stage_submit: site range out of bounds");
   HIPCHK(hipSetDevice(e->device));
+  // a piece below the in-order prefix rewrites sites that launched eager slices have read -- or are reading still: its
+  // preparation kernel would run beside them.  They are waited for and dropped, and none start again in this load.
+  // (Checked even once the load is out of order: a piece that jumped ahead left the slices valid, this one does not.)
+  if (e->eager_valid && s0 < e->stage_prefix) {
+    if (int rc = eager_discard(e)) return rc;
+    e->stage_in_order = false;
+  }
   const int b = e->pin_lent;
   hipStream_t cs = e->st_copy[0];
   e->n_staged++;
@@ -1263,6 +1270,9 @@ int ngd_commit(ngd_engine *e) {
     e->pin_lent = -1;
     if (flag) {  // reported once: a caller that uploads again starts from a clean flag and a fresh pipeline
       HIPCHK(hipMemset(e->d_nan, 0, sizeof(int)));
+      if (int rc = eager_discard(e)) return rc;  // (slices of the rejected data: none of them is kept)
+      e->stage_prefix = 0;
+      e->stage_in_order = true;
       return fail(NGD_E_NAN, "NaN found! Is the file format correct?");
     }
   }

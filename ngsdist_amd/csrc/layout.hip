@@ -21,7 +21,13 @@ __device__ __forceinline__ void emit(const ngd_geom &g, const ngd_score &sc, int
     d[0] = p0; d[1] = p1; d[2] = p2;
   }
   bool miss = ngd_miss(p0, p1, p2);
-  if (mask && !miss) atomicOr(&mask[(uint64_t)i * g.n_words + (s >> 6)], 1ull << (s & 63));
+  if (mask) {  // (set AND cleared: a site uploaded again holds its last missingness; other sites of the word may be written
+               // by other pieces at the same time)
+    unsigned long long *w = &mask[(uint64_t)i * g.n_words + (s >> 6)];
+    const unsigned long long bit = 1ull << (s & 63);
+    if (miss) atomicAnd(w, ~bit);
+    else atomicOr(w, bit);
+  }
   if (pairwise_del && miss) { p0 = 0; p1 = 0; p2 = 0; }  // a skipped site contributes nothing
   // congruent image of the reference's matrices, t = (p0 + p1 + p2, +-(p2 - p0), p1): the smaller of p0 and p2 is what
   // the image cannot hold to the last bit -- kept beside it (site-major: coalesced here), p is then recoverable (fixup.hip)
