@@ -339,9 +339,16 @@ int ngd_drop_caches(ngd_engine *e);
                                  /* first call after ngd_commit IS that pass (no bootstrap): anything else drops the work.    */
                                  /* MFMA kernel above 384 padded individuals and the table-driven EM kernel; else ignored.    */
 #define NGD_OPT_WIN_PLAN 13       /* [0] ngd_run_windows*: 0 auto (the cheaper plan by estimate), 1 one weighted pass per       */
-                                 /*     window only, 2 the segment-slab plan only (NGD_E_NOMEM if a window cannot fit it)      */
+                                 /*     window only, 2 the segment-slab plan only (NGD_E_NOMEM if a window cannot fit it).     */
+                                 /*     Engines with the segment-slab plan: the MFMA kernel with both operand images resident  */
+                                 /*     or the one congruent image, and NGD_KERNEL_EM_TABLE (what auto picks above 32          */
+                                 /*     individuals without indep_geno) with any ngd_config.variant.  On every other engine    */
+                                 /*     (one image + ranges of the second, NGD_KERNEL_EM_FAST / _EM_FAITHFUL / _STREAM) 0 and  */
+                                 /*     1 take the per-window plan and 2 is refused (NGD_E_INVALID)                            */
 #define NGD_OPT_WIN_MAX_BYTES 14  /* [0 = 85 % of free device memory, the rule of NGD_OPT_BOOT_MAX_BYTES] budget of one batch   */
-                                 /*     of the segment-slab plan (its partial results, counts and slice weights)              */
+                                 /*     of the segment-slab plan: its partial results and counts, + the MFMA kernel's slice    */
+                                 /*     weights.  An EM engine's batch is 8 n_pad^2 bytes per slice (+ 4 n_pad^2 per slice     */
+                                 /*     under pairwise_del), n_pad = n_ind rounded up to 128                                   */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -403,13 +410,17 @@ int ngd_last_em_work(const ngd_engine *e, uint64_t *tile_sites, uint64_t *table_
  * windows may overlap and nest.  NGD_E_INVALID for anything else, and on an engine that owns a share of the pairs.
  * Outputs are [n_win][n_pairs] with the meaning of ngd_run() (host memory; ..._device: device pointers of the caller's).
  * Two plans (NGD_OPT_WIN_PLAN):
- *  - segment slab (MFMA kernel, engines with both operands resident or the one congruent image): the elementary
+ *  - segment slab (MFMA kernel, engines with both operands resident or the one congruent image; the table-driven EM
+ *    kernel NGD_KERNEL_EM_TABLE, every workgroup shape of ngd_config.variant): the elementary
  *    intervals between consecutive window boundaries are the slices of ONE accumulation pass into per-segment partial
  *    results, then a banded reduction adds each window's segments, in ascending order, for a group of consecutive windows
  *    per read of their segments; --pairwise_del counts the same way from per-segment popcounts.  Calls whose segments do
  *    not fit the budget (NGD_OPT_WIN_MAX_BYTES) go in batches of consecutive windows; a segment two batches share is
  *    computed in both.  One-image engines (single_image = 2) then recompute with the two-operand arithmetic the pairs
- *    whose sum in some window is below 1e-6 x the window's length (x the pair's count under --pairwise_del);
+ *    whose sum in some window is below 1e-6 x the window's length (x the pair's count under --pairwise_del).  On an EM
+ *    engine a long interval is cut into several slices (as many workgroups as a plain pass), the per-site EM term is
+ *    the same in every window that holds the site, and a term that is not finite (an all-zero individual) reaches
+ *    exactly those windows; sums agree with the per-window plan's to rounding (<= 1e-12 relative);
  *  - per window (every other kernel, or when cheaper): one weighted pass per window over that window's sites (the pass
  *    ngd_run_mult() makes with 0/1 multiplicities).
  * Sums agree with the cut-down data set's ngd_run() to rounding (<= 1e-9 relative), counts exactly. */

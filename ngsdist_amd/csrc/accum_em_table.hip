@@ -381,19 +381,29 @@ constexpr int PACK_DENSE = NGD_PACK_DENSE;
 // at 1000 individuals; rowpg is the first live group's slot group minus that group's index).  Terms that are not finite (an all-zero individual: 0/0 in normalize(), as on the CPU) raise
 // the flag word `nanlist`; the chunk is then sanitised before it is contracted (0 x NaN must not reach the matrices
 // that do not draw the site).
-template <int NW, int CH, int WPS, bool WEIGHTED, bool PDEL, bool PACK, int RB, bool SPILL = false>
+//
+// SEGS (windows along the genome, engine.hip windows_slab): slice ks is the segment of sites [segtab[ks].s_lo, segtab[ks].s_hi) of
+// the slice table (NGD_SEG_SLO / NGD_SEG_SHI of ngd_internal.h; the k-group entries belong to the MFMA kernel and are not read)
+// -- any length from 1 site, any first site -- instead of the ks-th run of sites_per_slice sites.  Its plane of the slab
+// is [ks][n_pad][n_pad] as ever, which is what the banded reduction reads.  Nothing else differs: a (pair, site) term is the
+// plain pass's instruction for instruction, and a term that is not finite stays in its segment's plane.  Register budget
+// (hipcc --save-temps): every SEGS instantiation has the VGPR count of its unweighted neighbour (shape 0: 128) and no scratch;
+// the bounds arrive by scalar loads, five scalar instructions more than the neighbour's prologue.
+template <int NW, int CH, int WPS, bool WEIGHTED, bool PDEL, bool PACK, int RB, bool SPILL = false, bool SEGS = false>
 __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
     const double *__restrict__ PA, const uint32_t *__restrict__ ws, const double *__restrict__ Wb, ngd_score sc,
     const ngd_tile *__restrict__ tiles, uint32_t n_tiles, uint32_t n_ig, uint32_t n_pad, uint64_t n_ind,
     uint64_t n_sites_eff, uint64_t sites_per_slice, double *__restrict__ slab,
     unsigned long long *__restrict__ counters, uint64_t site_base = 0,
-    unsigned long long *__restrict__ nanlist = nullptr, uint32_t spill_q = 1, const uint32_t *__restrict__ rowpg = nullptr) {
+    unsigned long long *__restrict__ nanlist = nullptr, uint32_t spill_q = 1, const uint32_t *__restrict__ rowpg = nullptr,
+    const uint64_t *__restrict__ segtab = nullptr) {
 
   constexpr int RPW = TS / NW;  // rows per wavefront
   constexpr int RS = em_tables<CH, PACK>::RS;
   static_assert(!PACK || NW == 8, "packed units: 8 wavefronts x 8 rows");
   static_assert(RB == 1 || (PACK && WEIGHTED), "several matrices per pass: the packed form, weighted");
   static_assert(!SPILL || (PACK && !WEIGHTED && RB == 1), "spilled terms: the packed form, unweighted");
+  static_assert(!SEGS || (!WEIGHTED && RB == 1 && !SPILL), "a slice table: one matrix per segment, unweighted");
   // rows per group (one uniform "anything left?" test per group; their table reads are in flight together)
   constexpr int GR = (WPS >= 4 || PACK) ? 1 : 4;
   static_assert(RPW % GR == 0 && CH % 4 == 0 && (CH % 8 == 0 || CH % 8 == 4), "shape");
@@ -414,9 +424,16 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
 #if defined(NGD_EMT_YOUNG_FIRST)
   if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);  // A/B build: the younger half of the workgroup is served first
 #endif
-  const uint64_t s0 = site_base + (uint64_t)ks * sites_per_slice;
+  uint64_t s0 = site_base + (uint64_t)ks * sites_per_slice;
   uint64_t s1 = s0 + sites_per_slice;
   if (s1 > n_sites_eff) s1 = n_sites_eff;
+  if constexpr (SEGS) {  // the segment's bounds, in scalar registers (the address is uniform; readfirstlane states it)
+    const uint64_t *t = segtab + (uint64_t)ks * NGD_SEG_STRIDE;
+    const uint64_t lo = t[NGD_SEG_SLO], hi = t[NGD_SEG_SHI];
+    s0 = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(lo >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)lo);
+    s1 = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(hi >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)hi);
+    if (s1 > n_sites_eff) s1 = n_sites_eff;  // (the engine's table never reaches past the resident sites: a second fence)
+  }
 
   // scanning role: lane = column, rows wave*RPW .. +RPW-1
   const uint32_t j = J0 + lane;
@@ -780,6 +797,29 @@ void ngd_launch_accum_em_table_slices(hipStream_t st, const ngd_geom &g, const d
   }
 #undef NGD_EMT_SP
 #undef NGD_EMT_S
+}
+
+// Windows along the genome: slice ks = segment ks of the slice table d_seg ([n_seg][NGD_SEG_STRIDE], sites [s_lo, s_hi) below
+// g.n_sites), one plane of the slab per segment.  Every shape has the form (engine.hip windows_slab_applies()).
+void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,
+                                    int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_seg,
+                                    const uint64_t *d_seg, double *slab, unsigned long long *d_counters) {
+  if (!n_tiles64 || !n_seg) return;
+  const bool p = pairwise_del != 0;
+#define NGD_EMT_G(NW, CH, WPS, P, K)                                                                                        \
+  hipLaunchKernelGGL((k_accum_em_table<NW, CH, WPS, false, P, K, 1, false, true>), dim3(n_tiles64 * n_seg), dim3(NW * 64), 0, \
+                     st, PA, nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, g.n_sites, 0, slab,     \
+                     d_counters, 0, nullptr, 1, nullptr, d_seg)
+#define NGD_EMT_GP(NW, CH, WPS, K) do { if (p) NGD_EMT_G(NW, CH, WPS, true, K); else NGD_EMT_G(NW, CH, WPS, false, K); } while (0)
+  switch (shape) {
+    default: NGD_EMT_GP(8, 16, 4, true); break;
+    case 1: NGD_EMT_GP(4, 16, 2, false); break;
+    case 2: NGD_EMT_GP(8, 12, 4, false); break;
+    case 3: NGD_EMT_GP(4, 12, 2, false); break;
+    case 4: NGD_EMT_GP(8, 16, 4, false); break;
+  }
+#undef NGD_EMT_GP
+#undef NGD_EMT_G
 }
 
 // rb (4 or 8) matrices in one pass of the packed form; d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]

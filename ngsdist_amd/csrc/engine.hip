@@ -2734,11 +2734,14 @@ int ngd_run_mult_batch_dist(ngd_engine *e, const uint32_t *mult, uint32_t n_rep,
 // A window's matrix is what ngd_run() gives on a data set cut down to its sites.  Two plans:
 //  * per window: the weighted pass ngd_run_mult() makes with multiplicity 1 on the window's sites and 0 elsewhere (the MFMA
 //    kernel walks only the window's k-groups); serves every kernel;
-//  * segment slab (MFMA kernel, both operands resident or the one congruent image): the segments of a batch of windows --
-//    the elementary intervals between consecutive distinct window boundaries that some window covers -- are the slices of
-//    ONE accumulation pass (a slice table: each slice its own k-group range and 0/1 edge masks), their partial results
-//    [segment][n_pad][n_pad] are added into the windows by the banded reduction (reduce.hip k_reduce_band), counts under
-//    --pairwise_del from per-segment popcounts the same way.
+//  * segment slab (MFMA kernel, both operands resident or the one congruent image; the table-driven EM kernel): the segments
+//    of a batch of windows -- the elementary intervals between consecutive distinct window boundaries that some window
+//    covers -- are the slices of ONE accumulation pass (a slice table: each slice its own k-group range and 0/1 edge masks
+//    for the MFMA kernel, its own site range for the EM kernel, which walks single sites and needs neither), their partial
+//    results [segment][n_pad][n_pad] are added into the windows by the banded reduction (reduce.hip k_reduce_band), counts
+//    under --pairwise_del from per-segment popcounts the same way.  The EM of a (pair, site) runs on that site of the two
+//    individuals alone, so a term does not depend on the window it is added to.  A long EM segment is cut into pieces (more
+//    slices of the same table) so that the launch has about as many workgroups as a plain pass.
 
 static int windows_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const char *who) {
   if (!e) return fail(NGD_E_INVALID, std::string(who) + ": null engine");
@@ -2844,12 +2847,17 @@ static int windows_fixup(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, 
   return NGD_OK;
 }
 
-static bool windows_slab_applies(const ngd_engine *e) { return e->kernel == NGD_KERNEL_MFMA && !e->single_image; }
+// (the EM kernel's slice-table form exists for every workgroup shape: ngd_config.variant does not matter here)
+static bool windows_slab_applies(const ngd_engine *e) {
+  return (e->kernel == NGD_KERNEL_MFMA && !e->single_image) || e->kernel == NGD_KERNEL_EM_TABLE;
+}
 
 // bytes of one batch of the segment-slab plan: partial results (slices padded to the XCD deal's eights), counts, slice
-// weights and tables
+// weights and tables.  The EM kernel: a plane per segment, counts, tables -- no k-group weights, no padding slices.
 static uint64_t windows_batch_bytes(const ngd_engine *e, uint64_t n_seg, uint64_t span, uint64_t n_win) {
   const uint64_t plane = (uint64_t)e->g.n_pad * e->g.n_pad, n_ks = (n_seg + 7) / 8 * 8;
+  if (e->kernel == NGD_KERNEL_EM_TABLE)
+    return n_seg * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + n_seg * NGD_SEG_STRIDE * 8 + n_win * 16;
   const uint64_t wkg = 3 * span / 4 + n_ks * (3 + NGD_KG_TAIL) + 1 + NGD_KG_TAIL;
   return n_ks * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + wkg * 32 + n_ks * NGD_SEG_STRIDE * 8 + n_win * 16;
 }
@@ -2861,6 +2869,7 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   const uint64_t n_pairs = ngd_n_pairs(g.n_ind), plane = (uint64_t)g.n_pad * g.n_pad;
   const bool pdel = e->cfg.pairwise_del != 0;
   const bool fix = e->SM != nullptr;
+  const bool em = e->kernel == NGD_KERNEL_EM_TABLE;
   *fits = true;
   for (uint64_t w = 0; w < n_win; w++)
     if (windows_batch_bytes(e, 1, hi[w] - lo[w], 1) > budget) {
@@ -2891,42 +2900,67 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     // interval k = [x[k], x[k + 1]) is a segment if some window of the batch covers it
     std::vector<int64_t> cover(x.size(), 0);
     for (uint64_t w = a; w < b; w++) { cover[at(lo[w])]++; cover[at(hi[w])]--; }
-    std::vector<uint32_t> seg_of(x.size(), 0);
+    // EM kernel: an interval's slices are pieces of at most `piece` sites -- the covered sites over the slices of a plain
+    // pass, 64 sites or more (ngd_create's bound) -- unless the planes of the pieces would not fit the budget
+    uint64_t piece = ~0ull;
+    if (em) {
+      uint64_t covered = 0, n_cov = 0, n_cut = 0;
+      int64_t run = 0;
+      for (uint64_t k = 0; k + 1 < x.size(); k++)
+        if ((run += cover[k]) > 0) { covered += x[k + 1] - x[k]; n_cov++; }
+      piece = std::max<uint64_t>(64, (covered + e->n_ks - 1) / std::max<uint32_t>(1, e->n_ks));
+      run = 0;
+      for (uint64_t k = 0; k + 1 < x.size(); k++)
+        if ((run += cover[k]) > 0) n_cut += (x[k + 1] - x[k] - 1) / piece + 1;
+      if (n_cut > n_cov && (windows_batch_bytes(e, n_cut, hi_max - lo[a], nb) > budget || n_cut >= (1ull << 30))) piece = ~0ull;
+    }
+    std::vector<uint32_t> seg_of(x.size(), 0), seg_end(x.size(), 0);  // interval k = slices [seg_of[k], seg_end[k])
     std::vector<uint64_t> tab;
     uint64_t n_seg = 0, wkg = 0, max_wkg = 0;
     int64_t run = 0;
     for (uint64_t k = 0; k + 1 < x.size(); k++) {
       run += cover[k];
-      seg_of[k] = (uint32_t)n_seg;
+      seg_of[k] = seg_end[k] = (uint32_t)n_seg;
       if (run <= 0) continue;
-      const uint64_t kg0 = 3 * x[k] / 4, kg1 = (3 * x[k + 1] + 3) / 4, n_wkg = kg1 - kg0 + 1 + NGD_KG_TAIL;
-      tab.insert(tab.end(), {kg0, kg1, wkg, x[k], x[k + 1]});
-      wkg += n_wkg;
-      max_wkg = std::max(max_wkg, n_wkg);
-      n_seg++;
+      if (em) {  // (the k-group entries are the MFMA kernel's: not read)
+        const uint64_t len = x[k + 1] - x[k], n_p = len <= piece ? 1 : (len - 1) / piece + 1, per = (len + n_p - 1) / n_p;
+        for (uint64_t s = x[k]; s < x[k + 1]; s += per, n_seg++) tab.insert(tab.end(), {0, 0, 0, s, std::min(s + per, x[k + 1])});
+      } else {
+        const uint64_t kg0 = 3 * x[k] / 4, kg1 = (3 * x[k + 1] + 3) / 4, n_wkg = kg1 - kg0 + 1 + NGD_KG_TAIL;
+        tab.insert(tab.end(), {kg0, kg1, wkg, x[k], x[k + 1]});
+        wkg += n_wkg;
+        max_wkg = std::max(max_wkg, n_wkg);
+        n_seg++;
+      }
+      seg_end[k] = (uint32_t)n_seg;
     }
-    const uint64_t n_ks = (n_seg + 7) / 8 * 8;  // (the XCD deal of accum_mfma.hip; padding slices have no k-group and no sites)
+    // (the XCD deal of accum_mfma.hip; padding slices have no k-group and no sites.  The EM launch needs none.)
+    const uint64_t n_ks = em ? n_seg : (n_seg + 7) / 8 * 8;
     for (uint64_t q = n_seg; q < n_ks; q++) tab.insert(tab.end(), {0, 0, wkg, 0, 0});
     const uint64_t w_total = wkg + 1 + NGD_KG_TAIL;
     std::vector<unsigned long long> wt(2 * nb);
     for (uint64_t w = a; w < b; w++) {
-      const uint64_t f = seg_of[at(lo[w])], l = seg_of[at(hi[w]) - 1] + 1;
+      const uint64_t f = seg_of[at(lo[w])], l = seg_end[at(hi[w]) - 1];
       wt[2 * (w - a)] = f | (l << 32);
       wt[2 * (w - a) + 1] = hi[w] - lo[w];
     }
     int rc = ensure_cap(e, &e->slab_boot, &e->slab_boot_elems, n_ks * plane);
     if (!rc && pdel) rc = ensure_cap(e, &e->cnt_boot, &e->cnt_boot_elems, n_seg * plane);
-    if (!rc) rc = ensure_cap(e, &e->d_wslice, &e->cap_wslice, w_total * 4);
+    if (!rc && !em) rc = ensure_cap(e, &e->d_wslice, &e->cap_wslice, w_total * 4);
     if (!rc) rc = ensure_cap(e, &e->d_segtab, &e->cap_segtab, tab.size());
     if (!rc) rc = ensure_cap(e, &e->d_wintab, &e->cap_wintab, wt.size());
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev[0], e->st));
     HIPCHK(hipMemcpyAsync(e->d_segtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, e->st));
     HIPCHK(hipMemcpyAsync(e->d_wintab, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, e->st));
-    ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->d_wslice);
+    if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->d_wslice);
     HIPCHK(hipEventRecord(e->ev[1], e->st));
-    ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB, e->d_wslice, nullptr, e->d_jobs, e->n_wg, e->exact_shapes,
-                          e->wg_waves, (uint32_t)n_ks, 0, g.n_kg, 0, 1, e->slab_boot, e->d_clk, 0, 0, e->d_segtab);
+    if (em)
+      ngd_launch_accum_em_table_segs(e->st, g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64,
+                                     (uint32_t)n_seg, e->d_segtab, e->slab_boot, e->d_emcnt);
+    else
+      ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB, e->d_wslice, nullptr, e->d_jobs, e->n_wg, e->exact_shapes,
+                            e->wg_waves, (uint32_t)n_ks, 0, g.n_kg, 0, 1, e->slab_boot, e->d_clk, 0, 0, e->d_segtab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[2], e->st));
     double *bs = d_sum + a * n_pairs;
@@ -2972,7 +3006,7 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   const bool slab_ok = windows_slab_applies(e);
   if (e->opt_win_plan == 2 && !slab_ok)
     return fail(NGD_E_INVALID, "ngd_run_windows: the segment-slab plan needs the MFMA kernel with both operand images resident "
-                               "or the one congruent image (NGD_OPT_WIN_PLAN = 2)");
+                               "or the one congruent image, or the table-driven EM kernel (NGD_OPT_WIN_PLAN = 2)");
   bool slab = slab_ok && e->opt_win_plan != 1;
   uint64_t budget = e->opt_win_max_bytes;
   if (slab && !budget) {  // the rule of the bootstrap's per-block partial results
@@ -2983,7 +3017,8 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   if (slab && e->opt_win_plan == 0) {
     // auto: the cheaper plan by estimate (the rates partials_impl uses) -- one pass over the sites the
     // windows cover + the banded reduction's reads and writes + allocating a larger slab, against one weighted pass per
-    // window (~3/4 of a plain pass over its sites, + ~0.1 ms of launches and waits)
+    // window (~3/4 of a plain pass over its sites -- [measured] the EM kernel: 0.72, 37 windows of 10 000 sites in 1159 ms at
+    // 1000 individuals, the sites before a window loaded and skipped -- + ~0.1 ms of launches and waits)
     uint64_t covered = 0, sum_len = 0, end = 0;
     std::vector<uint64_t> bnd(lo, lo + n_win);
     bnd.insert(bnd.end(), hi, hi + n_win);
@@ -2993,7 +3028,10 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       sum_len += hi[w] - lo[w];
       if (hi[w] > end) { covered += hi[w] - std::max(lo[w], end); end = hi[w]; }
     }
-    const double rate = 1.05e10, np = (double)e->n_owned_pairs;  // pair-sites per ms
+    const bool em = e->kernel == NGD_KERNEL_EM_TABLE;
+    // pair-sites per ms: K1m; the table-driven EM kernel's slice-table form ([measured] tools/bench_windows.py, 1000 x 1e5,
+    // 160 slices: 224.8 ms -- DESIGN.md section 6; the plain pass's 2.22e8)
+    const double rate = em ? 2.22e8 : 1.05e10, np = (double)e->n_owned_pairs;
     const double plane_b = (double)e->g.n_pad * e->g.n_pad * 8;
     const double need = (double)windows_batch_bytes(e, std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win);
     const double have = (double)e->slab_boot_elems * 8 + (double)e->cnt_boot_elems * 4;

@@ -67,6 +67,7 @@
 // The engine's windowed entry point is referred to weakly: a host linked against an engine without it (a stub) still
 // links, and --win_size then fails with a message.  ngd_window_ranges (host_util.cpp) is always there.
 #pragma weak ngd_run_windows_dist
+#pragma weak ngd_last_windows
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
 static const double kInf = 1e15;          // INF, gen_func.hpp:15
@@ -1482,6 +1483,11 @@ int main(int argc, char **argv) {
       const int rc = ngd_run_windows_dist(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, wd.data());
       if (rc) die_engine("ngd_run_windows_dist", rc);
       report_fixup(eng.h, p.verbose);
+      ngd_windows_info wi;
+      if (p.verbose >= 2 && ngd_last_windows && ngd_last_windows(eng.h, &wi) == NGD_OK)  // the plan the engine took
+        fprintf(stderr, "> windows %lu to %lu: %lu segments in %lu batches of one pass each, %lu windows by a pass of their own (%.2f ms)\n",
+                (unsigned long)w0, (unsigned long)(w0 + n - 1), (unsigned long)wi.segments, (unsigned long)wi.batches,
+                (unsigned long)wi.windows_by_pass, wi.ms);
       t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
       for (uint64_t k = 0; k < n; k++) {
         const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";

@@ -130,7 +130,8 @@ void ngd_launch_accum_stream(hipStream_t st, const ngd_geom &g, const double *PI
 
 // Windows along the genome (engine.hip windows_slab): a slice table entry per segment of sites [s_lo, s_hi) --
 // k-groups [kg0, kg1) = [3 s_lo / 4, ceil(3 s_hi / 4)), its 0/1 weights (d3[k % 3] inside the segment, 0 outside) at k-group
-// woff of the weight array, kg1 - kg0 + 1 + NGD_KG_TAIL k-groups of them (the operand pipeline's run-ahead reads past kg1)
+// woff of the weight array, kg1 - kg0 + 1 + NGD_KG_TAIL k-groups of them (the operand pipeline's run-ahead reads past kg1).
+// The table-driven EM kernel and k_count_blocks read s_lo / s_hi alone (an EM engine's table leaves the other entries 0).
 #define NGD_SEG_STRIDE 5
 #define NGD_SEG_KG0 0
 #define NGD_SEG_KG1 1
@@ -166,6 +167,12 @@ void ngd_launch_accum_em_table(hipStream_t st, const ngd_geom &g, const double *
                                uint64_t n_sites_eff, const ngd_score &score, int pairwise_del, int shape,
                                const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice,
                                double *slab, unsigned long long *d_counters /* [4]: += (tile, site) visits, table rounds; [2..3] = clock counters */);
+
+// accum_em_table.hip, windows along the genome: slice ks = sites [s_lo, s_hi) of entry ks of the slice table (NGD_SEG_SLO /
+// NGD_SEG_SHI; any length from 1, any first site, all below g.n_sites), slab [n_seg][n_pad][n_pad]; every `shape` has the form
+void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,
+                                    int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_seg,
+                                    const uint64_t *d_seg, double *slab, unsigned long long *d_counters);
 
 // accum_em_table.hip, rb (4 or 8) matrices in one pass: d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]
 void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_geom &g, const double *PA, const double *d_Wb, int rb,
