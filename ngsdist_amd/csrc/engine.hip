@@ -22,119 +22,114 @@
 #include <thread>
 #include <vector>
 
+#include "ngd_buffers.h"
 #include "ngd_internal.h"
 #include "ngd_shard.h"
 
-static thread_local std::string g_err;
 
-static int fail(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
+// The per-block partial results of a bootstrap job (sums [slices][n_pad][n_pad]; counts [n_blocks][n_pad][n_pad] under
+// --pairwise_del; 0/1 weights per slice where blocks are not whole k-groups), cached from job to job -- and the scratch of
+// the EM batch pass, the spilled-terms plan and the windows' segment slab.  A borrower takes the memory through borrow_*(),
+// which drops that cache's key; only partials_impl, having filled it, names it again.
+struct BlockScratch {
+  DevBuf<double> wslice;
+  // the geometry of the cached sums: slices of per_slice k-groups (sites), `sub` to a block
+  uint64_t per_slice = 0;
+  uint32_t nks = 0, sub = 0;
+  bool has_sums(uint64_t B, uint64_t blocks) const { return boot_B == B && boot_blocks == blocks; }
+  bool has_counts(uint64_t B, uint64_t blocks) const { return cnt_B == B && cnt_blocks == blocks; }
+  uint64_t sums_block() const { return boot_B; }
+  const DevBuf<double> &sums() const { return slab_boot; }
+  const DevBuf<uint32_t> &counts() const { return cnt_boot; }
+  DevBuf<double> &borrow_sums() { boot_B = boot_blocks = 0; return slab_boot; }
+  DevBuf<uint32_t> &borrow_counts() { cnt_B = cnt_blocks = 0; return cnt_boot; }
+  void sums_filled(uint64_t B, uint64_t blocks) { boot_B = B; boot_blocks = blocks; }
+  void counts_filled(uint64_t B, uint64_t blocks) { cnt_B = B; cnt_blocks = blocks; }
+  void drop() { boot_B = boot_blocks = cnt_B = cnt_blocks = 0; }
+  uint64_t bytes() const { return slab_boot.bytes() + cnt_boot.bytes(); }  // what a budget rule already holds
 
-// A failed HIP call also leaves its code behind as the thread's "last error"; it is reported HERE, once, and cleared, so
-// that the hipGetLastError() after a later, unrelated kernel launch does not report it a second time (found by
-// tests/test_gpu_abi_misuse.py: an engine too large for the device poisoned the next engine's first launch).
-#define HIPCHK(call)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (call);                                                                \
-    if (_e != hipSuccess) {                                                                \
-      (void)hipGetLastError();                                                             \
-      return fail(_e == hipErrorOutOfMemory ? NGD_E_NOMEM : NGD_E_HIP,                     \
-                  std::string(#call) + ": " + hipGetErrorString(_e));                      \
-    }                                                                                      \
-  } while (0)
+ private:
+  DevBuf<double> slab_boot;
+  DevBuf<uint32_t> cnt_boot;
+  uint64_t boot_B = 0, boot_blocks = 0, cnt_B = 0, cnt_blocks = 0;  // block size and blocks of what is cached (0: nothing)
+};
 
-struct ngd_engine {
+// (device, st, dev_bytes and the piece ranges: ngd_mem, ngd_buffers.h)
+struct ngd_engine : ngd_mem {
   ngd_config cfg{};
   ngd_geom g{};
   ngd_score sc{};
-  int device = 0;
   int kernel = 0;  // resolved NGD_KERNEL_*
-  hipStream_t st = nullptr;
   hipEvent_t ev[5] = {};
   // resident data set
-  double *PA = nullptr, *QB = nullptr, *PI = nullptr;
+  DevBuf<double> PA, QB, PI;
   // ngd_config.single_image (MFMA kernel): QB is not resident; a launch forms it for a range of k-groups at a time
   bool single_image = false;    // (ngd_config.single_image = 1: q is formed range by range)
   bool congruent = false;       // ngd_config.single_image = 2: the image holds t (sc.c, sc.d), read for both operands
-  double *d_wD = nullptr;       // ... and these are the weights of a plain pass: sc.d[k % 3] per contraction index
+  DevBuf<double> d_wD;          // ... and these are the weights of a plain pass: sc.d[k % 3] per contraction index
   // ... and, for the reference's matrices (sc.fix), the fix-up pass of the pairs its arithmetic cannot hold to 1e-9
   // relative (fixup.hip): SM[site][individual] = min(p0, p2) beside the image, the pairs a reduction noted, scratch
-  double *SM = nullptr;
-  unsigned long long *d_fixlist = nullptr;
-  uint32_t *d_fixcount = nullptr, *d_fixseen = nullptr, *h_fixcount = nullptr;
-  double *d_fixparts = nullptr, *d_fixthr = nullptr;
-  uint64_t cap_fixthr = 0;
-  ngd_fix_tile *d_fixtiles = nullptr;  // 16 x 16 tiles of pairs that hold several noted pairs (fixup_pass)
-  double *d_fixtparts = nullptr;       // ... and their per-slice partial sums
-  uint64_t cap_fixtiles = 0, cap_fixtparts = 0;
-  double *fix_p = nullptr, *fix_q = nullptr, *d_fixnew = nullptr;  // the fix-up pass as a whole two-operand pass (fixup_by_pass)
-  uint64_t cap_fix_p = 0, cap_fix_q = 0, cap_fixnew = 0;
+  DevBuf<double> SM;
+  DevBuf<unsigned long long> d_fixlist;
+  DevBuf<uint32_t> d_fixcount, d_fixseen;
+  PinBuf<uint32_t> h_fixcount;
+  DevBuf<double> d_fixparts, d_fixthr;
+  DevBuf<ngd_fix_tile> d_fixtiles;  // 16 x 16 tiles of pairs that hold several noted pairs (fixup_pass)
+  DevBuf<double> d_fixtparts;       // ... and their per-slice partial sums
+  DevBuf<double> fix_p, fix_q, d_fixnew;  // the fix-up pass as a whole two-operand pass (fixup_by_pass)
   ngd_fixup_info fix_info{};
   std::vector<ngd_tile> h_tiles16;  // host copy of the owned 16 x 16 tiles that hold a pair (the fix-up pass's "every pair")
   uint32_t fix_cap = 0;  // pairs the reductions can note for the fix-up pass (ngd_internal.h NGD_FIX_LIST): the capacity of d_fixlist
   uint64_t opt_fix_work = 0;  // NGD_OPT_FIXUP_WORK: the pass's budget in pair-sites (0 = none: every noted pair is recomputed)
-  double *QB_res = nullptr;     // ... except its first qb_res_kg k-groups (ngd_config.second_image_mib), formed at ngd_commit()
+  DevBuf<double> QB_res;        // ... except its first qb_res_kg k-groups (ngd_config.second_image_mib), formed at ngd_commit()
   uint64_t qb_res_kg = 0;
-  double *qb_chunk = nullptr;
+  DevBuf<double> qb_chunk;      // the scratch a range is formed in
   uint64_t qb_chunk_kg = 0;     // k-groups a range may span (NGD_OPT_SINGLE_IMAGE_BYTES)
-  uint64_t qb_chunk_elems = 0;  // capacity of the scratch
-  unsigned long long *mask = nullptr, *planes = nullptr;
+  DevBuf<unsigned long long> mask, planes;
   // bootstrap
-  uint32_t *d_mult = nullptr, *d_ws = nullptr;
-  double *d_wk = nullptr;  // multiplicity per contraction index k, as a double (MFMA kernel)
-  uint32_t *d_kgl = nullptr, *d_kgcnt = nullptr;  // k-groups a replicate visits (list + compaction scratch)
-  uint32_t *h_mult = nullptr;                      // pinned: multiplicities counted from block maps
-  uint64_t cap_h_mult = 0;
-  uint64_t cap_blocks = 0;
+  DevBuf<uint32_t> d_mult, d_ws;
+  DevBuf<double> d_wk;  // multiplicity per contraction index k, as a double (MFMA kernel)
+  DevBuf<uint32_t> d_kgl, d_kgcnt;  // k-groups a replicate visits (list + compaction scratch)
+  PinBuf<uint32_t> h_mult;          // multiplicities counted from block maps
   // shard
-  ngd_tile *d_tiles = nullptr, *d_tiles16 = nullptr, *d_tiles64 = nullptr;
+  DevBuf<ngd_tile> d_tiles, d_tiles16, d_tiles64;
   uint32_t n_tiles = 0, n_tiles16 = 0, n_tiles64 = 0;
   int em_shape = 0;  // accum_em_table.hip: workgroup shape
-  unsigned long long *d_emcnt = nullptr;  // [4] work counters of the table-driven EM kernel + its clock counters
+  DevBuf<unsigned long long> d_emcnt;  // [4] work counters of the table-driven EM kernel + its clock counters
   unsigned long long em_counts[2] = {0, 0};  // ... of the last run
   // [2] MFMA kernel: shader-cycle / constant-rate counter deltas of one wavefront.  Pinned HOST memory mapped into the
   // device's address space: the wavefront's two stores cross PCIe, and reading them after the stream has been waited for
   // is a plain load (a 16-byte hipMemcpy per pass was 10 us of a 350 us job at cfg 2)
-  unsigned long long *d_clk = nullptr, *h_clk = nullptr;  // (the device's and the host's pointer to it)
+  PinBuf<unsigned long long> h_clk;
+  unsigned long long *d_clk = nullptr;  // (the device's pointer to it)
   double clk_mhz = 0;                   // shader clock of the last accumulation launch (0: not sampled)
   double wall_khz = 100000.0;           // rate of the constant counter (hipDeviceAttributeWallClockRate)
   // MFMA kernel: per-wavefront 64x64 jobs, 4 per workgroup; "tri" = blocks on the diagonal
-  ngd_job *d_jobs = nullptr;
+  DevBuf<ngd_job> d_jobs;
   uint32_t n_wg = 0;
   uint32_t wg_waves = 4;  // wavefronts (jobs) per workgroup of the MFMA kernel
   int exact_shapes = 0;  // small n_ind: one code path per block shape (accum_mfma.hip EXACT): 1 = blocks of 4 x 4 tiles, 2 = 2 x 4
   bool tri_diag = false;  // full 4 x 4 blocks (exact_shapes == 0) whose DIAGONAL blocks leave their lower triangle out
-  uint64_t *d_pairs = nullptr;
+  DevBuf<uint64_t> d_pairs;
   uint64_t n_owned_pairs = 0;
   // scratch + results
-  double *slab = nullptr;
+  DevBuf<double> slab;
   uint32_t n_ks = 0;
   uint64_t per_slice = 0;
-  double *d_sum = nullptr;
-  unsigned long long *d_cnt = nullptr;
-  // bootstrap by per-block partial sums (valid while boot_B != 0)
-  double *slab_boot = nullptr;
-  uint64_t boot_B = 0, boot_blocks = 0, boot_per_slice = 0, slab_boot_elems = 0;
-  uint32_t boot_nks = 0, boot_sub = 0;
+  DevBuf<double> d_sum;
+  DevBuf<unsigned long long> d_cnt;
+  BlockScratch blk;  // bootstrap by per-block partial sums, and the scratch the other plans borrow
   // a large slab costs ~12 ms per GB to allocate: until the passes it would have saved add up to that, calls are
   // served without it (rent_ms = their estimated cost so far, for the geometry rent_B / rent_blocks)
   double rent_ms = 0;
   uint64_t rent_B = 0, rent_blocks = 0;
-  double *d_wslice = nullptr;    // 0/1 weights per slice, bootstrap blocks that are not whole k-groups
-  uint64_t cap_wslice = 0;
-  uint32_t *cnt_boot = nullptr;  // per-block valid-site counts [n_blocks][n_pad][n_pad] (--pairwise_del)
-  uint64_t cnt_B = 0, cnt_blocks = 0, cnt_boot_elems = 0;
   // per-call bootstrap weights (slice-major doubles / block-major uint32) and per-replicate site totals
-  double *d_W = nullptr;
-  uint32_t *d_M = nullptr;
-  unsigned long long *d_drawn = nullptr;
-  uint64_t cap_W = 0, cap_M = 0, cap_drawn = 0;
+  DevBuf<double> d_W;
+  DevBuf<uint32_t> d_M;
+  DevBuf<unsigned long long> d_drawn;
   // batch results for the host-pointer entry points
-  double *d_bsum = nullptr;
-  unsigned long long *d_bcnt = nullptr;
-  uint64_t cap_batch = 0;
+  DevBuf<double> d_bsum;
+  DevBuf<unsigned long long> d_bcnt;
   uint32_t n_batch_valid = 0;  // matrices of the last batch / job call, still in d_bsum / d_bcnt (ngd_fetch_matrix)
   // ngd_run_job_dist / ngd_run_mult_batch_dist: the matrices of d_bsum / d_bcnt leave the device in chunks on a stream
   // of their own -- in the per-block-partials plan a group of replicates as soon as its reduction is over, beside the
@@ -144,9 +139,8 @@ struct ngd_engine {
     bool on = false, pdel = false;
     hipStream_t st = nullptr, st2 = nullptr;  // chunks alternate between two copy streams
     uint32_t n_chunk_seq = 0, n_landed = 0;    // chunks queued / declared landed so far in this call
-    double *h_sum = nullptr;
-    uint64_t *h_cnt = nullptr;
-    uint64_t cap_sum = 0, cap_cnt = 0;       // cells
+    PinBuf<double> h_sum;
+    PinBuf<uint64_t> h_cnt;
     uint32_t n_mat = 0, queued = 0;          // matrices of this call; matrices [0, queued) have their copies on st
     std::vector<hipEvent_t> pool;            // events, made on demand and kept
     uint32_t n_used = 0;
@@ -159,11 +153,12 @@ struct ngd_engine {
     int finisher_rc = 0;
     double t0 = 0, t_call = 0;  // NGD_TRACE_OUT
   } out;
-  double *staging = nullptr;
+  DevBuf<double> staging;
   uint64_t staging_sites = 0;
-  // raw-input pipeline: a ring of pinned host buffers, each with its device buffer; the copies run on a stream of
-  // their own (the copy engine never waits for a preparation kernel), K0 follows each on the engine's stream
+  // raw-input pipeline: a ring of slots (RingSlot: a pinned host buffer, its device buffer, two events); the copies run on
+  // a stream of their own (the copy engine never waits for a preparation kernel), K0 follows each on the engine's stream
   static constexpr int RING = 8;
+  RingSlot ring[RING];
   uint64_t opt_stage_piece_mib = 32, opt_stage_ring = 6;  // NGD_OPT_STAGE_PIECE_MIB, NGD_OPT_STAGE_RING
   // NGD_OPT_EAGER_FULL: the plain full-data pass starts DURING a staged load -- whenever enough leading slices of the site
   // axis have all their sites prepared, they are accumulated on a low-priority stream of their own beside the copies and
@@ -175,9 +170,6 @@ struct ngd_engine {
   bool stage_in_order = true;
   uint32_t eager_slices = 0;   // slices [0, eager_slices) of the plain pass have been launched on st_eager
   bool eager_valid = false;
-  double *pin[RING] = {}, *draw[RING] = {};
-  hipEvent_t pin_free[RING] = {};  // the copy out of pin[b] is done: the caller may fill it again
-  hipEvent_t k0_done[RING] = {};   // K0 has read draw[b]: the next copy may overwrite it
   hipStream_t st_copy[2] = {nullptr, nullptr};
   uint64_t n_staged = 0;
   int ring_slots = 0;
@@ -190,22 +182,9 @@ struct ngd_engine {
   int ring_maker_rc = 0;
   int pin_cur = 0, pin_lent = -1;
   uint64_t pin_sites = 0;
-  int *d_nan = nullptr;
+  DevBuf<int> d_nan;
   bool committed = false;
-  uint64_t dev_bytes = 0;
-  // Images and slabs of a GiB and more: an address range reserved at once, its physical memory created, mapped and
-  // zeroed 256 MiB at a time by a thread of the engine's own (dev_alloc_pieces, piece_worker) -- the staged load starts at
-  // once and waits, piece by piece, only for the part of an image it is about to write (piece_wait_sites).
-  enum PieceKind { PIECE_FRAG, PIECE_SITE_MAJOR, PIECE_WHOLE };  // how far into the range a site reaches
-  struct PieceRange {
-    void *va = nullptr;
-    size_t size = 0, ready = 0, n_mapped = 0;  // ready: bytes from the start that are mapped (and zeroed), under piece_mu
-    bool zero = false;
-    PieceKind kind = PIECE_WHOLE;
-    uint64_t bytes_per_site = 0;  // PIECE_SITE_MAJOR
-    std::vector<hipMemGenericAllocationHandle_t> hs;
-  };
-  std::vector<std::unique_ptr<PieceRange>> piece_ranges;
+  // the thread that maps the piece ranges (ngd_buffers.h PieceRange; dev_alloc_pieces, piece_worker)
   std::thread piece_thread;
   std::mutex piece_mu;
   std::condition_variable piece_cv;
@@ -220,41 +199,22 @@ struct ngd_engine {
   // again (0: nothing has failed) -- until ngd_drop_caches(), or until a smaller request (fewer matrices per pass) comes
   uint64_t em_batch_nofit_elems = 0;
   // EM bootstrap by spilled terms + one MFMA contraction (contract_mfma.hip): running sums and per-chunk NaN flags
-  double *d_D = nullptr;
-  unsigned long long *d_nanflag = nullptr;
-  uint64_t cap_D = 0, cap_nanflag = 0;
+  DevBuf<double> d_D;
+  DevBuf<unsigned long long> d_nanflag;
   // ... its pair slots: groups of 16 consecutive columns of one row of a 64 x 64 tile, dealt to the groups that hold a
   // pair only; d_rowpg[tile * 64 + row] + g = slot group of the row's column group g (a signed 32-bit number: the first live
   // group's slot group minus that group's index), n_pg_spill = their number (+ padding to 4)
-  uint32_t *d_rowpg = nullptr;
+  DevBuf<uint32_t> d_rowpg;
   uint32_t n_pg_spill = 0, n_pg_live = 0;
   std::vector<hipEvent_t> ev_spill;  // per chunk: before the weights, the EM pass, the sanitiser, the contraction; + one at the end
   ngd_spill_timing spill_timing{};
   // windows along the genome (ngd_run_windows*): the segment-slab plan's slice table and window table (its partial
-  // results, counts and slice weights take slab_boot, cnt_boot and d_wslice, whose bootstrap cache a windowed call drops)
-  uint64_t *d_segtab = nullptr;
-  unsigned long long *d_wintab = nullptr;
-  uint64_t cap_segtab = 0, cap_wintab = 0;
+  // results, counts and slice weights borrow blk)
+  DevBuf<uint64_t> d_segtab;
+  DevBuf<unsigned long long> d_wintab;
   uint64_t opt_win_plan = 0, opt_win_max_bytes = 0;  // NGD_OPT_WIN_PLAN, NGD_OPT_WIN_MAX_BYTES
   ngd_windows_info win_info{};
 };
-
-template <typename T>
-static int dev_alloc(ngd_engine *e, T **p, uint64_t count, bool zero) {
-  *p = nullptr;
-  if (!count) return NGD_OK;
-  // NGD_TRACE_ALLOC=1: what every allocation of 64 MiB and more costs (the driver clears memory other processes have used
-  // as it hands it out: seconds for tens of GB on a device that has just been busy, DESIGN.md section 3 "K0")
-  static const bool trace = getenv("NGD_TRACE_ALLOC") != nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-  if (trace && count * sizeof(T) >= (64u << 20))
-    fprintf(stderr, "> alloc: hipMalloc of %.2f GB took %.3f s\n", (double)(count * sizeof(T)) / 1e9,
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-  e->dev_bytes += count * sizeof(T);
-  if (zero) HIPCHK(hipMemsetAsync(*p, 0, count * sizeof(T), e->st));
-  return NGD_OK;
-}
 
 // The operand images and slabs (a GiB and more): an address range reserved at once, physical pieces of 256 MiB created,
 // mapped and zeroed behind it by a thread of the engine's own, in the order a load needs them.
@@ -268,23 +228,11 @@ static int dev_alloc(ngd_engine *e, T **p, uint64_t count, bool zero) {
 // the first call that needs the memory (ngd_stage_submit / ngd_upload_* / ngd_commit: NGD_E_NOMEM).
 // (pieces of ONE size per range: hipMemSetAccess refuses a shorter last piece -- [measured] 1 GiB + 512 MiB: invalid
 // argument; 15 x 256 MiB: fine -- so a range is rounded up to whole pieces, at most 256 MiB more than asked for)
-static const size_t kPiece = (size_t)256 << 20;
-
-static void release_pieces(ngd_engine::PieceRange &r) {
-  for (size_t c = 0; c < r.n_mapped; c++) (void)hipMemUnmap((char *)r.va + c * kPiece, std::min(kPiece, r.size - c * kPiece));
-  for (auto &h : r.hs) (void)hipMemRelease(h);
-  if (r.va) (void)hipMemAddressFree(r.va, r.size);
-  r.hs.clear();
-  r.va = nullptr;
-  r.n_mapped = 0;
-}
-
 template <typename T>
-static int dev_alloc_pieces(ngd_engine *e, T **p, uint64_t count, bool zero, ngd_engine::PieceKind kind = ngd_engine::PIECE_WHOLE,
+static int dev_alloc_pieces(ngd_engine *e, DevBuf<T> &buf, uint64_t count, bool zero, PieceKind kind = PIECE_WHOLE,
                             uint64_t bytes_per_site = 0) {
-  *p = nullptr;
   const uint64_t bytes = count * sizeof(T);
-  if (bytes < ((uint64_t)512 << 20)) return dev_alloc(e, p, count, zero);
+  if (bytes < ((uint64_t)512 << 20)) return buf.alloc(e, count, zero);
   hipMemAllocationProp prop = {};
   prop.type = hipMemAllocationTypePinned;
   prop.location.type = hipMemLocationTypeDevice;
@@ -292,21 +240,21 @@ static int dev_alloc_pieces(ngd_engine *e, T **p, uint64_t count, bool zero, ngd
   size_t gran = 0;
   if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !gran) {
     (void)hipGetLastError();
-    return dev_alloc(e, p, count, zero);
+    return buf.alloc(e, count, zero);
   }
-  if (kPiece % gran) return dev_alloc(e, p, count, zero);
-  std::unique_ptr<ngd_engine::PieceRange> r(new ngd_engine::PieceRange());
+  if (kPiece % gran) return buf.alloc(e, count, zero);
+  std::unique_ptr<PieceRange> r(new PieceRange());
   r->size = (size_t)((bytes + kPiece - 1) / kPiece * kPiece);
   r->zero = zero;
   r->kind = kind;
   r->bytes_per_site = bytes_per_site;
   if (hipMemAddressReserve(&r->va, r->size, 0, nullptr, 0) != hipSuccess) {
     (void)hipGetLastError();
-    return dev_alloc(e, p, count, zero);
+    return buf.alloc(e, count, zero);
   }
-  *p = (T *)r->va;
+  if (int rc = buf.release()) return rc;
+  buf.adopt(e, r.get(), count);
   e->piece_ranges.push_back(std::move(r));
-  e->dev_bytes += bytes;
   return NGD_OK;
 }
 
@@ -337,11 +285,11 @@ static void piece_worker(ngd_engine *e) {
     if (!strcmp(hook, "1"))
       if (const char *k = getenv("NGD_TEST_FAIL_PIECE")) fail_at = atol(k);
   for (;;) {
-    ngd_engine::PieceRange *r = nullptr;
+    PieceRange *r = nullptr;
     for (int whole = 0; whole < 2 && !r; whole++) {
       double best = 2.0;
       for (auto &q : e->piece_ranges) {
-        if ((q->kind == ngd_engine::PIECE_WHOLE) != (whole == 1) || q->n_mapped * kPiece >= q->size) continue;
+        if ((q->kind == PIECE_WHOLE) != (whole == 1) || q->n_mapped * kPiece >= q->size) continue;
         const double f = (double)(q->n_mapped * kPiece) / (double)q->size;
         if (f < best) { best = f; r = q.get(); }
       }
@@ -398,33 +346,15 @@ static int piece_wait_sites(ngd_engine *e, uint64_t s_end) {
   for (auto &q : e->piece_ranges) {
     size_t need = q->size;
     if (s_end < e->g.n_sites) {
-      if (q->kind == ngd_engine::PIECE_FRAG) need = std::min<size_t>(q->size, ((3 * s_end + 3) / 4 + 1) * (size_t)e->g.n_ig * 512);
-      else if (q->kind == ngd_engine::PIECE_SITE_MAJOR) need = std::min<size_t>(q->size, (size_t)(s_end * q->bytes_per_site));
-      else if (q->va == (void *)e->slab) continue;  // (nothing of a load goes there)
-    } else if (q->va == (void *)e->slab) {
+      if (q->kind == PIECE_FRAG) need = std::min<size_t>(q->size, ((3 * s_end + 3) / 4 + 1) * (size_t)e->g.n_ig * 512);
+      else if (q->kind == PIECE_SITE_MAJOR) need = std::min<size_t>(q->size, (size_t)(s_end * q->bytes_per_site));
+      else if (q.get() == e->slab.range()) continue;  // (nothing of a load goes there)
+    } else if (q.get() == e->slab.range()) {
       continue;
     }
     e->piece_cv.wait(lk, [&] { return q->ready >= need || e->piece_done; });
     if (q->ready < need && e->piece_rc) return fail(e->piece_rc, e->piece_err.c_str());  // (what IS mapped serves its sites)
   }
-  return NGD_OK;
-}
-
-static bool in_pieces(const ngd_engine *e, const void *p) {
-  for (auto &r : e->piece_ranges)
-    if (r->va == p) return true;
-  return false;
-}
-
-// grow-only device scratch
-template <typename T>
-static int ensure_cap(ngd_engine *e, T **p, uint64_t *cap, uint64_t need) {
-  if (need <= *cap) return NGD_OK;
-  if (*p) { HIPCHK(hipFree(*p)); e->dev_bytes -= *cap * sizeof(T); }
-  *p = nullptr; *cap = 0;
-  int rc = dev_alloc(e, p, need, false);
-  if (rc) return rc;
-  *cap = need;
   return NGD_OK;
 }
 
@@ -474,50 +404,30 @@ uint64_t ngd_pair_index(uint64_t n_ind, uint64_t i1, uint64_t i2) { return ngd_p
 uint64_t ngd_device_bytes(const ngd_engine *e) { return e ? e->dev_bytes : 0; }
 
 static void stage_reap(ngd_engine *e);
-static void pin_release(double *p);
+static void ring_maker_join(ngd_engine *e);
 
+// What is about ORDER: every thread of the engine's joined and every stream idle; then the members go -- each buffer and
+// ring slot frees itself (ngd_buffers.h) --; then the streams and events they were used on.
 void ngd_destroy(ngd_engine *e) {
   if (!e) return;
   hipSetDevice(e->device);
   if (e->piece_thread.joinable()) e->piece_thread.join();
   if (e->st) hipStreamSynchronize(e->st);
   if (e->st_eager) hipStreamSynchronize(e->st_eager);  // (slices started beside a load and never asked for)
-  e->ring_stop = true;
-  if (e->ring_maker.joinable()) e->ring_maker.join();
+  ring_maker_join(e);
   stage_reap(e);
-  void *ptrs[] = {e->PA, e->QB, e->QB_res, e->qb_chunk, e->PI, e->mask, e->planes, e->d_mult, e->d_ws, e->d_wk, e->d_wD, e->d_kgl, e->d_kgcnt,
-                  e->d_tiles, e->d_tiles16, e->d_tiles64, e->d_pairs, e->d_jobs, e->slab, e->d_sum, e->d_cnt, e->staging, e->slab_boot,
-                  e->cnt_boot, e->d_W, e->d_M, e->d_drawn, e->d_bsum, e->d_bcnt, e->d_wslice, e->d_emcnt, e->d_D, e->d_nanflag,
-                  e->d_rowpg, e->SM, e->d_fixlist, e->d_fixcount, e->d_fixseen, e->d_fixparts, e->d_fixthr, e->d_fixtiles, e->d_fixtparts, e->fix_p, e->fix_q, e->d_fixnew,
-                  e->d_segtab, e->d_wintab};
-  for (void *p : ptrs)
-    if (p && !in_pieces(e, p)) hipFree(p);
-  for (auto &r : e->piece_ranges) release_pieces(*r);
-  for (int b = 0; b < ngd_engine::RING; b++) {
-    pin_release(e->pin[b]);
-    if (e->draw[b]) hipFree(e->draw[b]);
-    if (e->pin_free[b]) hipEventDestroy(e->pin_free[b]);
-    if (e->k0_done[b]) hipEventDestroy(e->k0_done[b]);
-  }
-  for (int c = 0; c < 2; c++)
-    if (e->st_copy[c]) hipStreamDestroy(e->st_copy[c]);
-  if (e->st_eager) hipStreamDestroy(e->st_eager);
-  if (e->ev_eager) hipEventDestroy(e->ev_eager);
-  if (e->out.st) { hipStreamSynchronize(e->out.st); hipStreamDestroy(e->out.st); }
-  if (e->out.st2) { hipStreamSynchronize(e->out.st2); hipStreamDestroy(e->out.st2); }
-  for (hipEvent_t v : e->out.pool) hipEventDestroy(v);
-  if (e->out.h_sum) hipHostFree(e->out.h_sum);
-  if (e->out.h_cnt) hipHostFree(e->out.h_cnt);
-  if (e->h_clk) hipHostFree(e->h_clk);
-  if (e->h_fixcount) hipHostFree(e->h_fixcount);
-  if (e->d_nan) hipFree(e->d_nan);
-  if (e->h_mult) hipHostFree(e->h_mult);
-  for (auto &v : e->ev)
-    if (v) hipEventDestroy(v);
-  for (auto &v : e->ev_spill)
-    if (v) hipEventDestroy(v);
-  if (e->st) hipStreamDestroy(e->st);
+  if (e->out.st) hipStreamSynchronize(e->out.st);
+  if (e->out.st2) hipStreamSynchronize(e->out.st2);
+  const hipStream_t streams[] = {e->st_copy[0], e->st_copy[1], e->st_eager, e->out.st, e->out.st2, e->st};
+  std::vector<hipEvent_t> events(e->ev, e->ev + 5);
+  events.push_back(e->ev_eager);
+  events.insert(events.end(), e->out.pool.begin(), e->out.pool.end());
+  events.insert(events.end(), e->ev_spill.begin(), e->ev_spill.end());
   delete e;
+  for (hipEvent_t v : events)
+    if (v) hipEventDestroy(v);
+  for (hipStream_t st : streams)
+    if (st) hipStreamDestroy(st);
 }
 
 int ngd_create(const ngd_config *cfg, ngd_engine **out) {
@@ -773,34 +683,24 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
     rc = (x);                        \
     if (rc != NGD_OK) return bail(rc); \
   } while (0)
-  TRY(dev_alloc(e, &e->d_tiles, tiles.size(), false));
-  TRY(dev_alloc(e, &e->d_tiles16, tiles16.size(), false));
+  auto to_device = [&](auto &buf, const auto &v, const char *what) -> int {
+    if (int rc_a = buf.alloc(e, v.size(), false)) return rc_a;
+    if (!v.empty() && hipMemcpy(buf, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice) != hipSuccess)
+      return fail(NGD_E_HIP, std::string("ngd_create: ") + what + " upload failed");
+    return NGD_OK;
+  };
+  TRY(to_device(e->d_tiles, tiles, "tile list"));
+  TRY(to_device(e->d_tiles16, tiles16, "tile list"));
   e->h_tiles16 = tiles16;
-  TRY(dev_alloc(e, &e->d_tiles64, tiles64.size(), false));
-  TRY(dev_alloc(e, &e->d_pairs, pairs.size(), false));
-  TRY(dev_alloc(e, &e->d_jobs, jobs.size(), false));
-  if (!jobs.empty())
-    if (hipMemcpy(e->d_jobs, jobs.data(), jobs.size() * sizeof(ngd_job), hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(NGD_E_HIP, "ngd_create: job list upload failed"));
-
-  if (!tiles.empty())
-    if (hipMemcpy(e->d_tiles, tiles.data(), tiles.size() * sizeof(ngd_tile), hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(NGD_E_HIP, "ngd_create: tile list upload failed"));
-  if (!tiles16.empty())
-    if (hipMemcpy(e->d_tiles16, tiles16.data(), tiles16.size() * sizeof(ngd_tile), hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(NGD_E_HIP, "ngd_create: tile list upload failed"));
-  if (!tiles64.empty())
-    if (hipMemcpy(e->d_tiles64, tiles64.data(), tiles64.size() * sizeof(ngd_tile), hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(NGD_E_HIP, "ngd_create: tile list upload failed"));
-  if (!pairs.empty())
-    if (hipMemcpy(e->d_pairs, pairs.data(), pairs.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-      return bail(fail(NGD_E_HIP, "ngd_create: pair list upload failed"));
+  TRY(to_device(e->d_tiles64, tiles64, "tile list"));
+  TRY(to_device(e->d_pairs, pairs, "pair list"));
+  TRY(to_device(e->d_jobs, jobs, "job list"));
 
   // ---- resident images (zero-filled: padding individuals/sites contribute nothing) ----
   if (kernel == NGD_KERNEL_STREAM) {
-    TRY(dev_alloc_pieces(e, &e->PI, g.n_ind * g.n_sites_pad * 3, true));  // (a row of sites per individual: a load needs all of it)
+    TRY(dev_alloc_pieces(e, e->PI, g.n_ind * g.n_sites_pad * 3, true));  // (a row of sites per individual: a load needs all of it)
   } else {
-    TRY(dev_alloc_pieces(e, &e->PA, frag_elems, true, ngd_engine::PIECE_FRAG));
+    TRY(dev_alloc_pieces(e, e->PA, frag_elems, true, PIECE_FRAG));
     e->single_image = kernel == NGD_KERNEL_MFMA && cfg->single_image == 1;
     if (kernel == NGD_KERNEL_MFMA && (cfg->single_image == 2 || cfg->single_image == 0)) {
       const bool ok = ngd_score_congruence(cfg->score, e->sc.c, e->sc.d) == NGD_OK;
@@ -827,32 +727,32 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
       e->qb_res_kg = std::min<uint64_t>(g.n_kg, ((uint64_t)cfg->second_image_mib << 20) / ((uint64_t)g.n_ig * 64 * 8));
       if (e->qb_res_kg == g.n_kg) { e->single_image = false; e->qb_res_kg = 0; }  // all of it: the two-image engine
     }
-    if (kernel == NGD_KERNEL_MFMA && !e->single_image && !e->congruent) TRY(dev_alloc_pieces(e, &e->QB, frag_elems, true, ngd_engine::PIECE_FRAG));
-    if (e->qb_res_kg) TRY(dev_alloc(e, &e->QB_res, (e->qb_res_kg + NGD_KG_TAIL) * (uint64_t)g.n_ig * 64, false));
+    if (kernel == NGD_KERNEL_MFMA && !e->single_image && !e->congruent) TRY(dev_alloc_pieces(e, e->QB, frag_elems, true, PIECE_FRAG));
+    if (e->qb_res_kg) TRY(e->QB_res.alloc(e, (e->qb_res_kg + NGD_KG_TAIL) * (uint64_t)g.n_ig * 64, false));
   }
   if (cfg->pairwise_del) {
-    TRY(dev_alloc(e, &e->mask, g.n_ind * (uint64_t)g.n_words, true));
-    TRY(dev_alloc(e, &e->planes, 32ull * g.n_words, true));
+    TRY(e->mask.alloc(e, g.n_ind * (uint64_t)g.n_words, true));
+    TRY(e->planes.alloc(e, 32ull * g.n_words, true));
   }
-  TRY(dev_alloc(e, &e->d_ws, g.n_sites_pad + 4 * NGD_KG_TAIL, true));
-  if (kernel == NGD_KERNEL_MFMA) TRY(dev_alloc(e, &e->d_wk, 4 * (g.n_kg + NGD_KG_TAIL), true));
+  TRY(e->d_ws.alloc(e, g.n_sites_pad + 4 * NGD_KG_TAIL, true));
+  if (kernel == NGD_KERNEL_MFMA) TRY(e->d_wk.alloc(e, 4 * (g.n_kg + NGD_KG_TAIL), true));
   if (e->congruent) {
-    TRY(dev_alloc(e, &e->d_wD, 4 * (g.n_kg + NGD_KG_TAIL), false));
+    TRY(e->d_wD.alloc(e, 4 * (g.n_kg + NGD_KG_TAIL), false));
     ngd_launch_index_weights(e->st, 4 * (g.n_kg + NGD_KG_TAIL), e->sc.d, e->d_wD);
   }
   if (e->congruent && e->sc.fix) {
-    TRY(dev_alloc_pieces(e, &e->SM, g.n_sites * g.n_ind, true, ngd_engine::PIECE_SITE_MAJOR, g.n_ind * 8));
+    TRY(dev_alloc_pieces(e, e->SM, g.n_sites * g.n_ind, true, PIECE_SITE_MAJOR, g.n_ind * 8));
     e->fix_cap = (uint32_t)std::min<uint64_t>(n_pairs, NGD_FIX_LIST);
-    TRY(dev_alloc(e, &e->d_fixlist, e->fix_cap, false));
-    TRY(dev_alloc(e, &e->d_fixcount, 1, true));
-    TRY(dev_alloc(e, &e->d_fixseen, n_pairs / 32 + 1, true));
-    TRY(dev_alloc(e, &e->d_fixparts, NGD_FIX_CAP, false));
-    if (hipHostMalloc((void **)&e->h_fixcount, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+    TRY(e->d_fixlist.alloc(e, e->fix_cap, false));
+    TRY(e->d_fixcount.alloc(e, 1, true));
+    TRY(e->d_fixseen.alloc(e, n_pairs / 32 + 1, true));
+    TRY(e->d_fixparts.alloc(e, NGD_FIX_CAP, false));
+    if (e->h_fixcount.alloc(1))
       return bail(fail(NGD_E_NOMEM, "ngd_create: no pinned host memory for the fix-up count"));
     *e->h_fixcount = 0;
   }
-  TRY(dev_alloc(e, &e->d_sum, n_pairs, true));
-  TRY(dev_alloc(e, &e->d_cnt, n_pairs, true));
+  TRY(e->d_sum.alloc(e, n_pairs, true));
+  TRY(e->d_cnt.alloc(e, n_pairs, true));
 
   // ---- split over the site axis: slices -> slabs, reduced in fixed order ----
   if (kernel == NGD_KERNEL_MFMA) {
@@ -901,10 +801,9 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
     ks = std::max<uint64_t>(8, (ks + 7) / 8 * 8);
     e->n_ks = (uint32_t)ks;
     e->per_slice = ((g.n_kg + ks - 1) / ks + 3) / 4 * 4;  // whole pipeline trips (accum_mfma.hip DEPTH)
-    TRY(dev_alloc_pieces(e, &e->slab, ks * (uint64_t)g.n_pad * g.n_pad, false));
+    TRY(dev_alloc_pieces(e, e->slab, ks * (uint64_t)g.n_pad * g.n_pad, false));
     // ([0..1] the clock sample; [2] set by a block whose shape the kernel does not list: mfma_fault())
-    if (hipHostMalloc((void **)&e->h_clk, 4 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&e->d_clk, e->h_clk, 0) != hipSuccess)
+    if (e->h_clk.alloc(4, hipHostMallocMapped) || hipHostGetDevicePointer((void **)&e->d_clk, e->h_clk, 0) != hipSuccess)
       return bail(fail(NGD_E_NOMEM, "ngd_create: no pinned host memory for the clock sample"));
     e->h_clk[0] = e->h_clk[1] = e->h_clk[2] = e->h_clk[3] = 0;
     if (e->single_image) {
@@ -914,8 +813,7 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
       uint64_t n_ranges = 0;
       const uint64_t rest_kg = g.n_kg - e->qb_res_kg;  // (what is not resident: ngd_config.second_image_mib)
       const uint64_t range_kg = std::min<uint64_t>(rest_kg, qb_piece(rest_kg, e->n_ks, e->qb_chunk_kg, &n_ranges) * e->n_ks);
-      e->qb_chunk_elems = (range_kg + NGD_KG_TAIL) * (uint64_t)g.n_ig * 64;
-      TRY(dev_alloc(e, &e->qb_chunk, e->qb_chunk_elems, false));
+      TRY(e->qb_chunk.alloc(e, (range_kg + NGD_KG_TAIL) * (uint64_t)g.n_ig * 64, false));
     }
   } else if (kernel == NGD_KERNEL_EM_TABLE) {
     // 64 x 64 tiles x slices of sites; a workgroup works a site in ~10 us, so slices of a few thousand sites keep
@@ -928,8 +826,8 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
     if (cfg->n_slices) ks = std::min<uint64_t>(cfg->n_slices, g.n_sites);  // never more slices than sites
     e->n_ks = (uint32_t)ks;
     e->per_slice = (g.n_sites + ks - 1) / ks;
-    TRY(dev_alloc_pieces(e, &e->slab, ks * (uint64_t)g.n_pad * g.n_pad, true));
-    TRY(dev_alloc(e, &e->d_emcnt, 4, true));
+    TRY(dev_alloc_pieces(e, e->slab, ks * (uint64_t)g.n_pad * g.n_pad, true));
+    TRY(e->d_emcnt.alloc(e, 4, true));
     {
       // pair slots of the spilled-terms plan (em_spill_impl): a row of a tile takes one slot group per group of 16 columns
       // that holds a pair -- none for a diagonal tile's lower triangle or for the columns at and beyond n_ind
@@ -947,7 +845,7 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
       if (n_live + 4 < (1ull << 31)) {  // (else: the plan is not offered, em_spill_impl)
         e->n_pg_live = (uint32_t)n_live;
         e->n_pg_spill = (uint32_t)((n_live + 3) / 4 * 4);  // a wavefront of the contraction takes 2 or 4 slot groups
-        TRY(dev_alloc(e, &e->d_rowpg, rowpg.size(), false));
+        TRY(e->d_rowpg.alloc(e, rowpg.size(), false));
         if (!rowpg.empty() && hipMemcpy(e->d_rowpg, rowpg.data(), rowpg.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
           return bail(fail(NGD_E_HIP, "ngd_create: slot map upload failed"));
       }
@@ -960,7 +858,7 @@ int ngd_create(const ngd_config *cfg, ngd_engine **out) {
     if (cfg->n_slices) ks = std::min<uint64_t>(cfg->n_slices, g.n_sites);  // never more slices than sites
     e->n_ks = (uint32_t)ks;
     e->per_slice = (g.n_sites + ks - 1) / ks;
-    TRY(dev_alloc_pieces(e, &e->slab, ks * (uint64_t)g.n_pad * g.n_pad, false));
+    TRY(dev_alloc_pieces(e, e->slab, ks * (uint64_t)g.n_pad * g.n_pad, false));
   }
   // upload staging (ngd_upload_sites / _ind_major): at most ~256 MiB of raw doubles, allocated by the first upload that
   // needs it (a staged load -- ngd_stage_* -- never does)
@@ -983,7 +881,7 @@ static int upload_common(ngd_engine *e, const double *p, int ind_major, uint64_t
   if (int rc = eager_discard(e)) return rc;  // (sites may be uploaded again: nothing accumulated beside a staged load is kept)
   e->stage_in_order = false;
   if (!e->staging)
-    if (int rc = dev_alloc(e, &e->staging, e->staging_sites * e->g.n_ind * 3, false)) return rc;
+    if (int rc = e->staging.alloc(e, e->staging_sites * e->g.n_ind * 3, false)) return rc;
   const uint64_t n_ind = e->g.n_ind;
   for (uint64_t done = 0; done < n;) {
     const uint64_t c = std::min(e->staging_sites, n - done);
@@ -1071,7 +969,7 @@ static int eager_advance(ngd_engine *e, uint64_t s0, uint64_t n, int b) {
   {  // the slab's planes of these slices must be mapped (its memory arrives after the images': dev_alloc_pieces)
     std::lock_guard<std::mutex> lk(e->piece_mu);
     for (auto &q : e->piece_ranges)
-      if (q->va == (void *)e->slab && q->ready < std::min<size_t>(q->size, (size_t)done * g.n_pad * g.n_pad * 8)) return NGD_OK;  // (next piece)
+      if (q.get() == e->slab.range() && q->ready < std::min<size_t>(q->size, (size_t)done * g.n_pad * g.n_pad * 8)) return NGD_OK;  // (next piece)
   }
   if (!e->st_eager) {
     // (a stream confined to a part of the CUs -- hipExtStreamCreateWithCUMask, 7/8 or 3/4 of them -- lets the EM kernel keep
@@ -1082,7 +980,7 @@ static int eager_advance(ngd_engine *e, uint64_t s0, uint64_t n, int b) {
     HIPCHK(hipStreamCreateWithPriority(&e->st_eager, hipStreamNonBlocking, least));
     HIPCHK(hipEventCreateWithFlags(&e->ev_eager, hipEventDisableTiming));
   }
-  HIPCHK(hipStreamWaitEvent(e->st_eager, e->k0_done[b], 0));  // this piece's preparation -- and every earlier one's -- is done
+  HIPCHK(hipStreamWaitEvent(e->st_eager, e->ring[b].k0_done, 0));  // this piece's preparation -- and every earlier one's -- is done
   launch_plain_slices(e, e->st_eager, e->eager_slices, done - e->eager_slices, true);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev_eager, e->st_eager));
@@ -1112,7 +1010,7 @@ static int stage_init(ngd_engine *e) {
   e->n_staged = 0;
   e->pin_cur = 0;
   if (!e->d_nan)
-    if (int rc = dev_alloc(e, &e->d_nan, 1, true)) return rc;
+    if (int rc = e->d_nan.alloc(e, 1, true)) return rc;
   return stage_slots(e);
 }
 
@@ -1122,23 +1020,16 @@ static int stage_init(ngd_engine *e) {
 // in a process that created and destroyed engine after engine (tools/fuzz_large.py, case ~55 of 80) the GPU faulted on a HOST
 // heap address -- registered ranges are handed back to malloc and come round again at the same addresses, and a
 // registration that is released late takes the next one's mapping with it.  hipHostMalloc's buffers never share addresses.
-static int pin_alloc(ngd_engine *e, int b, uint64_t bytes) {
-  HIPCHK(hipHostMalloc((void **)&e->pin[b], bytes, hipHostMallocDefault));
-  return NGD_OK;
-}
-
-static void pin_release(double *p) {
-  if (p) (void)hipHostFree(p);
-}
+static int pin_alloc(ngd_engine *e, int b, uint64_t bytes) { return e->ring[b].pin.alloc(bytes / 8); }
 
 // every slot's device twin and events at once (cheap); pinned buffer 0 at once, the others by ring_maker
 static int stage_slots(ngd_engine *e) {
   const uint64_t bytes = e->pin_sites * e->g.n_ind * 24;
   for (int b = 0; b < e->ring_slots; b++) {
-    int rc = dev_alloc(e, &e->draw[b], bytes / 8, false);
+    int rc = e->ring[b].draw.alloc(e, bytes / 8, false);
     if (rc) return rc;
-    HIPCHK(hipEventCreateWithFlags(&e->pin_free[b], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->k0_done[b], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&e->ring[b].pin_free, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&e->ring[b].k0_done, hipEventDisableTiming));
   }
   if (int rc = pin_alloc(e, 0, bytes)) return rc;
   e->ring_ready = 1;
@@ -1149,9 +1040,7 @@ static int stage_slots(ngd_engine *e) {
     e->ring_maker = std::thread([e, dev, n, bytes]() {
       if (hipSetDevice(dev) != hipSuccess) { e->ring_maker_rc = NGD_E_HIP; return; }
       for (int b = 1; b < n && !e->ring_stop.load(std::memory_order_relaxed); b++) {
-        if (hipHostMalloc((void **)&e->pin[b], bytes, hipHostMallocDefault) != hipSuccess) {  // (the load goes on with the buffers it has)
-          e->pin[b] = nullptr;
-          (void)hipGetLastError();
+        if (pin_alloc(e, b, bytes)) {  // (the load goes on with the buffers it has)
           e->ring_maker_rc = NGD_E_NOMEM;
           return;
         }
@@ -1177,9 +1066,9 @@ int ngd_stage_acquire(ngd_engine *e, double **host_buf, uint64_t *capacity_sites
   // the copy out of this buffer, a turn of the ring ago, is done -- and so is the preparation kernel that read its device
   // twin (it follows the copy on the engine's stream, ~30 us): waited for HERE, on the host, so that the copy stream carries
   // no wait of its own ([measured] a stream-side wait on an event costs the copy engine ~50 us of idling per copy)
-  HIPCHK(hipEventSynchronize(e->k0_done[b]));
+  HIPCHK(hipEventSynchronize(e->ring[b].k0_done));
   e->pin_lent = b;
-  *host_buf = e->pin[b];
+  *host_buf = e->ring[b].pin;
   *capacity_sites = e->pin_sites;
   return NGD_OK;
 }
@@ -1202,15 +1091,15 @@ int ngd_stage_submit(ngd_engine *e, uint64_t s0, uint64_t n, const ngd_prep *pre
   const int b = e->pin_lent;
   hipStream_t cs = e->st_copy[0];
   e->n_staged++;
-  HIPCHK(hipMemcpyAsync(e->draw[b], e->pin[b], n * e->g.n_ind * 24, hipMemcpyHostToDevice, cs));
-  HIPCHK(hipEventRecord(e->pin_free[b], cs));
-  HIPCHK(hipStreamWaitEvent(e->st, e->pin_free[b], 0));
+  HIPCHK(hipMemcpyAsync(e->ring[b].draw, e->ring[b].pin, n * e->g.n_ind * 24, hipMemcpyHostToDevice, cs));
+  HIPCHK(hipEventRecord(e->ring[b].pin_free, cs));
+  HIPCHK(hipStreamWaitEvent(e->st, e->ring[b].pin_free, 0));
   if (int rc = piece_wait_sites(e, s0 + n)) return rc;  // (the part of the images these sites are written to is mapped)
-  ngd_launch_prep_layout(e->st, e->g, e->draw[b], s0, n, prep->in_logscale, prep->call_geno, prep->N_thresh,
+  ngd_launch_prep_layout(e->st, e->g, e->ring[b].draw, s0, n, prep->in_logscale, prep->call_geno, prep->N_thresh,
                          prep->call_thresh, e->sc, e->cfg.pairwise_del, e->PA, e->QB, e->congruent ? e->SM : e->PI, e->mask,
                          e->d_nan);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e->k0_done[b], e->st));
+  HIPCHK(hipEventRecord(e->ring[b].k0_done, e->st));
   if (int rc = eager_advance(e, s0, n, b)) return rc;
   e->pin_lent = -1;
   e->pin_cur = (b + 1) % std::max(1, e->ring_ready.load(std::memory_order_acquire));  // (the buffers that exist by now)
@@ -1242,28 +1131,22 @@ int ngd_commit(ngd_engine *e) {
     int flag = 0;
     HIPCHK(hipMemcpy(&flag, e->d_nan, sizeof(int), hipMemcpyDeviceToHost));
     ring_maker_join(e);
-    {  // the pipeline is over: its buffers go back on a thread of their own (6 x hipHostFree + hipFree are ~30 ms)
-      struct Slot { double *pin, *draw; hipEvent_t a, b; };
-      std::vector<Slot> slots;
-      for (int b = 0; b < ngd_engine::RING; b++) {
-        if (e->pin[b] || e->draw[b]) slots.push_back({e->pin[b], e->draw[b], e->pin_free[b], e->k0_done[b]});
-        if (e->draw[b]) e->dev_bytes -= e->pin_sites * e->g.n_ind * 24;
-        e->pin[b] = nullptr; e->draw[b] = nullptr; e->pin_free[b] = nullptr; e->k0_done[b] = nullptr;
-      }
+    {  // the pipeline is over: its slots go back on a thread of their own (6 x hipHostFree + hipFree are ~30 ms)
+      std::vector<RingSlot> slots;
+      for (RingSlot &slot : e->ring)
+        if (slot.pin || slot.draw) {
+          slot.draw.uncount();  // (HERE, not whenever the reaper comes to it)
+          slots.push_back(std::move(slot));
+        }
       e->pin_sites = 0;
       e->ring_slots = 0;
       e->ring_ready = 0;
       stage_reap(e);
       const int dev = e->device;
       if (!slots.empty())
-        e->ring_reaper = std::thread([slots, dev]() {
+        e->ring_reaper = std::thread([slots = std::move(slots), dev]() mutable {
           (void)hipSetDevice(dev);
-          for (const Slot &s : slots) {
-            pin_release(s.pin);
-            if (s.draw) (void)hipFree(s.draw);
-            if (s.a) (void)hipEventDestroy(s.a);
-            if (s.b) (void)hipEventDestroy(s.b);
-          }
+          slots.clear();
         });
     }
     e->pin_cur = 0;
@@ -1277,9 +1160,7 @@ int ngd_commit(ngd_engine *e) {
     }
   }
   if (e->staging) {  // upload is over: give the staging buffer back
-    HIPCHK(hipFree(e->staging));
-    e->dev_bytes -= e->staging_sites * e->g.n_ind * 24;
-    e->staging = nullptr;
+    if (int rc = e->staging.release()) return rc;
   }
   if (e->QB_res)  // single-image engine: the part of the second image it keeps (stream order: before any pass)
     ngd_launch_qb_range(e->st, e->g, e->sc, e->PA, 0, std::min<uint64_t>(e->qb_res_kg + NGD_KG_TAIL, e->g.n_kg + NGD_KG_TAIL),
@@ -1304,7 +1185,7 @@ int ngd_synth_fill(ngd_engine *e, uint64_t seed, double miss_frac) { return ngd_
 // w != NULL: one bootstrap replicate; for the MFMA kernel kgl is then the list of k-groups to visit and
 // per_slice / kg_lim count list entries
 // k_per_slice != 0 (MFMA, bootstrap blocks that are not whole k-groups): slices of k_per_slice contraction indices,
-// masked by the per-slice 0/1 weights in e->d_wslice (w_stride k-groups per slice)
+// masked by the per-slice 0/1 weights in e->blk.wslice (w_stride k-groups per slice)
 static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *kgl, uint64_t sites_eff, uint32_t n_ks,
                               uint64_t per_slice, uint64_t kg_lim, double *slab, uint64_t k_per_slice = 0,
                               uint32_t w_stride = 0) {
@@ -1314,7 +1195,7 @@ static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *k
       if (!e->single_image) {
         // (single_image = 2: both operands from the one image, the congruence's diagonal on the weights -- of a plain pass too)
         ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB,
-                              k_per_slice ? e->d_wslice : (w ? e->d_wk : (e->congruent ? e->d_wD : nullptr)),
+                              k_per_slice ? e->blk.wslice : (w ? e->d_wk : (e->congruent ? e->d_wD : nullptr)),
                                 (w && !k_per_slice) ? kgl : nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n_ks, per_slice,
                                 kg_lim, k_per_slice, w_stride, slab, e->d_clk);
       } else {
@@ -1338,7 +1219,7 @@ static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *k
         auto slice_kg1 = [&](uint64_t ks) {
           return std::min<uint64_t>(kg_lim, k_per_slice ? ((ks + 1) * k_per_slice + 3) >> 2 : (ks + 1) * per_slice);
         };
-        const double *wsel = k_per_slice ? e->d_wslice : (w ? e->d_wk : nullptr);
+        const double *wsel = k_per_slice ? e->blk.wslice : (w ? e->d_wk : nullptr);
         // what the engine keeps of the second image (its first qb_res_kg k-groups, ngd_config.second_image_mib) is read
         // where it lies: one launch over that part of a whole pass, or over the slices that end inside it
         const uint64_t res = std::min<uint64_t>(e->qb_res_kg, kg_lim);
@@ -1370,11 +1251,11 @@ static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *k
             hi = std::max(lo, slice_kg1(ks0 + n - 1));
           }
           const uint64_t need = (hi - lo + NGD_KG_TAIL) * kstride;
-          if (need > e->qb_chunk_elems) {
+          if (need > e->qb_chunk.capacity()) {
             // a range longer than the scratch was sized for (bootstrap blocks of very many sites: a partial-sum slice
             // is a whole block): the scratch grows to hold it -- the earlier ranges' launches have to be over first
             HIPCHK(hipStreamSynchronize(e->st));
-            int rc = ensure_cap(e, &e->qb_chunk, &e->qb_chunk_elems, need);
+            int rc = e->qb_chunk.ensure(e, need);
             if (rc) return rc;
           }
           ngd_launch_qb_range(e->st, g, e->sc, e->PA, lo, std::min<uint64_t>(hi + NGD_KG_TAIL, g.n_kg + NGD_KG_TAIL), e->qb_chunk);
@@ -1386,9 +1267,9 @@ static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *k
             // ... so every k-group a launched slice can touch -- its own [kg0, kg1) and the NGD_KG_TAIL k-groups its operand
             // pipeline (the prefetching wavefront included) runs ahead -- must lie inside the scratch as just formed
             const uint64_t first = slice_kg0(ks0), last = std::max(first, slice_kg1(ks0 + n - 1));
-            if ((first < lo && first < kg_lim) || last > hi || (hi - lo + NGD_KG_TAIL) * kstride > e->qb_chunk_elems)
+            if ((first < lo && first < kg_lim) || last > hi || (hi - lo + NGD_KG_TAIL) * kstride > e->qb_chunk.capacity())
               return fail(NGD_E_HIP, "launch_accumulate: internal -- a slice of the range reaches outside the scratch of the second image");
-            const double *moved_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->qb_chunk) - lo * kstride * sizeof(double));
+            const double *moved_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->qb_chunk.get()) - lo * kstride * sizeof(double));
             ngd_launch_accum_mfma(e->st, g, e->PA, moved_back, wsel, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n,
                                   per_slice, kg_lim, k_per_slice, w_stride, slab, e->d_clk, ks0);
           }
@@ -1445,7 +1326,7 @@ static void read_timing(ngd_engine *e, uint64_t n_eff, uint32_t launches, bool a
 // from p recovered out of the image and the side array (fixup.hip).  The stream is idle and *h_fixcount has arrived.
 //  * a single matrix (d_sum != NULL): over the sites [0, s_hi) with the per-site weights ws (NULL: none), the sums written
 //    over the MFMA pass's;
-//  * per-block partial results (d_sum == NULL): the noted pairs' entries of slab_boot, slice by slice -- the caller then
+//  * per-block partial results (d_sum == NULL): the noted pairs' entries of the block scratch's sums, slice by slice -- the caller then
 //    forms the replicates again.
 // The tolerance is unconditional: EVERY noted pair is recomputed, in launches of bounded size, however many there are
 // (round 6; rounds 4-5 gave up on all of them past a budget of ~0.33 s).  More noted pairs than the list holds (fix_cap):
@@ -1471,10 +1352,10 @@ static int fixup_by_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, doubl
   const uint64_t piece = qb_piece(kg_lim, e->n_ks, span, &n_ranges);
   const uint64_t range_kg = std::min<uint64_t>(kg_lim, piece * e->n_ks);
   const uint64_t need = (range_kg + NGD_KG_TAIL) * kstride;
-  int rc = ensure_cap(e, &e->fix_p, &e->cap_fix_p, need);
+  int rc = e->fix_p.ensure(e, need);
+  if (!rc) rc = e->fix_q.ensure(e, need);
+  if (!rc) rc = e->d_fixnew.ensure(e, ngd_n_pairs(g.n_ind));
   if (rc) return rc;
-  if ((rc = ensure_cap(e, &e->fix_q, &e->cap_fix_q, need))) return rc;
-  if ((rc = ensure_cap(e, &e->d_fixnew, &e->cap_fixnew, ngd_n_pairs(g.n_ind)))) return rc;
   for (uint64_t r = 0; r < n_ranges; r++) {
     const uint64_t lo = std::min<uint64_t>(r * piece * e->n_ks, kg_lim), hi = std::min<uint64_t>(lo + piece * e->n_ks, kg_lim);
     if (hi <= lo) break;
@@ -1496,8 +1377,8 @@ static int fixup_partials_by_pass(ngd_engine *e, uint64_t s_hi) {
   const ngd_geom &g = e->g;
   const uint64_t kstride = (uint64_t)g.n_ig * 64;
   const uint64_t kg_lim = std::min<uint64_t>(g.n_kg, 3 * s_hi / 4);
-  const uint64_t per_slice = e->boot_per_slice;
-  const uint32_t n_ks = e->boot_nks;
+  const uint64_t per_slice = e->blk.per_slice;
+  const uint32_t n_ks = e->blk.nks;
   if (!per_slice || !n_ks || n_ks % 8) return fail(NGD_E_HIP, "fix-up pass: internal -- the partial results' slices are not in eights");
   const uint64_t span = std::max<uint64_t>(8 * per_slice, ((uint64_t)1 << 30) / (kstride * 8));  // ~1 GiB per scratch image
   auto kg0 = [&](uint64_t ks) { return ks * per_slice; };
@@ -1508,14 +1389,14 @@ static int fixup_partials_by_pass(ngd_engine *e, uint64_t s_hi) {
     n = std::min(n, n_ks - ks0);
     const uint64_t lo = std::min<uint64_t>(kg0(ks0), kg_lim), hi = std::max(lo, kg1(ks0 + n - 1));
     const uint64_t need = (hi - lo + NGD_KG_TAIL) * kstride;
-    int rc = ensure_cap(e, &e->fix_p, &e->cap_fix_p, need);
+    int rc = e->fix_p.ensure(e, need);
+    if (!rc) rc = e->fix_q.ensure(e, need);
     if (rc) return rc;
-    if ((rc = ensure_cap(e, &e->fix_q, &e->cap_fix_q, need))) return rc;
     ngd_launch_pq_range(e->st, g, e->sc, e->PA, e->SM, nullptr, lo, std::min<uint64_t>(hi + NGD_KG_TAIL, g.n_kg + NGD_KG_TAIL), e->fix_p, e->fix_q);
-    const double *p_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->fix_p) - lo * kstride * sizeof(double));
-    const double *q_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->fix_q) - lo * kstride * sizeof(double));
+    const double *p_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->fix_p.get()) - lo * kstride * sizeof(double));
+    const double *q_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->fix_q.get()) - lo * kstride * sizeof(double));
     ngd_launch_accum_mfma(e->st, g, p_back, q_back, nullptr, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n, per_slice,
-                          kg_lim, 0, 0, e->slab_boot, e->d_clk, ks0);
+                          kg_lim, 0, 0, e->blk.sums(), e->d_clk, ks0);
     HIPCHK(hipGetLastError());
     ks0 += n;
   }
@@ -1613,8 +1494,8 @@ static int fixup_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, double *
   }
   // Per-block partial results (whole k-groups per block): where the noted tiles would cost more than the whole slab again
   // in the two-operand arithmetic, the whole slab it is (round 6; the tiles: 0.8 s for a data set of clones at cfg 3's size)
-  if (!d_sum && e->kernel == NGD_KERNEL_MFMA && e->exact_shapes == 0 && e->slab_boot && e->boot_per_slice &&
-      e->boot_B % 4 == 0 && (uint64_t)e->boot_per_slice * 4 == sites_per_slice * 3) {
+  if (!d_sum && e->kernel == NGD_KERNEL_MFMA && e->exact_shapes == 0 && e->blk.sums() && e->blk.per_slice &&
+      e->blk.sums_block() % 4 == 0 && (uint64_t)e->blk.per_slice * 4 == sites_per_slice * 3) {
     const double t_tiles = ((double)tiles.size() * 256.0 + (double)singles.size() * 60.0) * (double)s_hi / 6.5e11;
     const double t_pass = 6.0 * (double)e->n_owned_pairs * (double)s_hi / 50e12 + 80.0 * (double)e->g.n_pad * (double)s_hi / 2.4e12 + 2e-3;
     // (tests only, NGD_ENABLE_TEST_HOOKS=1: NGD_TEST_FIX_PARTIALS = "pass" / "tiles" takes the choice away from the estimate)
@@ -1640,13 +1521,13 @@ static int fixup_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, double *
   const uint64_t max_wg = 1ull << 22;
   if (!d_sum && n_slab_slices > max_wg) return fail(NGD_E_INVALID, "fix-up pass: more slab slices than a launch has workgroups");
   if (!tiles.empty()) {
-    int rc = ensure_cap(e, &e->d_fixtiles, &e->cap_fixtiles, tiles.size());
+    int rc = e->d_fixtiles.ensure(e, tiles.size());
     if (rc) return rc;
     HIPCHK(hipMemcpy(e->d_fixtiles, tiles.data(), tiles.size() * sizeof(ngd_fix_tile), hipMemcpyHostToDevice));
     if (d_sum) {
       // slices of 4096 sites (fewer, longer ones only where NGD_FIX_CAP of them would not cover the sites); as many tiles
       // to a launch as the partial-sum scratch holds (stream order: a launch's scratch is read before the next writes it)
-      rc = ensure_cap(e, &e->d_fixtparts, &e->cap_fixtparts, (uint64_t)NGD_FIX_CAP * 256);
+      rc = e->d_fixtparts.ensure(e, (uint64_t)NGD_FIX_CAP * 256);
       if (rc) return rc;
       const uint64_t sps = std::max<uint64_t>(4096, (s_hi + NGD_FIX_CAP - 1) / NGD_FIX_CAP);
       const uint64_t n_slices = (s_hi + sps - 1) / sps;
@@ -1662,7 +1543,7 @@ static int fixup_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, double *
       for (size_t off = 0; off < tiles.size(); off += per) {
         const uint32_t m = (uint32_t)std::min<size_t>(per, tiles.size() - off);
         ngd_launch_fixup_tiles(e->st, e->g, e->sc, e->PA, e->SM, nullptr, e->d_fixtiles + off, m, 0, s_hi, sites_per_slice,
-                               n_slab_slices, 1, e->slab_boot);
+                               n_slab_slices, 1, e->blk.sums());
       }
     }
   }
@@ -1682,7 +1563,7 @@ static int fixup_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, double *
     for (uint32_t off = 0; off < n1; off += per) {
       const uint32_t m = std::min<uint32_t>(per, n1 - off);
       ngd_launch_fixup(e->st, e->g, e->sc, e->PA, e->SM, nullptr, e->d_fixlist + off, m, 0, s_hi, sites_per_slice, n_slab_slices, 1,
-                       e->slab_boot);
+                       e->blk.sums());
     }
   }
   HIPCHK(hipGetLastError());
@@ -1712,21 +1593,15 @@ static int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
     n_eff = n_blocks * block_size;
     while (n_planes < 32 && (mult_max >> n_planes)) n_planes++;
     if (!n_planes) n_planes = 1;  // no block drawn (a site range of a larger job): one all-zero plane -- 0 planes means "unweighted"
-    if (n_blocks > e->cap_blocks) {
-      if (e->d_mult) { hipFree(e->d_mult); e->dev_bytes -= e->cap_blocks * 4; }
-      e->d_mult = nullptr; e->cap_blocks = 0;
-      int rc = dev_alloc(e, &e->d_mult, n_blocks, false);
-      if (rc) return rc;
-      e->cap_blocks = n_blocks;
-    }
+    if (int rc = e->d_mult.ensure(e, n_blocks)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_mult, mult, n_blocks * 4, hipMemcpyHostToDevice, e->st));
     ngd_launch_weights(e->st, n_blocks, block_size, g.n_sites_pad, e->d_mult, e->d_ws, e->d_wk, e->congruent ? e->sc.d : nullptr);
     if (list_pass) {  // the k-groups this replicate visits at all (about 1/e of the sites are not drawn)
       const uint32_t nb = ngd_kg_count_blocks(g.n_kg);
       if (!e->d_kgl) {
-        int rc = dev_alloc(e, &e->d_kgl, g.n_kg + NGD_KG_LIST_PAD, false);
+        int rc = e->d_kgl.alloc(e, g.n_kg + NGD_KG_LIST_PAD, false);
         if (rc) return rc;
-        rc = dev_alloc(e, &e->d_kgcnt, (uint64_t)nb + 1, false);
+        rc = e->d_kgcnt.alloc(e, (uint64_t)nb + 1, false);
         if (rc) return rc;
       }
       ngd_launch_kg_compact(e->st, e->d_wk, g.n_kg, (uint32_t)g.n_kg, e->d_kgcnt, e->d_kgl);
@@ -1955,11 +1830,11 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   if (n_blocks >= (1ull << 31)) return NGD_OK;
   // split large blocks so that there are enough workgroups; slices of one block share its weight
   const uint64_t unit = mfma ? 3 * block_size / 4 : block_size;  // k-groups or sites per block
-  const bool cached = e->boot_B == block_size && e->boot_blocks == n_blocks;
+  const bool cached = e->blk.has_sums(block_size, n_blocks);
   uint64_t sub = 1, nks = 0;
   if (cached) {
-    sub = e->boot_sub;
-    nks = e->boot_nks;
+    sub = e->blk.sub;
+    nks = e->blk.nks;
   } else {
     const uint32_t tiles_n = mfma ? std::max(1u, e->n_wg / (e->exact_shapes && e->exact_shapes < 3 ? 4 : 1))
                                   : e->kernel == NGD_KERNEL_EM_TABLE ? e->n_tiles64 : e->n_tiles16;
@@ -1972,17 +1847,17 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   }
   if (nks >= (1ull << 31)) return NGD_OK;
   const uint64_t elems = nks * plane, c_elems = pdel ? n_blocks * plane : 0;
-  const bool c_cached = !pdel || (e->cnt_B == block_size && e->cnt_blocks == n_blocks);
+  const bool c_cached = !pdel || e->blk.has_counts(block_size, n_blocks);
   if (!cached || !c_cached) {
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     const uint64_t need = elems * 8 + c_elems * 4;
-    const uint64_t have = e->slab_boot_elems * 8 + e->cnt_boot_elems * 4;
+    const uint64_t have = e->blk.bytes();
     // default budget: most of what the device has left -- one pass over a slab of tens of GB still beats
     // hundreds of accumulation passes
     const uint64_t budget = e->opt_boot_max_bytes ? e->opt_boot_max_bytes : (uint64_t)((free_b + have) / 100 * 85);
     if (need > budget) return NGD_OK;
-    if ((elems > e->slab_boot_elems || c_elems > e->cnt_boot_elems) && need + (1ull << 30) > free_b + have)
+    if ((elems > e->blk.sums().capacity() || c_elems > e->blk.counts().capacity()) && need + (1ull << 30) > free_b + have)
       return NGD_OK;
     const double alloc_ms = need > have ? (double)(need - have) * 12e-9 : 0.0;
     if (alloc_ms > 20.0 && e->opt_boot_partials < 2) {
@@ -2015,25 +1890,23 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   uint32_t launches = 0;
   HIPCHK(hipEventRecord(e->ev[1], e->st));
   if (!cached) {
-    e->boot_B = 0;
-    int rc = ensure_cap(e, &e->slab_boot, &e->slab_boot_elems, elems);
+    int rc = e->blk.borrow_sums().ensure(e, elems);
     if (rc) return rc;
-    e->boot_nks = (uint32_t)nks;
-    e->boot_sub = (uint32_t)sub;
-    e->boot_per_slice = unit / sub;
+    e->blk.nks = (uint32_t)nks;
+    e->blk.sub = (uint32_t)sub;
+    e->blk.per_slice = unit / sub;
     if (unaligned) {
       const uint32_t w_stride = (uint32_t)((3 * block_size + 3) / 4 + 1 + NGD_KG_TAIL);
-      rc = ensure_cap(e, &e->d_wslice, &e->cap_wslice, (uint64_t)e->boot_nks * w_stride * 4);
+      rc = e->blk.wslice.ensure(e, (uint64_t)e->blk.nks * w_stride * 4);
       if (rc) return rc;
-      ngd_launch_slice_weights(e->st, e->boot_nks, w_stride, 3 * block_size, 3 * n_eff, e->d_wslice, e->congruent ? e->sc.d : nullptr);
-      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->boot_nks, 0, (3 * n_eff + 3) / 4, e->slab_boot, 3 * block_size,
+      ngd_launch_slice_weights(e->st, e->blk.nks, w_stride, 3 * block_size, 3 * n_eff, e->blk.wslice, e->congruent ? e->sc.d : nullptr);
+      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, 0, (3 * n_eff + 3) / 4, e->blk.sums(), 3 * block_size,
                              w_stride);
     } else
-      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->boot_nks, e->boot_per_slice, mfma ? 3 * n_eff / 4 : 0, e->slab_boot);
+      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, e->blk.per_slice, mfma ? 3 * n_eff / 4 : 0, e->blk.sums());
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    e->boot_B = block_size;
-    e->boot_blocks = n_blocks;
+    e->blk.sums_filled(block_size, n_blocks);
     launches = 1;
   }
   HIPCHK(hipEventRecord(e->ev[2], e->st));
@@ -2048,7 +1921,7 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
       if (m != 0.0)
         for (uint64_t q = 0; q < sub; q++) W[(b * sub + q) * stride + r] = m;
     }
-  int rc = ensure_cap(e, &e->d_W, &e->cap_W, W.size());
+  int rc = e->d_W.ensure(e, W.size());
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(e->d_W, W.data(), W.size() * 8, hipMemcpyHostToDevice, e->st));
   if (e->cfg.shard_world > 1) {  // (the weighted reductions write every pair this engine owns, sums and counts)
@@ -2061,7 +1934,7 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   if (fix) {  // a pair is noted if its sum in ANY matrix is below NGD_FIX_MEAN x the sites that matrix visits
     thr.resize(n_rep);
     for (uint32_t r = 0; r < n_rep; r++) thr[r] = NGD_FIX_MEAN * (double)drawn[r];
-    rc = ensure_cap(e, &e->d_fixthr, &e->cap_fixthr, (uint64_t)n_rep);
+    rc = e->d_fixthr.ensure(e, (uint64_t)n_rep);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(e->d_fixthr, thr.data(), (uint64_t)n_rep * 8, hipMemcpyHostToDevice, e->st));
     HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
@@ -2069,41 +1942,43 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   }
   const bool fix_in_reduce = fix && !pdel;  // (--pairwise_del: noted once the counts are known, below)
   std::vector<uint32_t> M;
+  // the counts' inputs: --pairwise_del, the per-block counts (made if not cached) and the multiplicities M[block][r]; else
+  // the sites every matrix visits, filled in at once
+  auto counts_inputs = [&]() -> int {
+    if (pdel) {
+      if (!c_cached) {
+        int rc = e->blk.borrow_counts().ensure(e, c_elems);
+        if (rc) return rc;
+        ngd_launch_count_blocks(e->st, g, e->mask, block_size, (uint32_t)n_blocks, e->d_tiles16, e->n_tiles16, e->blk.counts());
+        HIPCHK(hipGetLastError());
+        e->blk.counts_filled(block_size, n_blocks);
+      }
+      M.assign(n_blocks * stride, 0u);
+      for (uint32_t r = 0; r < n_rep; r++)
+        for (uint64_t b = 0; b < n_blocks; b++) M[b * stride + r] = mult[(uint64_t)r * n_blocks + b];
+      if (int rc = e->d_M.ensure(e, M.size())) return rc;
+      HIPCHK(hipMemcpyAsync(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice, e->st));
+    } else {
+      if (int rc = e->d_drawn.ensure(e, (uint64_t)n_rep)) return rc;
+      HIPCHK(hipMemcpyAsync(e->d_drawn, drawn, (uint64_t)n_rep * 8, hipMemcpyHostToDevice, e->st));
+      ngd_launch_fill_cnt(e->st, g, e->d_tiles, e->n_tiles, 0, e->d_drawn, n_rep, d_cnt);
+    }
+    return NGD_OK;
+  };
   // ngd_run_*_dist, the job's first matrix at the head of d_bsum: a group of replicates is reduced by a launch of its own
   // and its copy to the host queued behind it, so that the copies run beside the later groups' reductions
   const bool stream_out = e->out.on && d_sum == e->d_bsum && d_cnt == e->d_bcnt && e->out.queued == 0;
   if (stream_out) {
     // the counts' inputs first: they do not depend on the sums
-    if (pdel) {
-      if (!c_cached) {
-        e->cnt_B = 0;
-        rc = ensure_cap(e, &e->cnt_boot, &e->cnt_boot_elems, c_elems);
-        if (rc) return rc;
-        ngd_launch_count_blocks(e->st, g, e->mask, block_size, (uint32_t)n_blocks, e->d_tiles16, e->n_tiles16, e->cnt_boot);
-        HIPCHK(hipGetLastError());
-        e->cnt_B = block_size;
-        e->cnt_blocks = n_blocks;
-      }
-      M.assign(n_blocks * stride, 0u);
-      for (uint32_t r = 0; r < n_rep; r++)
-        for (uint64_t b = 0; b < n_blocks; b++) M[b * stride + r] = mult[(uint64_t)r * n_blocks + b];
-      rc = ensure_cap(e, &e->d_M, &e->cap_M, M.size());
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice, e->st));
-    } else {
-      rc = ensure_cap(e, &e->d_drawn, &e->cap_drawn, (uint64_t)n_rep);
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(e->d_drawn, drawn, (uint64_t)n_rep * 8, hipMemcpyHostToDevice, e->st));
-      ngd_launch_fill_cnt(e->st, g, e->d_tiles, e->n_tiles, 0, e->d_drawn, n_rep, d_cnt);
-    }
+    if ((rc = counts_inputs())) return rc;
     const uint32_t rb = ngd_reduce_chunk(n_rep);
     for (uint32_t r0 = 0; r0 < n_rep; r0 += rb) {
       const uint32_t n = std::min(rb, n_rep - r0);
-      ngd_launch_reduce_w(e->st, g, e->slab_boot, (uint32_t)n_slices, e->d_W + r0, stride, n, e->d_tiles, e->n_tiles,
+      ngd_launch_reduce_w(e->st, g, e->blk.sums(), (uint32_t)n_slices, e->d_W + r0, stride, n, e->d_tiles, e->n_tiles,
                           d_sum + (uint64_t)r0 * n_pairs, fix_in_reduce ? &ff : nullptr, e->d_fixthr ? e->d_fixthr + r0 : nullptr, rb);
       if (r0 + rb >= n_rep) HIPCHK(hipEventRecord(e->ev[3], e->st));
       if (pdel)
-        ngd_launch_reduce_c(e->st, g, e->cnt_boot, (uint32_t)n_blocks, e->d_M + r0, stride, n, e->d_tiles, e->n_tiles,
+        ngd_launch_reduce_c(e->st, g, e->blk.counts(), (uint32_t)n_blocks, e->d_M + r0, stride, n, e->d_tiles, e->n_tiles,
                             d_cnt + (uint64_t)r0 * n_pairs, rb);
       HIPCHK(hipGetLastError());
       if ((rc = out_queue(e, r0 + n))) return rc;
@@ -2129,40 +2004,20 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
       __builtin_ia32_pause();
     }
   } else {
-    ngd_launch_reduce_w(e->st, g, e->slab_boot, (uint32_t)n_slices, e->d_W, stride, n_rep, e->d_tiles, e->n_tiles, d_sum,
+    ngd_launch_reduce_w(e->st, g, e->blk.sums(), (uint32_t)n_slices, e->d_W, stride, n_rep, e->d_tiles, e->n_tiles, d_sum,
                         fix_in_reduce ? &ff : nullptr, e->d_fixthr);
     if (fix_in_reduce) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[3], e->st));
 
+    if ((rc = counts_inputs())) return rc;
     if (pdel) {
-      if (!c_cached) {
-        e->cnt_B = 0;
-        rc = ensure_cap(e, &e->cnt_boot, &e->cnt_boot_elems, c_elems);
-        if (rc) return rc;
-        ngd_launch_count_blocks(e->st, g, e->mask, block_size, (uint32_t)n_blocks, e->d_tiles16, e->n_tiles16, e->cnt_boot);
-        HIPCHK(hipGetLastError());
-        e->cnt_B = block_size;
-        e->cnt_blocks = n_blocks;
-      }
-      M.assign(n_blocks * stride, 0u);
-      for (uint32_t r = 0; r < n_rep; r++)
-        for (uint64_t b = 0; b < n_blocks; b++) M[b * stride + r] = mult[(uint64_t)r * n_blocks + b];
-      rc = ensure_cap(e, &e->d_M, &e->cap_M, M.size());
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice, e->st));
-      ngd_launch_reduce_c(e->st, g, e->cnt_boot, (uint32_t)n_blocks, e->d_M, stride, n_rep, e->d_tiles, e->n_tiles, d_cnt);
+      ngd_launch_reduce_c(e->st, g, e->blk.counts(), (uint32_t)n_blocks, e->d_M, stride, n_rep, e->d_tiles, e->n_tiles, d_cnt);
       if (fix) {
         ngd_launch_fix_flag(e->st, g, d_sum, d_cnt, n_rep, e->d_tiles, e->n_tiles, ff);
         HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
       }
-    } else {
-      rc = ensure_cap(e, &e->d_drawn, &e->cap_drawn, (uint64_t)n_rep);
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(e->d_drawn, drawn, (uint64_t)n_rep * 8, hipMemcpyHostToDevice, e->st));
-      ngd_launch_fill_cnt(e->st, g, e->d_tiles, e->n_tiles, 0, e->d_drawn, n_rep, d_cnt);
     }
-
   }
   HIPCHK(hipGetLastError());
   if (!stream_out) HIPCHK(hipEventRecord(e->ev[4], e->st));
@@ -2176,7 +2031,7 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
     if (rc) return rc;
     if (patched) {
       if (stream_out && (rc = out_requeue(e))) return rc;  // (what has been copied so far: sums from before the patch)
-      ngd_launch_reduce_w(e->st, g, e->slab_boot, (uint32_t)n_slices, e->d_W, stride, n_rep, e->d_tiles, e->n_tiles, d_sum);
+      ngd_launch_reduce_w(e->st, g, e->blk.sums(), (uint32_t)n_slices, e->d_W, stride, n_rep, e->d_tiles, e->n_tiles, d_sum);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(e->st));
     }
@@ -2215,7 +2070,7 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   if (e->cfg.shard_world > 1) HIPCHK(hipMemsetAsync(d_sum, 0, (uint64_t)n_mat * n_pairs * sizeof(double), e->st));
   if (e->cfg.shard_world > 1 || e->cfg.pairwise_del)  // k_count adds with integer atomics
     HIPCHK(hipMemsetAsync(d_cnt, 0, (uint64_t)n_mat * n_pairs * sizeof(unsigned long long), e->st));
-  e->boot_B = 0;  // the partial-sum slab is re-used as this pass's scratch
+  DevBuf<double> &slab = e->blk.borrow_sums();  // the partial-sum slab is re-used as this pass's scratch
   for (uint32_t c0 = 0; c0 < n_mat; c0 += per_pass) {
     const uint32_t nr = std::min(per_pass, n_mat - c0);
     const int rb = nr <= 4 ? 4 : nr <= 8 ? 8 : 16;
@@ -2225,14 +2080,13 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     if (e->opt_boot_max_bytes && (uint64_t)b_ks * rb * plane * 8 > e->opt_boot_max_bytes)  // the caller's scratch budget
       return fail(NGD_E_NOMEM, "EM batch pass: result planes exceed NGD_OPT_BOOT_MAX_BYTES");
     const uint64_t want = (uint64_t)b_ks * rb * plane;
-    if (e->em_batch_nofit_elems && want >= e->em_batch_nofit_elems && want > e->slab_boot_elems)
+    if (e->em_batch_nofit_elems && want >= e->em_batch_nofit_elems && want > slab.capacity())
       return fail(NGD_E_NOMEM, "EM batch pass: result planes of this size did not fit the device before");
-    int rc = ensure_cap(e, &e->slab_boot, &e->slab_boot_elems, want);
+    int rc = slab.ensure(e, want);
     if (rc == NGD_E_NOMEM && !e->opt_boot_max_bytes) e->em_batch_nofit_elems = want;  // the device's verdict: remembered
     if (rc) return rc;
-    rc = ensure_cap(e, &e->d_W, &e->cap_W, g.n_sites * (uint64_t)rb);
-    if (rc) return rc;
-    rc = ensure_cap(e, &e->d_M, &e->cap_M, std::max<uint64_t>(1, (uint64_t)nq * n_blocks));
+    rc = e->d_W.ensure(e, g.n_sites * (uint64_t)rb);
+    if (!rc) rc = e->d_M.ensure(e, std::max<uint64_t>(1, (uint64_t)nq * n_blocks));
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev[0], e->st));
     if (nq) HIPCHK(hipMemcpyAsync(e->d_M, mult + (uint64_t)q0 * n_blocks, (uint64_t)nq * n_blocks * 4, hipMemcpyHostToDevice, e->st));
@@ -2241,14 +2095,14 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     HIPCHK(hipEventRecord(e->ev[1], e->st));
     if (table)
       ngd_launch_accum_em_table_batch(e->st, g, e->PA, e->d_W, rb, lead ? g.n_sites : n_eff, e->sc, e->cfg.pairwise_del,
-                                      e->d_tiles64, e->n_tiles64, b_ks, b_per, e->slab_boot, e->d_emcnt);
+                                      e->d_tiles64, e->n_tiles64, b_ks, b_per, slab, e->d_emcnt);
     else
       ngd_launch_accum_em_batch(e->st, g, e->PA, e->d_W, rb, lead ? g.n_sites : n_eff, e->sc, e->cfg.pairwise_del, fast,
-                                e->d_tiles16, e->n_tiles16, b_ks, b_per, e->slab_boot);
+                                e->d_tiles16, e->n_tiles16, b_ks, b_per, slab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[2], e->st));
     for (uint32_t r = 0; r < nr; r++)
-      ngd_launch_reduce(e->st, g, e->slab_boot + (uint64_t)r * plane, b_ks, (uint32_t)rb, e->d_tiles, e->n_tiles,
+      ngd_launch_reduce(e->st, g, slab + (uint64_t)r * plane, b_ks, (uint32_t)rb, e->d_tiles, e->n_tiles,
                         d_sum + (uint64_t)(c0 + r) * n_pairs);
     HIPCHK(hipEventRecord(e->ev[3], e->st));
     for (uint32_t r = 0; r < nr; r++) {
@@ -2309,7 +2163,7 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   const uint64_t d_elems = (uint64_t)n_rg * n_pg * 256;
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const uint64_t have = e->slab_boot_elems * 8 + e->cap_D * 8;
+  const uint64_t have = e->blk.sums().bytes() + e->d_D.bytes();
   // default scratch: 6 GB of terms (a device allocation costs ~12 ms per GB once; [measured] tools/em_boot_job.py)
   uint64_t budget = e->opt_em_spill_bytes ? e->opt_em_spill_bytes : (6ull << 30);
   if (e->opt_boot_max_bytes) budget = std::min(budget, e->opt_boot_max_bytes);
@@ -2324,16 +2178,12 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   const uint64_t chunk_sites = chunk_kg * 4 * q;
   const uint64_t n_chunks = (s_end + chunk_sites - 1) / chunk_sites;
 
-  e->boot_B = 0;  // the partial-sum slab is this plan's scratch
-  int rc = ensure_cap(e, &e->slab_boot, &e->slab_boot_elems, (chunk_kg + 1) * n_pg * 64);
-  if (rc) return rc;
-  rc = ensure_cap(e, &e->d_W, &e->cap_W, (chunk_kg + 1) * (uint64_t)n_rg * 64);
-  if (rc) return rc;
-  rc = ensure_cap(e, &e->d_M, &e->cap_M, std::max<uint64_t>(1, (uint64_t)n_rep * n_blocks));
-  if (rc) return rc;
-  rc = ensure_cap(e, &e->d_D, &e->cap_D, d_elems);
-  if (rc) return rc;
-  rc = ensure_cap(e, &e->d_nanflag, &e->cap_nanflag, n_chunks);
+  DevBuf<double> &C = e->blk.borrow_sums();  // the partial-sum slab is this plan's scratch
+  int rc = C.ensure(e, (chunk_kg + 1) * n_pg * 64);
+  if (!rc) rc = e->d_W.ensure(e, (chunk_kg + 1) * (uint64_t)n_rg * 64);
+  if (!rc) rc = e->d_M.ensure(e, std::max<uint64_t>(1, (uint64_t)n_rep * n_blocks));
+  if (!rc) rc = e->d_D.ensure(e, d_elems);
+  if (!rc) rc = e->d_nanflag.ensure(e, n_chunks);
   if (rc) return rc;
   while (e->ev_spill.size() < 4 * n_chunks + 1) {  // (kept for the engine's lifetime)
     hipEvent_t v = nullptr;
@@ -2350,7 +2200,6 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   if (e->cfg.shard_world > 1 || e->cfg.pairwise_del)  // k_count adds with integer atomics
     HIPCHK(hipMemsetAsync(d_cnt, 0, (uint64_t)n_mat * n_pairs * sizeof(unsigned long long), e->st));
   HIPCHK(hipEventRecord(e->ev[1], e->st));
-  double *C = e->slab_boot;
   uint64_t units_done = 0;
   for (uint64_t c = 0; c < n_chunks; c++) {
     const uint64_t s_lo = c * chunk_sites, s_hi = std::min(s_end, s_lo + chunk_sites);
@@ -2385,7 +2234,7 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   if (!e->cfg.pairwise_del) {  // every pair of matrix r counts the sites the matrix visits: one launch for the job
     visited.resize(n_mat);
     for (uint32_t r = 0; r < n_mat; r++) visited[r] = lead && r == 0 ? g.n_sites : drawn[r - (lead ? 1u : 0u)];
-    rc = ensure_cap(e, &e->d_drawn, &e->cap_drawn, (uint64_t)n_mat);
+    rc = e->d_drawn.ensure(e, (uint64_t)n_mat);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(e->d_drawn, visited.data(), (uint64_t)n_mat * 8, hipMemcpyHostToDevice, e->st));
     ngd_launch_fill_cnt(e->st, g, e->d_tiles, e->n_tiles, 0, e->d_drawn, n_mat, d_cnt);
@@ -2450,13 +2299,8 @@ static int run_impl(ngd_engine *e, const uint64_t *block_maps, const uint32_t *m
   // multiplicities of matrices lead..: counted into (or copied behind) a leading all-ones row, which stands for
   // the full data set when the blocks cover every site
   const uint64_t need = (uint64_t)(n_rep + lead) * n_blocks;
-  if (block_maps || lead) {
-    if (need > e->cap_h_mult) {  // pinned and kept: a replicate at block size 1 counts a million draws per call
-      if (e->h_mult) { HIPCHK(hipHostFree(e->h_mult)); e->h_mult = nullptr; e->cap_h_mult = 0; }
-      HIPCHK(hipHostMalloc((void **)&e->h_mult, need * sizeof(uint32_t), hipHostMallocDefault));
-      e->cap_h_mult = need;
-    }
-  }
+  if (block_maps || lead)  // pinned and kept: a replicate at block size 1 counts a million draws per call
+    if (int rc = e->h_mult.ensure(need)) return rc;
   const uint32_t *mult = mult_in;  // [n_rep][n_blocks]
   if (block_maps) {
     uint32_t *base = e->h_mult + (uint64_t)lead * n_blocks;
@@ -2570,14 +2414,19 @@ static int batch_buffers(ngd_engine *e, uint32_t n_rep) {
   e->n_batch_valid = 0;  // (the buffers may be freed and grown below; a failed call leaves nothing to fetch)
   HIPCHK(hipSetDevice(e->device));
   const uint64_t need = (uint64_t)n_rep * ngd_n_pairs(e->g.n_ind);
-  if (need <= e->cap_batch) return NGD_OK;
-  uint64_t cap_s = e->cap_batch, cap_c = e->cap_batch;
-  int rc = ensure_cap(e, &e->d_bsum, &cap_s, need);
-  if (rc) { e->cap_batch = 0; return rc; }
-  rc = ensure_cap(e, &e->d_bcnt, &cap_c, need);
-  if (rc) { e->cap_batch = 0; return rc; }
-  e->cap_batch = need;
-  return NGD_OK;
+  if (int rc = e->d_bsum.ensure(e, need)) return rc;
+  return e->d_bcnt.ensure(e, need);
+}
+
+// the host-pointer entry points: into the engine's own result arrays (n_batch = 0: one matrix) or its batch buffers, then out
+static int run_to_host(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, uint32_t n_rep, bool lead_full,
+                       uint64_t n_blocks, uint64_t block_size, uint32_t n_batch, double *sum, uint64_t *cnt) {
+  if (n_batch)
+    if (int rc = batch_buffers(e, n_batch)) return rc;
+  double *d_sum = n_batch ? e->d_bsum : e->d_sum;
+  unsigned long long *d_cnt = n_batch ? e->d_bcnt : e->d_cnt;
+  if (int rc = run_impl(e, block_maps, mult, n_rep, lead_full, n_blocks, block_size, d_sum, d_cnt)) return rc;
+  return copy_out(e, n_batch ? n_batch : 1, d_sum, d_cnt, sum, cnt);
 }
 
 int ngd_run_device(ngd_engine *e, const uint64_t *block_map, uint64_t n_blocks, uint64_t block_size,
@@ -2596,17 +2445,13 @@ int ngd_run_mult_device(ngd_engine *e, const uint32_t *mult, uint64_t n_blocks, 
 int ngd_run_mult(ngd_engine *e, const uint32_t *mult, uint64_t n_blocks, uint64_t block_size, double *sum,
                  uint64_t *cnt) {
   if (!e || !mult) return fail(NGD_E_INVALID, "ngd_run_mult: null argument");
-  int rc = run_impl(e, nullptr, mult, 1, false, n_blocks, block_size, e->d_sum, e->d_cnt);
-  if (rc) return rc;
-  return copy_out(e, 1, e->d_sum, e->d_cnt, sum, cnt);
+  return run_to_host(e, nullptr, mult, 1, false, n_blocks, block_size, 0, sum, cnt);
 }
 
 int ngd_run(ngd_engine *e, const uint64_t *block_map, uint64_t n_blocks, uint64_t block_size, double *sum,
             uint64_t *cnt) {
   if (!e) return fail(NGD_E_INVALID, "ngd_run: null engine");
-  int rc = run_impl(e, block_map, nullptr, block_map ? 1 : 0, false, n_blocks, block_size, e->d_sum, e->d_cnt);
-  if (rc) return rc;
-  return copy_out(e, 1, e->d_sum, e->d_cnt, sum, cnt);
+  return run_to_host(e, block_map, nullptr, block_map ? 1 : 0, false, n_blocks, block_size, 0, sum, cnt);
 }
 
 int ngd_run_batch_device(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks,
@@ -2624,21 +2469,13 @@ int ngd_run_mult_batch_device(ngd_engine *e, const uint32_t *mult, uint32_t n_re
 int ngd_run_batch(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                   double *sum, uint64_t *cnt) {
   if (!e || !block_maps || !n_rep) return fail(NGD_E_INVALID, "ngd_run_batch: null argument");
-  int rc = batch_buffers(e, n_rep);
-  if (rc) return rc;
-  rc = run_impl(e, block_maps, nullptr, n_rep, false, n_blocks, block_size, e->d_bsum, e->d_bcnt);
-  if (rc) return rc;
-  return copy_out(e, n_rep, e->d_bsum, e->d_bcnt, sum, cnt);
+  return run_to_host(e, block_maps, nullptr, n_rep, false, n_blocks, block_size, n_rep, sum, cnt);
 }
 
 int ngd_run_mult_batch(ngd_engine *e, const uint32_t *mult, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                        double *sum, uint64_t *cnt) {
   if (!e || !mult || !n_rep) return fail(NGD_E_INVALID, "ngd_run_mult_batch: null argument");
-  int rc = batch_buffers(e, n_rep);
-  if (rc) return rc;
-  rc = run_impl(e, nullptr, mult, n_rep, false, n_blocks, block_size, e->d_bsum, e->d_bcnt);
-  if (rc) return rc;
-  return copy_out(e, n_rep, e->d_bsum, e->d_bcnt, sum, cnt);
+  return run_to_host(e, nullptr, mult, n_rep, false, n_blocks, block_size, n_rep, sum, cnt);
 }
 
 int ngd_run_job_device(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks,
@@ -2651,11 +2488,7 @@ int ngd_run_job_device(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep
 int ngd_run_job(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                 double *sum, uint64_t *cnt) {
   if (!e || (n_rep && !block_maps)) return fail(NGD_E_INVALID, "ngd_run_job: null argument");
-  int rc = batch_buffers(e, n_rep + 1);
-  if (rc) return rc;
-  rc = run_impl(e, block_maps, nullptr, n_rep, n_rep != 0, n_blocks, block_size, e->d_bsum, e->d_bcnt);
-  if (rc) return rc;
-  return copy_out(e, n_rep + 1, e->d_bsum, e->d_bcnt, sum, cnt);
+  return run_to_host(e, block_maps, nullptr, n_rep, n_rep != 0, n_blocks, block_size, n_rep + 1, sum, cnt);
 }
 
 // A whole job AND the tail of gen_dist() (ngsDist.cpp:372-401) in one call: the sums (and, --pairwise_del, the counts) leave
@@ -2681,17 +2514,9 @@ static int run_dist(ngd_engine *e, const uint64_t *block_maps, const uint32_t *m
   const uint64_t cells = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
   if (!o.st) HIPCHK(hipStreamCreateWithFlags(&o.st, hipStreamNonBlocking));
   if (!o.st2) HIPCHK(hipStreamCreateWithFlags(&o.st2, hipStreamNonBlocking));
-  if (cells > o.cap_sum) {
-    if (o.h_sum) { HIPCHK(hipHostFree(o.h_sum)); o.h_sum = nullptr; o.cap_sum = 0; }
-    HIPCHK(hipHostMalloc((void **)&o.h_sum, std::max<uint64_t>(1, cells) * sizeof(double), hipHostMallocDefault));
-    o.cap_sum = cells;
-  }
+  if ((rc = o.h_sum.ensure(cells))) return rc;
   o.pdel = e->cfg.pairwise_del != 0;
-  if (o.pdel && cells > o.cap_cnt) {
-    if (o.h_cnt) { HIPCHK(hipHostFree(o.h_cnt)); o.h_cnt = nullptr; o.cap_cnt = 0; }
-    HIPCHK(hipHostMalloc((void **)&o.h_cnt, std::max<uint64_t>(1, cells) * sizeof(uint64_t), hipHostMallocDefault));
-    o.cap_cnt = cells;
-  }
+  if (o.pdel && (rc = o.h_cnt.ensure(cells))) return rc;
   o.n_mat = n_mat;
   o.queued = 0;
   o.n_used = 0;
@@ -2801,9 +2626,9 @@ static int windows_fixup(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, 
   hipEvent_t t0 = e->ev[0], t1 = e->ev[1];  // (the batch's own timings have been read)
   HIPCHK(hipEventRecord(t0, e->st));
   if (!tiles.empty()) {
-    int rc = ensure_cap(e, &e->d_fixtiles, &e->cap_fixtiles, tiles.size());
+    int rc = e->d_fixtiles.ensure(e, tiles.size());
+    if (!rc) rc = e->d_fixtparts.ensure(e, (uint64_t)NGD_FIX_CAP * 256);
     if (rc) return rc;
-    if ((rc = ensure_cap(e, &e->d_fixtparts, &e->cap_fixtparts, (uint64_t)NGD_FIX_CAP * 256))) return rc;
     HIPCHK(hipMemcpy(e->d_fixtiles, tiles.data(), tiles.size() * sizeof(ngd_fix_tile), hipMemcpyHostToDevice));
   }
   const uint32_t n1 = (uint32_t)singles.size();
@@ -2877,8 +2702,8 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       return NGD_OK;
     }
   // (the windowed call takes the scratch of the bootstrap's per-block partial results: their cache is dropped)
-  e->boot_B = e->boot_blocks = 0;
-  e->cnt_B = e->cnt_blocks = 0;
+  DevBuf<double> &seg_sums = e->blk.borrow_sums();
+  DevBuf<uint32_t> &seg_cnt = e->blk.borrow_counts();
   const ngd_fix_flags ff{e->d_fixlist, e->d_fixcount, e->d_fixseen, e->fix_cap};
   uint64_t batch = 0;
   for (uint64_t a = 0; a < n_win; batch++) {
@@ -2944,23 +2769,23 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       wt[2 * (w - a)] = f | (l << 32);
       wt[2 * (w - a) + 1] = hi[w] - lo[w];
     }
-    int rc = ensure_cap(e, &e->slab_boot, &e->slab_boot_elems, n_ks * plane);
-    if (!rc && pdel) rc = ensure_cap(e, &e->cnt_boot, &e->cnt_boot_elems, n_seg * plane);
-    if (!rc && !em) rc = ensure_cap(e, &e->d_wslice, &e->cap_wslice, w_total * 4);
-    if (!rc) rc = ensure_cap(e, &e->d_segtab, &e->cap_segtab, tab.size());
-    if (!rc) rc = ensure_cap(e, &e->d_wintab, &e->cap_wintab, wt.size());
+    int rc = seg_sums.ensure(e, n_ks * plane);
+    if (!rc && pdel) rc = seg_cnt.ensure(e, n_seg * plane);
+    if (!rc && !em) rc = e->blk.wslice.ensure(e, w_total * 4);
+    if (!rc) rc = e->d_segtab.ensure(e, tab.size());
+    if (!rc) rc = e->d_wintab.ensure(e, wt.size());
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev[0], e->st));
     HIPCHK(hipMemcpyAsync(e->d_segtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, e->st));
     HIPCHK(hipMemcpyAsync(e->d_wintab, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, e->st));
-    if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->d_wslice);
+    if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
     HIPCHK(hipEventRecord(e->ev[1], e->st));
     if (em)
       ngd_launch_accum_em_table_segs(e->st, g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64,
-                                     (uint32_t)n_seg, e->d_segtab, e->slab_boot, e->d_emcnt);
+                                     (uint32_t)n_seg, e->d_segtab, seg_sums, e->d_emcnt);
     else
-      ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB, e->d_wslice, nullptr, e->d_jobs, e->n_wg, e->exact_shapes,
-                            e->wg_waves, (uint32_t)n_ks, 0, g.n_kg, 0, 1, e->slab_boot, e->d_clk, 0, 0, e->d_segtab);
+      ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB, e->blk.wslice, nullptr, e->d_jobs, e->n_wg, e->exact_shapes,
+                            e->wg_waves, (uint32_t)n_ks, 0, g.n_kg, 0, 1, seg_sums, e->d_clk, 0, 0, e->d_segtab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[2], e->st));
     double *bs = d_sum + a * n_pairs;
@@ -2969,13 +2794,13 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
       HIPCHK(hipMemsetAsync(e->d_fixseen, 0, (n_pairs / 32 + 1) * sizeof(uint32_t), e->st));
     }
-    ngd_launch_reduce_band(e->st, g, e->slab_boot, nullptr, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, bs,
+    ngd_launch_reduce_band(e->st, g, seg_sums, nullptr, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, bs,
                            pdel ? nullptr : bc, fix && !pdel ? &ff : nullptr);
     HIPCHK(hipEventRecord(e->ev[3], e->st));
     e->win_info.band_launches++;
     if (pdel) {
-      ngd_launch_count_blocks(e->st, g, e->mask, 0, (uint32_t)n_seg, e->d_tiles16, e->n_tiles16, e->cnt_boot, e->d_segtab);
-      ngd_launch_reduce_band(e->st, g, nullptr, e->cnt_boot, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, nullptr, bc, nullptr);
+      ngd_launch_count_blocks(e->st, g, e->mask, 0, (uint32_t)n_seg, e->d_tiles16, e->n_tiles16, seg_cnt, e->d_segtab);
+      ngd_launch_reduce_band(e->st, g, nullptr, seg_cnt, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, nullptr, bc, nullptr);
       e->win_info.band_launches++;
       if (fix) ngd_launch_fix_flag(e->st, g, bs, bc, (uint32_t)nb, e->d_tiles, e->n_tiles, ff);
     }
@@ -3012,7 +2837,7 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   if (slab && !budget) {  // the rule of the bootstrap's per-block partial results
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    budget = (uint64_t)((free_b + e->slab_boot_elems * 8 + e->cnt_boot_elems * 4) / 100 * 85);
+    budget = (uint64_t)((free_b + e->blk.bytes()) / 100 * 85);
   }
   if (slab && e->opt_win_plan == 0) {
     // auto: the cheaper plan by estimate (the rates partials_impl uses) -- one pass over the sites the
@@ -3034,7 +2859,7 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     const double rate = em ? 2.22e8 : 1.05e10, np = (double)e->n_owned_pairs;
     const double plane_b = (double)e->g.n_pad * e->g.n_pad * 8;
     const double need = (double)windows_batch_bytes(e, std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win);
-    const double have = (double)e->slab_boot_elems * 8 + (double)e->cnt_boot_elems * 4;
+    const double have = (double)e->blk.bytes();
     const double t_slab = np * (double)covered / rate + (double)(n_bnd + 2 * n_win) * np * 8 / 4e9 +
                           (need > have ? (need - have) * 12e-9 : 0.0);
     const double t_pass = np * (double)sum_len / (0.75 * rate) + 0.1 * (double)n_win;
@@ -3193,10 +3018,7 @@ int ngd_set_option(ngd_engine *e, int option, uint64_t value) {
 
 int ngd_drop_caches(ngd_engine *e) {
   if (!e) return fail(NGD_E_INVALID, "ngd_drop_caches: null engine");
-  e->boot_B = 0;
-  e->boot_blocks = 0;
-  e->cnt_B = 0;
-  e->cnt_blocks = 0;
+  e->blk.drop();
   e->em_batch_nofit_elems = 0;  // (what did not fit may fit now: the partial results' slab is the same scratch)
   return NGD_OK;
 }
