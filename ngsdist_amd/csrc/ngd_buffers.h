@@ -1,4 +1,4 @@
-// ngd_buffers.h -- the owning types of the engine's memory (engine.hip): a device allocation (hipMalloc, or an address
+// ngd_buffers.h -- the owning types of the engine's memory (ngd_engine.h): a device allocation (hipMalloc, or an address
 // range whose physical pieces arrive behind ngd_create), a pinned host allocation, a slot of the staging ring.  Each frees
 // itself; a device buffer also keeps the engine's ngd_device_bytes() figure, by its own size.
 #pragma once
@@ -15,9 +15,12 @@
 
 #include "../../include/ngsdist_amd.h"
 
-static thread_local std::string g_err;
+#pragma GCC visibility push(hidden)
 
-static int fail(int code, const std::string &msg) {
+// ONE error state for the library's every unit (ngd_last_error(), engine.hip)
+inline thread_local std::string g_err;
+
+inline int fail(int code, const std::string &msg) {
   g_err = msg;
   return code;
 }
@@ -38,7 +41,7 @@ static int fail(int code, const std::string &msg) {
 // Images and slabs of a GiB and more: an address range reserved at once, its physical memory created, mapped and
 // zeroed 256 MiB at a time by a thread of the engine's own (dev_alloc_pieces, piece_worker) -- the staged load starts at
 // once and waits, piece by piece, only for the part of an image it is about to write (piece_wait_sites).
-static const size_t kPiece = (size_t)256 << 20;
+inline constexpr size_t kPiece = (size_t)256 << 20;
 enum PieceKind { PIECE_FRAG, PIECE_SITE_MAJOR, PIECE_WHOLE };  // how far into the range a site reaches
 struct PieceRange {
   void *va = nullptr;
@@ -50,7 +53,7 @@ struct PieceRange {
 };
 
 // (the piece thread has been joined; an empty range asks nothing more of piece_worker or piece_wait_sites)
-static void release_pieces(PieceRange &r) {
+inline void release_pieces(PieceRange &r) {
   for (size_t c = 0; c < r.n_mapped; c++) (void)hipMemUnmap((char *)r.va + c * kPiece, std::min(kPiece, r.size - c * kPiece));
   for (auto &h : r.hs) (void)hipMemRelease(h);
   if (r.va) (void)hipMemAddressFree(r.va, r.size);
@@ -67,7 +70,7 @@ struct ngd_mem {
   std::vector<std::unique_ptr<PieceRange>> piece_ranges;
 };
 
-static int dev_malloc(ngd_mem *m, void **out, uint64_t bytes) {
+inline int dev_malloc(ngd_mem *m, void **out, uint64_t bytes) {
   // NGD_TRACE_ALLOC=1: what every allocation of 64 MiB and more costs (the driver clears memory other processes have used
   // as it hands it out: seconds for tens of GB on a device that has just been busy, DESIGN.md section 3 "K0")
   static const bool trace = getenv("NGD_TRACE_ALLOC") != nullptr;
@@ -190,3 +193,5 @@ struct RingSlot {
     if (k0_done) (void)hipEventDestroy(k0_done);
   }
 };
+
+#pragma GCC visibility pop

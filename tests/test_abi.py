@@ -218,3 +218,39 @@ def test_finish_division_is_vectorised_and_exact():
                     got = N.finish(s, c, tot, 0)
                     want = s / (np.float64(tot) if tot else c.astype(np.float64))
                 assert np.array_equal(got.view(np.uint64), np.asarray(want).view(np.uint64)), (n, cmax, tot)
+
+
+def test_last_error_is_one_state_for_every_translation_unit(lib):
+    """The engine is several translation units (csrc/engine*.hip) and ngd_last_error() is defined in one of them, engine.hip:
+    a failure raised in any other must be readable through it (an error state per unit reads back empty).  Every call below
+    is refused on its arguments, before HIP is touched."""
+    from ngsdist_amd import _lib
+    INVALID = -1
+
+    def last():
+        return lib.ngd_last_error().decode()
+
+    # engine_create.hip
+    cfg = _lib.NgdConfig()
+    cfg.n_ind, cfg.n_sites = 1, 10
+    eng = C.c_void_p()
+    assert lib.ngd_create(C.byref(cfg), C.byref(eng)) == INVALID and not eng.value
+    assert "ngd_create" in last() and "2 individuals" in last()
+    # engine_stage.hip
+    assert lib.ngd_upload_sites(None, None, 0, 0) == INVALID
+    assert last() == "upload: null argument"
+    assert lib.ngd_stage_acquire(None, None, None) == INVALID
+    assert "ngd_stage_acquire" in last()
+    # engine_windows.hip
+    assert lib.ngd_run_windows(None, None, None, 0, None, None) == INVALID
+    assert last() == "ngd_run_windows: null engine"
+    # engine_out.hip (run_dist, behind the shim in engine.hip)
+    assert lib.ngd_run_job_dist(None, None, 0, 0, 0, 0, 0, None) == INVALID
+    assert last() == "ngd_run_job_dist: null argument"
+    # engine_plans.hip (run_impl, behind the shim)
+    out = (C.c_double * 1)()
+    assert lib.ngd_run_device(None, None, 0, 0, out, out) == INVALID
+    assert last() == "ngd_run: null engine"
+    # ... and engine.hip itself
+    assert lib.ngd_set_option(None, 0, 0) == INVALID
+    assert last() == "ngd_set_option: null engine"

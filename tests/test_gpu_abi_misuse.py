@@ -230,7 +230,7 @@ def test_a_block_shape_the_kernel_does_not_list_fails_the_run(form, shape, monke
 
 def test_device_memory_that_runs_out_behind_ngd_create_is_reported_by_the_first_call_that_needs_it(monkeypatch):
     """Images of a GiB and more are address ranges whose memory a thread of the engine maps 256 MiB at a time behind ngd_create
-    (engine.hip dev_alloc_pieces / piece_worker).  A piece that cannot be had -- forced here through the test hook
+    (ngd_engine.h dev_alloc_pieces / engine_mem.hip piece_worker).  A piece that cannot be had -- forced here through the test hook
     NGD_TEST_FAIL_PIECE -- is reported as NGD_E_NOMEM by the first call that needs the memory: the staged upload whose sites
     reach the missing part (the pieces before it serve the sites before it), ngd_upload_*, ngd_commit, ngd_synth_fill; the
     engine is destroyed cleanly and the device memory comes back."""

@@ -149,7 +149,7 @@ def test_one_image_engine_recomputes_a_large_data_set_of_clones_whatever_it_cost
     above the 4.1e9 at which the engines of rounds 4-5 gave up on ALL of them and returned the one-image sums (absolute
     error 4e-17 per site, i.e. 1e-3 relative on these sums of ~1e-8 per site).  The default engine now recomputes every one:
     1e-9 relative against the two-image engine on every pair and against the oracle on the pairs of 12 individuals -- by ONE
-    more pass in the two-image arithmetic over scratch images (engine.hip fixup_by_pass), since 3916 tiles cost more."""
+    more pass in the two-image arithmetic over scratch images (engine_fixup.hip fixup_by_pass), since 3916 tiles cost more."""
     n_ind, n_sites, eps, chunk = 1400, 250_000, 1e-9, 25_000
     sub = np.array([0, 1, 15, 16, 17, 200, 640, 641, 900, 1398, 1399, 777])
     keep = []

@@ -57,7 +57,7 @@ def plant_scattered_clones(p, groups, seed):
 @pytest.mark.parametrize("pairwise_del", [False, True])
 def test_one_image_engine_windows_with_and_without_pairwise_del(pairwise_del):
     """500 individuals: the default engine holds ONE image in congruent coordinates, and every window's nearly identical
-    pairs go through the fix-up (engine.hip windows_fixup), under --pairwise_del noted by k_fix_flag from their counts
+    pairs go through the fix-up (engine_windows.hip windows_fixup), under --pairwise_del noted by k_fix_flag from their counts
     across the batch's windows.  One clone of each group misses sites [1000, 1100): under --pairwise_del its pairs' counts
     are not the window's length there, without it those windows hold no nearly identical pair of it."""
     n_ind, n_sites = 500, 3000

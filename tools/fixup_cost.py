@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/fixup_cost.py [n_ind n_sites] -- what the fix-up pass of a one-image engine costs on a data set of copies of one
 individual: every pair noted and recomputed with the two-operand arithmetic (fixup.hip tile by tile, or -- where the tiles
-would cost more -- engine.hip fixup_by_pass: the whole matrix once more over scratch images); prints the pass's device time,
+would cost more -- engine_fixup.hip fixup_by_pass: the whole matrix once more over scratch images); prints the pass's device time,
 which way it went, and the worst relative difference from a two-image engine on the same data."""
 import os
 import sys

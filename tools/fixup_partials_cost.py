@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/fixup_partials_cost.py [n_ind n_sites block n_rep] -- what the fix-up pass of a bootstrap job by per-block partial results costs on
 a data set of copies of one individual (every pair noted): tile by tile, or the whole slab once more in the two-operand arithmetic
-(engine.hip fixup_partials_by_pass); both routes forced through the test hook, then the engine's own choice; worst relative difference
+(engine_fixup.hip fixup_partials_by_pass); both routes forced through the test hook, then the engine's own choice; worst relative difference
 from a two-image engine on the same data."""
 import os
 import sys

@@ -81,7 +81,7 @@ for case in range(first, first + n_cases):
                             if partials == 1 and not one_call_ok:
                                 # boot_partials = 1 lets the engine serve the first calls of a geometry WITHOUT the per-block
                                 # partial results while their slab would cost more to allocate than it has saved so far
-                                # (engine.hip partials_impl, "rent"): two calls of the same job may then take different plans
+                                # (engine_plans.hip partials_impl, "rent"): two calls of the same job may then take different plans
                                 # and agree to rounding, not bit for bit -- ngd_run_job twice does the same
                                 fin = np.isfinite(want)
                                 one_call_ok = np.array_equal(np.isfinite(got), fin) and bool(
