@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define NGD_ABI_VERSION 6 /* 6: ngd_run_job_dist, ngd_run_batch_dist, ngd_run_mult_batch_dist; 5: ngd_finish_stream, ngd_fixup_info.by_pass, NGD_OPT_STAGE_PIECE_MIB / _STAGE_RING / _EAGER_FULL, NGD_OPT_FIXUP_WORK 0 = no budget (every noted pair is recomputed); 4: ngd_last_spill_timing, ngd_last_fixup, ngd_image_mode, ngd_config.single_image 0 = auto / 3 = two images; 3: ngd_config.single_image / second_image_mib (were reserved, zero), ngd_fetch_matrix, ngd_score_congruence */
+#define NGD_ABI_VERSION 6 /* 6: ngd_run_job_dist, ngd_run_batch_dist, ngd_run_mult_batch_dist (and, added under 6: ngd_run_windows*, ngd_last_windows, ngd_window_ranges, ngd_run_windows_job / _job_device / _job_dist); 5: ngd_finish_stream, ngd_fixup_info.by_pass, NGD_OPT_STAGE_PIECE_MIB / _STAGE_RING / _EAGER_FULL, NGD_OPT_FIXUP_WORK 0 = no budget (every noted pair is recomputed); 4: ngd_last_spill_timing, ngd_last_fixup, ngd_image_mode, ngd_config.single_image 0 = auto / 3 = two images; 3: ngd_config.single_image / second_image_mib (were reserved, zero), ngd_fetch_matrix, ngd_score_congruence */
 
 #define NGD_OK 0
 #define NGD_E_INVALID (-1)  /* bad argument / bad state                    */
@@ -432,6 +432,48 @@ int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t
  * ngd_run_job_dist): dist is [n_win][n_pairs] host memory.  NGD_E_MODEL for evol_model > 2 before anything is launched. */
 int ngd_run_windows_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
                          uint64_t evol_model, double *dist);
+/* Bootstrap replicates INSIDE every window: for each window exactly what the reference prints when run on a file cut down to
+ * the window's sites with --n_boot_rep n_rep --boot_block_size block_size (the replicate loop ngsDist.cpp:217-289, the
+ * truncation :236, rnd_map_data :416-437).  The windows of a call have ONE length W (NGD_E_INVALID otherwise): every cut-down
+ * run seeds the generator anew, so all of them draw the same n_rep block maps, block_maps [n_rep][n_blocks] with
+ * n_blocks = W / block_size rounded down (ngd_boot_block_map from a fresh state, n_rep times).  Outputs are
+ * [n_win][n_rep + 1][n_pairs]: matrix 0 of a window is its full-data matrix (ngd_run_windows), matrix r visits the sites
+ * [lo + m q, lo + (m + 1) q), m = block_maps[r - 1][b], once for each b; the tail [lo + n_blocks q, hi) is matrix 0's alone.  A
+ * replicate's count is n_blocks * block_size, under --pairwise_del the multiplicity-weighted number of valid sites, exactly.
+ * n_rep = 0 is ngd_run_windows*, bit for bit (block_maps, n_blocks, block_size are then not read).
+ * NGD_E_INVALID: anything ngd_run_windows refuses (an engine that owns a share of the pairs included), windows of unequal
+ * length, block_size 0, n_blocks != W / block_size, a map entry >= n_blocks, null maps -- and W < block_size (no block: the
+ * "empty bootstrap geometry" ngd_run_job refuses on an engine of W sites; a host prints the replicates of such a window as
+ * 0 / 0 itself, ngsDist.cpp:236).
+ * The plans are those of ngd_run_windows (NGD_OPT_WIN_PLAN, NGD_OPT_WIN_MAX_BYTES; 2 returns NGD_E_INVALID / NGD_E_NOMEM alike):
+ *  - unit slab (where the segment slab applies): the block boundaries lo + b q and the ends hi of a batch of windows cut
+ *    the sites into the slices of ONE accumulation pass for ALL replicates of all windows -- where block_size divides the
+ *    windows' step a block is one slice and overlapping windows share all of them, else a block is a few slices --; a
+ *    window's replicates are the banded and weighted reduction of its slices (32 replicates per read of them), counts under
+ *    --pairwise_del the same in integers.  Matrix 0 of every window is computed by the segment-slab plan of
+ *    ngd_run_windows_device() on the same list of windows, from the windows' own segments, and carries its bits (finer
+ *    slices would add the same terms in another order): one more pass over the covered sites and one banded reduction.  A non-finite partial result (an all-zero individual on the EM path)
+ *    reaches exactly the matrices that visit its sites.  One-image engines recompute the noted pairs' entries of the slab with
+ *    the two-operand arithmetic and reduce again: 1e-9 relative at any distance in every matrix (ngd_last_fixup,
+ *    ngd_windows_info.fixup_pairs); matrix 0 is fixed as ngd_run_windows fixes it;
+ *  - per window (every other engine; windows that do not fit the budget; where cheaper by estimate -- block size 1):
+ *    ngd_run_mult_batch()'s plans on multiplicity vectors over blocks of B = gcd(lo, block_size, hi) sites (hi too, so that
+ *    the window's end is a block boundary for matrix 0), one call per window.  The vectors count blocks from the engine's
+ *    site 0: the host builds (n_rep + 1) x hi / B uint32 entries per window -- at block size 1 and a window near site 1e6
+ *    with 100 replicates 400 MB, built anew for every window; a plan for a few windows or coarse blocks.
+ * Sums of the two plans, and of the cut-down data set's ngd_run_job(), agree to rounding (<= 1e-12 relative; <= 1e-9 against
+ * the reference's order of additions), counts exactly.  ngd_last_windows() tells which plan ran. */
+int ngd_run_windows_job(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, const uint64_t *block_maps,
+                        uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, double *sum, uint64_t *cnt);
+int ngd_run_windows_job_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                               const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, void *d_sum,
+                               void *d_cnt);
+/* ... and the tail of gen_dist() on every matrix (as ngd_run_windows_dist): dist is [n_win][n_rep + 1][n_pairs] host memory;
+ * the windows go through the engine's batch buffers in groups of at least one.  NGD_E_MODEL for evol_model > 2 and
+ * NGD_E_INVALID for tot_sites with --pairwise_del, both before anything is launched. */
+int ngd_run_windows_job_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                             const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                             uint64_t tot_sites, uint64_t evol_model, double *dist);
 /* What the last ngd_run_windows* call did */
 typedef struct ngd_windows_info {
   uint64_t segments;       /* slices of the segment-slab plan's accumulation passes, summed over its batches          */

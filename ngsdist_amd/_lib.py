@@ -74,7 +74,7 @@ EXPORTS = [
     "ngd_run_mult_batch_device", "ngd_run_job", "ngd_run_job_device", "ngd_run_job_dist", "ngd_run_batch_dist", "ngd_run_mult_batch_dist", "ngd_fetch_matrix", "ngd_drop_caches", "ngd_set_option", "ngd_last_timing", "ngd_last_spill_timing", "ngd_last_fixup", "ngd_image_mode", "ngd_last_shader_clock", "ngd_last_em_work", "ngd_finish", "ngd_finish_stream", "ngd_format_matrix", "ngd_taus_seed", "ngd_taus_get",
     "ngd_taus_uniform", "ngd_boot_block_map", "ngd_n_pairs", "ngd_pair_index", "ngd_device_bytes", "ngd_device_memory", "ngd_shard_of_pair", "ngd_shard_map",
     "ngd_score_congruence", "ngd_run_windows", "ngd_run_windows_device", "ngd_run_windows_dist", "ngd_last_windows",
-    "ngd_window_ranges",
+    "ngd_window_ranges", "ngd_run_windows_job", "ngd_run_windows_job_device", "ngd_run_windows_job_dist",
 ]
 
 _lib = None
@@ -166,6 +166,9 @@ def load():
     L.ngd_run_windows_device.argtypes = [vp, u64p, u64p, u64, vp, vp]
     L.ngd_run_windows_dist.argtypes = [vp, u64p, u64p, u64, u64, u64, dp]
     L.ngd_last_windows.argtypes = [vp, C.POINTER(NgdWindowsInfo)]
+    L.ngd_run_windows_job.argtypes = [vp, u64p, u64p, u64, u64p, C.c_uint32, u64, u64, dp, u64p]
+    L.ngd_run_windows_job_device.argtypes = [vp, u64p, u64p, u64, u64p, C.c_uint32, u64, u64, vp, vp]
+    L.ngd_run_windows_job_dist.argtypes = [vp, u64p, u64p, u64, u64p, C.c_uint32, u64, u64, u64, u64, dp]
     L.ngd_window_ranges.argtypes = [u32p, u64, u64, u64, u64p, u64p, u64]
     L.ngd_window_ranges.restype = C.c_int64
     L.ngd_device_bytes.argtypes = [vp]

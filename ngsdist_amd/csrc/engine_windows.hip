@@ -1,7 +1,8 @@
-// engine_windows.hip -- the windowed calls: their two plans, the fix-up of a batch of windows, the host-memory forms.
+// engine_windows.hip -- the windowed calls: their two plans, the fix-up of a batch of windows, the host-memory forms; and the
+// jobs that draw bootstrap replicates inside every window.
 #include <functional>
 #include <numeric>
-#include <set>
+#include <iterator>
 
 #include "ngd_engine.h"
 
@@ -17,6 +18,25 @@
 //    under --pairwise_del from per-segment popcounts the same way.  The EM of a (pair, site) runs on that site of the two
 //    individuals alone, so a term does not depend on the window it is added to.  A long EM segment is cut into pieces (more
 //    slices of the same table) so that the launch has about as many workgroups as a plain pass.
+
+// ---- bootstrap replicates inside the windows (ngd_run_windows_job*) ----
+// Every window of a call has one length W and draws the same block maps (a run on the cut-down file seeds the generator
+// anew): matrix 0 of a window is its full-data matrix, matrix r visits block map[r][b] of the window -- sites
+// [lo + map[r][b] q, lo + (map[r][b] + 1) q) -- once for each b < n_blocks = W / q (ngsDist.cpp:217-289, :236, :416-437); the
+// tail [lo + n_blocks q, hi) is matrix 0's alone.  The same two plans:
+//  * unit slab (where the segment slab applies): the boundaries of a batch are its windows' block boundaries lo + b q and
+//    ends hi, the covered intervals between them the slices of ONE accumulation pass -- where q divides the step,
+//    overlapping windows share every slice and a block is one slice, else a block is a few consecutive slices.  Matrix 0 of
+//    every window comes from the banded reduction as before, the replicates from the banded and weighted one (reduce.hip
+//    k_reduce_band_w), counts under --pairwise_del from per-slice popcounts by the integer forms of both;
+//  * per window: one run_impl() per window on multiplicity vectors over blocks of gcd(lo, q, hi) sites counted from the
+//    engine's site 0 -- vector 0 is 1 on the window's sites, vector r the multiplicities of replicate r.  Serves every
+//    kernel, windows that do not fit the budget, and blocks so small that a slice per block loses.
+struct WinBoot {
+  uint32_t n_rep;
+  uint64_t n_blocks, q;
+  const uint32_t *mult;  // [n_rep][n_blocks]: draws of block b in replicate r
+};
 
 static int windows_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const char *who) {
   if (!e) return fail(NGD_E_INVALID, std::string(who) + ": null engine");
@@ -53,10 +73,102 @@ static int windows_by_pass(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
   return NGD_OK;
 }
 
+// the per-window plan of a job: window w's n_rep + 1 matrices by the replicate loop's plans on multiplicity vectors
+static int windows_job_by_pass(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot &bt,
+                               double *d_sum, unsigned long long *d_cnt) {
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = (uint64_t)bt.n_rep + 1;
+  std::vector<uint32_t> mult;
+  for (uint64_t w = 0; w < n_win; w++) {
+    const uint64_t B = std::gcd(std::gcd(lo[w], bt.q), hi[w]), n_eb = hi[w] / B, per = bt.q / B, first = lo[w] / B;
+    mult.assign(n_mat * n_eb, 0u);
+    std::fill(mult.begin() + first, mult.begin() + n_eb, 1u);
+    for (uint32_t r = 0; r < bt.n_rep; r++)
+      for (uint64_t b = 0; b < bt.n_blocks; b++) {
+        const uint32_t m = bt.mult[(uint64_t)r * bt.n_blocks + b];
+        if (m) std::fill_n(mult.begin() + (r + 1) * n_eb + first + b * per, per, m);
+      }
+    const ngd_fixup_info fi = e->fix_info;
+    int rc = run_impl(e, nullptr, mult.data(), (uint32_t)n_mat, false, n_eb, B, d_sum + w * n_mat * n_pairs,
+                      d_cnt + w * n_mat * n_pairs);
+    if (rc) return rc;
+    e->win_info.ms += e->timing.ms_total + e->fix_info.ms;
+    e->win_info.fixup_pairs += e->fix_info.recomputed;
+    // (run_impl reports its own call: the job's report is the sum over its windows)
+    e->fix_info.flagged += fi.flagged; e->fix_info.recomputed += fi.recomputed; e->fix_info.skipped += fi.skipped;
+    e->fix_info.ms += fi.ms; e->fix_info.by_pass += fi.by_pass;
+    e->win_info.windows_by_pass++;
+  }
+  return NGD_OK;
+}
+
+// single_image = 2 engines, the unit slab of a job: the noted pairs' entries of the slab -- every slice of the batch --
+// recomputed with the two-operand arithmetic (fixup.hip, the route of the bootstrap's per-block partial results); the
+// caller then runs the weighted reductions of the batch again.  The slice table gives each slice its site range: a run of
+// consecutive slices of one length that follow each other without a gap is one launch.  The stream is idle.
+static int windows_job_fixup(ngd_engine *e, const std::vector<uint64_t> &tab, uint64_t n_seg, double *slab, uint64_t n_out,
+                             bool *patched) {
+  *patched = false;
+  const uint32_t n = *(volatile uint32_t *)e->h_fixcount;
+  e->fix_info.flagged += n;
+  if (!n) return NGD_OK;
+  const bool all = n > e->fix_cap;
+  std::vector<ngd_fix_tile> tiles;
+  std::vector<unsigned long long> singles;
+  if (int rc = fix_collect(e, n, all, tiles, singles)) return rc;
+  auto slo = [&](uint64_t k) { return tab[k * NGD_SEG_STRIDE + NGD_SEG_SLO]; };
+  auto shi = [&](uint64_t k) { return tab[k * NGD_SEG_STRIDE + NGD_SEG_SHI]; };
+  if (e->opt_fix_work) {  // a caller's budget (NGD_OPT_FIXUP_WORK), in pair-sites over the batch's slices
+    double sites = 0;
+    for (uint64_t k = 0; k < n_seg; k++) sites += (double)(shi(k) - slo(k));
+    if (((double)tiles.size() * NGD_FIX_TILE_COST_X10 / 10.0 + (double)singles.size()) * sites > (double)e->opt_fix_work) {
+      e->fix_info.skipped += n;
+      return NGD_OK;
+    }
+  }
+  const uint64_t plane = (uint64_t)e->g.n_pad * e->g.n_pad;
+  hipEvent_t t0 = e->ev[0], t1 = e->ev[1];  // (the batch's own timings have been read)
+  HIPCHK(hipEventRecord(t0, e->st));
+  if (!tiles.empty()) {
+    if (int rc = e->d_fixtiles.ensure(e, tiles.size())) return rc;
+    HIPCHK(hipMemcpy(e->d_fixtiles, tiles.data(), tiles.size() * sizeof(ngd_fix_tile), hipMemcpyHostToDevice));
+  }
+  const uint32_t n1 = (uint32_t)singles.size();
+  if (n1) HIPCHK(hipMemcpy(e->d_fixlist, singles.data(), (size_t)n1 * 8, hipMemcpyHostToDevice));
+  const uint64_t max_wg = 1ull << 22;  // (workgroups per launch, as fixup_pass)
+  for (uint64_t k = 0; k < n_seg;) {
+    const uint64_t len = shi(k) - slo(k);
+    uint64_t k1 = k + 1;
+    while (k1 < n_seg && k1 - k < max_wg && slo(k1) == shi(k1 - 1) && shi(k1) - slo(k1) == len) k1++;
+    const uint32_t run = (uint32_t)(k1 - k);
+    const size_t per = (size_t)std::max<uint64_t>(1, max_wg / run);
+    for (size_t off = 0; off < tiles.size(); off += per)
+      ngd_launch_fixup_tiles(e->st, e->g, e->sc, e->PA, e->SM, nullptr, e->d_fixtiles + off,
+                             (uint32_t)std::min<size_t>(per, tiles.size() - off), slo(k), shi(k1 - 1), len, run, 1, slab + k * plane);
+    for (size_t off = 0; off < n1; off += per)
+      ngd_launch_fixup(e->st, e->g, e->sc, e->PA, e->SM, nullptr, e->d_fixlist + off, (uint32_t)std::min<size_t>(per, n1 - off),
+                       slo(k), shi(k1 - 1), len, run, 1, slab + k * plane);
+    k = k1;
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(t1, e->st));
+  HIPCHK(hipStreamSynchronize(e->st));
+  float ms = 0;
+  hipEventElapsedTime(&ms, t0, t1);
+  e->fix_info.ms += ms;
+  e->win_info.ms += ms;
+  const uint64_t pairs = all ? e->n_owned_pairs : n;
+  e->fix_info.recomputed += pairs;
+  e->win_info.fixup_pairs += pairs * n_out;
+  *patched = true;
+  return NGD_OK;
+}
+
 // single_image = 2 engines: the pairs the banded reduction noted (a sum below NGD_FIX_MEAN x the window's length in some
 // window of the batch; under --pairwise_del x the pair's count there) recomputed with the two-operand arithmetic in every
 // window of the batch, tile by tile / pair by pair over the window's sites (fixup.hip).  The stream is idle.
-static int windows_fixup(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum) {
+// (window w's matrix is matrix w * out_stride of d_sum: a job's matrices 0 lie n_rep + 1 matrices apart)
+static int windows_fixup(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
+                         uint64_t out_stride = 1) {
   const uint32_t n = *(volatile uint32_t *)e->h_fixcount;
   e->fix_info.flagged += n;
   if (!n) return NGD_OK;
@@ -85,7 +197,7 @@ static int windows_fixup(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, 
   if (n1) HIPCHK(hipMemcpy(e->d_fixlist, singles.data(), (size_t)n1 * 8, hipMemcpyHostToDevice));
   for (uint64_t w = 0; w < n_win; w++) {
     const uint64_t len = hi[w] - lo[w];
-    double *out = d_sum + w * n_pairs;
+    double *out = d_sum + w * out_stride * n_pairs;
     if (!tiles.empty()) {  // (the slicing of fixup_pass: a pair's slices depend on the window alone)
       const uint64_t sps = std::max<uint64_t>(4096, (len + NGD_FIX_CAP - 1) / NGD_FIX_CAP);
       const uint64_t n_slices = (len + sps - 1) / sps;
@@ -129,28 +241,64 @@ static bool windows_slab_applies(const ngd_engine *e) {
 
 // bytes of one batch of the segment-slab plan: partial results (slices padded to the XCD deal's eights), counts, slice
 // weights and tables.  The EM kernel: a plane per segment, counts, tables -- no k-group weights, no padding slices.
-static uint64_t windows_batch_bytes(const ngd_engine *e, uint64_t n_seg, uint64_t span, uint64_t n_win) {
+// A job (bt != NULL): + every window's table of block starts and the replicates' weights (doubles; uint32 for the counts).
+static uint64_t windows_batch_bytes(const ngd_engine *e, uint64_t n_seg, uint64_t span, uint64_t n_win, const WinBoot *bt = nullptr) {
   const uint64_t plane = (uint64_t)e->g.n_pad * e->g.n_pad, n_ks = (n_seg + 7) / 8 * 8;
+  uint64_t job = 0;
+  if (bt) {
+    const uint64_t rb = ngd_reduce_chunk(bt->n_rep), stride = (bt->n_rep + rb - 1) / rb * rb;
+    job = n_win * (bt->n_blocks + 1) * 4 + bt->n_blocks * stride * (e->cfg.pairwise_del ? 12 : 8);
+  }
   if (e->kernel == NGD_KERNEL_EM_TABLE)
-    return n_seg * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + n_seg * NGD_SEG_STRIDE * 8 + n_win * 16;
+    return n_seg * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + n_seg * NGD_SEG_STRIDE * 8 + n_win * 16 + job;
   const uint64_t wkg = 3 * span / 4 + n_ks * (3 + NGD_KG_TAIL) + 1 + NGD_KG_TAIL;
-  return n_ks * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + wkg * 32 + n_ks * NGD_SEG_STRIDE * 8 + n_win * 16;
+  return n_ks * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + wkg * 32 + n_ks * NGD_SEG_STRIDE * 8 + n_win * 16 + job;
 }
 
 // the segment-slab plan; *fits = false (nothing launched): some window alone does not fit the budget
+// bt != NULL: the unit slab of a job, outputs [n_win][n_rep + 1][n_pairs] -- the replicates alone, matrix 0 is not written;
+// else window w's matrix is matrix w * out_stride of the outputs (a job's matrices 0: windows_job_slab)
 static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
-                        unsigned long long *d_cnt, uint64_t budget, bool *fits) {
+                        unsigned long long *d_cnt, uint64_t budget, bool *fits, const WinBoot *bt = nullptr,
+                        uint64_t out_stride = 1) {
   const ngd_geom &g = e->g;
   const uint64_t n_pairs = ngd_n_pairs(g.n_ind), plane = (uint64_t)g.n_pad * g.n_pad;
   const bool pdel = e->cfg.pairwise_del != 0;
   const bool fix = e->SM != nullptr;
   const bool em = e->kernel == NGD_KERNEL_EM_TABLE;
+  const uint64_t n_mat = bt ? (uint64_t)bt->n_rep + 1 : out_stride;  // matrices of the output per window
   *fits = true;
   for (uint64_t w = 0; w < n_win; w++)
-    if (windows_batch_bytes(e, 1, hi[w] - lo[w], 1) > budget) {
+    if (windows_batch_bytes(e, bt ? bt->n_blocks + 1 : 1, hi[w] - lo[w], 1, bt) > budget) {
       *fits = false;
       return NGD_OK;
     }
+  // the boundaries a window brings to its batch, ascending: its ends, and in a job the starts of its blocks
+  std::vector<uint64_t> wb, merged;
+  auto win_bnd = [&](uint64_t w) {
+    wb.clear();
+    wb.push_back(lo[w]);
+    for (uint64_t b = 1; bt && b <= bt->n_blocks; b++) wb.push_back(lo[w] + b * bt->q);
+    if (wb.back() != hi[w]) wb.push_back(hi[w]);
+  };
+  // a job's weights, the same for every window: Wt[b][r] (zero padded to whole chunks of replicates), as integers for the counts
+  uint32_t stride = 0;
+  if (bt) {
+    const uint32_t rb = ngd_reduce_chunk(bt->n_rep);
+    stride = (bt->n_rep + rb - 1) / rb * rb;
+    std::vector<double> Wt(bt->n_blocks * stride, 0.0);
+    for (uint32_t r = 0; r < bt->n_rep; r++)
+      for (uint64_t b = 0; b < bt->n_blocks; b++) Wt[b * stride + r] = (double)bt->mult[(uint64_t)r * bt->n_blocks + b];
+    int rc = e->d_W.ensure(e, Wt.size());
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(e->d_W, Wt.data(), Wt.size() * 8, hipMemcpyHostToDevice));
+    if (pdel) {
+      std::vector<uint32_t> M(Wt.size());
+      for (size_t k = 0; k < M.size(); k++) M[k] = (uint32_t)Wt[k];
+      if ((rc = e->d_M.ensure(e, M.size()))) return rc;
+      HIPCHK(hipMemcpy(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice));
+    }
+  }
   // (the windowed call takes the scratch of the bootstrap's per-block partial results: their cache is dropped)
   DevBuf<double> &seg_sums = e->blk.borrow_sums();
   DevBuf<uint32_t> &seg_cnt = e->blk.borrow_counts();
@@ -158,19 +306,19 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   uint64_t batch = 0;
   for (uint64_t a = 0; a < n_win; batch++) {
     // the batch: windows a .. b-1, as many as fit the budget (its segments bounded by its distinct boundaries - 1)
-    std::set<uint64_t> bnd;
+    std::vector<uint64_t> x;  // the batch's boundaries, ascending: one merge of two sorted lists per window
     uint64_t b = a, hi_max = 0;
     while (b < n_win) {
-      const uint64_t n_new = (bnd.count(lo[b]) ? 0 : 1) + (bnd.count(hi[b]) ? 0 : 1);
-      const uint64_t n_seg_ub = bnd.size() + n_new - 1, hm = std::max(hi_max, hi[b]);
-      if (b > a && (windows_batch_bytes(e, n_seg_ub, hm - lo[a], b + 1 - a) > budget || n_seg_ub >= (1ull << 30))) break;
-      bnd.insert(lo[b]);
-      bnd.insert(hi[b]);
+      win_bnd(b);
+      merged.clear();
+      std::set_union(x.begin(), x.end(), wb.begin(), wb.end(), std::back_inserter(merged));
+      const uint64_t n_seg_ub = merged.size() - 1, hm = std::max(hi_max, hi[b]);
+      if (b > a && (windows_batch_bytes(e, n_seg_ub, hm - lo[a], b + 1 - a, bt) > budget || n_seg_ub >= (1ull << 30))) break;
+      x.swap(merged);
       hi_max = hm;
       b++;
     }
     const uint64_t nb = b - a;
-    const std::vector<uint64_t> x(bnd.begin(), bnd.end());  // boundaries, ascending
     auto at = [&](uint64_t s) { return (uint64_t)(std::lower_bound(x.begin(), x.end(), s) - x.begin()); };
     // interval k = [x[k], x[k + 1]) is a segment if some window of the batch covers it
     std::vector<int64_t> cover(x.size(), 0);
@@ -187,7 +335,7 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       run = 0;
       for (uint64_t k = 0; k + 1 < x.size(); k++)
         if ((run += cover[k]) > 0) n_cut += (x[k + 1] - x[k] - 1) / piece + 1;
-      if (n_cut > n_cov && (windows_batch_bytes(e, n_cut, hi_max - lo[a], nb) > budget || n_cut >= (1ull << 30))) piece = ~0ull;
+      if (n_cut > n_cov && (windows_batch_bytes(e, n_cut, hi_max - lo[a], nb, bt) > budget || n_cut >= (1ull << 30))) piece = ~0ull;
     }
     std::vector<uint32_t> seg_of(x.size(), 0), seg_end(x.size(), 0);  // interval k = slices [seg_of[k], seg_end[k])
     std::vector<uint64_t> tab;
@@ -209,6 +357,7 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       }
       seg_end[k] = (uint32_t)n_seg;
     }
+    seg_of[x.size() - 1] = seg_end[x.size() - 1] = (uint32_t)n_seg;  // (the last boundary: where the slices end)
     // (the XCD deal of accum_mfma.hip; padding slices have no k-group and no sites.  The EM launch needs none.)
     const uint64_t n_ks = em ? n_seg : (n_seg + 7) / 8 * 8;
     for (uint64_t q = n_seg; q < n_ks; q++) tab.insert(tab.end(), {0, 0, wkg, 0, 0});
@@ -219,7 +368,19 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
       wt[2 * (w - a)] = f | (l << 32);
       wt[2 * (w - a) + 1] = hi[w] - lo[w];
     }
+    std::vector<uint32_t> blk;  // a job: the first slice of each block of each window, and the end of its last block
+    if (bt) {
+      blk.resize(nb * (bt->n_blocks + 1));
+      for (uint64_t w = a; w < b; w++) {
+        uint64_t i = at(lo[w]);  // (the window's block starts ascend: one walk along the boundaries)
+        for (uint64_t k = 0; k <= bt->n_blocks; k++) {
+          while (x[i] < lo[w] + k * bt->q) i++;
+          blk[(w - a) * (bt->n_blocks + 1) + k] = seg_of[i];
+        }
+      }
+    }
     int rc = seg_sums.ensure(e, n_ks * plane);
+    if (!rc && bt) rc = e->d_winblk.ensure(e, blk.size());
     if (!rc && pdel) rc = seg_cnt.ensure(e, n_seg * plane);
     if (!rc && !em) rc = e->blk.wslice.ensure(e, w_total * 4);
     if (!rc) rc = e->d_segtab.ensure(e, tab.size());
@@ -228,6 +389,7 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     HIPCHK(hipEventRecord(e->ev[0], e->st));
     HIPCHK(hipMemcpyAsync(e->d_segtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, e->st));
     HIPCHK(hipMemcpyAsync(e->d_wintab, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, e->st));
+    if (bt) HIPCHK(hipMemcpyAsync(e->d_winblk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, e->st));
     if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
     HIPCHK(hipEventRecord(e->ev[1], e->st));
     if (em)
@@ -238,21 +400,44 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
                             e->wg_waves, (uint32_t)n_ks, 0, g.n_kg, 0, 1, seg_sums, e->d_clk, 0, 0, e->d_segtab);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[2], e->st));
-    double *bs = d_sum + a * n_pairs;
-    unsigned long long *bc = d_cnt + a * n_pairs;
+    double *bs = d_sum + a * n_mat * n_pairs;
+    unsigned long long *bc = d_cnt + a * n_mat * n_pairs;
     if (fix) {
       HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
       HIPCHK(hipMemsetAsync(e->d_fixseen, 0, (n_pairs / 32 + 1) * sizeof(uint32_t), e->st));
     }
-    ngd_launch_reduce_band(e->st, g, seg_sums, nullptr, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, bs,
-                           pdel ? nullptr : bc, fix && !pdel ? &ff : nullptr);
+    // (a job: window w's full-data matrix is matrix w (n_rep + 1) of the output, its replicates follow it)
+    const uint32_t n_blk = bt ? (uint32_t)bt->n_blocks : 0, n_rep = bt ? bt->n_rep : 0;
+    const uint64_t n_vis = bt ? bt->n_blocks * bt->q : 0;  // sites a replicate visits
+    // (a job's matrix 0 is NOT reduced from these slices: windows_job_slab has filled it from the windows' own segments)
+    auto reduce_sums = [&](bool first) {
+      if (!bt) {
+        ngd_launch_reduce_band(e->st, g, seg_sums, nullptr, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, bs,
+                               first && !pdel ? bc : nullptr, first && fix && !pdel ? &ff : nullptr, (uint32_t)n_mat);
+        e->win_info.band_launches++;
+      } else {
+        ngd_launch_reduce_band_w(e->st, g, seg_sums, nullptr, e->d_winblk, (uint32_t)nb, n_blk, e->d_W.get(), stride, n_rep,
+                                 (uint32_t)n_mat, e->d_tiles, e->n_tiles, bs + n_pairs, first && !pdel ? bc + n_pairs : nullptr,
+                                 n_vis, first && fix && !pdel ? &ff : nullptr, NGD_FIX_MEAN * (double)n_vis);
+        e->win_info.band_launches++;
+      }
+    };
+    reduce_sums(true);
     HIPCHK(hipEventRecord(e->ev[3], e->st));
-    e->win_info.band_launches++;
     if (pdel) {
       ngd_launch_count_blocks(e->st, g, e->mask, 0, (uint32_t)n_seg, e->d_tiles16, e->n_tiles16, seg_cnt, e->d_segtab);
-      ngd_launch_reduce_band(e->st, g, nullptr, seg_cnt, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, nullptr, bc, nullptr);
-      e->win_info.band_launches++;
-      if (fix) ngd_launch_fix_flag(e->st, g, bs, bc, (uint32_t)nb, e->d_tiles, e->n_tiles, ff);
+      if (!bt) {
+        ngd_launch_reduce_band(e->st, g, nullptr, seg_cnt, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, nullptr, bc, nullptr,
+                               (uint32_t)n_mat);
+        e->win_info.band_launches++;
+      } else {
+        ngd_launch_reduce_band_w(e->st, g, nullptr, seg_cnt, e->d_winblk, (uint32_t)nb, n_blk, e->d_M.get(), stride, n_rep,
+                                 (uint32_t)n_mat, e->d_tiles, e->n_tiles, nullptr, bc + n_pairs, 0, nullptr, 0.0);
+        e->win_info.band_launches++;
+      }
+      // (a job: over every matrix of the batch -- the windows' matrices 0 are in place already and hold their final sums)
+      if (fix && bt) ngd_launch_fix_flag(e->st, g, bs, bc, (uint32_t)(nb * n_mat), e->d_tiles, e->n_tiles, ff);
+      if (fix && !bt) ngd_launch_fix_flag(e->st, g, bs, bc, (uint32_t)nb, e->d_tiles, e->n_tiles, ff, (uint32_t)n_mat);
     }
     if (fix) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipGetLastError());
@@ -266,15 +451,50 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     e->win_info.segments += n_seg;
     e->win_info.slab_bytes = std::max<uint64_t>(e->win_info.slab_bytes, n_ks * plane * 8 + (pdel ? n_seg * plane * 4 : 0));
     e->win_info.batches++;
-    if (fix && (rc = windows_fixup(e, lo + a, hi + a, nb, bs))) return rc;
+    if (fix && !bt && (rc = windows_fixup(e, lo + a, hi + a, nb, bs, n_mat))) return rc;
+    if (fix && bt) {  // the noted pairs' slab entries exactly, then the weighted reductions of the batch again
+      bool patched = false;
+      if ((rc = windows_job_fixup(e, tab, n_seg, seg_sums, nb * n_mat, &patched))) return rc;
+      if (patched) {  // (timed like the recomputation: part of the fix-up and of the call)
+        HIPCHK(hipEventRecord(e->ev[0], e->st));
+        reduce_sums(false);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(e->ev[1], e->st));
+        HIPCHK(hipStreamSynchronize(e->st));
+        float ms2 = 0;
+        hipEventElapsedTime(&ms2, e->ev[0], e->ev[1]);
+        e->fix_info.ms += ms2;
+        e->win_info.ms += ms2;
+      }
+    }
     a = b;
   }
   return NGD_OK;
 }
 
-// one call's windows into device memory [n_win][n_pairs]; the plan by NGD_OPT_WIN_PLAN
+// The slab plan of a job.  Matrix 0 of every window must carry ngd_run_windows_device()'s bits (NGD_OPT_WIN_PLAN = 2), and the
+// unit slab's finer slices would add the same terms in another order: so matrix 0 comes from the windows' OWN segments -- the
+// segment-slab plan exactly as ngd_run_windows runs it on this list of windows, batches and fix-up included, written to its
+// places [w][0] of the output -- and only the replicates from the unit slab.  The cost is stated where the plans are
+// compared (windows_impl): a second pass over the covered sites and the banded reduction.
+static int windows_job_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
+                            unsigned long long *d_cnt, uint64_t budget, bool *fits, const WinBoot *bt) {
+  *fits = true;
+  for (uint64_t w = 0; w < n_win; w++)  // (before anything is launched: the unit slab's own test)
+    if (windows_batch_bytes(e, bt->n_blocks + 1, hi[w] - lo[w], 1, bt) > budget) {
+      *fits = false;
+      return NGD_OK;
+    }
+  bool fits0 = true;
+  if (int rc = windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits0, nullptr, (uint64_t)bt->n_rep + 1)) return rc;
+  if (!fits0) return fail(NGD_E_NOMEM, "ngd_run_windows_job: internal -- a window fits the unit slab and not its own segment");
+  return windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, fits, bt);
+}
+
+// one call's windows into device memory [n_win][n_pairs] (a job, bt != NULL: [n_win][n_rep + 1][n_pairs]); the plan by
+// NGD_OPT_WIN_PLAN
 static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
-                        unsigned long long *d_cnt) {
+                        unsigned long long *d_cnt, const WinBoot *bt = nullptr) {
   HIPCHK(hipSetDevice(e->device));
   if (int rc = eager_discard(e)) return rc;
   e->spill_timing = ngd_spill_timing{};
@@ -297,6 +517,8 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     uint64_t covered = 0, sum_len = 0, end = 0;
     std::vector<uint64_t> bnd(lo, lo + n_win);
     bnd.insert(bnd.end(), hi, hi + n_win);
+    for (uint64_t w = 0; bt && w < n_win; w++)  // (a job: + the starts of every window's blocks)
+      for (uint64_t b = 1; b <= bt->n_blocks; b++) bnd.push_back(lo[w] + b * bt->q);
     std::sort(bnd.begin(), bnd.end());
     const uint64_t n_bnd = (uint64_t)(std::unique(bnd.begin(), bnd.end()) - bnd.begin());  // (segments < distinct boundaries)
     for (uint64_t w = 0; w < n_win; w++) {
@@ -308,20 +530,48 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     // 160 slices: 224.8 ms -- DESIGN.md section 6; the plain pass's 2.22e8)
     const double rate = em ? 2.22e8 : 1.05e10, np = (double)e->n_owned_pairs;
     const double plane_b = (double)e->g.n_pad * e->g.n_pad * 8;
-    const double need = (double)windows_batch_bytes(e, std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win);
+    const double need = (double)windows_batch_bytes(e, std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win, bt);
     const double have = (double)e->blk.bytes();
-    const double t_slab = np * (double)covered / rate + (double)(n_bnd + 2 * n_win) * np * 8 / 4e9 +
-                          (need > have ? (need - have) * 12e-9 : 0.0);
-    const double t_pass = np * (double)sum_len / (0.75 * rate) + 0.1 * (double)n_win;
-    slab = t_slab < t_pass;
+    if (!bt) {
+      const double t_slab = np * (double)covered / rate + (double)(n_bnd + 2 * n_win) * np * 8 / 4e9 +
+                            (need > have ? (need - have) * 12e-9 : 0.0);
+      const double t_pass = np * (double)sum_len / (0.75 * rate) + 0.1 * (double)n_win;
+      slab = t_slab < t_pass;
+    } else {
+      // A job.  [predicted -- nothing here has been measured on a device yet; tools/bench_windows_boot.py gives the legs]
+      //  * unit slab: matrix 0 of every window by the plain segment slab first (its bits are ngd_run_windows()': one pass
+      //    over the covered sites + the banded reduction), then the pass over the covered sites, every slice with the start-up of a short slice (the MFMA kernel's
+      //    operand pipeline runs NGD_KG_TAIL k-groups ahead: ~12 sites' worth; the EM kernel walks single sites) and a
+      //    plane of the slab to write; the banded reduction as above; the weighted one reads a window's slices once per
+      //    chunk of replicates and both write (n_rep + 1) matrices of sums and counts per window;
+      //  * per window: run_impl() on multiplicity vectors over blocks of gcd(lo, q, hi) sites from site 0 -- the MFMA
+      //    kernel by per-block partial results of the sites [0, hi) where its blocks are whole k-groups, else ~3/4 of a
+      //    pass over the window per matrix; the EM kernel by ONE spilled-terms pass over [0, hi) (1.1 plain passes).
+      const double n_mat = (double)bt->n_rep + 1, chunks = (double)((bt->n_rep + 31) / 32);
+      const double per_win = covered ? (double)n_bnd * (double)(hi[0] - lo[0]) / (double)covered : 0.0;  // slices of a window
+      const double t_slab = np * (2.0 * (double)covered + (em ? 0.0 : 12.0) * (double)n_bnd) / rate + (double)n_bnd * plane_b / 4e9 +
+                            (double)(2 * n_win + 2 * n_win) * np * 8 / 4e9 +
+                            ((double)n_bnd + (double)n_win * (chunks * per_win + 2 * n_mat)) * np * 8 / 4e9 +
+                            (need > have ? (need - have) * 12e-9 : 0.0);
+      double t_pass = 0;
+      for (uint64_t w = 0; w < n_win; w++) {
+        const uint64_t B = std::gcd(std::gcd(lo[w], bt->q), hi[w]);
+        const double by_matrix = n_mat * np * (double)(hi[w] - lo[w]) / (0.75 * rate);
+        const double shared = np * (double)hi[w] / rate * (em ? 1.1 : 1.0) + (em ? 0.0 : chunks * (double)(hi[w] / B) * np * 8 / 4e9);
+        t_pass += ((em || B % 4 == 0) ? std::min(by_matrix, shared) : by_matrix) + 0.1 + n_mat * np * 16 / 4e9;
+      }
+      slab = t_slab < t_pass;
+    }
   }
   if (slab) {
     bool fits = true;
-    int rc = windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits);
+    int rc = bt ? windows_job_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits, bt)
+                : windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits);
     if (rc || fits) return rc;
     if (e->opt_win_plan == 2)
       return fail(NGD_E_NOMEM, "ngd_run_windows: a window does not fit the segment-slab plan's budget (NGD_OPT_WIN_MAX_BYTES)");
   }
+  if (bt) return windows_job_by_pass(e, lo, hi, n_win, *bt, d_sum, d_cnt);
   return windows_by_pass(e, lo, hi, n_win, d_sum, d_cnt);
 }
 
@@ -337,17 +587,18 @@ int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t
 
 // the host-memory forms: windows in groups whose results fit ~2 GB of the engine's batch buffers; fn(first, count) takes
 // each group's results out of d_bsum / d_bcnt
+// (a job, bt != NULL: n_rep + 1 matrices per window, at least one window per group)
 static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win,
-                           const std::function<int(uint64_t, uint64_t)> &fn) {
-  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
-  const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (16 * std::max<uint64_t>(1, n_pairs))));
+                           const std::function<int(uint64_t, uint64_t)> &fn, const WinBoot *bt = nullptr) {
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = bt ? (uint64_t)bt->n_rep + 1 : 1;
+  const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (16 * n_mat * std::max<uint64_t>(1, n_pairs))));
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
-  int rc = batch_buffers(e, (uint32_t)per);
+  int rc = batch_buffers(e, (uint32_t)(per * n_mat));
   if (rc) return rc;
   for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
     const uint64_t n = std::min(per, n_win - w0);
-    if ((rc = windows_impl(e, lo + w0, hi + w0, n, e->d_bsum, e->d_bcnt))) return rc;
+    if ((rc = windows_impl(e, lo + w0, hi + w0, n, e->d_bsum, e->d_bcnt, bt))) return rc;
     if ((rc = fn(w0, n))) return rc;
   }
   e->n_batch_valid = 0;
@@ -385,6 +636,90 @@ int ngd_run_windows_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *
     // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
     return ngd_finish(h_sum.data(), h_cnt.data(), n * n_pairs, tot_sites, evol_model, dist + w0 * n_pairs);
   });
+}
+
+// ---- ngd_run_windows_job*: the arguments of a job, and the replicates' multiplicities counted from the block maps ----
+static int windows_job_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps,
+                             uint32_t n_rep, uint64_t n_blocks, uint64_t q, const char *who, std::vector<uint32_t> &mult) {
+  if (int rc = windows_check(e, lo, hi, n_win, who)) return rc;
+  if (!n_rep) return NGD_OK;  // (the windows alone: n_blocks and block_size are not read, as by ngd_run_job)
+  const std::string w(who);
+  if (!q) return fail(NGD_E_INVALID, w + ": block size 0");
+  const uint64_t W = hi[0] - lo[0];
+  for (uint64_t k = 1; k < n_win; k++)
+    if (hi[k] - lo[k] != W) return fail(NGD_E_INVALID, w + ": the windows of a job must have one length (they share the block maps)");
+  if (n_blocks != W / q) return fail(NGD_E_INVALID, w + ": n_blocks is not the window length / block_size (ngsDist.cpp:236)");
+  if (!maps) return fail(NGD_E_INVALID, w + ": null block maps");
+  if (!n_blocks) return fail(NGD_E_INVALID, w + ": empty bootstrap geometry (windows shorter than one block), as ngd_run_job");
+  if (n_win * ((uint64_t)n_rep + 1) >= (1ull << 31)) return fail(NGD_E_INVALID, w + ": too many matrices in one call");
+  if (n_rep > (1u << 20)) return fail(NGD_E_INVALID, w + ": more than 2^20 replicates in one call");  // (grid.y: chunks of 32)
+  mult.assign((uint64_t)n_rep * n_blocks, 0u);
+  for (uint32_t r = 0; r < n_rep; r++)
+    for (uint64_t b = 0; b < n_blocks; b++) {
+      const uint64_t src = maps[(uint64_t)r * n_blocks + b];
+      if (src >= n_blocks) return fail(NGD_E_INVALID, w + ": block_map entry out of range");
+      mult[(uint64_t)r * n_blocks + src]++;
+    }
+  return NGD_OK;
+}
+
+int ngd_run_windows_job_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                               const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, void *d_sum,
+                               void *d_cnt) {
+  std::vector<uint32_t> mult;
+  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job_device", mult))
+    return rc;
+  if (!n_rep) return ngd_run_windows_device(e, win_lo, win_hi, n_win, d_sum, d_cnt);
+  if (!d_sum || !d_cnt) return fail(NGD_E_INVALID, "ngd_run_windows_job_device: null output");
+  const WinBoot bt{n_rep, n_blocks, block_size, mult.data()};
+  e->win_info = ngd_windows_info{};
+  e->fix_info = ngd_fixup_info{};
+  e->n_batch_valid = 0;
+  return windows_impl(e, win_lo, win_hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, &bt);
+}
+
+int ngd_run_windows_job(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, const uint64_t *block_maps,
+                        uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, double *sum, uint64_t *cnt) {
+  std::vector<uint32_t> mult;
+  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job", mult))
+    return rc;
+  if (!n_rep) return ngd_run_windows(e, win_lo, win_hi, n_win, sum, cnt);
+  HIPCHK(hipSetDevice(e->device));
+  const WinBoot bt{n_rep, n_blocks, block_size, mult.data()};
+  const uint64_t per_win = ((uint64_t)n_rep + 1) * ngd_n_pairs(e->g.n_ind);
+  return windows_chunked(e, win_lo, win_hi, n_win, [&](uint64_t w0, uint64_t n) {
+    int rc = copy_out(e, (uint32_t)(n * (n_rep + 1)), e->d_bsum, e->d_bcnt, sum ? sum + w0 * per_win : nullptr,
+                      cnt ? cnt + w0 * per_win : nullptr);
+    e->n_batch_valid = 0;
+    return rc;
+  }, &bt);
+}
+
+int ngd_run_windows_job_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                             const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                             uint64_t tot_sites, uint64_t evol_model, double *dist) {
+  std::vector<uint32_t> mult;
+  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job_dist", mult))
+    return rc;
+  if (!n_rep) return ngd_run_windows_dist(e, win_lo, win_hi, n_win, tot_sites, evol_model, dist);
+  if (!dist) return fail(NGD_E_INVALID, "ngd_run_windows_job_dist: null argument");
+  if (tot_sites && e->cfg.pairwise_del)
+    return fail(NGD_E_INVALID, "ngd_run_windows_job_dist: a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
+  if (evol_model > 2) return fail(NGD_E_MODEL, "ngd_run_windows_job_dist: evolutionary model not supported (ngsDist.cpp:398-399)");
+  HIPCHK(hipSetDevice(e->device));
+  const WinBoot bt{n_rep, n_blocks, block_size, mult.data()};
+  const uint64_t per_win = ((uint64_t)n_rep + 1) * ngd_n_pairs(e->g.n_ind);
+  std::vector<double> h_sum;
+  std::vector<uint64_t> h_cnt;
+  return windows_chunked(e, win_lo, win_hi, n_win, [&](uint64_t w0, uint64_t n) {
+    h_sum.resize(n * per_win);
+    h_cnt.resize(n * per_win);
+    int rc = copy_out(e, (uint32_t)(n * (n_rep + 1)), e->d_bsum, e->d_bcnt, h_sum.data(), h_cnt.data());
+    e->n_batch_valid = 0;
+    if (rc) return rc;
+    // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
+    return ngd_finish(h_sum.data(), h_cnt.data(), n * per_win, tot_sites, evol_model, dist + w0 * per_win);
+  }, &bt);
 }
 
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {

@@ -68,6 +68,7 @@
 // links, and --win_size then fails with a message.  ngd_window_ranges (host_util.cpp) is always there.
 #pragma weak ngd_run_windows_dist
 #pragma weak ngd_last_windows
+#pragma weak ngd_run_windows_job_dist  // (--win_boot_rep)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
 static const double kInf = 1e15;          // INF, gen_func.hpp:15
@@ -102,6 +103,10 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // --win_size / --win_step: one matrix per window of sites along the genome (not in the reference)
   bool win = false, win_step_set = false;
   uint64_t win_size = 0, win_step = 0;
+  // --win_boot_rep: bootstrap replicates drawn INSIDE every window (blocks of --boot_block_size sites of the window, --seed):
+  // per window what the reference prints for the cut-down file with --n_boot_rep.  Not --n_boot_rep, which resamples the genome.
+  bool win_boot = false;
+  uint64_t win_boot_rep = 0;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -200,6 +205,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"eager", required_argument, nullptr, 1010},
                                  {"win_size", required_argument, nullptr, 1011},
                                  {"win_step", required_argument, nullptr, 1012},
+                                 {"win_boot_rep", required_argument, nullptr, 1013},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -234,6 +240,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1010: p.eager = atoi(optarg); break;
       case 1011: p.win = true; p.win_size = strtoull(optarg, nullptr, 10); break;
       case 1012: p.win_step_set = true; p.win_step = strtoull(optarg, nullptr, 10); break;
+      case 1013: p.win_boot = true; p.win_boot_rep = strtoull(optarg, nullptr, 10); break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -275,6 +282,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
             p.boot_block_size, p.out, p.n_threads, p.verbose, p.seed, kVersion);
     if (p.win || p.win_step_set)
       fprintf(stderr, "\twin_size: %lu\n\twin_step: %lu\n\n", p.win_size, p.win_step_set ? p.win_step : p.win_size);
+    if (p.win_boot) fprintf(stderr, "\twin_boot_rep: %lu\n\n", p.win_boot_rep);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -293,6 +301,10 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
   if (p.n_gpus < 1) die(__FUNCTION__, "number of GPUs cannot be less than 1!");
   if (p.boot_block_size < 1) die(__FUNCTION__, "bootstrap block size cannot be less than 1!");
   if (p.win_step_set && !p.win) die(__FUNCTION__, "window step (--win_step) requires a window size (--win_size)!");
+  if (p.win_boot && !p.win) die(__FUNCTION__, "bootstrap replicates inside windows (--win_boot_rep) require a window size (--win_size)!");
+  if (p.win_boot && p.n_boot_rep > 0)
+    die(__FUNCTION__, "bootstrap replicates inside windows (--win_boot_rep) cannot be combined with bootstrap replicates of the whole data set (--n_boot_rep)!");
+  if (p.win_boot && p.win_boot_rep >= (1ull << 31)) die(__FUNCTION__, "too many bootstrap replicates inside windows (--win_boot_rep)!");
   if (p.win) {
     if (!p.win_step_set) p.win_step = p.win_size;
     if (p.win_size < 1) die(__FUNCTION__, "window size (--win_size) cannot be less than 1!");
@@ -1135,6 +1147,8 @@ int main(int argc, char **argv) {
     ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win_lo.data(), win_hi.data(), (uint64_t)n_win);
     if (!ngd_run_windows_dist)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
+    if (p.win_boot_rep && !ngd_run_windows_job_dist)
+      die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows (--win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
   }
 
@@ -1474,14 +1488,41 @@ int main(int argc, char **argv) {
     // ---- windows along the genome: one matrix per window, in window order, a group of windows per engine call (their
     // distances in ~2 GB of host memory), each window's block formatted and written like the full data set's ----
     const uint64_t n_win = win_lo.size();
-    const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * std::max<uint64_t>(1, n_comb))));
+    // --win_boot_rep: R replicates inside every window, its R + 1 blocks printed one after the other -- the file is the
+    // concatenation of the cut-down runs' files.  Every cut-down run seeds the generator anew and the windows have one
+    // length, so ONE set of block maps, drawn from a fresh state, serves them all (ngsDist.cpp:179-180, :235-238, :416-437)
+    const uint64_t R = p.win_boot_rep, n_mat = R + 1;
+    const uint64_t wb_blocks = R ? p.win_size / p.boot_block_size : 0;
+    std::vector<uint64_t> wb_maps(R * wb_blocks);
+    if (R && wb_blocks) {
+      uint32_t wrng[3];
+      ngd_taus_seed(wrng, p.seed);
+      for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(wrng, wb_blocks, &wb_maps[r * wb_blocks]);
+    }
+    // (a window shorter than one block: the reference truncates its replicates to 0 sites and prints 0 / 0, ngsDist.cpp:236)
+    std::vector<double> wb_empty;
+    if (R && !wb_blocks) {
+      const std::vector<double> zs(n_comb, 0.0);
+      const std::vector<uint64_t> zc(n_comb, 0);
+      wb_empty.resize(n_comb);
+      if (ngd_finish(zs.data(), zc.data(), n_comb, p.tot_sites, p.evol_model, wb_empty.data()))
+        die("gen_dist", "invalid evolutionary model specified!");
+    }
+    const bool job = R && wb_blocks;
+    const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * (job ? n_mat : 1) * std::max<uint64_t>(1, n_comb))));
     std::vector<double> wd;
     for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
       const uint64_t n = std::min(per, n_win - w0);
       const auto t_c0 = std::chrono::steady_clock::now();
-      wd.resize(n * n_comb);
-      const int rc = ngd_run_windows_dist(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, wd.data());
-      if (rc) die_engine("ngd_run_windows_dist", rc);
+      wd.resize(n * (job ? n_mat : 1) * n_comb);
+      if (job) {
+        const int rc = ngd_run_windows_job_dist(eng.h, &win_lo[w0], &win_hi[w0], n, wb_maps.data(), (uint32_t)R, wb_blocks,
+                                                p.boot_block_size, p.tot_sites, p.evol_model, wd.data());
+        if (rc) die_engine("ngd_run_windows_job_dist", rc);
+      } else {
+        const int rc = ngd_run_windows_dist(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, wd.data());
+        if (rc) die_engine("ngd_run_windows_dist", rc);
+      }
       report_fixup(eng.h, p.verbose);
       ngd_windows_info wi;
       if (p.verbose >= 2 && ngd_last_windows && ngd_last_windows(eng.h, &wi) == NGD_OK)  // the plan the engine took
@@ -1491,7 +1532,11 @@ int main(int argc, char **argv) {
       t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
       for (uint64_t k = 0; k < n; k++) {
         const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
-        emit(w0 + k, nullptr, nullptr, nullptr, 0, &wd[k * n_comb], 0, name.c_str());
+        emit(w0 + k, nullptr, nullptr, nullptr, 0, &wd[k * (job ? n_mat : 1) * n_comb], 0, name.c_str());
+        for (uint64_t r = 1; r <= R; r++) {
+          const std::string rname = name + ", bootstrap replicate # " + std::to_string(r);
+          emit(w0 + k, nullptr, nullptr, nullptr, 0, job ? &wd[(k * n_mat + r) * n_comb] : wb_empty.data(), 0, rname.c_str());
+        }
       }
       writer.wait_idle();  // (the last block's text is written before the next group's call)
     }

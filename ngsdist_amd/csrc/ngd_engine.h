@@ -207,6 +207,7 @@ struct ngd_engine : ngd_mem {
   // results, counts and slice weights borrow blk)
   DevBuf<uint64_t> d_segtab;
   DevBuf<unsigned long long> d_wintab;
+  DevBuf<uint32_t> d_winblk;  // a job's replicates (ngd_run_windows_job*): [window][block] first slice of the block
   uint64_t opt_win_plan = 0, opt_win_max_bytes = 0;  // NGD_OPT_WIN_PLAN, NGD_OPT_WIN_MAX_BYTES
   ngd_windows_info win_info{};
 };

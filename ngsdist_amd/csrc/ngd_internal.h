@@ -274,7 +274,8 @@ void ngd_launch_pq_range(hipStream_t st, const ngd_geom &g, const ngd_score &sco
 void ngd_launch_fix_merge(hipStream_t st, const ngd_geom &g, const double *d_new, double *d_sum, const unsigned long long *d_cnt,
                           double thr, const ngd_tile *d_tiles, uint32_t n_tiles);
 void ngd_launch_fix_flag(hipStream_t st, const ngd_geom &g, const double *d_sum, const unsigned long long *d_cnt,
-                         uint32_t n_rep, const ngd_tile *d_tiles, uint32_t n_tiles, const ngd_fix_flags &fix);
+                         uint32_t n_rep, const ngd_tile *d_tiles, uint32_t n_tiles, const ngd_fix_flags &fix,
+                         uint32_t mat_stride = 1 /* matrix r of the n_rep is matrix r * mat_stride of d_sum / d_cnt */);
 // host_util.cpp: ngd_finish_stream over n_mat matrices, counts per cell (cnt) or one per matrix (cnt_mat)
 int ngd_finish_matrices_stream(const double *sum, const uint64_t *cnt, const uint64_t *cnt_mat, uint32_t n_mat, uint64_t n_pairs,
                                uint64_t evol_model, double *dist, const volatile uint64_t *landed);
@@ -295,7 +296,17 @@ void ngd_launch_count_blocks(hipStream_t st, const ngd_geom &g, const unsigned l
 uint32_t ngd_band_windows();  // windows per group (grid.y)
 void ngd_launch_reduce_band(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C,
                             const unsigned long long *d_win, uint32_t n_win, const ngd_tile *d_tiles, uint32_t n_tiles,
-                            double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags *fix);
+                            double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags *fix,
+                            uint32_t mat_stride = 1 /* window w's matrix is matrix w * mat_stride of the output */);
+// bootstrap replicates inside windows: the banded and weighted reduction (k_reduce_band_w) of per-slice sums (C == NULL) or
+// valid-site counts into matrices [w * mat_stride + r][n_pairs], r < n_rep; d_blk[w][0 .. n_blocks] = first slice of each
+// block of window w; d_Wt = [n_blocks][w_stride] doubles (sums) or uint32 (counts), w_stride a multiple of
+// ngd_reduce_chunk(n_rep) and zero padded.  A sum launch writes cnt_value as every count when d_cnt != NULL and notes the
+// pairs whose sum in any matrix is below fix_thr when fix != NULL
+void ngd_launch_reduce_band_w(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
+                              uint32_t n_win, uint32_t n_blocks, const void *d_Wt, uint32_t w_stride, uint32_t n_rep,
+                              uint32_t mat_stride, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
+                              unsigned long long *d_cnt, unsigned long long cnt_value, const ngd_fix_flags *fix, double fix_thr);
 void ngd_launch_count(hipStream_t st, const ngd_geom &g, const unsigned long long *mask,
                       const unsigned long long *planes, uint32_t n_planes, const ngd_tile *d_tiles,
                       uint32_t n_tiles, unsigned long long *d_cnt);  // owned 128-tiles

@@ -411,6 +411,131 @@ __global__ __launch_bounds__(128) void k_reduce_band(const void *__restrict__ sl
   }
 }
 
+// Bootstrap replicates inside windows (engine_windows.hip, the unit slab): the banded AND weighted reduction,
+//   sum[w][r][pair] = SUM_b Wt[b][r] * SUM_{s in slices of block b of window w} slab[s][pair],
+// k_reduce_wb's tiling, pair order and output order; grid.y = (window of the batch) x (chunk of RB replicates).  A
+// workgroup reads its window's slices ONCE per chunk, in ascending order, one fma per slice with the weight of the slice's
+// block.  blk[w][0 .. n_blocks] = first slice of each block of window w (blk[w][n_blocks] = the end of its last block: the
+// window's tail, which only its full-data matrix visits, is never read here).  Every window of a call draws the same block
+// maps, so Wt is [n_blocks][w_stride], zero padded to a multiple of RB: the RB weights of a block are one uniform load.
+// A non-finite partial result is treated as in k_reduce_wb: noted in the main loop, and a pair that met one is summed again
+// with the blocks a replicate did not draw left out (an all-zero individual on the EM path).
+// Matrix r of window w goes to d_out[(w * mat_stride + r) * n_pairs] (the caller has moved d_out past the window's full-data
+// matrix).  CNT = false: sums; d_cnt != NULL (no --pairwise_del): cnt_value as every pair's count; single_image = 2 engines
+// note a pair whose sum in any matrix is below fix_thr.  CNT = true: per-slice valid-site counts (k_count_blocks) and uint32
+// multiplicities -> d_cnt, in integers: exact.
+template <int RB, bool CNT>
+__global__ __launch_bounds__(128) void k_reduce_band_w(const void *__restrict__ slab_v, const uint32_t *__restrict__ blk,
+                                                        uint32_t n_blocks, const void *__restrict__ Wt_v, uint32_t w_stride,
+                                                        uint32_t n_rep, uint32_t n_chunks, uint32_t mat_stride,
+                                                        const ngd_tile *__restrict__ tiles, uint32_t n_pad, uint64_t n_ind,
+                                                        uint64_t n_pairs, double *__restrict__ d_sum,
+                                                        unsigned long long *__restrict__ d_cnt, unsigned long long cnt_value,
+                                                        ngd_fix_flags fix, double fix_thr) {
+  typedef typename std::conditional<CNT, uint32_t, double>::type T;
+  typedef typename std::conditional<CNT, unsigned long long, double>::type A;
+  const uint32_t tile = blockIdx.x >> 7, row = blockIdx.x & 127;
+  const uint32_t i = tiles[tile].ti * NGD_TILE + row;
+  const uint32_t j = tiles[tile].tj * NGD_TILE + threadIdx.x;
+  if (!(i < j && j < n_ind)) return;
+  const uint32_t w = blockIdx.y / n_chunks, r0 = (blockIdx.y % n_chunks) * RB;
+  const uint32_t *bf = blk + (uint64_t)w * (n_blocks + 1);  // (uniform across the workgroup, like the weights)
+  const T *Wt = reinterpret_cast<const T *>(Wt_v) + r0;
+  const uint64_t plane = (uint64_t)n_pad * n_pad;
+  const T *p = reinterpret_cast<const T *>(slab_v) + (uint64_t)i * n_pad + j;
+  A acc[RB];
+#pragma unroll
+  for (int r = 0; r < RB; r++) acc[r] = 0;
+  const uint32_t s_begin = bf[0], s_end = bf[n_blocks];
+  constexpr int U = 4;  // slices in flight per thread
+  uint32_t s = s_begin, b = 0, next = n_blocks ? bf[1] : s_end;  // slice s lies in block b, which ends before slice `next`
+  bool bad = false;  // a non-finite partial among this pair's slices
+  for (; s + U <= s_end; s += U) {
+    T v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) v[u] = p[(uint64_t)(s + u) * plane];
+    if (!CNT) {
+#pragma unroll
+      for (int u = 0; u < U; u++) bad |= !ngd_finite((double)v[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      while (s + u >= next) next = bf[++b + 1];
+      const T *wb = Wt + (uint64_t)b * w_stride;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        if (CNT) acc[r] += (A)wb[r] * (A)v[u];
+        else acc[r] = (A)__builtin_fma((double)wb[r], (double)v[u], (double)acc[r]);
+      }
+    }
+  }
+  for (; s < s_end; s++) {
+    const T v = p[(uint64_t)s * plane];
+    if (!CNT) bad |= !ngd_finite((double)v);
+    while (s >= next) next = bf[++b + 1];
+    const T *wb = Wt + (uint64_t)b * w_stride;
+#pragma unroll
+    for (int r = 0; r < RB; r++) {
+      if (CNT) acc[r] += (A)wb[r] * (A)v;
+      else acc[r] = (A)__builtin_fma((double)wb[r], (double)v, (double)acc[r]);
+    }
+  }
+  if (!CNT && __builtin_expect(bad, 0)) {  // again, slices in the same order, blocks that are not drawn left out
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = 0;
+    for (b = 0; b < n_blocks; b++) {
+      const T *wb = Wt + (uint64_t)b * w_stride;
+      for (s = bf[b]; s < bf[b + 1]; s++) {
+        const T v = p[(uint64_t)s * plane];
+#pragma unroll
+        for (int r = 0; r < RB; r++)
+          if (wb[r] != 0) acc[r] = (A)__builtin_fma((double)wb[r], (double)v, (double)acc[r]);
+      }
+    }
+  }
+  const uint64_t idx = ngd_pair_idx(n_ind, i, j);
+  bool small = false;
+#pragma unroll
+  for (int r = 0; r < RB; r++)
+    if (r0 + r < n_rep) {
+      const uint64_t o = ((uint64_t)w * mat_stride + r0 + r) * n_pairs + idx;
+      if (CNT) {
+        d_cnt[o] = (unsigned long long)acc[r];
+      } else {
+        d_sum[o] = (double)acc[r];
+        if (d_cnt) d_cnt[o] = cnt_value;
+        if (fix.list) small = small || (double)acc[r] < fix_thr;
+      }
+    }
+  // single_image = 2 engines (see k_reduce): noted once, whichever window, matrix or launch of the batch sees a small sum first
+  if (!CNT && small && !((atomicOr(&fix.seen[idx >> 5], 1u << (idx & 31)) >> (idx & 31)) & 1u)) {
+    const uint32_t slot = atomicAdd(fix.count, 1u);
+    if (slot < fix.cap) fix.list[slot] = ((unsigned long long)i << 32) | j;
+  }
+}
+
+template <int RB>
+void reduce_band_w(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
+                   uint32_t n_win, uint32_t n_blocks, const void *d_Wt, uint32_t w_stride, uint32_t n_rep, uint32_t mat_stride,
+                   const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum, unsigned long long *d_cnt,
+                   unsigned long long cnt_value, const ngd_fix_flags &f, double fix_thr) {
+  const uint64_t n_pairs = g.n_ind * (g.n_ind - 1) / 2;
+  const uint32_t n_chunks = (n_rep + RB - 1) / RB, per = 65535u / n_chunks;  // (grid.y holds 65 535)
+  for (uint32_t w0 = 0; w0 < n_win; w0 += per) {
+    const uint32_t n = n_win - w0 < per ? n_win - w0 : per;
+    const dim3 grid(n_tiles * NGD_TILE, n * n_chunks);
+    const uint32_t *blk = d_blk + (uint64_t)w0 * (n_blocks + 1);
+    const uint64_t off = (uint64_t)w0 * mat_stride * n_pairs;
+    if (C)
+      hipLaunchKernelGGL((k_reduce_band_w<RB, true>), grid, dim3(128), 0, st, (const void *)C, blk, n_blocks, d_Wt, w_stride,
+                         n_rep, n_chunks, mat_stride, d_tiles, g.n_pad, g.n_ind, n_pairs, nullptr, d_cnt + off, 0ull, f, 0.0);
+    else
+      hipLaunchKernelGGL((k_reduce_band_w<RB, false>), grid, dim3(128), 0, st, (const void *)slab, blk, n_blocks, d_Wt,
+                         w_stride, n_rep, n_chunks, mat_stride, d_tiles, g.n_pad, g.n_ind, n_pairs, d_sum + off,
+                         d_cnt ? d_cnt + off : nullptr, cnt_value, f, fix_thr);
+  }
+}
+
 template <int RB>
 void reduce_wb(hipStream_t st, const ngd_geom &g, const double *slab, uint32_t n_ks, const double *d_W,
                uint32_t w_stride, uint32_t n_rep, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
@@ -438,10 +563,11 @@ void ngd_launch_reduce(hipStream_t st, const ngd_geom &g, const double *slab, ui
 }
 
 void ngd_launch_fix_flag(hipStream_t st, const ngd_geom &g, const double *d_sum, const unsigned long long *d_cnt,
-                         uint32_t n_rep, const ngd_tile *d_tiles, uint32_t n_tiles, const ngd_fix_flags &fix) {
+                         uint32_t n_rep, const ngd_tile *d_tiles, uint32_t n_tiles, const ngd_fix_flags &fix, uint32_t mat_stride) {
   if (!n_tiles || !n_rep) return;
+  // (the kernel's distance between two matrices: mat_stride matrices of n_pairs entries)
   hipLaunchKernelGGL(k_fix_flag, dim3(n_tiles * NGD_TILE), dim3(128), 0, st, d_sum, d_cnt, n_rep, d_tiles, g.n_ind,
-                     ngd_n_pairs(g.n_ind), NGD_FIX_MEAN, fix);
+                     ngd_n_pairs(g.n_ind) * mat_stride, NGD_FIX_MEAN, fix);
 }
 
 void ngd_launch_fix_merge(hipStream_t st, const ngd_geom &g, const double *d_new, double *d_sum, const unsigned long long *d_cnt,
@@ -492,20 +618,35 @@ uint32_t ngd_band_windows() { return 16; }
 
 void ngd_launch_reduce_band(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C,
                             const unsigned long long *d_win, uint32_t n_win, const ngd_tile *d_tiles, uint32_t n_tiles,
-                            double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags *fix) {
+                            double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags *fix, uint32_t mat_stride) {
   if (!n_tiles || !n_win) return;
-  const uint64_t n_pairs = g.n_ind * (g.n_ind - 1) / 2;
+  // (window w's matrix at [w * mat_stride][n_pairs]: the kernel's distance between two windows' matrices)
+  const uint64_t n_pairs = g.n_ind * (g.n_ind - 1) / 2, w_pairs = n_pairs * mat_stride;
   const ngd_fix_flags f = fix ? *fix : ngd_fix_flags{nullptr, nullptr, nullptr, 0};
   for (uint32_t w0 = 0; w0 < n_win; w0 += 16 * 32768) {  // (grid.y holds 65 535)
     const uint32_t n = n_win - w0 < 16 * 32768 ? n_win - w0 : 16 * 32768;
     const dim3 grid(n_tiles * NGD_TILE, (n + 15) / 16);
     if (C)
       hipLaunchKernelGGL((k_reduce_band<16, true>), grid, dim3(128), 0, st, (const void *)C, d_win + 2 * (uint64_t)w0, n, d_tiles,
-                         g.n_pad, g.n_ind, n_pairs, nullptr, d_cnt + (uint64_t)w0 * n_pairs, f);
+                         g.n_pad, g.n_ind, w_pairs, nullptr, d_cnt + (uint64_t)w0 * w_pairs, f);
     else
       hipLaunchKernelGGL((k_reduce_band<16, false>), grid, dim3(128), 0, st, (const void *)slab, d_win + 2 * (uint64_t)w0, n,
-                         d_tiles, g.n_pad, g.n_ind, n_pairs, d_sum + (uint64_t)w0 * n_pairs,
-                         d_cnt ? d_cnt + (uint64_t)w0 * n_pairs : nullptr, f);
+                         d_tiles, g.n_pad, g.n_ind, w_pairs, d_sum + (uint64_t)w0 * w_pairs,
+                         d_cnt ? d_cnt + (uint64_t)w0 * w_pairs : nullptr, f);
+  }
+}
+
+void ngd_launch_reduce_band_w(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
+                              uint32_t n_win, uint32_t n_blocks, const void *d_Wt, uint32_t w_stride, uint32_t n_rep,
+                              uint32_t mat_stride, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
+                              unsigned long long *d_cnt, unsigned long long cnt_value, const ngd_fix_flags *fix, double fix_thr) {
+  if (!n_tiles || !n_win || !n_rep || !n_blocks) return;
+  const ngd_fix_flags f = fix ? *fix : ngd_fix_flags{nullptr, nullptr, nullptr, 0};
+  switch (ngd_reduce_chunk(n_rep)) {  // (the weights' stride is a multiple of it)
+    case 1: reduce_band_w<1>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr); break;
+    case 4: reduce_band_w<4>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr); break;
+    case 16: reduce_band_w<16>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr); break;
+    default: reduce_band_w<32>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr);
   }
 }
 

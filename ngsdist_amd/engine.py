@@ -258,6 +258,42 @@ class Engine:
                                             d.ctypes.data_as(C.POINTER(C.c_double))))
         return d
 
+    @staticmethod
+    def _job_maps(block_maps):
+        """block maps [n_rep][n_blocks] of a windowed job -> (array kept alive, pointer, n_rep, n_blocks)"""
+        if block_maps is None or len(block_maps) == 0:
+            return None, None, 0, 0
+        a = np.ascontiguousarray(block_maps, dtype=np.uint64)
+        if a.ndim != 2:
+            raise ValueError("expected [n_rep][n_blocks]")
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint64)), a.shape[0], a.shape[1]
+
+    def run_windows_job(self, lo, hi, block_maps, block_size=1, d_sum_ptr=None, d_cnt_ptr=None):
+        """bootstrap replicates inside every window (ngd_run_windows_job): windows of ONE length W, block_maps
+        [n_rep][W // block_size] shared by all of them; -> (sum, cnt) of shape (n_win, n_rep + 1, n_pairs), matrix 0 of a
+        window its full-data matrix, matrix r what run_job() gives for replicate r on the data set cut down to the window;
+        with device pointers (ngd_run_windows_job_device) the results go there and None is returned"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        if d_sum_ptr is not None:
+            _check(self._L.ngd_run_windows_job_device(self._h, lp, hp, lo.size, ap, n_rep, n_blocks, int(block_size),
+                                                      C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr)))
+            return None
+        s = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.float64)
+        c = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.uint64)
+        _check(self._L.ngd_run_windows_job(self._h, lp, hp, lo.size, ap, n_rep, n_blocks, int(block_size),
+                                           s.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return s, c
+
+    def run_windows_job_dist(self, lo, hi, block_maps, block_size=1, evol_model=1, tot_sites=0):
+        """the job and the tail of gen_dist() on every matrix (ngd_run_windows_job_dist): float64 (n_win, n_rep + 1, n_pairs)"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        d = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.float64)
+        _check(self._L.ngd_run_windows_job_dist(self._h, lp, hp, lo.size, ap, n_rep, n_blocks, int(block_size), int(tot_sites),
+                                                int(evol_model), d.ctypes.data_as(C.POINTER(C.c_double))))
+        return d
+
     def windows_info(self):
         """what the last windowed call did (ngd_last_windows): segments, slab_bytes, batches, band_launches,
         windows_by_pass, fixup_pairs, ms"""
