@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define NGD_ABI_VERSION 6 /* 6: ngd_run_job_dist, ngd_run_batch_dist, ngd_run_mult_batch_dist (and, added under 6: ngd_run_windows*, ngd_last_windows, ngd_window_ranges, ngd_run_windows_job / _job_device / _job_dist); 5: ngd_finish_stream, ngd_fixup_info.by_pass, NGD_OPT_STAGE_PIECE_MIB / _STAGE_RING / _EAGER_FULL, NGD_OPT_FIXUP_WORK 0 = no budget (every noted pair is recomputed); 4: ngd_last_spill_timing, ngd_last_fixup, ngd_image_mode, ngd_config.single_image 0 = auto / 3 = two images; 3: ngd_config.single_image / second_image_mib (were reserved, zero), ngd_fetch_matrix, ngd_score_congruence */
+#define NGD_ABI_VERSION 6 /* 6: ngd_run_job_dist, ngd_run_batch_dist, ngd_run_mult_batch_dist (and, added under 6: ngd_run_windows*, ngd_last_windows, ngd_window_ranges, ngd_run_windows_job / _job_device / _job_dist; NGD_OPT_EM_EXACT / _EM_EXACT_CAP, ngd_last_em_exact, ngd_em_exact_entries, ngd_em2_site); 5: ngd_finish_stream, ngd_fixup_info.by_pass, NGD_OPT_STAGE_PIECE_MIB / _STAGE_RING / _EAGER_FULL, NGD_OPT_FIXUP_WORK 0 = no budget (every noted pair is recomputed); 4: ngd_last_spill_timing, ngd_last_fixup, ngd_image_mode, ngd_config.single_image 0 = auto / 3 = two images; 3: ngd_config.single_image / second_image_mib (were reserved, zero), ngd_fetch_matrix, ngd_score_congruence */
 
 #define NGD_OK 0
 #define NGD_E_INVALID (-1)  /* bad argument / bad state                    */
@@ -349,6 +349,23 @@ int ngd_drop_caches(ngd_engine *e);
                                  /*     of the segment-slab plan: its partial results and counts, + the MFMA kernel's slice    */
                                  /*     weights.  An EM engine's batch is 8 n_pad^2 bytes per slice (+ 4 n_pad^2 per slice     */
                                  /*     under pairwise_del), n_pad = n_ind rounded up to 128                                   */
+#define NGD_OPT_EM_EXACT 15       /* [0] 1: the plain full-data pass of the table-driven EM kernel (ngd_run with no block map)  */
+                                 /*     stops every (pair, site) at the REFERENCE's step.  The kernels decide the stopping rule */
+                                 /*     fabs(lik - oldLik) < 0.001 (emOptim2.cpp:127) from ratios of power sums; within rounding */
+                                 /*     of the tolerance they may stop one EM step from the reference, which changes that site's */
+                                 /*     term by tens of percent.  With the option the pass notes every stop whose criterion is   */
+                                 /*     within 2^-36 (relative) of the threshold, the host reruns those sites the reference's   */
+                                 /*     way (ngd_em2_site) and the pair's sum takes c_ref - c_dev before it leaves the engine.    */
+                                 /*     Pairs without a noted site carry the bits of the option-off pass; results are           */
+                                 /*     reproducible run to run.  ngd_last_em_exact() / ngd_em_exact_entries() report the pass. */
+                                 /*     kernel = auto then means NGD_KERNEL_EM_TABLE at any number of individuals (an engine of */
+                                 /*     32 or fewer stays on it when the option goes back to 0).  NGD_E_INVALID on an           */
+                                 /*     --indep_geno engine, for an explicit kernel other than NGD_KERNEL_EM_TABLE, and         */
+                                 /*     together with NGD_OPT_EAGER_FULL (either refuses the other).                            */
+                                 /*     While it is 1, ngd_run* with a block map or multiplicities, the batch, job and windowed */
+                                 /*     calls return NGD_E_INVALID before anything is launched            */
+#define NGD_OPT_EM_EXACT_CAP 16   /* [0 = 2^20] entries the list of noted (pair, site)s holds, 32 bytes each.  A pass that notes */
+                                 /*     more is counted in full, the list grows to the count and the pass runs ONCE more        */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -403,6 +420,30 @@ int ngd_last_shader_clock(const ngd_engine *e, double *mhz);
  * of (64 x 64 pair tile, site) visits and of table rounds (16 EM steps of a tile's 128 individuals each) -- the
  * data-dependent part of its operation count (the EM's iteration count, emOptim2.cpp:118-133).  Zero for other kernels. */
 int ngd_last_em_work(const ngd_engine *e, uint64_t *tile_sites, uint64_t *table_rounds);
+
+/* NGD_OPT_EM_EXACT: the recheck of the last plain pass (zeros when the option was off) */
+typedef struct ngd_em_exact_info {
+  uint64_t noted;   /* (pair, site)s whose stop was within 2^-36 of the tolerance                                   */
+  uint64_t changed; /* ... of them, those the reference stops at another step than the device did                   */
+  uint64_t passes;  /* accumulation passes: 1, or 2 when the list had to grow                                       */
+  double ms;        /* gather + host recheck + patch, wall clock                                                    */
+} ngd_em_exact_info;
+int ngd_last_em_exact(const ngd_engine *e, ngd_em_exact_info *info);
+/* ... and its entries, sorted by (i1, i2, site): the step and term of the device, the step and term of the reference's
+ * em2() on the same six likelihoods.  Returns the number of entries of the last pass (or a negative NGD_E_* code) and
+ * writes the first min(count, cap) of them if out is not NULL. */
+typedef struct ngd_em_exact_entry {
+  uint32_t i1, i2;
+  uint64_t site;
+  uint32_t t_dev, t_ref;
+  double c_dev, c_ref;
+} ngd_em_exact_entry;
+int64_t ngd_em_exact_entries(const ngd_engine *e, ngd_em_exact_entry *out, uint64_t cap);
+/* One site of the reference's default mode, ngsDist.cpp:340-349: em2() of emOptim2.cpp:112-135 (with emStep2, normalize
+ * and lik2) over the 3 x 3 sfs, tolerance 0.001, at most 50 steps, in the reference's order of operations and with the
+ * host's log().  sfs is read as the start (the reference fills it with 1/9) and receives the result; *n_iter (may be
+ * NULL) the number of EM steps taken.  Pure host arithmetic: callable without a device. */
+void ngd_em2_site(const double gl1[3], const double gl2[3], double sfs[9], int *n_iter);
 
 /* Windows along the genome: one matrix per window [lo, hi) of the engine's sites, each exactly what ngd_run() gives on a
  * data set that holds only those sites (gen_dist() over an input cut down to the window; --pairwise_del counts, called

@@ -65,6 +65,15 @@ class NgdFixupInfo(C.Structure):
                 ("by_pass", C.c_uint64)]
 
 
+class NgdEmExactInfo(C.Structure):
+    _fields_ = [("noted", C.c_uint64), ("changed", C.c_uint64), ("passes", C.c_uint64), ("ms", C.c_double)]
+
+
+class NgdEmExactEntry(C.Structure):
+    _fields_ = [("i1", C.c_uint32), ("i2", C.c_uint32), ("site", C.c_uint64), ("t_dev", C.c_uint32), ("t_ref", C.c_uint32),
+                ("c_dev", C.c_double), ("c_ref", C.c_double)]
+
+
 # every symbol include/ngsdist_amd.h declares (tests/test_abi.py checks the header against this)
 EXPORTS = [
     "ngd_last_error", "ngd_abi_version", "ngd_device_count", "ngd_create", "ngd_destroy",
@@ -75,6 +84,7 @@ EXPORTS = [
     "ngd_taus_uniform", "ngd_boot_block_map", "ngd_n_pairs", "ngd_pair_index", "ngd_device_bytes", "ngd_device_memory", "ngd_shard_of_pair", "ngd_shard_map",
     "ngd_score_congruence", "ngd_run_windows", "ngd_run_windows_device", "ngd_run_windows_dist", "ngd_last_windows",
     "ngd_window_ranges", "ngd_run_windows_job", "ngd_run_windows_job_device", "ngd_run_windows_job_dist",
+    "ngd_last_em_exact", "ngd_em_exact_entries", "ngd_em2_site",
 ]
 
 _lib = None
@@ -171,6 +181,11 @@ def load():
     L.ngd_run_windows_job_dist.argtypes = [vp, u64p, u64p, u64, u64p, C.c_uint32, u64, u64, u64, u64, dp]
     L.ngd_window_ranges.argtypes = [u32p, u64, u64, u64, u64p, u64p, u64]
     L.ngd_window_ranges.restype = C.c_int64
+    L.ngd_last_em_exact.argtypes = [vp, C.POINTER(NgdEmExactInfo)]
+    L.ngd_em_exact_entries.argtypes = [vp, C.POINTER(NgdEmExactEntry), u64]
+    L.ngd_em_exact_entries.restype = C.c_int64
+    L.ngd_em2_site.argtypes = [dp, dp, dp, C.POINTER(C.c_int)]
+    L.ngd_em2_site.restype = None
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

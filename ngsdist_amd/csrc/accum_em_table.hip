@@ -141,7 +141,7 @@ __device__ __forceinline__ double rcp_nr(double a) {
 // One wavefront's share of a table round: steps tfirst+1 .. tfirst+SEG of its 64 individuals (lane = individual),
 // v = GL^tfirst.  One role per call, so that the whole share is one block of straight-line code: the SEG+2 power
 // sums and their reciprocals are independent of each other and the scheduler can keep the FP64 pipe full.
-template <int CH, int SEG, bool ROW, bool PACK>
+template <int CH, int SEG, bool ROW, bool PACK, bool NOTE = false>
 __device__ __forceinline__ void build_round(em_tables<CH, PACK> &L, const double *v, const double *g, const ngd_score &sc,
                                             uint32_t lane, uint32_t seg, int tfirst, bool miss) {
   constexpr int RS = em_tables<CH, PACK>::RS;
@@ -182,6 +182,7 @@ __device__ __forceinline__ void build_round(em_tables<CH, PACK> &L, const double
       const bool force = miss || tfirst + c >= MAX_ITER;
       if (ROW) {
         double q = (E * (A[c] * A[c])) * (r[c + 1] * r[c - 1]);
+        if constexpr (NOTE) q = q * (1.0 + NGD_EM_EXACT_BETA);  // the widened threshold Qw (row_nostop follows it)
         if (force) q = __builtin_inf();
         L.Qr[lane * RS + tt] = q;
         // a pair stops where R(column) < q, and the R the column builders write is 1 or more up to a few units in
@@ -201,6 +202,38 @@ __device__ __forceinline__ void build_round(em_tables<CH, PACK> &L, const double
   }
 }
 
+// NOTE (NGD_OPT_EM_EXACT, ngd_internal.h): where a term is added, the pair's own R and Qw of the step it stopped at are
+// fetched beside f and g, and the stop is unambiguous if R < Qw * kappa, kappa = (1 - beta) / (1 + beta), i.e. R below the
+// unwidened threshold narrowed by beta: the term is then the one the plain form adds at that step, and no earlier step
+// came within beta of stopping.  Otherwise (rare) the term is added all the same and the (pair, site) is noted.  A forced
+// stop has Qw = inf and is never noted; nor is a term that is not finite.
+struct em_note {  // (the plain forms carry none: a null pointer, and nothing of this is compiled)
+  unsigned long long *buf;  // the note buffer
+  uint32_t row0;            // the wavefront's first row of the tile
+  uint32_t t0;              // steps before this round
+  uint64_t site;
+};
+constexpr double EM_NOTE_KAPPA = (1.0 - NGD_EM_EXACT_BETA) / (1.0 + NGD_EM_EXACT_BETA);
+
+// The entry leaves as (workgroup, row and column of its tile): k_note_gather (layout.hip) turns that into (i1, i2) -- the
+// tile's coordinates would otherwise sit in registers through the search for the sake of this branch.  (The asm pins the
+// entry's words inside the branch for the same reason.)
+__device__ __forceinline__ void note_append(const em_note &nt, uint32_t row, uint32_t col, uint32_t T, double c) {
+  const unsigned long long slot = atomicAdd(&nt.buf[0], 1ull);  // (an integer atomic: the count is exact; the ORDER of the
+                                                                 // entries is not reproducible -- the host sorts them)
+  if (slot < *(const volatile unsigned long long *)&nt.buf[1]) {
+    asm volatile("" : "+v"(row), "+v"(col));
+    unsigned long long *e = nt.buf + NGD_NOTE_HEAD + NGD_NOTE_WORDS * slot;
+    e[0] = (unsigned long long)blockIdx.x | ((unsigned long long)(row | (col << 8)) << 32);
+    e[1] = nt.site;
+    e[2] = nt.t0 + T;
+    e[3] = (unsigned long long)__double_as_longlong(c);
+  }
+}
+__device__ __forceinline__ bool note_wanted(double rT, double qT, double c) {
+  return !(rT < qT * EM_NOTE_KAPPA) && __builtin_fabs(c) <= 1.7976931348623157e308;
+}
+
 typedef __attribute__((address_space(3))) volatile double ngd_lds_vd;
 typedef __attribute__((address_space(3))) volatile uint8_t ngd_lds_vb;
 typedef __attribute__((address_space(3))) const volatile ngd_d2 ngd_lds_cvd2;
@@ -217,11 +250,11 @@ typedef __attribute__((address_space(3))) const volatile ngd_d2 ngd_lds_cvd2;
 // RB matrices at once (the full data set and bootstrap replicates, or replicates only): the pair's term is added to
 // accr[b] with the site's weight wv[b] in matrix b -- product first, then the sum, like the one-matrix kernel, so a
 // matrix carries the same bits from either.
-template <int CH, bool WEIGHTED, bool PACK, int RB>
+template <int CH, bool WEIGHTED, bool PACK, int RB, bool NOTE = false>
 __device__ __forceinline__ void scan_row(const em_tables<CH, PACK> &L, uint32_t rb /* row * RS */, uint32_t rb_next,
                                          uint32_t lane, int r, const double (&R2)[CH], ngd_d2 (&QA)[4], uint32_t &todo,
                                          double (&accr)[RB], const double (&wv)[RB], uint32_t skip, bool load,
-                                         bool pref) {
+                                         bool pref, const em_note *nt = nullptr) {
   static_assert(CH == 16, "two blocks of eight steps");
   const bool mine = (todo >> r) & 1;
   uint64_t m = __builtin_amdgcn_ballot_w64(mine);
@@ -263,6 +296,11 @@ __device__ __forceinline__ void scan_row(const em_tables<CH, PACK> &L, uint32_t 
   const double f0 = lds_b64(&L.Fr[0][a]), g0 = lds_b64(&L.Gc[0][b]);
   const double f1 = lds_b64(&L.Fr[1][a]), g1 = lds_b64(&L.Gc[1][b]);
   const double f2 = lds_b64(&L.Fr[2][a]), g2 = lds_b64(&L.Gc[2][b]);
+  double rT = 0, qT = 0;
+  if constexpr (NOTE) {  // (the second block of thresholds is dead here: these take its registers)
+    rT = lds_b64(&L.Rc[b]);
+    qT = lds_b64(&L.Qr[a]);
+  }
   if (pref) {
 #pragma unroll
     for (int h = 0; h < 4; h++) QA[h] = *(ngd_lds_cvd2 *)&L.Qr[rb_next + 2 * h];
@@ -274,6 +312,9 @@ __device__ __forceinline__ void scan_row(const em_tables<CH, PACK> &L, uint32_t 
 #pragma unroll
     for (int b = 0; b < RB; b++) accr[b] = accr[b] + (WEIGHTED ? c * wv[b] : c);
     todo &= ~(1u << r);
+    if constexpr (NOTE) {
+      if (note_wanted(rT, qT, c)) note_append(*nt, nt->row0 + (uint32_t)r, lane, (uint32_t)T, c);
+    }
   }
 }
 
@@ -284,9 +325,9 @@ __device__ __forceinline__ void scan_row(const em_tables<CH, PACK> &L, uint32_t 
 // address; the search and the term are the plain row's, instruction for instruction (same bits).  The terms then travel
 // inside the wavefront -- through its 512 bytes of unit_c -- to the lanes that own the pairs (lane = column), which
 // add them in the same order as ever: one term per pair and site, 0.0 from the slots that had nothing to add.
-template <int CH, bool WEIGHTED, int RB>
+template <int CH, bool WEIGHTED, int RB, bool NOTE = false>
 __device__ __forceinline__ void packed_units(em_tables<CH, true> &L, uint32_t wave, uint32_t lane, uint32_t &todo,
-                                             double (&acc)[8][RB], const double (&wv)[RB]) {
+                                             double (&acc)[8][RB], const double (&wv)[RB], const em_note *nt = nullptr) {
   constexpr int RS = em_tables<CH, true>::RS;
   static_assert(CH % 8 == 0, "shape");
   ngd_lds_vd *uc = (ngd_lds_vd *)&L.unit_c[wave * 64];
@@ -324,6 +365,10 @@ __device__ __forceinline__ void packed_units(em_tables<CH, true> &L, uint32_t wa
     double c = lds_b64(&L.Fr[0][a]) * lds_b64(&L.Gc[0][b]);
     c = __builtin_fma(lds_b64(&L.Fr[1][a]), lds_b64(&L.Gc[1][b]), c);
     c = __builtin_fma(lds_b64(&L.Fr[2][a]), lds_b64(&L.Gc[2][b]), c);
+    if constexpr (NOTE) {  // (the lane that computed the term notes it: the owner only adds)
+      const double rT = lds_b64(&L.Rc[b]), qT = lds_b64(&L.Qr[a]);
+      if (T && note_wanted(rT, qT, c)) note_append(*nt, nt->row0 + r, col, (uint32_t)T, c);
+    }
     const uint64_t done = __builtin_amdgcn_ballot_w64(T != 0);  // bit = 8 * slot + row
     uc[lane] = T ? c : 0.0;  // (unweighted: the owner multiplies; 0 x weight adds nothing)
     if (sel) {  // the owners of this unit's columns collect their 8 rows
@@ -389,7 +434,12 @@ constexpr int PACK_DENSE = NGD_PACK_DENSE;
 // plain pass's instruction for instruction, and a term that is not finite stays in its segment's plane.  Register budget
 // (hipcc --save-temps): every SEGS instantiation has the VGPR count of its unweighted neighbour (shape 0: 128) and no scratch;
 // the bounds arrive by scalar loads, five scalar instructions more than the neighbour's prologue.
-template <int NW, int CH, int WPS, bool WEIGHTED, bool PDEL, bool PACK, int RB, bool SPILL = false, bool SEGS = false>
+//
+// NOTE (NGD_OPT_EM_EXACT): the plain pass that also notes the (pair, site)s whose stop is within 2^-36 of the tolerance
+// (em_note above).  The note buffer arrives in `nanlist`, which only the SPILL form reads otherwise: the kernel's
+// arguments, and with them every other instantiation, are what they were.
+template <int NW, int CH, int WPS, bool WEIGHTED, bool PDEL, bool PACK, int RB, bool SPILL = false, bool SEGS = false,
+          bool NOTE = false>
 __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
     const double *__restrict__ PA, const uint32_t *__restrict__ ws, const double *__restrict__ Wb, ngd_score sc,
     const ngd_tile *__restrict__ tiles, uint32_t n_tiles, uint32_t n_ig, uint32_t n_pad, uint64_t n_ind,
@@ -404,6 +454,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
   static_assert(RB == 1 || (PACK && WEIGHTED), "several matrices per pass: the packed form, weighted");
   static_assert(!SPILL || (PACK && !WEIGHTED && RB == 1), "spilled terms: the packed form, unweighted");
   static_assert(!SEGS || (!WEIGHTED && RB == 1 && !SPILL), "a slice table: one matrix per segment, unweighted");
+  static_assert(!NOTE || (!WEIGHTED && RB == 1 && !SPILL && !SEGS), "the noting form: the plain one-matrix pass");
   // rows per group (one uniform "anything left?" test per group; their table reads are in flight together)
   constexpr int GR = (WPS >= 4 || PACK) ? 1 : 4;
   static_assert(RPW % GR == 0 && CH % 4 == 0 && (CH % 8 == 0 || CH % 8 == 4), "shape");
@@ -564,8 +615,8 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
     for (int t0 = 0; t0 < MAX_ITER; t0 += CH, round++) {  // steps t0+1 .. t0+CH
       {
         const int tfirst = t0 + (int)seg * SEG;  // this wavefront's steps are tfirst+1 .. tfirst+SEG
-        if (is_row) build_round<CH, SEG, true, PACK>(L, v, g, sc, lane, seg, tfirst, miss);
-        else build_round<CH, SEG, false, PACK>(L, v, g, sc, lane, seg, tfirst, miss);
+        if (is_row) build_round<CH, SEG, true, PACK, NOTE>(L, v, g, sc, lane, seg, tfirst, miss);
+        else build_round<CH, SEG, false, PACK, NOTE>(L, v, g, sc, lane, seg, tfirst, miss);
 #pragma unroll
         for (int x = 0; x < 3; x++) v[x] *= gch[x];
       }
@@ -608,7 +659,13 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
               // every barrier ~9 % earlier (cycle stamps); alternating their priorities row by row shares the SIMD evenly
               if (((r & 1) != 0) != (wave >= NW / 2)) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
 #endif
-              if ((go >> r) & 1)
+              if constexpr (NOTE) {
+                const em_note nt{nanlist, wave * RPW, (uint32_t)t0, s};
+                if ((go >> r) & 1)
+                  scan_row<CH, WEIGHTED, PACK, RB, true>(L, (wave * RPW + r) * RS, (wave * RPW + r + 1) * RS, lane, r, R2, QA,
+                                                         todo, acc[r], wv, ((ska >> r) & 1) | (((skb >> r) & 1) << 1),
+                                                         (load >> r) & 1, (pref >> r) & 1, &nt);
+              } else if ((go >> r) & 1)
                 scan_row<CH, WEIGHTED, PACK, RB>(L, (wave * RPW + r) * RS, (wave * RPW + r + 1) * RS, lane, r, R2, QA,
                                                  todo, acc[r], wv, ((ska >> r) & 1) | (((skb >> r) & 1) << 1),
                                                  (load >> r) & 1, (pref >> r) & 1);
@@ -617,7 +674,10 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
             __builtin_amdgcn_s_setprio(0);
 #endif
           }
-          if (t0 != 0) packed_units<CH, WEIGHTED, RB>(L, wave, lane, todo, acc, wv);
+          if constexpr (NOTE) {
+            const em_note nt{nanlist, wave * RPW, (uint32_t)t0, s};
+            if (t0 != 0) packed_units<CH, WEIGHTED, RB, true>(L, wave, lane, todo, acc, wv, &nt);
+          } else if (t0 != 0) packed_units<CH, WEIGHTED, RB>(L, wave, lane, todo, acc, wv);
         }
       } else if (__builtin_amdgcn_ballot_w64(todo != 0)) {
         double R2[CH];
@@ -660,6 +720,13 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
             c = __builtin_fma(lds_b64(&L.Fr[1][a]), lds_b64(&L.Gc[1][b]), c);
             c = __builtin_fma(lds_b64(&L.Fr[2][a]), lds_b64(&L.Gc[2][b]), c);
             if (WEIGHTED) c = c * wgt;
+            if constexpr (NOTE) {
+              const double rT = lds_b64(&L.Rc[b]), qT = lds_b64(&L.Qr[a]);
+              if (T[q] && note_wanted(rT, qT, c)) {
+                const em_note nt{nanlist, wave * RPW, (uint32_t)t0, s};
+                note_append(nt, nt.row0 + (uint32_t)r, lane, (uint32_t)T[q], c);
+              }
+            }
             if (T[q]) {
               acc[r][0] = acc[r][0] + c;
               todo &= ~(1u << r);
@@ -770,6 +837,30 @@ void ngd_launch_accum_em_table(hipStream_t st, const ngd_geom &g, const double *
   }
 #undef NGD_EMT_WP
 #undef NGD_EMT
+}
+
+// The noting form of the plain pass (NGD_OPT_EM_EXACT): d_note as ngd_internal.h lays it out, its count zeroed and its
+// capacity set by the caller.  Every shape has the form.
+void ngd_launch_accum_em_table_note(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score,
+                                    int pairwise_del, int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks,
+                                    uint64_t sites_per_slice, double *slab, unsigned long long *d_counters,
+                                    unsigned long long *d_note) {
+  if (!n_tiles64) return;
+  const bool p = pairwise_del != 0;
+#define NGD_EMT_N(NW, CH, WPS, P, K)                                                                                          \
+  hipLaunchKernelGGL((k_accum_em_table<NW, CH, WPS, false, P, K, 1, false, false, true>), dim3(n_tiles64 * n_ks), dim3(NW * 64), \
+                     0, st, PA, nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, g.n_sites,             \
+                     sites_per_slice, slab, d_counters, 0, d_note)
+#define NGD_EMT_NP(NW, CH, WPS, K) do { if (p) NGD_EMT_N(NW, CH, WPS, true, K); else NGD_EMT_N(NW, CH, WPS, false, K); } while (0)
+  switch (shape) {
+    default: NGD_EMT_NP(8, 16, 4, true); break;
+    case 1: NGD_EMT_NP(4, 16, 2, false); break;
+    case 2: NGD_EMT_NP(8, 12, 4, false); break;
+    case 3: NGD_EMT_NP(4, 12, 2, false); break;
+    case 4: NGD_EMT_NP(8, 16, 4, false); break;
+  }
+#undef NGD_EMT_NP
+#undef NGD_EMT_N
 }
 
 // Slices ks0 .. ks0 + n_sub - 1 of a plain (unweighted) pass on their own -- the sites of the others need not be resident yet

@@ -132,8 +132,14 @@ int ngd_set_option(ngd_engine *e, int option, uint64_t value) {
       e->opt_win_plan = value;
       break;
     case NGD_OPT_WIN_MAX_BYTES: e->opt_win_max_bytes = value; break;
+    case NGD_OPT_EM_EXACT: return em_exact_set(e, value);
+    case NGD_OPT_EM_EXACT_CAP:
+      if (value >= (1ull << 31)) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT_CAP is below 2^31 entries");
+      e->note_cap = value ? value : 1ull << 20;
+      break;
     case NGD_OPT_EAGER_FULL:
       if (e->pin_sites || e->committed) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EAGER_FULL before the first ngd_stage_acquire");
+      if (value && e->opt_em_exact) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EAGER_FULL and NGD_OPT_EM_EXACT refuse each other (the eager pass does not note)");
       e->opt_eager = value != 0 && eager_supported(e);  // (kernels without a slice-range launch: silently off)
       break;
     case NGD_OPT_STAGE_PIECE_MIB:

@@ -7,9 +7,10 @@
 // per_slice / kg_lim count list entries
 // k_per_slice != 0 (MFMA, bootstrap blocks that are not whole k-groups): slices of k_per_slice contraction indices,
 // masked by the per-slice 0/1 weights in e->blk.wslice (w_stride k-groups per slice)
+// note (NGD_OPT_EM_EXACT, table-driven EM kernel, a plain pass): the noting form, into e->d_note
 static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *kgl, uint64_t sites_eff, uint32_t n_ks,
                               uint64_t per_slice, uint64_t kg_lim, double *slab, uint64_t k_per_slice = 0,
-                              uint32_t w_stride = 0) {
+                              uint32_t w_stride = 0, bool note = false) {
   const ngd_geom &g = e->g;
   switch (e->kernel) {
     case NGD_KERNEL_MFMA:
@@ -99,6 +100,10 @@ static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *k
       }
       break;
     case NGD_KERNEL_EM_TABLE:
+      if (note)
+        ngd_launch_accum_em_table_note(e->st, g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64, n_ks,
+                                       per_slice, slab, e->d_emcnt, e->d_note);
+      else
       ngd_launch_accum_em_table(e->st, g, e->PA, w, sites_eff, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64,
                                 e->n_tiles64, n_ks, per_slice, slab, e->d_emcnt);
       break;
@@ -144,8 +149,9 @@ void read_timing(ngd_engine *e, uint64_t n_eff, uint32_t launches, bool add) {
 
 // One accumulation pass over the resident data set: the full data set (mult == NULL) or one bootstrap
 // replicate given as block multiplicities (applied inside the accumulation kernel).
-int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n_blocks, uint64_t block_size,
-              uint64_t n_drawn, double *d_sum, unsigned long long *d_cnt, bool add_timing) {
+// note: the plain pass in its noting form (NGD_OPT_EM_EXACT); pass_impl then rechecks what it noted
+static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n_blocks, uint64_t block_size,
+                     uint64_t n_drawn, double *d_sum, unsigned long long *d_cnt, bool add_timing, bool note) {
   const ngd_geom &g = e->g;
   const uint64_t n_pairs = ngd_n_pairs(g.n_ind);
   uint64_t n_eff = g.n_sites;
@@ -182,6 +188,8 @@ int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n
   const bool zero_cnt = zero_sum || e->cfg.pairwise_del;  // k_count adds with integer atomics
   if (zero_sum) HIPCHK(hipMemsetAsync(d_sum, 0, n_pairs * sizeof(double), e->st));
   if (zero_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, n_pairs * sizeof(unsigned long long), e->st));
+  if (note)
+    if (int rc = em_exact_begin(e)) return rc;
   HIPCHK(hipEventRecord(e->ev[1], e->st));
   int rc_acc = NGD_OK;
   if (e->kernel == NGD_KERNEL_STREAM)
@@ -197,7 +205,7 @@ int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n
     e->eager_valid = false;
     e->eager_slices = 0;
   } else
-    rc_acc = launch_accumulate(e, ws, nullptr, n_eff, e->n_ks, e->per_slice, g.n_kg, e->slab);
+    rc_acc = launch_accumulate(e, ws, nullptr, n_eff, e->n_ks, e->per_slice, g.n_kg, e->slab, 0, 0, note);
   if (rc_acc) return rc_acc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev[2], e->st));
@@ -231,6 +239,25 @@ int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n
   if (fix)
     return fixup_pass(e, ws, n_eff, d_sum, 0, 0, nullptr, e->cfg.pairwise_del ? d_cnt : nullptr,
                       NGD_FIX_MEAN * (double)(mult ? n_drawn : n_eff));
+  return NGD_OK;
+}
+
+int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n_blocks, uint64_t block_size,
+              uint64_t n_drawn, double *d_sum, unsigned long long *d_cnt, bool add_timing) {
+  // (the option refuses every call but the plain pass, and the eager pass: em_exact_refuse, ngd_set_option)
+  const bool note = e->opt_em_exact && !mult && e->kernel == NGD_KERNEL_EM_TABLE;
+  int rc = pass_once(e, mult, mult_max, n_blocks, block_size, n_drawn, d_sum, d_cnt, add_timing, note);
+  if (rc || !note) return rc;
+  // what the pass noted, rechecked on the host before any sum leaves the engine.  A list that was too short has counted
+  // what it needs: it grows to that and the pass runs once more (the count is a function of the data: it fits then)
+  bool again = false;
+  if ((rc = em_exact_finish(e, d_sum, &again))) return rc;
+  if (again) {
+    if ((rc = pass_once(e, mult, mult_max, n_blocks, block_size, n_drawn, d_sum, d_cnt, add_timing, true))) return rc;
+    if ((rc = em_exact_finish(e, d_sum, &again))) return rc;
+    if (again) return fail(NGD_E_HIP, "NGD_OPT_EM_EXACT: internal -- the second pass noted more than the first counted");
+    e->exact_info.passes = 2;
+  }
   return NGD_OK;
 }
 
@@ -708,8 +735,12 @@ int run_impl(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult_in,
              uint64_t n_blocks, uint64_t block_size, double *d_sum, unsigned long long *d_cnt) {
   if (!e) return fail(NGD_E_INVALID, "ngd_run: null engine");
   if (!e->committed) return fail(NGD_E_INVALID, "ngd_run: call ngd_commit() first");
+  if (n_rep)
+    if (int rc = em_exact_refuse(e, "a run with a block map or multiplicities, a batch or a job")) return rc;
   HIPCHK(hipSetDevice(e->device));
   const ngd_geom &g = e->g;
+  e->exact_info = ngd_em_exact_info{};
+  e->exact_entries.clear();
   e->spill_timing = ngd_spill_timing{};
   e->fix_info = ngd_fixup_info{};
   e->n_batch_valid = 0;  // (the matrices of an earlier batch are not this call's: set again by copy_out() on success)

@@ -42,6 +42,7 @@ static int windows_check(const ngd_engine *e, const uint64_t *lo, const uint64_t
   if (!e) return fail(NGD_E_INVALID, std::string(who) + ": null engine");
   if (!lo || !hi || !n_win) return fail(NGD_E_INVALID, std::string(who) + ": no windows");
   if (!e->committed) return fail(NGD_E_INVALID, std::string(who) + ": call ngd_commit() first");
+  if (int rc = em_exact_refuse(e, who)) return rc;
   if (e->cfg.shard_world > 1)
     return fail(NGD_E_INVALID, std::string(who) + ": windows on an engine that owns a share of the pairs are not supported");
   if (n_win >= (1ull << 31)) return fail(NGD_E_INVALID, std::string(who) + ": too many windows in one call");

@@ -69,6 +69,7 @@
 #pragma weak ngd_run_windows_dist
 #pragma weak ngd_last_windows
 #pragma weak ngd_run_windows_job_dist  // (--win_boot_rep)
+#pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
 static const double kInf = 1e15;          // INF, gen_func.hpp:15
@@ -107,6 +108,9 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // per window what the reference prints for the cut-down file with --n_boot_rep.  Not --n_boot_rep, which resamples the genome.
   bool win_boot = false;
   uint64_t win_boot_rep = 0;
+  // --em_exact: on the EM path the full-data pass stops every (pair, site) at the reference's EM step (NGD_OPT_EM_EXACT: the
+  // stops within rounding of the tolerance are rerun on the host).  Not in the reference.
+  bool em_exact = false;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -151,7 +155,13 @@ static void die_engine(const char *func, int rc) {
 // fix-up pass of nearly identical pairs did in the last engine call.  Pairs it had to leave alone (more of them than its
 // budget covers: a large data set of copies of one individual) keep an ABSOLUTE error bound -- far below what "%.10f"
 // prints, but the user should know; said once.  --verbose 2: the pairs recomputed, every call.
+static uint64_t g_exact_noted = 0, g_exact_changed = 0;  // --em_exact: over every engine's plain pass (site ranges add up)
 static void report_fixup(ngd_engine *h, uint64_t verbose) {
+  ngd_em_exact_info x;
+  if (ngd_last_em_exact && ngd_last_em_exact(h, &x) == NGD_OK) {
+    g_exact_noted += x.noted;
+    g_exact_changed += x.changed;
+  }
   ngd_fixup_info f;
   if (ngd_last_fixup(h, &f) != NGD_OK) return;
   static bool warned = false;
@@ -206,6 +216,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"win_size", required_argument, nullptr, 1011},
                                  {"win_step", required_argument, nullptr, 1012},
                                  {"win_boot_rep", required_argument, nullptr, 1013},
+                                 {"em_exact", no_argument, nullptr, 1014},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -241,6 +252,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1011: p.win = true; p.win_size = strtoull(optarg, nullptr, 10); break;
       case 1012: p.win_step_set = true; p.win_step = strtoull(optarg, nullptr, 10); break;
       case 1013: p.win_boot = true; p.win_boot_rep = strtoull(optarg, nullptr, 10); break;
+      case 1014: p.em_exact = true; break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -283,6 +295,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.win || p.win_step_set)
       fprintf(stderr, "\twin_size: %lu\n\twin_step: %lu\n\n", p.win_size, p.win_step_set ? p.win_step : p.win_size);
     if (p.win_boot) fprintf(stderr, "\twin_boot_rep: %lu\n\n", p.win_boot_rep);
+    if (p.em_exact) fprintf(stderr, "\tem_exact: true\n\n");
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -305,6 +318,13 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
   if (p.win_boot && p.n_boot_rep > 0)
     die(__FUNCTION__, "bootstrap replicates inside windows (--win_boot_rep) cannot be combined with bootstrap replicates of the whole data set (--n_boot_rep)!");
   if (p.win_boot && p.win_boot_rep >= (1ull << 31)) die(__FUNCTION__, "too many bootstrap replicates inside windows (--win_boot_rep)!");
+  if (p.em_exact) {
+    if (p.indep_geno || p.call_geno || !p.in_probs)  // (genotypes, given or called, go the --indep_geno way: ngsDist.cpp:55-65)
+      die(__FUNCTION__, "the reference's EM stopping step (--em_exact) belongs to the EM path: not with --indep_geno / --call_geno or genotype input!");
+    if (p.n_boot_rep > 0) die(__FUNCTION__, "the reference's EM stopping step (--em_exact) cannot be combined with bootstrap replicates (--n_boot_rep)!");
+    if (p.win) die(__FUNCTION__, "the reference's EM stopping step (--em_exact) cannot be combined with windows (--win_size)!");
+    p.eager = 0;  // (the pass started beside the load does not note)
+  }
   if (p.win) {
     if (!p.win_step_set) p.win_step = p.win_size;
     if (p.win_size < 1) die(__FUNCTION__, "window size (--win_size) cannot be less than 1!");
@@ -1179,6 +1199,7 @@ int main(int argc, char **argv) {
     if (p.eager && (!p.indep_geno || p.eager >= 2) && (p.n_boot_rep == 0 || eager_ranges) && !p.win &&
         (rc = ngd_set_option(eng.h, NGD_OPT_EAGER_FULL, 1)))
       die_engine("ngd_set_option", rc);
+    if (p.em_exact && (rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT, 1))) die_engine("ngd_set_option", rc);
     if (p.stage_piece && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_PIECE_MIB, p.stage_piece))) die_engine("ngd_set_option", rc);
     if (p.stage_ring && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_RING, p.stage_ring))) die_engine("ngd_set_option", rc);
   };
@@ -1662,6 +1683,9 @@ int main(int argc, char **argv) {
     g_phases.add("of_matrices_format_write", t_write);
     g_phases.print();
   }
+  if (p.em_exact && p.verbose >= 1)
+    fprintf(stderr, "==> em_exact: %lu (pair, site)s within rounding of the EM's tolerance rechecked, %lu moved to the reference's step\n",
+            (unsigned long)g_exact_noted, (unsigned long)g_exact_changed);
   if (p.verbose >= 1) fprintf(stderr, "==> Freeing memory...\n");
   if (p.verbose >= 1) fprintf(stderr, "Done!\n");
   return 0;

@@ -524,6 +524,49 @@ int ngd_finish_stream(const double *sum, const uint64_t *cnt, uint64_t n_pairs, 
 
 // --win_size / --win_step: per chromosome (a maximal run of equal ids) the windows of `size` sites every `step` sites that
 // fit inside it.  The host and the Python package both call this, so that they agree on the list.
+// One site of the reference's EM for two individuals: em2() (emOptim2.cpp:112-135) around emStep2 (:91-109), normalize
+// (:69-75) and lik2 (:77-89), restated for GL1.x == 1 and dim == 9 -- the operation order is the reference's: every
+// product is (sfs * g1) * g2, sums run left to right from 0, the step's posterior is normalised twice (the site's own
+// terms, then their "sum over sites", 0 + inner).  Built like the tail of gen_dist() above: g++ -O3, glibc log, no FMA
+// contraction -- the engine's NGD_OPT_EM_EXACT recheck decides the stopping step with it (engine_em_exact.hip).
+static inline void em2_normalize(double *tmp) {
+  double s = 0;
+  for (int i = 0; i < 9; i++) s += tmp[i];
+  for (int i = 0; i < 9; i++) tmp[i] /= s;
+}
+static inline double em2_lik(const double *sfs, const double *g1, const double *g2) {
+  double res = 0, tmp = 0;
+  int inc = 0;
+  for (int x = 0; x < 3; x++)
+    for (int y = 0; y < 3; y++) tmp += sfs[inc++] * g1[x] * g2[y];
+  res += log(tmp);
+  return res;
+}
+void ngd_em2_site(const double gl1[3], const double gl2[3], double sfs[9], int *n_iter) {
+  const double tole = 0.001;  // ngsDist.cpp:349
+  const int max_iter = 50;
+  double old_lik = em2_lik(sfs, gl1, gl2), inner[9], post[9];
+  int it = 0;
+  while (it < max_iter) {
+    int inc = 0;
+    for (int x = 0; x < 9; x++) post[x] = 0.0;
+    for (int x = 0; x < 3; x++)
+      for (int y = 0; y < 3; y++) {
+        inner[inc] = sfs[inc] * gl1[x] * gl2[y];
+        inc++;
+      }
+    em2_normalize(inner);
+    for (int x = 0; x < 9; x++) post[x] += inner[x];
+    em2_normalize(post);
+    for (int i = 0; i < 9; i++) sfs[i] = post[i];
+    it++;
+    const double lik = em2_lik(sfs, gl1, gl2);
+    if (fabs(lik - old_lik) < tole) break;
+    old_lik = lik;
+  }
+  if (n_iter) *n_iter = it;
+}
+
 int64_t ngd_window_ranges(const uint32_t *chrom_id, uint64_t n_sites, uint64_t size, uint64_t step, uint64_t *lo, uint64_t *hi,
                           uint64_t cap) {
   if (!size || !step) return NGD_E_INVALID;

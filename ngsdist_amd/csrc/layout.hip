@@ -498,3 +498,31 @@ void ngd_launch_seg_weights(hipStream_t st, const uint64_t *d_seg, uint32_t n_se
   const uint32_t ny = (uint32_t)(want < 64 ? want : 64);
   hipLaunchKernelGGL(k_seg_weights, dim3(n_seg, ny ? ny : 1), dim3(256), 0, st, d_seg, d_W, d3_of(d3));
 }
+
+// NGD_OPT_EM_EXACT: the noted (pair, site)s of a pass (the note buffer of ngd_internal.h).  Word 0 of an entry arrives as
+// workgroup | row << 32 | column << 40 of the workgroup's 64 x 64 tile and leaves as i1 | i2 << 32; the six likelihoods of
+// the entry's site are read out of the fragment-major image: element (i, k = 3 site + x) at ngd_frag_off(k, i).
+namespace {
+__global__ __launch_bounds__(256) void k_note_gather(const double *__restrict__ PA, const ngd_tile *__restrict__ tiles64,
+                                                     uint32_t n_tiles64, uint32_t n_ig, unsigned long long *__restrict__ entries,
+                                                     uint32_t n, double *__restrict__ gl) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= n) return;
+  unsigned long long *e = entries + (uint64_t)q * NGD_NOTE_WORDS;
+  const unsigned long long w = e[0], site = e[1];
+  const ngd_tile t = tiles64[(uint32_t)w % n_tiles64];
+  const uint32_t i1 = t.ti * 64u + (uint32_t)((w >> 32) & 0xff), i2 = t.tj * 64u + (uint32_t)((w >> 40) & 0xff);
+  e[0] = (unsigned long long)i1 | ((unsigned long long)i2 << 32);
+#pragma unroll
+  for (int x = 0; x < 3; x++) {
+    gl[6 * (uint64_t)q + x] = PA[ngd_frag_off(3 * site + x, i1, n_ig)];
+    gl[6 * (uint64_t)q + 3 + x] = PA[ngd_frag_off(3 * site + x, i2, n_ig)];
+  }
+}
+}  // namespace
+
+void ngd_launch_note_gather(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_tile *d_tiles64, uint32_t n_tiles64,
+                            unsigned long long *d_entries, uint32_t n, double *d_gl) {
+  if (!n || !n_tiles64) return;
+  hipLaunchKernelGGL(k_note_gather, dim3((n + 255) / 256), dim3(256), 0, st, PA, d_tiles64, n_tiles64, g.n_ig, d_entries, n, d_gl);
+}

@@ -210,6 +210,17 @@ struct ngd_engine : ngd_mem {
   DevBuf<uint32_t> d_winblk;  // a job's replicates (ngd_run_windows_job*): [window][block] first slice of the block
   uint64_t opt_win_plan = 0, opt_win_max_bytes = 0;  // NGD_OPT_WIN_PLAN, NGD_OPT_WIN_MAX_BYTES
   ngd_windows_info win_info{};
+  // NGD_OPT_EM_EXACT (engine_em_exact.hip): the plain pass of the table-driven EM kernel notes the (pair, site)s whose stop
+  // is within 2^-36 of the tolerance; the host reruns them the reference's way and the pairs' sums are patched
+  bool opt_em_exact = false;
+  uint64_t note_cap = 1ull << 20;      // entries the list is to hold (NGD_OPT_EM_EXACT_CAP; grown by a pass that noted more)
+  DevBuf<unsigned long long> d_note;   // the note buffer (ngd_internal.h): count, capacity, the entries
+  unsigned long long note_head[NGD_NOTE_HEAD] = {0, 0, 0, 0};  // what a pass starts from (alive while its copy is in flight)
+  DevBuf<double> d_note_gl, d_note_delta;  // the entries' likelihoods; the corrections in (pair, site) order
+  DevBuf<unsigned long long> d_note_pair;  // ... the distinct pairs' indices
+  DevBuf<uint32_t> d_note_first;           // ... and where each pair's corrections start (+ one past the last)
+  ngd_em_exact_info exact_info{};
+  std::vector<ngd_em_exact_entry> exact_entries;  // of the last plain pass, sorted
 };
 
 // The operand images and slabs (a GiB and more): an address range reserved at once, physical pieces of 256 MiB created,
@@ -280,6 +291,11 @@ int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n
               uint64_t n_drawn, double *d_sum, unsigned long long *d_cnt, bool add_timing);
 int run_impl(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult_in, uint32_t n_rep, bool lead_full,
              uint64_t n_blocks, uint64_t block_size, double *d_sum, unsigned long long *d_cnt);
+// engine_em_exact.hip
+int em_exact_refuse(const ngd_engine *e, const char *who);  // NGD_E_INVALID while the option is on: `who` is not served
+int em_exact_set(ngd_engine *e, uint64_t value);            // NGD_OPT_EM_EXACT
+int em_exact_begin(ngd_engine *e);                          // before the noting pass: the list is there and empty
+int em_exact_finish(ngd_engine *e, double *d_sum, bool *again);  // after it (stream idle): recheck + patch, or grow the list
 // engine_out.hip
 bool out_trace();
 double out_now();

@@ -168,6 +168,27 @@ void ngd_launch_accum_em_table(hipStream_t st, const ngd_geom &g, const double *
                                const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice,
                                double *slab, unsigned long long *d_counters /* [4]: += (tile, site) visits, table rounds; [2..3] = clock counters */);
 
+// NGD_OPT_EM_EXACT: the noting form of the plain pass.  The rows' thresholds are widened by (1 + NGD_EM_EXACT_BETA), so
+// that no step before the one a pair stops at can be the reference's stopping step; a stop whose criterion is not below
+// the threshold narrowed by as much -- R < Q (1 - beta) -- is within rounding of the tolerance, and is noted for the
+// host's recheck (engine_em_exact.hip).  The note buffer: [0] entries noted (counts on past the capacity), [1] the
+// capacity in entries, then from word NGD_NOTE_HEAD on NGD_NOTE_WORDS words per entry:
+//   i1 | i2 << 32,  site,  the step the pair stopped at (1 .. 50),  the bits of the term it added
+// (word 0 leaves the accumulation kernel as workgroup | row of the tile << 32 | column << 40; ngd_launch_note_gather rewrites it)
+#define NGD_EM_EXACT_BETA 0x1p-36
+#define NGD_NOTE_HEAD 4
+#define NGD_NOTE_WORDS 4
+void ngd_launch_accum_em_table_note(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score,
+                                    int pairwise_del, int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks,
+                                    uint64_t sites_per_slice, double *slab, unsigned long long *d_counters,
+                                    unsigned long long *d_note);
+// layout.hip: the six likelihoods of every noted (pair, site) out of the image: gl[6 e ..] = GL_i1[0..2], GL_i2[0..2]
+void ngd_launch_note_gather(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_tile *d_tiles64, uint32_t n_tiles64,
+                            unsigned long long *d_entries, uint32_t n, double *d_gl);
+// reduce.hip: d_sum[pair[q]] += delta[first[q]] + ... + delta[first[q + 1] - 1], added one by one in that order
+void ngd_launch_note_patch(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
+                           uint32_t n_pairs_noted, double *d_sum);
+
 // accum_em_table.hip, windows along the genome: slice ks = sites [s_lo, s_hi) of entry ks of the slice table (NGD_SEG_SLO /
 // NGD_SEG_SHI; any length from 1, any first site, all below g.n_sites), slab [n_seg][n_pad][n_pad]; every `shape` has the form
 void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,

@@ -672,3 +672,23 @@ void ngd_launch_count(hipStream_t st, const ngd_geom &g, const unsigned long lon
   hipLaunchKernelGGL(k_count, dim3(n_tiles * 16, ny), dim3(256), 0, st, mask, planes, n_planes, g.n_words, d_tiles,
                      g.n_ind, d_cnt);
 }
+
+// NGD_OPT_EM_EXACT: the host's verdict on the noted (pair, site)s, one thread per distinct pair: the pair's corrections
+// c_ref - c_dev are added to its sum one by one, in site order (the order the host sorted them in)
+namespace {
+__global__ __launch_bounds__(256) void k_note_patch(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ first,
+                                                    const double *__restrict__ delta, uint32_t n, double *__restrict__ d_sum) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= n) return;
+  double s = d_sum[pair[q]];
+  for (uint32_t k = first[q]; k < first[q + 1]; k++) s = s + delta[k];
+  d_sum[pair[q]] = s;
+}
+}  // namespace
+
+void ngd_launch_note_patch(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
+                           uint32_t n_pairs_noted, double *d_sum) {
+  if (!n_pairs_noted) return;
+  hipLaunchKernelGGL(k_note_patch, dim3((n_pairs_noted + 255) / 256), dim3(256), 0, st, d_pair, d_first, d_delta, n_pairs_noted,
+                     d_sum);
+}

@@ -16,7 +16,11 @@ KERNELS = {"auto": 0, "stream": 1, "mfma": 2, "em_faithful": 3, "em_fast": 4, "e
 # NGD_OPT_* of include/ngsdist_amd.h
 OPTIONS = {"boot_partials": 1, "boot_max_bytes": 2, "boot_wg": 3, "boot_unaligned": 4, "em_batch": 5,
            "em_spill": 6, "em_spill_bytes": 7, "single_image_bytes": 8, "fixup_work": 9, "stage_piece_mib": 10,
-           "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "debug_forge_job": 100}
+           "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "em_exact": 15, "em_exact_cap": 16,
+           "debug_forge_job": 100}
+# ngd_em_exact_entry
+EM_EXACT_ENTRY = np.dtype([("i1", np.uint32), ("i2", np.uint32), ("site", np.uint64), ("t_dev", np.uint32),
+                           ("t_ref", np.uint32), ("c_dev", np.float64), ("c_ref", np.float64)], align=True)
 
 # parse_args.cpp:25-27
 DEFAULT_SCORE = (0.0, 0.5, 1.0, 0.5, 0.0, 0.5, 1.0, 0.5, 0.0)
@@ -322,7 +326,9 @@ class Engine:
 
     def set_option(self, name, value):
         """plan selection for the replicate loop (ngd_set_option): boot_partials, boot_max_bytes, boot_wg, boot_unaligned,
-        em_batch, em_spill, em_spill_bytes, single_image_bytes, fixup_work, win_plan, win_max_bytes"""
+        em_batch, em_spill, em_spill_bytes, single_image_bytes, fixup_work, win_plan, win_max_bytes; em_exact (the plain
+        pass of the table-driven EM kernel stops where the reference does: last_em_exact(), em_exact_entries()) and
+        em_exact_cap"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self
 
@@ -353,6 +359,23 @@ class Engine:
         _check(self._L.ngd_last_fixup(self._h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_}
 
+    def last_em_exact(self):
+        """the recheck of the last plain pass under the em_exact option (ngd_last_em_exact): noted, changed, passes, ms"""
+        t = _lib.NgdEmExactInfo()
+        _check(self._L.ngd_last_em_exact(self._h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_}
+
+    def em_exact_entries(self):
+        """the noted (pair, site)s of that pass, sorted by (i1, i2, site) (ngd_em_exact_entries): a structured array with
+        i1, i2, site, t_dev, t_ref, c_dev, c_ref"""
+        n = self._L.ngd_em_exact_entries(self._h, None, 0)
+        if n < 0:
+            _check(int(n))
+        out = np.zeros(int(n), dtype=EM_EXACT_ENTRY)
+        if n:
+            self._L.ngd_em_exact_entries(self._h, out.ctypes.data_as(C.POINTER(_lib.NgdEmExactEntry)), int(n))
+        return out
+
     def em_work(self):
         """table-driven EM kernel: ((tile, site) visits, table rounds) of the last run"""
         a, b = C.c_uint64(0), C.c_uint64(0)
@@ -382,6 +405,19 @@ def finish(sum_, cnt, tot_sites=0, evol_model=1, out=None):
     _check(L.ngd_finish(s.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_uint64)),
                         s.size, int(tot_sites), int(evol_model), out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+def em2_site(g1, g2):
+    """one site of the reference's two-individual EM (ngd_em2_site: em2() of emOptim2.cpp over a 3 x 3 sfs that starts at
+    1/9, tolerance 0.001, at most 50 steps) on the host: -> (sfs float64[9], number of EM steps).  Needs no device."""
+    L = _lib.load()
+    a = np.ascontiguousarray(g1, dtype=np.float64).reshape(3)
+    b = np.ascontiguousarray(g2, dtype=np.float64).reshape(3)
+    sfs = np.full(9, 1.0 / 9)
+    n = C.c_int(0)
+    dp = C.POINTER(C.c_double)
+    L.ngd_em2_site(a.ctypes.data_as(dp), b.ctypes.data_as(dp), sfs.ctypes.data_as(dp), C.byref(n))
+    return sfs, int(n.value)
 
 
 def window_ranges(n_sites, size, step=None, chrom=None):

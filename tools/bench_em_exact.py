@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""What NGD_OPT_EM_EXACT costs: the plain full-data pass of the table-driven EM kernel with the option off and on, on the
+synthetic data set of bench.py's EM configuration (1000 individuals x 1e5 sites unless told otherwise), in ONE process
+and alternating, so that the two share the clock and the machine's other load.  Prints one JSON line:
+
+  ms_off / ms_on        median over the timed steps of the accumulation kernel alone (device events, ngd_last_timing)
+  ms_total_off / _on    ... of the whole run call on the device (accumulation + reduction + counts)
+  wall_on_ms            median host wall clock of the option-on call (includes the recheck: gather + host + patch)
+  noted, changed, recheck_ms, passes   ngd_last_em_exact() of the last option-on step
+  max_rel_diff          largest relative difference between the option-on and option-off sums (the pairs that were patched)
+  pairs_patched         pairs whose sum differs at all
+
+The option-off figure is the comparison: that instantiation of the kernel is the one the engine has always run
+(cfg 4)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n_ind", type=int, default=1000)
+    ap.add_argument("--n_sites", type=int, default=100000)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--pairwise_del", action="store_true")
+    ap.add_argument("--variant", type=int, default=0)
+    a = ap.parse_args()
+    import ngsdist_amd as N
+    if N.device_count() < 1:
+        sys.exit("bench_em_exact: no GPU (nothing is measured without one)")
+    res = {"tool": "bench_em_exact", "n_ind": a.n_ind, "n_sites": a.n_sites, "steps": a.steps, "warmup": a.warmup,
+           "pairwise_del": bool(a.pairwise_del), "variant": a.variant}
+    with N.Engine(a.n_ind, a.n_sites, indep_geno=False, kernel="em_table", pairwise_del=a.pairwise_del,
+                  variant=a.variant) as e:
+        e.synth_fill(a.seed, 0.05 if a.pairwise_del else 0.0)
+        t = {0: {"accum": [], "total": [], "wall": []}, 1: {"accum": [], "total": [], "wall": []}}
+        sums = {}
+        for step in range(a.warmup + a.steps):
+            for on in (0, 1):  # alternating: both see the same clock and the same neighbours
+                e.set_option("em_exact", on)
+                w0 = time.perf_counter()
+                s, c = e.run()
+                wall = (time.perf_counter() - w0) * 1e3
+                if step >= a.warmup:
+                    tm = e.timing()
+                    t[on]["accum"].append(tm["ms_accum"])
+                    t[on]["total"].append(tm["ms_total"])
+                    t[on]["wall"].append(wall)
+                sums[on] = s
+                if on:
+                    info = e.last_em_exact()
+        res["shader_clock_mhz"] = e.shader_clock_mhz()
+        res["pair_sites"] = e.timing()["pair_sites"]
+    med = statistics.median
+    res.update(ms_off=med(t[0]["accum"]), ms_on=med(t[1]["accum"]), ms_total_off=med(t[0]["total"]),
+               ms_total_on=med(t[1]["total"]), wall_off_ms=med(t[0]["wall"]), wall_on_ms=med(t[1]["wall"]),
+               ms_off_all=t[0]["accum"], ms_on_all=t[1]["accum"])
+    res["on_over_off"] = res["ms_on"] / res["ms_off"]
+    res.update(noted=int(info["noted"]), changed=int(info["changed"]), recheck_ms=info["ms"], passes=int(info["passes"]))
+    d = np.abs(sums[1] - sums[0])
+    res["pairs_patched"] = int(np.count_nonzero(d))
+    with np.errstate(all="ignore"):
+        res["max_rel_diff"] = float(np.nanmax(d / np.abs(sums[0]))) if d.size else 0.0
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
