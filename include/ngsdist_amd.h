@@ -364,6 +364,15 @@ int ngd_drop_caches(ngd_engine *e);
                                  /*     together with NGD_OPT_EAGER_FULL (either refuses the other).                            */
                                  /*     While it is 1, ngd_run* with a block map or multiplicities, the batch, job and windowed */
                                  /*     calls return NGD_E_INVALID before anything is launched            */
+                                 /*     2: everything 1 means, and ngd_run* with a block map or multiplicities, the batch and    */
+                                 /*     the job calls (_device / _dist forms included) are served: the list of in-band (pair,    */
+                                 /*     site)s does not depend on the replicate, so the plan's one EM launch notes it (per-block */
+                                 /*     partials, else the spilled-terms pass in its noting form) and matrix r takes its         */
+                                 /*     multiplicity of the site's block times (c_ref - c_dev), in site order, before any sum    */
+                                 /*     leaves the engine.  ngd_last_em_exact() / ngd_em_exact_entries() then report the call:  */
+                                 /*     each noted (pair, site) once.  A call neither plan can serve (ngd_config.variant != 0 or */
+                                 /*     NGD_OPT_EM_SPILL = 0 where partials do not apply) fails with NGD_E_INVALID and computes  */
+                                 /*     nothing; the windowed calls stay refused.  Values above 2: NGD_E_INVALID                 */
 #define NGD_OPT_EM_EXACT_CAP 16   /* [0 = 2^20] entries the list of noted (pair, site)s holds, 32 bytes each.  A pass that notes */
                                  /*     more is counted in full, the list grows to the count and the pass runs ONCE more        */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
@@ -421,7 +430,7 @@ int ngd_last_shader_clock(const ngd_engine *e, double *mhz);
  * data-dependent part of its operation count (the EM's iteration count, emOptim2.cpp:118-133).  Zero for other kernels. */
 int ngd_last_em_work(const ngd_engine *e, uint64_t *tile_sites, uint64_t *table_rounds);
 
-/* NGD_OPT_EM_EXACT: the recheck of the last plain pass (zeros when the option was off) */
+/* NGD_OPT_EM_EXACT: the recheck of the last plain pass, or of the last call served under value 2 (zeros when the option was off) */
 typedef struct ngd_em_exact_info {
   uint64_t noted;   /* (pair, site)s whose stop was within 2^-36 of the tolerance                                   */
   uint64_t changed; /* ... of them, those the reference stops at another step than the device did                   */

@@ -438,6 +438,9 @@ constexpr int PACK_DENSE = NGD_PACK_DENSE;
 // NOTE (NGD_OPT_EM_EXACT): the plain pass that also notes the (pair, site)s whose stop is within 2^-36 of the tolerance
 // (em_note above).  The note buffer arrives in `nanlist`, which only the SPILL form reads otherwise: the kernel's
 // arguments, and with them every other instantiation, are what they were.
+// SPILL && NOTE (NGD_OPT_EM_EXACT = 2: the spilled-terms plan of a job under the option): the note is per SITE -- the site's
+// own term c, before it joins its unit's running sum, under the absolute site index -- and the buffer arrives in `segtab`
+// (nanlist is the flag word there).  The buffer's count runs on from chunk to chunk of the plan: the engine zeroes it once.
 template <int NW, int CH, int WPS, bool WEIGHTED, bool PDEL, bool PACK, int RB, bool SPILL = false, bool SEGS = false,
           bool NOTE = false>
 __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
@@ -454,7 +457,11 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
   static_assert(RB == 1 || (PACK && WEIGHTED), "several matrices per pass: the packed form, weighted");
   static_assert(!SPILL || (PACK && !WEIGHTED && RB == 1), "spilled terms: the packed form, unweighted");
   static_assert(!SEGS || (!WEIGHTED && RB == 1 && !SPILL), "a slice table: one matrix per segment, unweighted");
-  static_assert(!NOTE || (!WEIGHTED && RB == 1 && !SPILL && !SEGS), "the noting form: the plain one-matrix pass");
+  static_assert(!NOTE || (!WEIGHTED && RB == 1 && !SEGS), "the noting form: the plain one-matrix pass, or its spilled terms");
+  // (SPILL && NOTE: `nanlist` is the non-finite flag word there; the note buffer arrives in `segtab`, which SPILL never reads)
+  unsigned long long *const note_buf =
+      (SPILL && NOTE) ? const_cast<unsigned long long *>(reinterpret_cast<const unsigned long long *>(segtab)) : nanlist;
+  (void)note_buf;
   // rows per group (one uniform "anything left?" test per group; their table reads are in flight together)
   constexpr int GR = (WPS >= 4 || PACK) ? 1 : 4;
   static_assert(RPW % GR == 0 && CH % 4 == 0 && (CH % 8 == 0 || CH % 8 == 4), "shape");
@@ -660,7 +667,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
               if (((r & 1) != 0) != (wave >= NW / 2)) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
 #endif
               if constexpr (NOTE) {
-                const em_note nt{nanlist, wave * RPW, (uint32_t)t0, s};
+                const em_note nt{note_buf, wave * RPW, (uint32_t)t0, s};
                 if ((go >> r) & 1)
                   scan_row<CH, WEIGHTED, PACK, RB, true>(L, (wave * RPW + r) * RS, (wave * RPW + r + 1) * RS, lane, r, R2, QA,
                                                          todo, acc[r], wv, ((ska >> r) & 1) | (((skb >> r) & 1) << 1),
@@ -675,7 +682,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
 #endif
           }
           if constexpr (NOTE) {
-            const em_note nt{nanlist, wave * RPW, (uint32_t)t0, s};
+            const em_note nt{note_buf, wave * RPW, (uint32_t)t0, s};
             if (t0 != 0) packed_units<CH, WEIGHTED, RB, true>(L, wave, lane, todo, acc, wv, &nt);
           } else if (t0 != 0) packed_units<CH, WEIGHTED, RB>(L, wave, lane, todo, acc, wv);
         }
@@ -723,7 +730,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
             if constexpr (NOTE) {
               const double rT = lds_b64(&L.Rc[b]), qT = lds_b64(&L.Qr[a]);
               if (T[q] && note_wanted(rT, qT, c)) {
-                const em_note nt{nanlist, wave * RPW, (uint32_t)t0, s};
+                const em_note nt{note_buf, wave * RPW, (uint32_t)t0, s};
                 note_append(nt, nt.row0 + (uint32_t)r, lane, (uint32_t)T[q], c);
               }
             }
@@ -934,13 +941,23 @@ void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_geom &g, const do
 // The terms of sites [s_lo, s_hi), added up over units of q consecutive sites, of every live pair slot into C
 // (fragment-major, n_pg groups of 16 pair slots per k-group of 4 units; see the SPILL note at the kernel; d_rowpg is the
 // slot group of every tile row's first live group).  sites_per_slice must be a multiple of q.  *d_nanflag is set to 1
-// if a term of the chunk was not finite.
+// if a term of the chunk was not finite.  d_note != NULL: the noting form -- every site's own term whose stop is within
+// 2^-36 of the tolerance is appended to the note buffer (ngd_internal.h; absolute site indices; the count is NOT reset).
 void ngd_launch_accum_em_table_spill(hipStream_t st, const ngd_geom &g, const double *PA, uint64_t s_lo, uint64_t s_hi,
                                      const ngd_score &score, int pairwise_del, const ngd_tile *d_tiles64,
                                      uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice, uint32_t q,
                                      const uint32_t *d_rowpg, uint32_t n_pg, double *C, unsigned long long *d_counters,
-                                     unsigned long long *d_nanflag) {
+                                     unsigned long long *d_nanflag, unsigned long long *d_note) {
   if (!n_tiles64 || s_hi <= s_lo) return;
+  if (d_note) {  // the noting twin (NGD_OPT_EM_EXACT = 2): the same launch, the note buffer in the slice table's place
+#define NGD_EMTSN(P)                                                                                                            \
+  hipLaunchKernelGGL((k_accum_em_table<8, 16, 4, false, P, true, 1, true, false, true>), dim3(n_tiles64 * n_ks), dim3(512), 0, st, \
+                     PA, nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, n_pg, g.n_ind, s_hi, sites_per_slice, C,         \
+                     d_counters, s_lo, d_nanflag, q, d_rowpg, reinterpret_cast<const uint64_t *>(d_note))
+    if (pairwise_del) NGD_EMTSN(true); else NGD_EMTSN(false);
+#undef NGD_EMTSN
+    return;
+  }
 #define NGD_EMTS(P)                                                                                                      \
   hipLaunchKernelGGL((k_accum_em_table<8, 16, 4, false, P, true, 1, true>), dim3(n_tiles64 * n_ks), dim3(512), 0, st, PA, \
                      nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, n_pg, g.n_ind, s_hi, sites_per_slice, C,      \

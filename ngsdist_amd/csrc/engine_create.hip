@@ -425,6 +425,32 @@ static int create_images(ngd_engine *e) {
 }
 
 // ---- split over the site axis: slices -> slabs, reduced in fixed order ----
+// Pair slots of the spilled-terms plan (em_spill_impl): a row of a tile takes one slot group per group of 16 columns that
+// holds a pair -- none for a diagonal tile's lower triangle or for the columns at and beyond n_ind.  tiles64: the engine's
+// owned 64 x 64 tiles, in the order of d_tiles64.  (ngd_create for a table-driven engine; em_exact_set for one it moves there)
+int spill_slot_map(ngd_engine *e, const std::vector<ngd_tile> &tiles64) {
+  const ngd_geom &g = e->g;
+  std::vector<uint32_t> rowpg((size_t)tiles64.size() * 64, 0xffffffffu);
+  uint64_t n_live = 0;
+  for (size_t t = 0; t < tiles64.size(); t++)
+    for (uint32_t row = 0; row < 64; row++) {
+      const uint64_t i = (uint64_t)tiles64[t].ti * 64 + row, j0 = (uint64_t)tiles64[t].tj * 64;
+      if (i >= g.n_ind || j0 >= g.n_ind) continue;
+      const uint64_t first = tiles64[t].ti == tiles64[t].tj ? row + 1 : 0, last = std::min<uint64_t>(63, g.n_ind - 1 - j0);
+      if (first > last) continue;
+      rowpg[t * 64 + row] = (uint32_t)n_live - (uint32_t)(first >> 4);  // (+ a column group's index = its slot group)
+      n_live += (last >> 4) - (first >> 4) + 1;
+    }
+  if (n_live + 4 < (1ull << 31)) {  // (else: the plan is not offered, em_spill_impl)
+    e->n_pg_live = (uint32_t)n_live;
+    e->n_pg_spill = (uint32_t)((n_live + 3) / 4 * 4);  // a wavefront of the contraction takes 2 or 4 slot groups
+    TRY(e->d_rowpg.alloc(e, rowpg.size(), false));
+    if (!rowpg.empty() && hipMemcpy(e->d_rowpg, rowpg.data(), rowpg.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return fail(NGD_E_HIP, "spill_slot_map: slot map upload failed");
+  }
+  return NGD_OK;
+}
+
 static int create_slices(ngd_engine *e, const std::vector<ngd_tile> &tiles64) {
   const ngd_config *cfg = &e->cfg;
   const ngd_geom &g = e->g;
@@ -502,28 +528,7 @@ static int create_slices(ngd_engine *e, const std::vector<ngd_tile> &tiles64) {
     e->per_slice = (g.n_sites + ks - 1) / ks;
     TRY(dev_alloc_pieces(e, e->slab, ks * (uint64_t)g.n_pad * g.n_pad, true));
     TRY(e->d_emcnt.alloc(e, 4, true));
-    {
-      // pair slots of the spilled-terms plan (em_spill_impl): a row of a tile takes one slot group per group of 16 columns
-      // that holds a pair -- none for a diagonal tile's lower triangle or for the columns at and beyond n_ind
-      std::vector<uint32_t> rowpg((size_t)tiles64.size() * 64, 0xffffffffu);
-      uint64_t n_live = 0;
-      for (size_t t = 0; t < tiles64.size(); t++)
-        for (uint32_t row = 0; row < 64; row++) {
-          const uint64_t i = (uint64_t)tiles64[t].ti * 64 + row, j0 = (uint64_t)tiles64[t].tj * 64;
-          if (i >= g.n_ind || j0 >= g.n_ind) continue;
-          const uint64_t first = tiles64[t].ti == tiles64[t].tj ? row + 1 : 0, last = std::min<uint64_t>(63, g.n_ind - 1 - j0);
-          if (first > last) continue;
-          rowpg[t * 64 + row] = (uint32_t)n_live - (uint32_t)(first >> 4);  // (+ a column group's index = its slot group)
-          n_live += (last >> 4) - (first >> 4) + 1;
-        }
-      if (n_live + 4 < (1ull << 31)) {  // (else: the plan is not offered, em_spill_impl)
-        e->n_pg_live = (uint32_t)n_live;
-        e->n_pg_spill = (uint32_t)((n_live + 3) / 4 * 4);  // a wavefront of the contraction takes 2 or 4 slot groups
-        TRY(e->d_rowpg.alloc(e, rowpg.size(), false));
-        if (!rowpg.empty() && hipMemcpy(e->d_rowpg, rowpg.data(), rowpg.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-          return fail(NGD_E_HIP, "ngd_create: slot map upload failed");
-      }
-    }
+    TRY(spill_slot_map(e, tiles64));
   } else if (kernel == NGD_KERNEL_EM_FAST || kernel == NGD_KERNEL_EM_FAITHFUL) {
     uint64_t want = cfg->wg_target ? cfg->wg_target : 4096;
     uint64_t ks = e->n_tiles16 ? (want + e->n_tiles16 - 1) / e->n_tiles16 : 1;

@@ -4,7 +4,12 @@
 // lists the stops whose criterion is within 2^-36 of the threshold; here the list's sites are run again the reference's
 // way on the host (ngd_em2_site, host_util.cpp) and each pair's sum takes its corrections c_ref - c_dev, in site order,
 // before it leaves the engine -- the same role fixup.hip plays on the --indep_geno path.
+// Value 2 of the option also serves the calls that weight sites (a block map, multiplicities, a batch, a job): the list of
+// in-band (pair, site)s does not depend on the replicate, so the plan's one noting launch (per-block partials, or the
+// spilled-terms pass in its noting form) gives the list, and matrix r takes m_r(site) * (c_ref - c_dev) (em_exact_finish_w).
 #include "ngd_engine.h"
+
+#include <iterator>
 
 static const char *const kExactOnly =
     "NGD_OPT_EM_EXACT is on: it serves the plain full-data pass (ngd_run / ngd_run_device with no block map) only -- ";
@@ -14,10 +19,15 @@ int em_exact_refuse(const ngd_engine *e, const char *who) {
   return fail(NGD_E_INVALID, std::string(kExactOnly) + who + " is not served (replicates and windows from the same list: DESIGN.md section 8)");
 }
 
+int em_exact_refuse_weighted(const ngd_engine *e, const char *who) {
+  if (e && e->opt_em_exact_boot) return NGD_OK;  // (value 2: run_impl serves it, or says which plan it lacks)
+  return em_exact_refuse(e, who);
+}
+
 int em_exact_set(ngd_engine *e, uint64_t value) {
-  if (value > 1) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT is 0 or 1");
+  if (value > 2) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT is 0, 1 or 2");
   if (!value) {
-    e->opt_em_exact = false;
+    e->opt_em_exact = e->opt_em_exact_boot = false;
     return NGD_OK;
   }
   if (e->cfg.indep_geno) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT belongs to the EM path (no --indep_geno)");
@@ -26,7 +36,7 @@ int em_exact_set(ngd_engine *e, uint64_t value) {
   if (e->opt_eager) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT and NGD_OPT_EAGER_FULL refuse each other (the eager pass does not note)");
   if (e->kernel != NGD_KERNEL_EM_TABLE) {
     // kernel = auto at 32 individuals or fewer resolved to the per-pair kernel: the engine moves to the table-driven one
-    // (the geometry ngd_create gives it; the spilled-terms plan's slot map is not built -- the option serves no job)
+    // (the geometry ngd_create gives it; the spilled-terms plan's slot map is built below for value 2, which serves jobs)
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->st));
     const ngd_geom &g = e->g;
@@ -40,7 +50,14 @@ int em_exact_set(ngd_engine *e, uint64_t value) {
     e->per_slice = (g.n_sites + ks - 1) / ks;
     e->kernel = NGD_KERNEL_EM_TABLE;
   }
+  if (value == 2 && !e->d_rowpg) {  // (an engine that was moved above, now or by an earlier value 1: it has no slot map yet)
+    HIPCHK(hipSetDevice(e->device));
+    std::vector<ngd_tile> tiles64(e->n_tiles64);  // (ngd_create keeps no host copy of the list)
+    if (e->n_tiles64) HIPCHK(hipMemcpy(tiles64.data(), e->d_tiles64, tiles64.size() * sizeof(ngd_tile), hipMemcpyDeviceToHost));
+    if (int rc = spill_slot_map(e, tiles64)) return rc;
+  }
   e->opt_em_exact = true;
+  e->opt_em_exact_boot = value == 2;
   return NGD_OK;
 }
 
@@ -54,9 +71,13 @@ int em_exact_begin(ngd_engine *e) {
   return NGD_OK;
 }
 
-int em_exact_finish(ngd_engine *e, double *d_sum, bool *again) {
-  const auto t0 = std::chrono::steady_clock::now();
+// What the noting launch(es) since em_exact_begin listed, rechecked (stream idle): the entries sorted by (pair, site) into
+// e->exact_entries, the corrections c_ref - c_dev in that order on the device (d_note_delta), the distinct pairs
+// (d_note_pair) and where each pair's corrections start (d_note_first); with_sites: the entries' sites too (d_note_site).
+// *again: the list was too short and has grown to what the launch counted -- nothing else has been done.
+static int em_exact_recheck(ngd_engine *e, bool with_sites, bool *again, uint32_t *n_noted_pairs) {
   *again = false;
+  *n_noted_pairs = 0;
   unsigned long long head[2] = {0, 0};
   HIPCHK(hipMemcpy(head, e->d_note, sizeof(head), hipMemcpyDeviceToHost));
   ngd_em_exact_info &info = e->exact_info;
@@ -93,7 +114,7 @@ int em_exact_finish(ngd_engine *e, double *d_sum, bool *again) {
   std::vector<ngd_em_exact_entry> &ent = e->exact_entries;
   ent.resize(n);
   std::vector<double> delta(n);
-  std::vector<unsigned long long> pair;
+  std::vector<unsigned long long> pair, sites(with_sites ? n : 0);
   std::vector<uint32_t> first;
   for (uint32_t q = 0; q < n; q++) {
     const uint32_t k = ord[q];
@@ -117,6 +138,7 @@ int em_exact_finish(ngd_engine *e, double *d_sum, bool *again) {
     x.t_ref = (uint32_t)it;
     x.c_ref = c_ref;
     delta[q] = c_ref - x.c_dev;
+    if (with_sites) sites[q] = x.site;
     if (x.t_ref != x.t_dev) info.changed++;
     const unsigned long long pi = ngd_pair_idx(g.n_ind, x.i1, x.i2);
     if (pair.empty() || pair.back() != pi) {
@@ -129,15 +151,62 @@ int em_exact_finish(ngd_engine *e, double *d_sum, bool *again) {
   int rc = e->d_note_delta.ensure(e, n);
   if (!rc) rc = e->d_note_pair.ensure(e, np);
   if (!rc) rc = e->d_note_first.ensure(e, (uint64_t)np + 1);
+  if (!rc && with_sites) rc = e->d_note_site.ensure(e, n);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(e->d_note_delta, delta.data(), (uint64_t)n * 8, hipMemcpyHostToDevice, e->st));
   HIPCHK(hipMemcpyAsync(e->d_note_pair, pair.data(), (uint64_t)np * 8, hipMemcpyHostToDevice, e->st));
   HIPCHK(hipMemcpyAsync(e->d_note_first, first.data(), ((uint64_t)np + 1) * 4, hipMemcpyHostToDevice, e->st));
+  if (with_sites) HIPCHK(hipMemcpyAsync(e->d_note_site, sites.data(), (uint64_t)n * 8, hipMemcpyHostToDevice, e->st));
+  HIPCHK(hipStreamSynchronize(e->st));  // (delta, pair, first, sites are host temporaries)
+  *n_noted_pairs = np;
+  return NGD_OK;
+}
+
+int em_exact_finish(ngd_engine *e, double *d_sum, bool *again) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t np = 0;
+  if (int rc = em_exact_recheck(e, false, again, &np)) return rc;
+  if (*again || !np) return NGD_OK;
   ngd_launch_note_patch(e->st, e->d_note_pair, e->d_note_first, e->d_note_delta, np, d_sum);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(e->st));  // (delta, pair, first are host temporaries)
-  info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  HIPCHK(hipStreamSynchronize(e->st));
+  e->exact_info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return NGD_OK;
+}
+
+int em_exact_finish_w(ngd_engine *e, double *d_sum, const ngd_note_weights &w, bool *again) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t np = 0;
+  if (int rc = em_exact_recheck(e, true, again, &np)) return rc;
+  if (*again || !np) return NGD_OK;
+  ngd_launch_note_patch_w(e->st, e->d_note_pair, e->d_note_first, e->d_note_delta, e->d_note_site, np, w, e->g.n_sites,
+                          ngd_n_pairs(e->g.n_ind), d_sum);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->st));
+  e->exact_info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return NGD_OK;
+}
+
+// Two noting launches of one call (the replicates' per-block partials and the lead matrix's own plain pass): the call's
+// list is their union, each (pair, site) once.  `first` / `info1` are the earlier launch's, e->exact_* the later one's.
+void em_exact_merge(ngd_engine *e, const std::vector<ngd_em_exact_entry> &first, const ngd_em_exact_info &info1) {
+  auto key_less = [](const ngd_em_exact_entry &a, const ngd_em_exact_entry &b) {
+    return a.i1 != b.i1 ? a.i1 < b.i1 : a.i2 != b.i2 ? a.i2 < b.i2 : a.site < b.site;
+  };
+  std::vector<ngd_em_exact_entry> all;
+  all.reserve(first.size() + e->exact_entries.size());
+  std::merge(e->exact_entries.begin(), e->exact_entries.end(), first.begin(), first.end(), std::back_inserter(all), key_less);
+  all.erase(std::unique(all.begin(), all.end(), [](const ngd_em_exact_entry &a, const ngd_em_exact_entry &b) {
+              return a.i1 == b.i1 && a.i2 == b.i2 && a.site == b.site;
+            }), all.end());
+  e->exact_entries.swap(all);
+  ngd_em_exact_info &info = e->exact_info;
+  info.noted = e->exact_entries.size();
+  info.changed = 0;
+  for (const ngd_em_exact_entry &x : e->exact_entries)
+    if (x.t_ref != x.t_dev) info.changed++;
+  info.passes = std::max(info.passes, info1.passes);
+  info.ms += info1.ms;
 }
 
 extern "C" {

@@ -160,7 +160,7 @@ int batch_buffers(ngd_engine *e, uint32_t n_rep) {
 int run_to_host(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, uint32_t n_rep, bool lead_full,
                 uint64_t n_blocks, uint64_t block_size, uint32_t n_batch, double *sum, uint64_t *cnt) {
   if (n_rep)
-    if (int rc = em_exact_refuse(e, "a run with a block map or multiplicities, a batch or a job")) return rc;
+    if (int rc = em_exact_refuse_weighted(e, "a run with a block map or multiplicities, a batch or a job")) return rc;
   if (n_batch)
     if (int rc = batch_buffers(e, n_batch)) return rc;
   double *d_sum = n_batch ? e->d_bsum : e->d_sum;
@@ -184,7 +184,7 @@ int run_dist(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, ui
                                "shares together first (ngd_run_job_device + the ranks' exchange), then ngd_finish()");
   if (!e->committed) return fail(NGD_E_INVALID, std::string(who) + ": call ngd_commit() first");
   if (n_rep)
-    if (int rc = em_exact_refuse(e, who)) return rc;
+    if (int rc = em_exact_refuse_weighted(e, who)) return rc;
   const double t_enter = out_now();
   HIPCHK(hipSetDevice(e->device));
   const uint32_t n_mat = n_rep ? n_rep + (lead_full ? 1u : 0u) : 1u;

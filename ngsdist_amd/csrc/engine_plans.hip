@@ -244,7 +244,8 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
 
 int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n_blocks, uint64_t block_size,
               uint64_t n_drawn, double *d_sum, unsigned long long *d_cnt, bool add_timing) {
-  // (the option refuses every call but the plain pass, and the eager pass: em_exact_refuse, ngd_set_option)
+  // (value 1 refuses every call but the plain pass, and the eager pass: em_exact_refuse, ngd_set_option; value 2 serves the
+  // weighted calls by plans of its own, run_impl, and never by a weighted pass of this kind)
   const bool note = e->opt_em_exact && !mult && e->kernel == NGD_KERNEL_EM_TABLE;
   int rc = pass_once(e, mult, mult_max, n_blocks, block_size, n_drawn, d_sum, d_cnt, add_timing, note);
   if (rc || !note) return rc;
@@ -266,9 +267,13 @@ int pass_impl(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n
 // for the valid-site counts).  One accumulation pass fills S_b; replicates are then weighted reductions of
 // the partials, up to 32 per pass over them.  MFMA slices are whole k-groups of 4 contraction indices, so
 // blocks must be multiples of 4 sites there.  *feasible = false: the caller falls back to pass_impl().
+// note (NGD_OPT_EM_EXACT = 2, table-driven EM kernel): the pass over the blocks runs in its noting form, into e->d_note, in
+// THIS call -- cached partial sums carry no list, and the slab this call fills is not named as the cache afterwards (it
+// holds unpatched terms of the widened threshold) -- and the matrices stay on the device until the caller has patched them
+// (no copies queued from here); the weights stay in e->d_W: W[(block * sub) * stride + r], stride = the matrices rounded up to ngd_reduce_chunk.
 static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]*/, const unsigned long long *drawn,
                          uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, double *d_sum,
-                         unsigned long long *d_cnt, bool *feasible) {
+                         unsigned long long *d_cnt, bool *feasible, bool note = false) {
   const ngd_geom &g = e->g;
   const uint64_t n_pairs = ngd_n_pairs(g.n_ind);
   const uint64_t n_eff = n_blocks * block_size;
@@ -284,7 +289,7 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   if (n_blocks >= (1ull << 31)) return NGD_OK;
   // split large blocks so that there are enough workgroups; slices of one block share its weight
   const uint64_t unit = mfma ? 3 * block_size / 4 : block_size;  // k-groups or sites per block
-  const bool cached = e->blk.has_sums(block_size, n_blocks);
+  const bool cached = !note && e->blk.has_sums(block_size, n_blocks);
   uint64_t sub = 1, nks = 0;
   if (cached) {
     sub = e->blk.sub;
@@ -356,11 +361,16 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
       ngd_launch_slice_weights(e->st, e->blk.nks, w_stride, 3 * block_size, 3 * n_eff, e->blk.wslice, e->congruent ? e->sc.d : nullptr);
       rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, 0, (3 * n_eff + 3) / 4, e->blk.sums(), 3 * block_size,
                              w_stride);
-    } else
-      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, e->blk.per_slice, mfma ? 3 * n_eff / 4 : 0, e->blk.sums());
+    } else {
+      if (note && (rc = em_exact_begin(e))) return rc;
+      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, e->blk.per_slice, mfma ? 3 * n_eff / 4 : 0, e->blk.sums(),
+                             0, 0, note);
+    }
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    e->blk.sums_filled(block_size, n_blocks);
+    // (a slab the noting form filled is not the cache: it stops in-band pairs at the widened threshold, and only the
+    // matrices are patched -- an option-off job must never be reduced from it; borrow_sums() above dropped the key)
+    if (!note) e->blk.sums_filled(block_size, n_blocks);
     launches = 1;
   }
   HIPCHK(hipEventRecord(e->ev[2], e->st));
@@ -421,7 +431,7 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   };
   // ngd_run_*_dist, the job's first matrix at the head of d_bsum: a group of replicates is reduced by a launch of its own
   // and its copy to the host queued behind it, so that the copies run beside the later groups' reductions
-  const bool stream_out = e->out.on && d_sum == e->d_bsum && d_cnt == e->d_bcnt && e->out.queued == 0;
+  const bool stream_out = !note && e->out.on && d_sum == e->d_bsum && d_cnt == e->d_bcnt && e->out.queued == 0;
   if (stream_out) {
     // the counts' inputs first: they do not depend on the sums
     if ((rc = counts_inputs())) return rc;
@@ -593,6 +603,9 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
 // are those of n_sites / q.  The chunk is as many units as the scratch budget holds (NGD_OPT_EM_SPILL_BYTES).
 // Outputs: [lead + n_rep][n_pairs]; every matrix agrees with its own ngd_run() pass to rounding (the sums are formed in
 // another order).  *done = false: the plan does not apply (no room for a useful chunk) and nothing has been written.
+// note (NGD_OPT_EM_EXACT = 2): the EM pass runs in its noting form (accum_em_table.hip SPILL && NOTE) into e->d_note, which
+// is emptied once, before the first chunk -- its count runs on from chunk to chunk; any number of matrices from 1 is
+// served, chunks of a few sites too (no other plan of the option could take the call).  The multiplicities stay in e->d_M.
 static uint32_t spill_unit(uint64_t block_size) {
   uint32_t q = 1;
   for (uint32_t d = 2; d <= 64 && d <= block_size; d++)
@@ -602,7 +615,7 @@ static uint32_t spill_unit(uint64_t block_size) {
 
 static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mult_max, const unsigned long long *drawn,
                          uint32_t n_rep, bool lead, uint64_t n_blocks, uint64_t block_size, double *d_sum,
-                         unsigned long long *d_cnt, bool *done) {
+                         unsigned long long *d_cnt, bool *done, bool note = false) {
   const ngd_geom &g = e->g;
   *done = false;
   const uint64_t n_pairs = ngd_n_pairs(g.n_ind);
@@ -628,7 +641,7 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   const uint64_t units_all = (s_end + q - 1) / q;
   chunk_kg = std::min<uint64_t>(chunk_kg - 1, (units_all + 3) / 4);  // (one k-group of tail for the operand run-ahead)
   // chunks of a few sites are launch-bound: the plan is left to the others (unless the caller set the scratch size)
-  if (!e->opt_em_spill_bytes && chunk_kg * 4 * q < std::min<uint64_t>(s_end, 64)) return NGD_OK;
+  if (!note && !e->opt_em_spill_bytes && chunk_kg * 4 * q < std::min<uint64_t>(s_end, 64)) return NGD_OK;
   const uint64_t chunk_sites = chunk_kg * 4 * q;
   const uint64_t n_chunks = (s_end + chunk_sites - 1) / chunk_sites;
 
@@ -644,6 +657,7 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     HIPCHK(hipEventCreate(&v));
     e->ev_spill.push_back(v);
   }
+  if (note && (rc = em_exact_begin(e))) return rc;
   *done = true;
 
   HIPCHK(hipEventRecord(e->ev[0], e->st));
@@ -672,7 +686,8 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     const uint64_t sps = ((len + ks - 1) / ks + q - 1) / q * q;
     ks = (len + sps - 1) / sps;
     ngd_launch_accum_em_table_spill(e->st, g, e->PA, s_lo, s_hi, e->sc, e->cfg.pairwise_del, e->d_tiles64, e->n_tiles64,
-                                    (uint32_t)ks, sps, q, e->d_rowpg, (uint32_t)n_pg, C, e->d_emcnt, e->d_nanflag + c);
+                                    (uint32_t)ks, sps, q, e->d_rowpg, (uint32_t)n_pg, C, e->d_emcnt, e->d_nanflag + c,
+                                    note ? e->d_note.get() : nullptr);
     HIPCHK(hipEventRecord(ev[2], e->st));
     ngd_launch_spill_sanitize(e->st, C, e->d_nanflag + c, n_kg, (uint32_t)n_pg, e->d_M, n_mat, lead ? 1 : 0, s_lo, q,
                               g.n_sites, n_eff, n_blocks, block_size, e->d_D);
@@ -736,7 +751,7 @@ int run_impl(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult_in,
   if (!e) return fail(NGD_E_INVALID, "ngd_run: null engine");
   if (!e->committed) return fail(NGD_E_INVALID, "ngd_run: call ngd_commit() first");
   if (n_rep)
-    if (int rc = em_exact_refuse(e, "a run with a block map or multiplicities, a batch or a job")) return rc;
+    if (int rc = em_exact_refuse_weighted(e, "a run with a block map or multiplicities, a batch or a job")) return rc;
   HIPCHK(hipSetDevice(e->device));
   const ngd_geom &g = e->g;
   e->exact_info = ngd_em_exact_info{};
@@ -794,6 +809,51 @@ int run_impl(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult_in,
   double *rep_sum = d_sum + (uint64_t)lead * n_pairs;
   unsigned long long *rep_cnt = d_cnt + (uint64_t)lead * n_pairs;
 
+  // 0. NGD_OPT_EM_EXACT = 2: only plans whose one EM launch notes -- per-block partials (the plain form over slices that are
+  //    blocks), else the spilled-terms pass -- and every matrix takes its weight times (c_ref - c_dev) before anything
+  //    leaves.  A list that was too short has counted what it needs: the plan runs once more.  No plan: the call fails.
+  if (e->opt_em_exact) {
+    if (e->kernel != NGD_KERNEL_EM_TABLE) return fail(NGD_E_INVALID, "NGD_OPT_EM_EXACT: internal -- not the table-driven EM kernel");
+    const bool ride = lead && n_eff == g.n_sites;  // the full data set as the partials' all-ones row
+    bool by_partials = false;
+    for (int pass = 1;; pass++) {
+      bool feasible = false, done = false, again = false;
+      int rc = ride ? partials_impl(e, e->h_mult, drawn.data(), n_rep + 1, n_blocks, block_size, d_sum, d_cnt, &feasible, true)
+                    : partials_impl(e, mult, drawn.data() + lead, n_rep, n_blocks, block_size, rep_sum, rep_cnt, &feasible, true);
+      if (rc) return rc;
+      if (feasible) {
+        by_partials = true;
+        const uint32_t n_rows = n_rep + (ride ? 1u : 0u), ch = ngd_reduce_chunk(n_rows);
+        const ngd_note_weights w{n_rows, 0, e->d_W, nullptr, 1, (uint64_t)e->blk.sub * ((n_rows + ch - 1) / ch * ch), n_blocks, block_size};
+        if ((rc = em_exact_finish_w(e, ride ? d_sum : rep_sum, w, &again))) return rc;
+      } else {
+        if (e->em_shape == 0 && e->opt_em_spill) {
+          rc = em_spill_impl(e, mult, mult_max.data() + lead, drawn.data() + lead, n_rep, lead != 0, n_blocks, block_size, d_sum,
+                             d_cnt, &done, true);
+          if (rc == NGD_E_NOMEM) { (void)hipGetLastError(); g_err.clear(); done = false; rc = NGD_OK; }
+          if (rc) return rc;
+        }
+        if (!done)
+          return fail(NGD_E_INVALID, "NGD_OPT_EM_EXACT = 2: no plan that notes can serve this call -- per-block partials do not apply "
+                                     "(NGD_OPT_BOOT_PARTIALS, the device's memory) and the spilled-terms plan does not either (variant "
+                                     "0 only, NGD_OPT_EM_SPILL, scratch for two k-groups of terms); nothing was computed");
+        const ngd_note_weights w{n_rep + lead, lead, nullptr, e->d_M, n_blocks, 1, n_blocks, block_size};
+        if ((rc = em_exact_finish_w(e, d_sum, w, &again))) return rc;
+      }
+      if (!again) {
+        e->exact_info.passes = (uint64_t)pass;
+        break;
+      }
+      if (pass == 2) return fail(NGD_E_HIP, "NGD_OPT_EM_EXACT: internal -- the second pass noted more than the first counted");
+    }
+    if (by_partials && lead && !ride) {  // the lead matrix's own plain pass notes, and is patched, as ever
+      const std::vector<ngd_em_exact_entry> first = e->exact_entries;
+      const ngd_em_exact_info info1 = e->exact_info;
+      if (int rc = pass_impl(e, nullptr, 0, 0, 0, 0, d_sum, d_cnt, true)) return rc;
+      em_exact_merge(e, first, info1);
+    }
+    return NGD_OK;
+  }
   // 1. per-block partials; the full data set rides along as the all-ones row when the blocks cover every site
   bool feasible = false;
   int rc;

@@ -213,12 +213,14 @@ struct ngd_engine : ngd_mem {
   // NGD_OPT_EM_EXACT (engine_em_exact.hip): the plain pass of the table-driven EM kernel notes the (pair, site)s whose stop
   // is within 2^-36 of the tolerance; the host reruns them the reference's way and the pairs' sums are patched
   bool opt_em_exact = false;
+  bool opt_em_exact_boot = false;      // value 2: the calls that weight sites are served too (run_impl: noting plans only)
   uint64_t note_cap = 1ull << 20;      // entries the list is to hold (NGD_OPT_EM_EXACT_CAP; grown by a pass that noted more)
   DevBuf<unsigned long long> d_note;   // the note buffer (ngd_internal.h): count, capacity, the entries
   unsigned long long note_head[NGD_NOTE_HEAD] = {0, 0, 0, 0};  // what a pass starts from (alive while its copy is in flight)
   DevBuf<double> d_note_gl, d_note_delta;  // the entries' likelihoods; the corrections in (pair, site) order
   DevBuf<unsigned long long> d_note_pair;  // ... the distinct pairs' indices
   DevBuf<uint32_t> d_note_first;           // ... and where each pair's corrections start (+ one past the last)
+  DevBuf<unsigned long long> d_note_site;  // ... and the corrections' sites (value 2: a matrix weights each by its block)
   ngd_em_exact_info exact_info{};
   std::vector<ngd_em_exact_entry> exact_entries;  // of the last plain pass, sorted
 };
@@ -274,6 +276,7 @@ int piece_join(ngd_engine *e);
 int piece_wait_sites(ngd_engine *e, uint64_t s_end);
 // engine_create.hip
 uint64_t qb_piece(uint64_t kg_lim, uint32_t n_ks, uint64_t span, uint64_t *n_ranges);
+int spill_slot_map(ngd_engine *e, const std::vector<ngd_tile> &tiles64);  // d_rowpg, n_pg_spill, n_pg_live
 // engine_stage.hip
 void stage_reap(ngd_engine *e);
 void ring_maker_join(ngd_engine *e);
@@ -296,6 +299,10 @@ int em_exact_refuse(const ngd_engine *e, const char *who);  // NGD_E_INVALID whi
 int em_exact_set(ngd_engine *e, uint64_t value);            // NGD_OPT_EM_EXACT
 int em_exact_begin(ngd_engine *e);                          // before the noting pass: the list is there and empty
 int em_exact_finish(ngd_engine *e, double *d_sum, bool *again);  // after it (stream idle): recheck + patch, or grow the list
+int em_exact_refuse_weighted(const ngd_engine *e, const char *who);  // as em_exact_refuse, but value 2 lets `who` through
+// value 2, after a plan's noting launch (stream idle): recheck + the weighted patch of every matrix of d_sum, or grow the list
+int em_exact_finish_w(ngd_engine *e, double *d_sum, const ngd_note_weights &w, bool *again);
+void em_exact_merge(ngd_engine *e, const std::vector<ngd_em_exact_entry> &first, const ngd_em_exact_info &info1);
 // engine_out.hip
 bool out_trace();
 double out_now();

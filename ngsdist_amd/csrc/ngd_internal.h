@@ -188,6 +188,20 @@ void ngd_launch_note_gather(hipStream_t st, const ngd_geom &g, const double *PA,
 // reduce.hip: d_sum[pair[q]] += delta[first[q]] + ... + delta[first[q + 1] - 1], added one by one in that order
 void ngd_launch_note_patch(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
                            uint32_t n_pairs_noted, double *d_sum);
+// reduce.hip, NGD_OPT_EM_EXACT = 2: the same corrections into n_mat matrices that weight sites by bootstrap block.  Matrix
+// r < lead is the full data set (weight 1 on every site); matrix lead + q weights a site of block b = site / block_size by
+// W[b * bs + q * rs] (doubles; per-block partials) or M[b * bs + q * rs] (multiplicities; the spilled-terms plan), and
+// by 0 from site n_blocks * block_size on (ngsDist.cpp:236).  d_sum[r * n_pairs + pair] += (double)m * delta, one by one in
+// site order, where m != 0.
+struct ngd_note_weights {
+  uint32_t n_mat, lead;
+  const double *W;
+  const uint32_t *M;
+  uint64_t rs, bs, n_blocks, block_size;
+};
+void ngd_launch_note_patch_w(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
+                             const unsigned long long *d_site, uint32_t n_pairs_noted, const ngd_note_weights &w,
+                             uint64_t n_sites, uint64_t n_pairs, double *d_sum);
 
 // accum_em_table.hip, windows along the genome: slice ks = sites [s_lo, s_hi) of entry ks of the slice table (NGD_SEG_SLO /
 // NGD_SEG_SHI; any length from 1, any first site, all below g.n_sites), slab [n_seg][n_pad][n_pad]; every `shape` has the form
@@ -208,7 +222,7 @@ void ngd_launch_accum_em_table_spill(hipStream_t st, const ngd_geom &g, const do
                                      const ngd_score &score, int pairwise_del, const ngd_tile *d_tiles64,
                                      uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice, uint32_t q,
                                      const uint32_t *d_rowpg, uint32_t n_pg, double *C, unsigned long long *d_counters,
-                                     unsigned long long *d_nanflag);
+                                     unsigned long long *d_nanflag, unsigned long long *d_note = nullptr);
 
 // contract_mfma.hip : running sums D[matrix][pair slot] += W[matrix][unit] * C[unit][pair slot] over a chunk of sites
 // (a unit = q consecutive sites of one bootstrap block; site s_lo is the first site of the chunk's unit 0)

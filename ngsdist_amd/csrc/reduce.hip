@@ -684,7 +684,39 @@ __global__ __launch_bounds__(256) void k_note_patch(const unsigned long long *__
   for (uint32_t k = first[q]; k < first[q + 1]; k++) s = s + delta[k];
   d_sum[pair[q]] = s;
 }
+// NGD_OPT_EM_EXACT = 2: one thread per (noted pair, matrix); the pair's corrections in site order, each weighted by the
+// matrix's multiplicity of the site's block -- product first, then the sum (-ffp-contract=off), like the weighted passes
+__global__ __launch_bounds__(256) void k_note_patch_w(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ first,
+                                                      const double *__restrict__ delta, const unsigned long long *__restrict__ site,
+                                                      uint32_t n, ngd_note_weights w, uint64_t n_sites, uint64_t n_pairs,
+                                                      double *__restrict__ d_sum) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (uint64_t)n * w.n_mat) return;
+  const uint32_t r = (uint32_t)(idx / n), q = (uint32_t)(idx % n);
+  double *out = d_sum + (uint64_t)r * n_pairs + pair[q];
+  double s = *out;
+  for (uint32_t k = first[q]; k < first[q + 1]; k++) {
+    const uint64_t st = site[k];
+    double m = 0.0;
+    if (r < w.lead) m = st < n_sites ? 1.0 : 0.0;
+    else {
+      const uint64_t b = st / w.block_size, at = b * w.bs + (uint64_t)(r - w.lead) * w.rs;
+      if (b < w.n_blocks) m = w.W ? w.W[at] : (double)w.M[at];
+    }
+    if (m != 0.0) s = s + m * delta[k];
+  }
+  *out = s;
+}
 }  // namespace
+
+void ngd_launch_note_patch_w(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
+                             const unsigned long long *d_site, uint32_t n_pairs_noted, const ngd_note_weights &w,
+                             uint64_t n_sites, uint64_t n_pairs, double *d_sum) {
+  if (!n_pairs_noted || !w.n_mat || !w.block_size) return;
+  const uint64_t n = (uint64_t)n_pairs_noted * w.n_mat;
+  hipLaunchKernelGGL(k_note_patch_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pair, d_first, d_delta, d_site,
+                     n_pairs_noted, w, n_sites, n_pairs, d_sum);
+}
 
 void ngd_launch_note_patch(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
                            uint32_t n_pairs_noted, double *d_sum) {

@@ -327,8 +327,8 @@ class Engine:
     def set_option(self, name, value):
         """plan selection for the replicate loop (ngd_set_option): boot_partials, boot_max_bytes, boot_wg, boot_unaligned,
         em_batch, em_spill, em_spill_bytes, single_image_bytes, fixup_work, win_plan, win_max_bytes; em_exact (the plain
-        pass of the table-driven EM kernel stops where the reference does: last_em_exact(), em_exact_entries()) and
-        em_exact_cap"""
+        pass of the table-driven EM kernel stops where the reference does: last_em_exact(), em_exact_entries(); 2: block
+        maps, multiplicities, batches and jobs are served that way too) and em_exact_cap"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self
 

@@ -11,7 +11,20 @@ and alternating, so that the two share the clock and the machine's other load.  
   pairs_patched         pairs whose sum differs at all
 
 The option-off figure is the comparison: that instantiation of the kernel is the one the engine has always run
-(cfg 4)."""
+(cfg 4).
+
+--job R --block_size B: the full data + R bootstrap replicates (block maps from Taus(seed + r)) as ONE ngd_run_job_dist call
+(the job and its tail, evolutionary model 2: the emboot workload of bench.py), the option alternating 0 / 2 in one process:
+
+  wall_off_ms / wall_on_ms   median host wall clock of the call (option 2: includes the recheck and the weighted patch)
+  wall_off_all / wall_on_all every timed step: the spread the ratio on_over_off is to be read against
+  ms_total_off / _on         ... of the engine's stream (ngd_last_timing)
+  spill_off / spill_on       ngd_last_spill_timing() of the last step (the EM pass is ms_terms; zeros under another plan)
+  plan_off_all / plan_on_all every timed step's plan: the spilled-terms plan's chunk count, 0 = per-block partials (the
+                             engine buys the partials' slab only once the calls it would have saved add up to its allocation)
+  terms_off_all / _on_all    every timed step's EM pass under the spilled-terms plan, ms (0 under per-block partials)
+  noted, changed, recheck_ms, passes   ngd_last_em_exact() of the last option-2 step
+  max_rel_diff, cells_patched          over every (matrix, pair) cell of the finished distances"""
 import argparse
 import json
 import os
@@ -24,6 +37,46 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def job(N, a, res):
+    B = a.block_size
+    maps = np.stack([N.Taus(a.seed + r).block_map(a.n_sites // B) for r in range(a.job)])
+    res.update(job=a.job, block_size=B)
+    med = statistics.median
+    with N.Engine(a.n_ind, a.n_sites, indep_geno=False, kernel="em_table", pairwise_del=a.pairwise_del,
+                  variant=a.variant) as e:
+        e.synth_fill(a.seed, 0.05 if a.pairwise_del else 0.0)
+        t = {k: {"total": [], "wall": [], "plan": [], "terms": []} for k in (0, 2)}
+        out = {0: np.empty((a.job + 1, e.n_pairs)), 2: np.empty((a.job + 1, e.n_pairs))}
+        spill, info = {}, None
+        for step in range(a.warmup + a.steps):
+            for on in (0, 2):  # alternating: both see the same clock and the same neighbours
+                e.set_option("em_exact", on)
+                w0 = time.perf_counter()
+                e.run_job_dist(maps, B, 2, out=out[on])
+                wall = (time.perf_counter() - w0) * 1e3
+                if step >= a.warmup:
+                    t[on]["total"].append(e.timing()["ms_total"])
+                    t[on]["wall"].append(wall)
+                spill[on] = e.spill_timing()
+                if step >= a.warmup:
+                    t[on]["plan"].append(int(spill[on]["chunks"]))
+                    t[on]["terms"].append(spill[on]["ms_terms"])
+                if on:
+                    info = e.last_em_exact()
+        res["shader_clock_mhz"] = e.shader_clock_mhz()
+    res.update(wall_off_ms=med(t[0]["wall"]), wall_on_ms=med(t[2]["wall"]), ms_total_off=med(t[0]["total"]),
+               ms_total_on=med(t[2]["total"]), wall_off_all=t[0]["wall"], wall_on_all=t[2]["wall"], plan_off_all=t[0]["plan"],
+               plan_on_all=t[2]["plan"], terms_off_all=t[0]["terms"], terms_on_all=t[2]["terms"], spill_off=spill[0],
+               spill_on=spill[2])
+    res["on_over_off"] = res["wall_on_ms"] / res["wall_off_ms"]
+    res.update(noted=int(info["noted"]), changed=int(info["changed"]), recheck_ms=info["ms"], passes=int(info["passes"]))
+    with np.errstate(all="ignore"):
+        d = np.abs(out[2] - out[0])
+        res["cells_patched"] = int(np.count_nonzero(d > 0))
+        res["max_rel_diff"] = float(np.nanmax(d / np.abs(out[0])))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_ind", type=int, default=1000)
@@ -33,12 +86,16 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--pairwise_del", action="store_true")
     ap.add_argument("--variant", type=int, default=0)
+    ap.add_argument("--job", type=int, default=0, help="R: time the full data + R replicates (option 0 / 2) instead of the plain pass")
+    ap.add_argument("--block_size", type=int, default=1)
     a = ap.parse_args()
     import ngsdist_amd as N
     if N.device_count() < 1:
         sys.exit("bench_em_exact: no GPU (nothing is measured without one)")
     res = {"tool": "bench_em_exact", "n_ind": a.n_ind, "n_sites": a.n_sites, "steps": a.steps, "warmup": a.warmup,
            "pairwise_del": bool(a.pairwise_del), "variant": a.variant}
+    if a.job:
+        return job(N, a, res)
     with N.Engine(a.n_ind, a.n_sites, indep_geno=False, kernel="em_table", pairwise_del=a.pairwise_del,
                   variant=a.variant) as e:
         e.synth_fill(a.seed, 0.05 if a.pairwise_del else 0.0)
