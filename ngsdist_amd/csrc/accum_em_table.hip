@@ -813,129 +813,107 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
   }
 }
 
-}  // namespace
-
 // shape: 0 = 8 wavefronts x 8 rows, 16 steps per round, 4 waves per SIMD, a site's later rounds in packed units
 //            (default: [measured] 1000 x 2e4, ms per launch: 44.5; shape 4, the same with every round scanned row by
 //            row: 49.2 -- same bits; shape 1: 59.6; 2: 51.9; 3: 51.3; k_accum_em<fast> 122.7);
 //        1 = 4 wavefronts x 16 rows, 16 steps, 2 waves per SIMD (register-rich);  2 / 3 = 0's and 1's shapes with 12
 //            steps per round, rows only
-void ngd_launch_accum_em_table(hipStream_t st, const ngd_geom &g, const double *PA, const uint32_t *d_ws,
-                               uint64_t n_sites_eff, const ngd_score &score, int pairwise_del, int shape,
-                               const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice,
-                               double *slab, unsigned long long *d_counters) {
-  if (!n_tiles64) return;
-  const bool w = d_ws != nullptr, p = pairwise_del != 0;
-#define NGD_EMT(NW, CH, WPS, W, P, K)                                                                                 \
-  hipLaunchKernelGGL((k_accum_em_table<NW, CH, WPS, W, P, K, 1>), dim3(n_tiles64 * n_ks), dim3(NW * 64), 0, st, PA, d_ws, \
-                     nullptr, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, n_sites_eff, sites_per_slice, slab,  \
-                     d_counters)
-#define NGD_EMT_WP(NW, CH, WPS, K)                                                 \
-  do {                                                                             \
-    if (w) { if (p) NGD_EMT(NW, CH, WPS, true, true, K); else NGD_EMT(NW, CH, WPS, true, false, K); }   \
-    else   { if (p) NGD_EMT(NW, CH, WPS, false, true, K); else NGD_EMT(NW, CH, WPS, false, false, K); } \
-  } while (0)
-  switch (shape) {
-    default: NGD_EMT_WP(8, 16, 4, true); break;
-    case 1: NGD_EMT_WP(4, 16, 2, false); break;
-    case 2: NGD_EMT_WP(8, 12, 4, false); break;
-    case 3: NGD_EMT_WP(4, 12, 2, false); break;
-    case 4: NGD_EMT_WP(8, 16, 4, false); break;
-  }
-#undef NGD_EMT_WP
-#undef NGD_EMT
+template <int NW_, int CH_, int WPS_, bool PACK_>
+struct emt_shape {
+  static constexpr int NW = NW_, CH = CH_, WPS = WPS_;
+  static constexpr bool PACK = PACK_;
+};
+
+// f(PDEL as a std::bool_constant)
+template <typename F>
+void with_pdel(int pairwise_del, F &&f) {
+  if (pairwise_del) f(std::true_type{}); else f(std::false_type{});
+}
+
+// f(an emt_shape, PDEL): the one table from (shape, pairwise_del) to <NW, CH, WPS, PACK, PDEL>
+template <typename F>
+void with_shape(const ngd_emt_common &c, F &&f) {
+  with_pdel(c.pairwise_del, [&](auto P) {
+    switch (c.shape) {
+      default: f(emt_shape<8, 16, 4, true>{}, P); break;
+      case 1: f(emt_shape<4, 16, 2, false>{}, P); break;
+      case 2: f(emt_shape<8, 12, 4, false>{}, P); break;
+      case 3: f(emt_shape<4, 12, 2, false>{}, P); break;
+      case 4: f(emt_shape<8, 16, 4, false>{}, P); break;
+    }
+  });
+}
+
+}  // namespace
+
+void ngd_launch_accum_em_table(hipStream_t st, const ngd_emt_common &c, const uint32_t *d_ws, uint64_t n_sites_eff, uint32_t n_ks,
+                               uint64_t sites_per_slice, double *slab) {
+  if (!c.n_tiles64) return;
+  with_shape(c, [&](auto S, auto P) {
+    using T = decltype(S);
+    auto launch = [&](auto W) {
+      hipLaunchKernelGGL((k_accum_em_table<T::NW, T::CH, T::WPS, decltype(W)::value, decltype(P)::value, T::PACK, 1>),
+                         dim3(c.n_tiles64 * n_ks), dim3(T::NW * 64), 0, st, c.PA, d_ws, nullptr, c.score, c.d_tiles64, c.n_tiles64,
+                         c.g.n_ig, c.g.n_pad, c.g.n_ind, n_sites_eff, sites_per_slice, slab, c.d_counters);
+    };
+    if (d_ws) launch(std::true_type{}); else launch(std::false_type{});
+  });
 }
 
 // The noting form of the plain pass (NGD_OPT_EM_EXACT): d_note as ngd_internal.h lays it out, its count zeroed and its
 // capacity set by the caller.  Every shape has the form.
-void ngd_launch_accum_em_table_note(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score,
-                                    int pairwise_del, int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks,
-                                    uint64_t sites_per_slice, double *slab, unsigned long long *d_counters,
+void ngd_launch_accum_em_table_note(hipStream_t st, const ngd_emt_common &c, uint32_t n_ks, uint64_t sites_per_slice, double *slab,
                                     unsigned long long *d_note) {
-  if (!n_tiles64) return;
-  const bool p = pairwise_del != 0;
-#define NGD_EMT_N(NW, CH, WPS, P, K)                                                                                          \
-  hipLaunchKernelGGL((k_accum_em_table<NW, CH, WPS, false, P, K, 1, false, false, true>), dim3(n_tiles64 * n_ks), dim3(NW * 64), \
-                     0, st, PA, nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, g.n_sites,             \
-                     sites_per_slice, slab, d_counters, 0, d_note)
-#define NGD_EMT_NP(NW, CH, WPS, K) do { if (p) NGD_EMT_N(NW, CH, WPS, true, K); else NGD_EMT_N(NW, CH, WPS, false, K); } while (0)
-  switch (shape) {
-    default: NGD_EMT_NP(8, 16, 4, true); break;
-    case 1: NGD_EMT_NP(4, 16, 2, false); break;
-    case 2: NGD_EMT_NP(8, 12, 4, false); break;
-    case 3: NGD_EMT_NP(4, 12, 2, false); break;
-    case 4: NGD_EMT_NP(8, 16, 4, false); break;
-  }
-#undef NGD_EMT_NP
-#undef NGD_EMT_N
+  if (!c.n_tiles64) return;
+  with_shape(c, [&](auto S, auto P) {
+    using T = decltype(S);
+    hipLaunchKernelGGL((k_accum_em_table<T::NW, T::CH, T::WPS, false, decltype(P)::value, T::PACK, 1, false, false, true>),
+                       dim3(c.n_tiles64 * n_ks), dim3(T::NW * 64), 0, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64,
+                       c.g.n_ig, c.g.n_pad, c.g.n_ind, c.g.n_sites, sites_per_slice, slab, c.d_counters, 0, d_note);
+  });
 }
 
 // Slices ks0 .. ks0 + n_sub - 1 of a plain (unweighted) pass on their own -- the sites of the others need not be resident yet
-// (engine.hip: the full-data pass started during a staged load).  lds_pad: bytes of dynamic LDS a workgroup asks for on top
-// of its tables: enough of it and a CU holds ONE workgroup instead of two, which leaves registers and wave slots for the
+// (engine_stage.hip: the full-data pass started during a staged load).  lds_pad: bytes of dynamic LDS a workgroup asks for on
+// top of its tables: enough of it and a CU holds ONE workgroup instead of two, which leaves registers and wave slots for the
 // preparation kernels of the pieces that are still arriving.
-void ngd_launch_accum_em_table_slices(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,
-                                      int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t ks0, uint32_t n_sub,
-                                      uint64_t sites_per_slice, double *slab, unsigned long long *d_counters, uint32_t lds_pad) {
-  if (!n_tiles64 || !n_sub) return;
-  const uint64_t s_lo = (uint64_t)ks0 * sites_per_slice, s_hi = std::min<uint64_t>(g.n_sites, s_lo + (uint64_t)n_sub * sites_per_slice);
-  double *out = slab + (uint64_t)ks0 * g.n_pad * g.n_pad;
-  const bool p = pairwise_del != 0;
-#define NGD_EMT_S(NW, CH, WPS, P, K)                                                                                       \
-  hipLaunchKernelGGL((k_accum_em_table<NW, CH, WPS, false, P, K, 1>), dim3(n_tiles64 * n_sub), dim3(NW * 64), lds_pad, st, PA, \
-                     nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, s_hi, sites_per_slice, out,    \
-                     d_counters, s_lo)
-#define NGD_EMT_SP(NW, CH, WPS, K) do { if (p) NGD_EMT_S(NW, CH, WPS, true, K); else NGD_EMT_S(NW, CH, WPS, false, K); } while (0)
-  switch (shape) {
-    default: NGD_EMT_SP(8, 16, 4, true); break;
-    case 1: NGD_EMT_SP(4, 16, 2, false); break;
-    case 2: NGD_EMT_SP(8, 12, 4, false); break;
-    case 3: NGD_EMT_SP(4, 12, 2, false); break;
-    case 4: NGD_EMT_SP(8, 16, 4, false); break;
-  }
-#undef NGD_EMT_SP
-#undef NGD_EMT_S
+void ngd_launch_accum_em_table_slices(hipStream_t st, const ngd_emt_common &c, uint32_t ks0, uint32_t n_sub, uint64_t sites_per_slice,
+                                      double *slab, uint32_t lds_pad) {
+  if (!c.n_tiles64 || !n_sub) return;
+  const uint64_t s_lo = (uint64_t)ks0 * sites_per_slice, s_hi = std::min<uint64_t>(c.g.n_sites, s_lo + (uint64_t)n_sub * sites_per_slice);
+  double *out = slab + (uint64_t)ks0 * c.g.n_pad * c.g.n_pad;
+  with_shape(c, [&](auto S, auto P) {
+    using T = decltype(S);
+    hipLaunchKernelGGL((k_accum_em_table<T::NW, T::CH, T::WPS, false, decltype(P)::value, T::PACK, 1>), dim3(c.n_tiles64 * n_sub),
+                       dim3(T::NW * 64), lds_pad, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64, c.g.n_ig, c.g.n_pad,
+                       c.g.n_ind, s_hi, sites_per_slice, out, c.d_counters, s_lo);
+  });
 }
 
 // Windows along the genome: slice ks = segment ks of the slice table d_seg ([n_seg][NGD_SEG_STRIDE], sites [s_lo, s_hi) below
-// g.n_sites), one plane of the slab per segment.  Every shape has the form (engine.hip windows_slab_applies()).
-void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,
-                                    int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_seg,
-                                    const uint64_t *d_seg, double *slab, unsigned long long *d_counters) {
-  if (!n_tiles64 || !n_seg) return;
-  const bool p = pairwise_del != 0;
-#define NGD_EMT_G(NW, CH, WPS, P, K)                                                                                        \
-  hipLaunchKernelGGL((k_accum_em_table<NW, CH, WPS, false, P, K, 1, false, true>), dim3(n_tiles64 * n_seg), dim3(NW * 64), 0, \
-                     st, PA, nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, g.n_sites, 0, slab,     \
-                     d_counters, 0, nullptr, 1, nullptr, d_seg)
-#define NGD_EMT_GP(NW, CH, WPS, K) do { if (p) NGD_EMT_G(NW, CH, WPS, true, K); else NGD_EMT_G(NW, CH, WPS, false, K); } while (0)
-  switch (shape) {
-    default: NGD_EMT_GP(8, 16, 4, true); break;
-    case 1: NGD_EMT_GP(4, 16, 2, false); break;
-    case 2: NGD_EMT_GP(8, 12, 4, false); break;
-    case 3: NGD_EMT_GP(4, 12, 2, false); break;
-    case 4: NGD_EMT_GP(8, 16, 4, false); break;
-  }
-#undef NGD_EMT_GP
-#undef NGD_EMT_G
+// c.g.n_sites), one plane of the slab per segment.  Every shape has the form (engine_windows.hip windows_slab_applies()).
+void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_emt_common &c, uint32_t n_seg, const uint64_t *d_seg, double *slab) {
+  if (!c.n_tiles64 || !n_seg) return;
+  with_shape(c, [&](auto S, auto P) {
+    using T = decltype(S);
+    hipLaunchKernelGGL((k_accum_em_table<T::NW, T::CH, T::WPS, false, decltype(P)::value, T::PACK, 1, false, true>),
+                       dim3(c.n_tiles64 * n_seg), dim3(T::NW * 64), 0, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64,
+                       c.g.n_ig, c.g.n_pad, c.g.n_ind, c.g.n_sites, 0, slab, c.d_counters, 0, nullptr, 1, nullptr, d_seg);
+  });
 }
 
 // rb (4 or 8) matrices in one pass of the packed form; d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]
-void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_geom &g, const double *PA, const double *d_Wb, int rb,
-                                     uint64_t n_sites_eff, const ngd_score &score, int pairwise_del,
-                                     const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks,
-                                     uint64_t sites_per_slice, double *slab, unsigned long long *d_counters) {
-  if (!n_tiles64) return;
-#define NGD_EMTB(P, RB)                                                                                                  \
-  hipLaunchKernelGGL((k_accum_em_table<8, 16, 2, true, P, true, RB>), dim3(n_tiles64 * n_ks), dim3(512), 0, st, PA,       \
-                     nullptr, d_Wb, score, d_tiles64, n_tiles64, g.n_ig, g.n_pad, g.n_ind, n_sites_eff, sites_per_slice, \
-                     slab, d_counters)
-  if (rb == 8) {
-    if (pairwise_del) NGD_EMTB(true, 8); else NGD_EMTB(false, 8);
-  } else {
-    if (pairwise_del) NGD_EMTB(true, 4); else NGD_EMTB(false, 4);
-  }
-#undef NGD_EMTB
+void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_emt_common &c, const double *d_Wb, int rb, uint64_t n_sites_eff,
+                                     uint32_t n_ks, uint64_t sites_per_slice, double *slab) {
+  if (!c.n_tiles64) return;
+  with_pdel(c.pairwise_del, [&](auto P) {
+    auto launch = [&](auto RB) {
+      hipLaunchKernelGGL((k_accum_em_table<8, 16, 2, true, decltype(P)::value, true, decltype(RB)::value>), dim3(c.n_tiles64 * n_ks),
+                         dim3(512), 0, st, c.PA, nullptr, d_Wb, c.score, c.d_tiles64, c.n_tiles64, c.g.n_ig, c.g.n_pad, c.g.n_ind,
+                         n_sites_eff, sites_per_slice, slab, c.d_counters);
+    };
+    if (rb == 8) launch(std::integral_constant<int, 8>{}); else launch(std::integral_constant<int, 4>{});
+  });
 }
 
 // The terms of sites [s_lo, s_hi), added up over units of q consecutive sites, of every live pair slot into C
@@ -943,25 +921,18 @@ void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_geom &g, const do
 // slot group of every tile row's first live group).  sites_per_slice must be a multiple of q.  *d_nanflag is set to 1
 // if a term of the chunk was not finite.  d_note != NULL: the noting form -- every site's own term whose stop is within
 // 2^-36 of the tolerance is appended to the note buffer (ngd_internal.h; absolute site indices; the count is NOT reset).
-void ngd_launch_accum_em_table_spill(hipStream_t st, const ngd_geom &g, const double *PA, uint64_t s_lo, uint64_t s_hi,
-                                     const ngd_score &score, int pairwise_del, const ngd_tile *d_tiles64,
-                                     uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice, uint32_t q,
-                                     const uint32_t *d_rowpg, uint32_t n_pg, double *C, unsigned long long *d_counters,
+void ngd_launch_accum_em_table_spill(hipStream_t st, const ngd_emt_common &c, uint64_t s_lo, uint64_t s_hi, uint32_t n_ks,
+                                     uint64_t sites_per_slice, uint32_t q, const uint32_t *d_rowpg, uint32_t n_pg, double *C,
                                      unsigned long long *d_nanflag, unsigned long long *d_note) {
-  if (!n_tiles64 || s_hi <= s_lo) return;
-  if (d_note) {  // the noting twin (NGD_OPT_EM_EXACT = 2): the same launch, the note buffer in the slice table's place
-#define NGD_EMTSN(P)                                                                                                            \
-  hipLaunchKernelGGL((k_accum_em_table<8, 16, 4, false, P, true, 1, true, false, true>), dim3(n_tiles64 * n_ks), dim3(512), 0, st, \
-                     PA, nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, n_pg, g.n_ind, s_hi, sites_per_slice, C,         \
-                     d_counters, s_lo, d_nanflag, q, d_rowpg, reinterpret_cast<const uint64_t *>(d_note))
-    if (pairwise_del) NGD_EMTSN(true); else NGD_EMTSN(false);
-#undef NGD_EMTSN
-    return;
-  }
-#define NGD_EMTS(P)                                                                                                      \
-  hipLaunchKernelGGL((k_accum_em_table<8, 16, 4, false, P, true, 1, true>), dim3(n_tiles64 * n_ks), dim3(512), 0, st, PA, \
-                     nullptr, nullptr, score, d_tiles64, n_tiles64, g.n_ig, n_pg, g.n_ind, s_hi, sites_per_slice, C,      \
-                     d_counters, s_lo, d_nanflag, q, d_rowpg)
-  if (pairwise_del) NGD_EMTS(true); else NGD_EMTS(false);
-#undef NGD_EMTS
+  if (!c.n_tiles64 || s_hi <= s_lo) return;
+  with_pdel(c.pairwise_del, [&](auto P) {
+    if (d_note)  // the noting twin (NGD_OPT_EM_EXACT = 2): the same launch, the note buffer in the slice table's place
+      hipLaunchKernelGGL((k_accum_em_table<8, 16, 4, false, decltype(P)::value, true, 1, true, false, true>), dim3(c.n_tiles64 * n_ks),
+                         dim3(512), 0, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64, c.g.n_ig, n_pg, c.g.n_ind, s_hi,
+                         sites_per_slice, C, c.d_counters, s_lo, d_nanflag, q, d_rowpg, reinterpret_cast<const uint64_t *>(d_note));
+    else
+      hipLaunchKernelGGL((k_accum_em_table<8, 16, 4, false, decltype(P)::value, true, 1, true>), dim3(c.n_tiles64 * n_ks), dim3(512),
+                         0, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64, c.g.n_ig, n_pg, c.g.n_ind, s_hi,
+                         sites_per_slice, C, c.d_counters, s_lo, d_nanflag, q, d_rowpg);
+  });
 }

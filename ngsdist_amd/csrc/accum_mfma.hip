@@ -593,13 +593,16 @@ __global__ __launch_bounds__(EXACT >= 4 ? 1024 : EXACT == 3 ? 768 : EXACT ? 64 :
 
 }  // namespace
 
-void ngd_launch_accum_mfma(hipStream_t st, const ngd_geom &g, const double *PA, const double *QB,
-                           const double *d_ws /* wk */, const uint32_t *d_kgl, const ngd_job *d_jobs, uint32_t n_wg,
-                           int exact_shapes /* 3: n_wg = 1 workgroup of wg_waves wavefronts per slice */, uint32_t wg_waves, uint32_t n_ks, uint64_t kg_per_slice, uint64_t n_kg_eff,
-                           uint64_t k_per_slice, uint32_t w_slice_stride, double *slab, unsigned long long *d_clk,
-                           uint32_t ks0, uint32_t resume, const uint64_t *d_seg) {
+void ngd_launch_accum_mfma(hipStream_t st, const ngd_mfma_engine &en, const ngd_mfma_launch &l) {
+  const ngd_geom &g = en.g;
+  const uint32_t n_wg = en.n_wg, n_ks = l.n_ks;
   if (!n_wg) return;
-  if (d_seg) k_per_slice = 0;  // (the table holds the slices' ranges; w_slice_stride != 0 says their weights are per slice)
+  int exact_shapes = en.exact_shapes;
+  uint32_t wg_waves = en.wg_waves;
+  const double *d_ws = l.d_wk;
+  const uint32_t *d_kgl = l.d_kgl;
+  const uint64_t *d_seg = l.d_seg;
+  const uint64_t k_per_slice = d_seg ? 0 : l.k_per_slice;  // (the table holds the slices' ranges; w_slice_stride != 0 says their weights are per slice)
   // EXACT = 3: a prefetching wavefront beside the jobs where a twelfth fits and the slices are plain k-group ranges
   uint32_t touch_igv = 0;
   const uint32_t n_igv = (uint32_t)((g.n_ind + 15) / 16);
@@ -618,8 +621,9 @@ void ngd_launch_accum_mfma(hipStream_t st, const ngd_geom &g, const double *PA, 
   // wavefront that is done should not wait for three siblings before its slot is handed on
 #define NGD_MFMA(W, D, P, X)                                                                                    \
   hipLaunchKernelGGL((k_accum_mfma<W, D, P, X>), dim3(n_wg * n_ks), dim3(X >= 3 ? 64 * wg_waves : X ? 64 : 256),       \
-                     X == 5 ? 2 * 32 * 64 * sizeof(double) : 0, st, PA, QB, d_ws, d_kgl, d_jobs,                        \
-                     n_wg, g.n_ig, g.n_pad, kg_per_slice, n_kg_eff, k_per_slice, w_slice_stride, slab, touch_igv, d_clk, ks0, resume, d_seg)
+                     X == 5 ? 2 * 32 * 64 * sizeof(double) : 0, st, l.PA, l.QB, d_ws, d_kgl, en.d_jobs,                 \
+                     n_wg, g.n_ig, g.n_pad, l.kg_per_slice, l.n_kg_eff, k_per_slice, l.w_slice_stride, l.slab, touch_igv, en.d_clk, \
+                     l.ks0, l.resume, d_seg)
   // No in-wave run-ahead (DEPTH 1), 3 wavefronts per SIMD: the third wavefront covers the others' load phases.
   // Measured against a 4-deep register ring at 2 wavefronts per SIMD (56.0 vs 51.0 ms on the same job layout) and
   // against LDS-staged operand panels (tools/experiments/accum_mfma_lds.hip; profiles/r01_cfg3_mfma_*): both lose.

@@ -7,15 +7,6 @@ static uint64_t single_image_span(const ngd_geom &g) {
   return std::max<uint64_t>(1, std::min<uint64_t>(g.n_kg, (4ull << 30) / ((uint64_t)g.n_ig * 64 * 8)));
 }
 
-// Single-image engines, a whole pass in ranges: the piece of a range one slice takes (k-groups: whole pipeline trips, and
-// long enough to carry a block's 128 KB of running sums in and out) so that a range is about `span` k-groups.
-uint64_t qb_piece(uint64_t kg_lim, uint32_t n_ks, uint64_t span, uint64_t *n_ranges) {
-  uint64_t r = std::max<uint64_t>(1, (kg_lim + span - 1) / span);
-  const uint64_t piece = std::max<uint64_t>(64, ((kg_lim + r * n_ks - 1) / (r * n_ks) + 3) / 4 * 4);
-  *n_ranges = std::max<uint64_t>(1, (kg_lim + piece * n_ks - 1) / (piece * n_ks));
-  return piece;
-}
-
 int ngd_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -482,7 +473,7 @@ static int create_slices(ngd_engine *e, const std::vector<ngd_tile> &tiles64) {
       // of 248 (6.36 instead of 6.54 ms per matrix, the accumulation itself is flat from 88 to 500 slices).
       const double accum_s = 6.0 * (double)e->n_owned_pairs * (double)g.n_sites / (0.8 * 78.6e12);
       const double reduce_s_per_slice = 8.0 * (double)e->n_owned_pairs / 5e12;
-      // A single-image engine walks the pass in ranges (launch_accumulate()): every launch has all the slices, and every
+      // A single-image engine walks the pass in ranges (accumulate_single_image()): every launch has all the slices, and every
       // block adds to its plane of the slab at the end of each ([measured] cfg 3, 248 slices, 12 ranges: +0.53 ms per
       // launch, 2.1 us per slice -- 2.7 reductions' worth).  Fewer slices then: as few as fill their rounds.
       const uint64_t qb_ranges =
@@ -507,7 +498,7 @@ static int create_slices(ngd_engine *e, const std::vector<ngd_tile> &tiles64) {
       return fail(NGD_E_NOMEM, "ngd_create: no pinned host memory for the clock sample");
     e->h_clk[0] = e->h_clk[1] = e->h_clk[2] = e->h_clk[3] = 0;
     if (e->single_image) {
-      // scratch for QB: one range of a whole pass (launch_accumulate(); partial-sum passes grow it if a bootstrap
+      // scratch for QB: one range of a whole pass (accumulate_single_image(); partial-sum passes grow it if a bootstrap
       // block is longer)
       e->qb_chunk_kg = single_image_span(g);
       uint64_t n_ranges = 0;

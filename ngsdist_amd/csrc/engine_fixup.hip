@@ -4,7 +4,7 @@
 
 // The whole matrix once more in the two-image arithmetic -- P and Q = score . P formed a range of k-groups at a time from
 // the image and SM (layout.hip k_pq_range), K1m over the pair of scratch images range by range, every block adding to its
-// plane of the slab (the walk of the single_image = 1 engines, launch_accumulate()) -- then the noting rule once more:
+// plane of the slab (the walk of the single_image = 1 engines, kg_ranges.h) -- then the noting rule once more:
 // exactly the pairs it picks take the new sums.  Costs a pass and a half (~70 ms at cfg 3's size) WHATEVER the data, where
 // tile by tile a data set of clones costs 0.8 s: fixup_pass() takes this way when its tiles would cost more.
 static int fixup_by_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, double *d_sum, const unsigned long long *d_cnt, double thr) {
@@ -12,21 +12,20 @@ static int fixup_by_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, doubl
   const uint64_t kstride = (uint64_t)g.n_ig * 64;
   const uint64_t kg_lim = std::min<uint64_t>(g.n_kg, (3 * s_hi + 3) / 4);
   // ranges of about 1 GiB per scratch image (two of them), every slice a piece of every range
-  const uint64_t span = std::max<uint64_t>(256, ((uint64_t)1 << 30) / (kstride * 8));
-  uint64_t n_ranges = 0;
-  const uint64_t piece = qb_piece(kg_lim, e->n_ks, span, &n_ranges);
-  const uint64_t range_kg = std::min<uint64_t>(kg_lim, piece * e->n_ks);
-  const uint64_t need = (range_kg + NGD_KG_TAIL) * kstride;
+  const kg_pass_ranges pr(kg_lim, e->n_ks, std::max<uint64_t>(256, ((uint64_t)1 << 30) / (kstride * 8)), 0);
+  const uint64_t need = (std::min<uint64_t>(kg_lim, pr.piece * e->n_ks) + NGD_KG_TAIL) * kstride;
   int rc = e->fix_p.ensure(e, need);
   if (!rc) rc = e->fix_q.ensure(e, need);
   if (!rc) rc = e->d_fixnew.ensure(e, ngd_n_pairs(g.n_ind));
   if (rc) return rc;
-  for (uint64_t r = 0; r < n_ranges; r++) {
-    const uint64_t lo = std::min<uint64_t>(r * piece * e->n_ks, kg_lim), hi = std::min<uint64_t>(lo + piece * e->n_ks, kg_lim);
-    if (hi <= lo) break;
+  for (uint64_t r = 0; r < pr.n_ranges; r++) {
+    const uint64_t lo = pr.lo(r), hi = pr.hi(r);
     ngd_launch_pq_range(e->st, g, e->sc, e->PA, e->SM, ws, lo, hi + NGD_KG_TAIL, e->fix_p, e->fix_q);
-    ngd_launch_accum_mfma(e->st, g, e->fix_p, e->fix_q, nullptr, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, e->n_ks,
-                          piece, hi - lo, 0, 0, e->slab, e->d_clk, 0, r > 0);
+    ngd_mfma_launch l;
+    l.PA = e->fix_p; l.QB = e->fix_q;
+    l.n_ks = e->n_ks; l.kg_per_slice = pr.piece; l.n_kg_eff = hi - lo;
+    l.slab = e->slab; l.resume = r > 0;
+    ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
   }
   ngd_launch_reduce(e->st, g, e->slab, e->n_ks, 1, e->d_tiles, e->n_tiles, e->d_fixnew, nullptr, 0, nullptr, 0.0);
   ngd_launch_fix_merge(e->st, g, e->d_fixnew, d_sum, d_cnt, thr, e->d_tiles, e->n_tiles);
@@ -36,34 +35,30 @@ static int fixup_by_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, doubl
 
 // The same for the per-block partial results of a bootstrap job whose blocks are whole k-groups: EVERY entry of the slab is
 // formed again by the two-operand arithmetic, the scratch images made for a range of whole slices at a time (in eights: the
-// XCD deal of accum_mfma.hip) and handed to the kernel moved back by the range's first k-group, as launch_accumulate() does
-// for ngd_config.single_image = 1.  The replicates are then reduced from the slab again (partials_impl).
+// XCD deal of accum_mfma.hip) and handed to the kernel moved back by the range's first k-group, as accumulate_single_image()
+// does for ngd_config.single_image = 1.  The replicates are then reduced from the slab again (partials_impl).
 static int fixup_partials_by_pass(ngd_engine *e, uint64_t s_hi) {
   const ngd_geom &g = e->g;
   const uint64_t kstride = (uint64_t)g.n_ig * 64;
-  const uint64_t kg_lim = std::min<uint64_t>(g.n_kg, 3 * s_hi / 4);
-  const uint64_t per_slice = e->blk.per_slice;
-  const uint32_t n_ks = e->blk.nks;
-  if (!per_slice || !n_ks || n_ks % 8) return fail(NGD_E_HIP, "fix-up pass: internal -- the partial results' slices are not in eights");
-  const uint64_t span = std::max<uint64_t>(8 * per_slice, ((uint64_t)1 << 30) / (kstride * 8));  // ~1 GiB per scratch image
-  auto kg0 = [&](uint64_t ks) { return ks * per_slice; };
-  auto kg1 = [&](uint64_t ks) { return std::min<uint64_t>(kg_lim, (ks + 1) * per_slice); };
-  for (uint32_t ks0 = 0; ks0 < n_ks;) {
-    uint32_t n = 8;
-    while (ks0 + n < n_ks && kg1(ks0 + n + 7) - kg0(ks0) <= span && kg0(ks0 + n) < kg_lim) n += 8;
-    n = std::min(n, n_ks - ks0);
-    const uint64_t lo = std::min<uint64_t>(kg0(ks0), kg_lim), hi = std::max(lo, kg1(ks0 + n - 1));
-    const uint64_t need = (hi - lo + NGD_KG_TAIL) * kstride;
+  const kg_slices sl{e->blk.nks, e->blk.per_slice, 0, std::min<uint64_t>(g.n_kg, 3 * s_hi / 4)};
+  if (!sl.per_slice || !sl.n_ks || sl.n_ks % 8) return fail(NGD_E_HIP, "fix-up pass: internal -- the partial results' slices are not in eights");
+  const uint64_t span = std::max<uint64_t>(8 * sl.per_slice, ((uint64_t)1 << 30) / (kstride * 8));  // ~1 GiB per scratch image
+  for (uint32_t ks0 = 0; ks0 < sl.n_ks;) {
+    const kg_slice_group r = kg_slice_group_at(sl, span, ks0);
+    const uint64_t need = (r.hi - r.lo + NGD_KG_TAIL) * kstride;
     int rc = e->fix_p.ensure(e, need);
     if (!rc) rc = e->fix_q.ensure(e, need);
     if (rc) return rc;
-    ngd_launch_pq_range(e->st, g, e->sc, e->PA, e->SM, nullptr, lo, std::min<uint64_t>(hi + NGD_KG_TAIL, g.n_kg + NGD_KG_TAIL), e->fix_p, e->fix_q);
-    const double *p_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->fix_p.get()) - lo * kstride * sizeof(double));
-    const double *q_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->fix_q.get()) - lo * kstride * sizeof(double));
-    ngd_launch_accum_mfma(e->st, g, p_back, q_back, nullptr, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n, per_slice,
-                          kg_lim, 0, 0, e->blk.sums(), e->d_clk, ks0);
+    ngd_launch_pq_range(e->st, g, e->sc, e->PA, e->SM, nullptr, r.lo, std::min<uint64_t>(r.hi + NGD_KG_TAIL, g.n_kg + NGD_KG_TAIL), e->fix_p, e->fix_q);
+    ngd_mfma_launch l;
+    l.PA = kg_moved_back(e->fix_p, e->fix_p.capacity(), kstride, NGD_KG_TAIL, sl, r);
+    l.QB = kg_moved_back(e->fix_q, e->fix_q.capacity(), kstride, NGD_KG_TAIL, sl, r);
+    if (!l.PA || !l.QB) return fail(NGD_E_HIP, "fix-up pass: internal -- a slice of the range reaches outside the scratch images");
+    l.ks0 = r.ks0; l.n_ks = r.n; l.kg_per_slice = sl.per_slice; l.n_kg_eff = sl.kg_lim;
+    l.slab = e->blk.sums();
+    ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
     HIPCHK(hipGetLastError());
-    ks0 += n;
+    ks0 += r.n;
   }
   return NGD_OK;
 }

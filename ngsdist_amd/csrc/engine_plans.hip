@@ -3,114 +3,158 @@
 // run_impl, which picks the cheapest that applies.
 #include "ngd_engine.h"
 
-// w != NULL: one bootstrap replicate; for the MFMA kernel kgl is then the list of k-groups to visit and
-// per_slice / kg_lim count list entries
-// k_per_slice != 0 (MFMA, bootstrap blocks that are not whole k-groups): slices of k_per_slice contraction indices,
-// masked by the per-slice 0/1 weights in e->blk.wslice (w_stride k-groups per slice)
-// note (NGD_OPT_EM_EXACT, table-driven EM kernel, a plain pass): the noting form, into e->d_note
-static int launch_accumulate(ngd_engine *e, const uint32_t *w, const uint32_t *kgl, uint64_t sites_eff, uint32_t n_ks,
-                              uint64_t per_slice, uint64_t kg_lim, double *slab, uint64_t k_per_slice = 0,
-                              uint32_t w_stride = 0, bool note = false) {
+// The slices of one accumulation pass.
+struct pass_slices {
+  // one bootstrap replicate: its per-site weights (NULL: none); for the MFMA kernel kgl is then the list of k-groups to
+  // visit and per_slice / kg_lim count list entries
+  const uint32_t *w = nullptr, *kgl = nullptr;
+  uint64_t sites_eff = 0;
+  uint32_t n_ks = 0;
+  uint64_t per_slice = 0, kg_lim = 0;
+  double *slab = nullptr;
+  // k_per_slice != 0 (MFMA, bootstrap blocks that are not whole k-groups): slices of k_per_slice contraction indices,
+  // masked by the per-slice 0/1 weights in e->blk.wslice (w_stride k-groups per slice)
+  uint64_t k_per_slice = 0;
+  uint32_t w_stride = 0;
+  bool note = false;  // NGD_OPT_EM_EXACT, table-driven EM kernel, a plain pass: the noting form, into e->d_note
+};
+
+// the MFMA launch over the pass's slices as they are, but for the second image and the k-group list
+static ngd_mfma_launch slices_launch(const ngd_engine *e, const pass_slices &p, const double *d_w_plain) {
+  ngd_mfma_launch l;
+  l.PA = e->PA;
+  l.d_wk = p.k_per_slice ? e->blk.wslice : (p.w ? e->d_wk : d_w_plain);
+  l.n_ks = p.n_ks; l.kg_per_slice = p.per_slice; l.n_kg_eff = p.kg_lim;
+  l.k_per_slice = p.k_per_slice; l.w_slice_stride = p.w_stride;
+  l.slab = p.slab;
+  return l;
+}
+
+// ngd_config.single_image = 1:
+// QB is formed range by range into a scratch (k_qb_range: HBM work, 49 GB a pass at cfg 3) on the accumulation
+// kernel's own stream, each range before the launch that reads it (the ranges: kg_ranges.h).
+//  * a whole pass (slab == e->slab): EVERY slice takes a piece of every range, so that each launch has the
+//    pass's full grid (a launch over a few whole slices would not fill the chip once: cfg 3 has 34 workgroups
+//    per slice and room for 768); a block adds its sums over the range to its plane of the slab (`resume`).  A
+//    slice is then not one contiguous run of k-groups, as it is with both images resident: the sums of the two
+//    engines agree to rounding (exactly where the arithmetic is exact: called genotypes), not bit for bit.
+//  * per-block partial sums (a slice = a bootstrap block, thousands of them): ranges of whole slices, in eights
+//    (the XCD deal of accum_mfma.hip); the kernel is handed the scratch moved back by the range's first k-group.
+// (single-image engines make no k-group lists: pass_impl() walks every k-group of a weighted pass)
+// [measured, cfg 3] forming a range on a second stream beside the launch over the range before it gains nothing:
+// the accumulation kernel slows by what the overlap hides, however few blocks form the range and with or
+// without non-temporal accesses (profiles/r04_single_image.txt; tools/experiments/single_image_two_streams.patch).
+static int accumulate_single_image(ngd_engine *e, const pass_slices &p) {
   const ngd_geom &g = e->g;
-  switch (e->kernel) {
-    case NGD_KERNEL_MFMA:
-      if (!e->single_image) {
-        // (single_image = 2: both operands from the one image, the congruence's diagonal on the weights -- of a plain pass too)
-        ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB,
-                              k_per_slice ? e->blk.wslice : (w ? e->d_wk : (e->congruent ? e->d_wD : nullptr)),
-                                (w && !k_per_slice) ? kgl : nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n_ks, per_slice,
-                                kg_lim, k_per_slice, w_stride, slab, e->d_clk);
-      } else {
-        // QB is formed range by range into a scratch (k_qb_range: HBM work, 49 GB a pass at cfg 3) on the accumulation
-        // kernel's own stream, each range before the launch that reads it.
-        //  * a whole pass (slab == e->slab): EVERY slice takes a piece of every range, so that each launch has the
-        //    pass's full grid (a launch over a few whole slices would not fill the chip once: cfg 3 has 34 workgroups
-        //    per slice and room for 768); a block adds its sums over the range to its plane of the slab (`resume`).  A
-        //    slice is then not one contiguous run of k-groups, as it is with both images resident: the sums of the two
-        //    engines agree to rounding (exactly where the arithmetic is exact: called genotypes), not bit for bit.
-        //  * per-block partial sums (a slice = a bootstrap block, thousands of them): ranges of whole slices, in eights
-        //    (the XCD deal of accum_mfma.hip); the kernel is handed the scratch moved back by the range's first k-group.
-        // (single-image engines make no k-group lists: pass_impl() walks every k-group of a weighted pass)
-        // [measured, cfg 3] forming a range on a second stream beside the launch over the range before it gains nothing:
-        // the accumulation kernel slows by what the overlap hides, however few blocks form the range and with or
-        // without non-temporal accesses (profiles/r04_single_image.txt; tools/experiments/single_image_two_streams.patch).
-        const uint64_t kstride = (uint64_t)g.n_ig * 64;
-        const uint64_t span = std::max<uint64_t>(1, e->qb_chunk_kg);
-        const bool whole_pass = slab == e->slab && !k_per_slice;
-        auto slice_kg0 = [&](uint64_t ks) { return k_per_slice ? (ks * k_per_slice) >> 2 : ks * per_slice; };
-        auto slice_kg1 = [&](uint64_t ks) {
-          return std::min<uint64_t>(kg_lim, k_per_slice ? ((ks + 1) * k_per_slice + 3) >> 2 : (ks + 1) * per_slice);
-        };
-        const double *wsel = k_per_slice ? e->blk.wslice : (w ? e->d_wk : nullptr);
-        // what the engine keeps of the second image (its first qb_res_kg k-groups, ngd_config.second_image_mib) is read
-        // where it lies: one launch over that part of a whole pass, or over the slices that end inside it
-        const uint64_t res = std::min<uint64_t>(e->qb_res_kg, kg_lim);
-        uint32_t ks_first = 0;
-        if (res && whole_pass) {
-          const uint64_t piece_r = std::max<uint64_t>(4, ((res + n_ks - 1) / n_ks + 3) / 4 * 4);
-          ngd_launch_accum_mfma(e->st, g, e->PA, e->QB_res, wsel, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n_ks,
-                                piece_r, res, 0, 0, slab, e->d_clk, 0, 0);
-        } else if (res) {
-          while (ks_first + 8 <= n_ks && slice_kg1(ks_first + 7) <= res && slice_kg0(ks_first + 7) < kg_lim) ks_first += 8;
-          if (ks_first)
-            ngd_launch_accum_mfma(e->st, g, e->PA, e->QB_res, wsel, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves,
-                                  ks_first, per_slice, kg_lim, k_per_slice, w_stride, slab, e->d_clk, 0);
-        }
-        const uint64_t rest0 = whole_pass ? res : 0;  // a whole pass goes on from here
-        uint64_t piece = 0, n_ranges = 0;
-        if (whole_pass && kg_lim > rest0) piece = qb_piece(kg_lim - rest0, n_ks, span, &n_ranges);
-        uint32_t r = 0;
-        for (uint32_t ks0 = ks_first; whole_pass ? r < n_ranges : ks0 < n_ks; r++) {
-          uint32_t n = 8;
-          uint64_t lo, hi;
-          if (whole_pass) {
-            lo = std::min<uint64_t>(rest0 + (uint64_t)r * piece * n_ks, kg_lim);
-            hi = std::min<uint64_t>(lo + piece * n_ks, kg_lim);
-          } else {
-            while (ks0 + n < n_ks && slice_kg1(ks0 + n + 7) - slice_kg0(ks0) <= span && slice_kg0(ks0 + n) < kg_lim) n += 8;
-            n = std::min(n, n_ks - ks0);
-            lo = std::min<uint64_t>(slice_kg0(ks0), kg_lim);
-            hi = std::max(lo, slice_kg1(ks0 + n - 1));
-          }
-          const uint64_t need = (hi - lo + NGD_KG_TAIL) * kstride;
-          if (need > e->qb_chunk.capacity()) {
-            // a range longer than the scratch was sized for (bootstrap blocks of very many sites: a partial-sum slice
-            // is a whole block): the scratch grows to hold it -- the earlier ranges' launches have to be over first
-            HIPCHK(hipStreamSynchronize(e->st));
-            int rc = e->qb_chunk.ensure(e, need);
-            if (rc) return rc;
-          }
-          ngd_launch_qb_range(e->st, g, e->sc, e->PA, lo, std::min<uint64_t>(hi + NGD_KG_TAIL, g.n_kg + NGD_KG_TAIL), e->qb_chunk);
-          if (whole_pass)
-            ngd_launch_accum_mfma(e->st, g, e->PA + lo * kstride, e->qb_chunk, wsel ? wsel + lo * 4 : nullptr, nullptr, e->d_jobs,
-                                  e->n_wg, e->exact_shapes, e->wg_waves, n_ks, piece, hi - lo, 0, 0, slab, e->d_clk, 0,
-                                  r > 0 || res > 0);
-          else {  // (the kernel indexes the image by absolute k-group: an address below the scratch, formed as an integer)
-            // ... so every k-group a launched slice can touch -- its own [kg0, kg1) and the NGD_KG_TAIL k-groups its operand
-            // pipeline (the prefetching wavefront included) runs ahead -- must lie inside the scratch as just formed
-            const uint64_t first = slice_kg0(ks0), last = std::max(first, slice_kg1(ks0 + n - 1));
-            if ((first < lo && first < kg_lim) || last > hi || (hi - lo + NGD_KG_TAIL) * kstride > e->qb_chunk.capacity())
-              return fail(NGD_E_HIP, "launch_accumulate: internal -- a slice of the range reaches outside the scratch of the second image");
-            const double *moved_back = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(e->qb_chunk.get()) - lo * kstride * sizeof(double));
-            ngd_launch_accum_mfma(e->st, g, e->PA, moved_back, wsel, nullptr, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, n,
-                                  per_slice, kg_lim, k_per_slice, w_stride, slab, e->d_clk, ks0);
-          }
-          ks0 += n;
-        }
-      }
-      break;
-    case NGD_KERNEL_EM_TABLE:
-      if (note)
-        ngd_launch_accum_em_table_note(e->st, g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64, n_ks,
-                                       per_slice, slab, e->d_emcnt, e->d_note);
-      else
-      ngd_launch_accum_em_table(e->st, g, e->PA, w, sites_eff, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64,
-                                e->n_tiles64, n_ks, per_slice, slab, e->d_emcnt);
-      break;
-    default:
-      ngd_launch_accum_em(e->st, g, e->PA, w, sites_eff, e->sc, e->cfg.pairwise_del,
-                          e->kernel == NGD_KERNEL_EM_FAST, e->d_tiles16, e->n_tiles16, n_ks, per_slice, slab);
+  const ngd_mfma_engine en = mfma_engine(e);
+  const uint64_t kstride = (uint64_t)g.n_ig * 64;
+  const uint64_t span = std::max<uint64_t>(1, e->qb_chunk_kg);
+  // what the engine keeps of the second image (its first qb_res_kg k-groups, ngd_config.second_image_mib) is read
+  // where it lies: one launch over that part of a whole pass, or over the slices that end inside it
+  const uint64_t res = std::min<uint64_t>(e->qb_res_kg, p.kg_lim);
+  ngd_mfma_launch l = slices_launch(e, p, nullptr);
+  // k-groups [lo, hi) of the second image (+ the tail the operand pipeline runs ahead) into the scratch
+  auto form = [&](uint64_t lo, uint64_t hi) -> int {
+    const uint64_t need = (hi - lo + NGD_KG_TAIL) * kstride;
+    if (need > e->qb_chunk.capacity()) {
+      // a range longer than the scratch was sized for (bootstrap blocks of very many sites: a partial-sum slice
+      // is a whole block): the scratch grows to hold it -- the earlier ranges' launches have to be over first
+      HIPCHK(hipStreamSynchronize(e->st));
+      if (int rc = e->qb_chunk.ensure(e, need)) return rc;
+    }
+    ngd_launch_qb_range(e->st, g, e->sc, e->PA, lo, std::min<uint64_t>(hi + NGD_KG_TAIL, g.n_kg + NGD_KG_TAIL), e->qb_chunk);
+    return NGD_OK;
+  };
+  if (p.slab == e->slab && !p.k_per_slice) {  // a whole pass
+    const double *w = l.d_wk;
+    if (res) {
+      l.QB = e->QB_res;
+      l.kg_per_slice = std::max<uint64_t>(4, ((res + p.n_ks - 1) / p.n_ks + 3) / 4 * 4); l.n_kg_eff = res;
+      ngd_launch_accum_mfma(e->st, en, l);
+    }
+    const kg_pass_ranges pr(p.kg_lim, p.n_ks, span, res);  // ... goes on from the resident part
+    for (uint64_t r = 0; r < pr.n_ranges; r++) {
+      const uint64_t lo = pr.lo(r), hi = pr.hi(r);
+      if (int rc = form(lo, hi)) return rc;
+      l.PA = e->PA + lo * kstride; l.QB = e->qb_chunk;
+      l.d_wk = w ? w + lo * 4 : nullptr;
+      l.kg_per_slice = pr.piece; l.n_kg_eff = hi - lo;
+      l.resume = r > 0 || res > 0;
+      ngd_launch_accum_mfma(e->st, en, l);
+    }
+    return NGD_OK;
   }
+  const kg_slices sl{p.n_ks, p.per_slice, p.k_per_slice, p.kg_lim};
+  const uint32_t ks_first = res ? kg_slices_resident(sl, res) : 0;
+  if (ks_first) {
+    l.QB = e->QB_res;
+    l.n_ks = ks_first;
+    ngd_launch_accum_mfma(e->st, en, l);
+  }
+  for (uint32_t ks0 = ks_first; ks0 < p.n_ks; ks0 += l.n_ks) {
+    const kg_slice_group r = kg_slice_group_at(sl, span, ks0);
+    if (int rc = form(r.lo, r.hi)) return rc;
+    l.QB = kg_moved_back(e->qb_chunk, e->qb_chunk.capacity(), kstride, NGD_KG_TAIL, sl, r);
+    if (!l.QB) return fail(NGD_E_HIP, "single-image pass: internal -- a slice of the range reaches outside the scratch of the second image");
+    l.ks0 = r.ks0; l.n_ks = r.n;
+    ngd_launch_accum_mfma(e->st, en, l);
+  }
+  return NGD_OK;
+}
+
+static void accumulate_em(ngd_engine *e, const pass_slices &p) {
+  if (e->kernel != NGD_KERNEL_EM_TABLE)
+    ngd_launch_accum_em(e->st, e->g, e->PA, p.w, p.sites_eff, e->sc, e->cfg.pairwise_del, e->kernel == NGD_KERNEL_EM_FAST,
+                        e->d_tiles16, e->n_tiles16, p.n_ks, p.per_slice, p.slab);
+  else if (p.note)
+    ngd_launch_accum_em_table_note(e->st, emt_common(e), p.n_ks, p.per_slice, p.slab, e->d_note);
+  else
+    ngd_launch_accum_em_table(e->st, emt_common(e), p.w, p.sites_eff, p.n_ks, p.per_slice, p.slab);
+}
+
+// both images resident (single_image = 2: both operands from the one image, the congruence's diagonal on the weights -- of a
+// plain pass too)
+static void accumulate_two_images(ngd_engine *e, const pass_slices &p) {
+  ngd_mfma_launch l = slices_launch(e, p, e->congruent ? e->d_wD.get() : nullptr);
+  l.QB = e->congruent ? e->PA : e->QB;
+  l.d_kgl = (p.w && !p.k_per_slice) ? p.kgl : nullptr;
+  ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
+}
+
+static int launch_accumulate(ngd_engine *e, const pass_slices &p) {
+  if (e->kernel != NGD_KERNEL_MFMA) accumulate_em(e, p);
+  else if (e->single_image) return accumulate_single_image(e, p);
+  else accumulate_two_images(e, p);
+  return NGD_OK;
+}
+
+// bit planes that hold multiplicities up to mult_max (none drawn: one all-zero plane -- 0 planes means "unweighted")
+static uint32_t count_planes(uint32_t mult_max) {
+  uint32_t n = 1;
+  while (n < 32 && (mult_max >> n)) n++;
+  return n;
+}
+
+// --pairwise_del: the valid-site counts of one matrix of a job -- the full data set (d_mult == NULL) or the replicate whose
+// block multiplicities are d_mult (on the device; at most mult_max)
+static void count_matrix(ngd_engine *e, const uint32_t *d_mult, uint32_t mult_max, uint64_t n_blocks, uint64_t block_size,
+                         unsigned long long *d_cnt) {
+  const ngd_geom &g = e->g;
+  const uint32_t n_planes = d_mult ? count_planes(mult_max) : 0;
+  if (d_mult) {
+    ngd_launch_weights(e->st, n_blocks, block_size, g.n_sites_pad, d_mult, e->d_ws, nullptr);
+    ngd_launch_planes(e->st, e->d_ws, g.n_sites, g.n_words, n_planes, e->planes);
+  }
+  ngd_launch_count(e->st, g, e->mask, e->planes, n_planes, e->d_tiles, e->n_tiles, d_cnt);
+}
+
+// pairs outside this engine's shard are returned as 0 / 0; an engine that owns every pair overwrites them all
+// (a device memset moves ~0.15 TB/s: 0.8 ms for the 130 MB of a 65-matrix cfg 5 batch).  counts_add: the counts are
+// added to what is there (k_count adds with integer atomics)
+static int zero_outputs(ngd_engine *e, uint32_t n_mat, double *d_sum, unsigned long long *d_cnt, bool counts_add) {
+  const uint64_t n = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
+  if (e->cfg.shard_world > 1) HIPCHK(hipMemsetAsync(d_sum, 0, n * sizeof(double), e->st));
+  if (e->cfg.shard_world > 1 || counts_add) HIPCHK(hipMemsetAsync(d_cnt, 0, n * sizeof(unsigned long long), e->st));
   return NGD_OK;
 }
 
@@ -153,17 +197,13 @@ void read_timing(ngd_engine *e, uint64_t n_eff, uint32_t launches, bool add) {
 static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uint64_t n_blocks, uint64_t block_size,
                      uint64_t n_drawn, double *d_sum, unsigned long long *d_cnt, bool add_timing, bool note) {
   const ngd_geom &g = e->g;
-  const uint64_t n_pairs = ngd_n_pairs(g.n_ind);
   uint64_t n_eff = g.n_sites;
   const uint32_t *ws = nullptr;
-  uint32_t n_planes = 0;
   uint32_t n_list = 0;
   const bool list_pass = mult && e->kernel == NGD_KERNEL_MFMA && !e->single_image;
   HIPCHK(hipEventRecord(e->ev[0], e->st));
   if (mult) {
     n_eff = n_blocks * block_size;
-    while (n_planes < 32 && (mult_max >> n_planes)) n_planes++;
-    if (!n_planes) n_planes = 1;  // no block drawn (a site range of a larger job): one all-zero plane -- 0 planes means "unweighted"
     if (int rc = e->d_mult.ensure(e, n_blocks)) return rc;
     HIPCHK(hipMemcpyAsync(e->d_mult, mult, n_blocks * 4, hipMemcpyHostToDevice, e->st));
     ngd_launch_weights(e->st, n_blocks, block_size, g.n_sites_pad, e->d_mult, e->d_ws, e->d_wk, e->congruent ? e->sc.d : nullptr);
@@ -182,30 +222,29 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
     HIPCHK(hipStreamSynchronize(e->st));  // `mult` is pageable host memory; n_list has arrived
     ws = e->d_ws;
   }
-  // pairs outside this engine's shard are returned as 0 / 0; an engine that owns every pair overwrites them all
-  // (a device memset moves ~0.15 TB/s: 0.8 ms for the 130 MB of a 65-matrix cfg 5 batch)
-  const bool zero_sum = e->cfg.shard_world > 1;
-  const bool zero_cnt = zero_sum || e->cfg.pairwise_del;  // k_count adds with integer atomics
-  if (zero_sum) HIPCHK(hipMemsetAsync(d_sum, 0, n_pairs * sizeof(double), e->st));
-  if (zero_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, n_pairs * sizeof(unsigned long long), e->st));
+  if (int rc = zero_outputs(e, 1, d_sum, d_cnt, e->cfg.pairwise_del)) return rc;
   if (note)
     if (int rc = em_exact_begin(e)) return rc;
   HIPCHK(hipEventRecord(e->ev[1], e->st));
   int rc_acc = NGD_OK;
+  pass_slices ps;
+  ps.w = ws; ps.sites_eff = n_eff; ps.n_ks = e->n_ks; ps.slab = e->slab;
   if (e->kernel == NGD_KERNEL_STREAM)
     ngd_launch_accum_stream(e->st, g, e->PI, ws, n_eff, e->sc, e->cfg.pairwise_del,
                             e->cfg.shard_world > 1 ? e->d_pairs : nullptr, e->n_owned_pairs, d_sum);
-  else if (list_pass)  // slices are equal shares of the list (whole multiples of 4 entries: the deepest operand ring)
-    rc_acc = launch_accumulate(e, ws, e->d_kgl, n_eff, e->n_ks, (((uint64_t)n_list + e->n_ks - 1) / e->n_ks + 3) / 4 * 4,
-                               n_list, e->slab);
-  else if (!mult && e->eager_valid && e->eager_slices) {
+  else if (list_pass) {  // slices are equal shares of the list (whole multiples of 4 entries: the deepest operand ring)
+    ps.kgl = e->d_kgl; ps.per_slice = (((uint64_t)n_list + e->n_ks - 1) / e->n_ks + 3) / 4 * 4; ps.kg_lim = n_list;
+    rc_acc = launch_accumulate(e, ps);
+  } else if (!mult && e->eager_valid && e->eager_slices) {
     // the leading slices were accumulated beside the load (eager_advance): what is left, behind them
     HIPCHK(hipStreamWaitEvent(e->st, e->ev_eager, 0));
     if (e->eager_slices < e->n_ks) launch_plain_slices(e, e->st, e->eager_slices, e->n_ks - e->eager_slices, false);
     e->eager_valid = false;
     e->eager_slices = 0;
-  } else
-    rc_acc = launch_accumulate(e, ws, nullptr, n_eff, e->n_ks, e->per_slice, g.n_kg, e->slab, 0, 0, note);
+  } else {
+    ps.per_slice = e->per_slice; ps.kg_lim = g.n_kg; ps.note = note;
+    rc_acc = launch_accumulate(e, ps);
+  }
   if (rc_acc) return rc_acc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev[2], e->st));
@@ -222,8 +261,9 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
   if (fix_in_reduce) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
   HIPCHK(hipEventRecord(e->ev[3], e->st));
   if (e->cfg.pairwise_del) {
-    if (ws) ngd_launch_planes(e->st, ws, g.n_sites, g.n_words, n_planes, e->planes);
-    ngd_launch_count(e->st, g, e->mask, e->planes, ws ? n_planes : 0, e->d_tiles, e->n_tiles, d_cnt);
+    // (no block drawn -- a site range of a larger job: one all-zero plane, count_planes)
+    if (ws) ngd_launch_planes(e->st, ws, g.n_sites, g.n_words, count_planes(mult_max), e->planes);
+    ngd_launch_count(e->st, g, e->mask, e->planes, ws ? count_planes(mult_max) : 0, e->d_tiles, e->n_tiles, d_cnt);
     if (fix) {
       ngd_launch_fix_flag(e->st, g, d_sum, d_cnt, 1, e->d_tiles, e->n_tiles, ff);
       HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
@@ -354,18 +394,19 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
     e->blk.nks = (uint32_t)nks;
     e->blk.sub = (uint32_t)sub;
     e->blk.per_slice = unit / sub;
+    pass_slices ps;  // a slice = a block (or an equal part of one)
+    ps.sites_eff = n_eff; ps.n_ks = e->blk.nks; ps.slab = e->blk.sums();
     if (unaligned) {
       const uint32_t w_stride = (uint32_t)((3 * block_size + 3) / 4 + 1 + NGD_KG_TAIL);
       rc = e->blk.wslice.ensure(e, (uint64_t)e->blk.nks * w_stride * 4);
       if (rc) return rc;
       ngd_launch_slice_weights(e->st, e->blk.nks, w_stride, 3 * block_size, 3 * n_eff, e->blk.wslice, e->congruent ? e->sc.d : nullptr);
-      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, 0, (3 * n_eff + 3) / 4, e->blk.sums(), 3 * block_size,
-                             w_stride);
+      ps.kg_lim = (3 * n_eff + 3) / 4; ps.k_per_slice = 3 * block_size; ps.w_stride = w_stride;
     } else {
       if (note && (rc = em_exact_begin(e))) return rc;
-      rc = launch_accumulate(e, nullptr, nullptr, n_eff, e->blk.nks, e->blk.per_slice, mfma ? 3 * n_eff / 4 : 0, e->blk.sums(),
-                             0, 0, note);
+      ps.per_slice = e->blk.per_slice; ps.kg_lim = mfma ? 3 * n_eff / 4 : 0; ps.note = note;
     }
+    rc = launch_accumulate(e, ps);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     // (a slab the noting form filled is not the cache: it stops in-band pairs at the widened threshold, and only the
@@ -388,10 +429,8 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
   int rc = e->d_W.ensure(e, W.size());
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(e->d_W, W.data(), W.size() * 8, hipMemcpyHostToDevice, e->st));
-  if (e->cfg.shard_world > 1) {  // (the weighted reductions write every pair this engine owns, sums and counts)
-    HIPCHK(hipMemsetAsync(d_sum, 0, (uint64_t)n_rep * n_pairs * sizeof(double), e->st));
-    HIPCHK(hipMemsetAsync(d_cnt, 0, (uint64_t)n_rep * n_pairs * sizeof(unsigned long long), e->st));
-  }
+  // (the weighted reductions write every pair this engine owns, sums and counts)
+  if ((rc = zero_outputs(e, n_rep, d_sum, d_cnt, false))) return rc;
   const bool fix = e->SM != nullptr && mfma;  // (see pass_impl)
   const ngd_fix_flags ff{e->d_fixlist, e->d_fixcount, e->d_fixseen, e->fix_cap};
   std::vector<double> thr;
@@ -531,9 +570,7 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     b_ks = (uint32_t)ks;
     b_per = (g.n_sites + ks - 1) / ks;
   }
-  if (e->cfg.shard_world > 1) HIPCHK(hipMemsetAsync(d_sum, 0, (uint64_t)n_mat * n_pairs * sizeof(double), e->st));
-  if (e->cfg.shard_world > 1 || e->cfg.pairwise_del)  // k_count adds with integer atomics
-    HIPCHK(hipMemsetAsync(d_cnt, 0, (uint64_t)n_mat * n_pairs * sizeof(unsigned long long), e->st));
+  if (int rc = zero_outputs(e, n_mat, d_sum, d_cnt, e->cfg.pairwise_del)) return rc;
   DevBuf<double> &slab = e->blk.borrow_sums();  // the partial-sum slab is re-used as this pass's scratch
   for (uint32_t c0 = 0; c0 < n_mat; c0 += per_pass) {
     const uint32_t nr = std::min(per_pass, n_mat - c0);
@@ -558,8 +595,7 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
                              e->d_W);
     HIPCHK(hipEventRecord(e->ev[1], e->st));
     if (table)
-      ngd_launch_accum_em_table_batch(e->st, g, e->PA, e->d_W, rb, lead ? g.n_sites : n_eff, e->sc, e->cfg.pairwise_del,
-                                      e->d_tiles64, e->n_tiles64, b_ks, b_per, slab, e->d_emcnt);
+      ngd_launch_accum_em_table_batch(e->st, emt_common(e), e->d_W, rb, lead ? g.n_sites : n_eff, b_ks, b_per, slab);
     else
       ngd_launch_accum_em_batch(e->st, g, e->PA, e->d_W, rb, lead ? g.n_sites : n_eff, e->sc, e->cfg.pairwise_del, fast,
                                 e->d_tiles16, e->n_tiles16, b_ks, b_per, slab);
@@ -573,19 +609,10 @@ static int em_batch_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
       unsigned long long *cnt_r = d_cnt + (uint64_t)(c0 + r) * n_pairs;
       const bool is_lead = lead && r == 0;
       const uint32_t q = q0 + r - (lead ? 1u : 0u);
-      if (!e->cfg.pairwise_del) {
+      if (!e->cfg.pairwise_del)
         ngd_launch_fill_cnt(e->st, g, e->d_tiles, e->n_tiles, is_lead ? g.n_sites : drawn[q], nullptr, 1, cnt_r);
-      } else if (is_lead) {
-        ngd_launch_count(e->st, g, e->mask, e->planes, 0, e->d_tiles, e->n_tiles, cnt_r);
-      } else {
-        uint32_t n_planes = 0;
-        while (n_planes < 32 && (mult_max[q] >> n_planes)) n_planes++;
-        if (!n_planes) n_planes = 1;  // (as in pass_impl: a replicate that drew none of these blocks counts 0 sites)
-        ngd_launch_weights(e->st, n_blocks, block_size, g.n_sites_pad, e->d_M + (uint64_t)(q - q0) * n_blocks, e->d_ws,
-                           nullptr);
-        ngd_launch_planes(e->st, e->d_ws, g.n_sites, g.n_words, n_planes, e->planes);
-        ngd_launch_count(e->st, g, e->mask, e->planes, n_planes, e->d_tiles, e->n_tiles, cnt_r);
-      }
+      else
+        count_matrix(e, is_lead ? nullptr : e->d_M + (uint64_t)(q - q0) * n_blocks, is_lead ? 0 : mult_max[q], n_blocks, block_size, cnt_r);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[4], e->st));
@@ -664,9 +691,7 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
   if (n_rep) HIPCHK(hipMemcpyAsync(e->d_M, mult, (uint64_t)n_rep * n_blocks * 4, hipMemcpyHostToDevice, e->st));
   HIPCHK(hipMemsetAsync(e->d_D, 0, d_elems * 8, e->st));
   HIPCHK(hipMemsetAsync(e->d_nanflag, 0, n_chunks * 8, e->st));
-  if (e->cfg.shard_world > 1) HIPCHK(hipMemsetAsync(d_sum, 0, (uint64_t)n_mat * n_pairs * sizeof(double), e->st));
-  if (e->cfg.shard_world > 1 || e->cfg.pairwise_del)  // k_count adds with integer atomics
-    HIPCHK(hipMemsetAsync(d_cnt, 0, (uint64_t)n_mat * n_pairs * sizeof(unsigned long long), e->st));
+  if ((rc = zero_outputs(e, n_mat, d_sum, d_cnt, e->cfg.pairwise_del))) return rc;
   HIPCHK(hipEventRecord(e->ev[1], e->st));
   uint64_t units_done = 0;
   for (uint64_t c = 0; c < n_chunks; c++) {
@@ -685,9 +710,8 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     uint64_t ks = std::max<uint64_t>(1, std::min<uint64_t>((8192 + e->n_tiles64 - 1) / e->n_tiles64, len / 8));
     const uint64_t sps = ((len + ks - 1) / ks + q - 1) / q * q;
     ks = (len + sps - 1) / sps;
-    ngd_launch_accum_em_table_spill(e->st, g, e->PA, s_lo, s_hi, e->sc, e->cfg.pairwise_del, e->d_tiles64, e->n_tiles64,
-                                    (uint32_t)ks, sps, q, e->d_rowpg, (uint32_t)n_pg, C, e->d_emcnt, e->d_nanflag + c,
-                                    note ? e->d_note.get() : nullptr);
+    ngd_launch_accum_em_table_spill(e->st, emt_common(e), s_lo, s_hi, (uint32_t)ks, sps, q, e->d_rowpg, (uint32_t)n_pg, C,
+                                    e->d_nanflag + c, note ? e->d_note.get() : nullptr);
     HIPCHK(hipEventRecord(ev[2], e->st));
     ngd_launch_spill_sanitize(e->st, C, e->d_nanflag + c, n_kg, (uint32_t)n_pg, e->d_M, n_mat, lead ? 1 : 0, s_lo, q,
                               g.n_sites, n_eff, n_blocks, block_size, e->d_D);
@@ -709,19 +733,10 @@ static int em_spill_impl(ngd_engine *e, const uint32_t *mult, const uint32_t *mu
     ngd_launch_fill_cnt(e->st, g, e->d_tiles, e->n_tiles, 0, e->d_drawn, n_mat, d_cnt);
   }
   for (uint32_t r = 0; r < n_mat && e->cfg.pairwise_del; r++) {
-    unsigned long long *cnt_r = d_cnt + (uint64_t)r * n_pairs;
     const bool is_lead = lead && r == 0;
     const uint32_t qr = r - (lead ? 1u : 0u);
-    if (is_lead) {
-      ngd_launch_count(e->st, g, e->mask, e->planes, 0, e->d_tiles, e->n_tiles, cnt_r);
-    } else {
-      uint32_t n_planes = 0;
-      while (n_planes < 32 && (mult_max[qr] >> n_planes)) n_planes++;
-      if (!n_planes) n_planes = 1;  // (as in pass_impl: a replicate that drew none of these blocks counts 0 sites)
-      ngd_launch_weights(e->st, n_blocks, block_size, g.n_sites_pad, e->d_M + (uint64_t)qr * n_blocks, e->d_ws, nullptr);
-      ngd_launch_planes(e->st, e->d_ws, g.n_sites, g.n_words, n_planes, e->planes);
-      ngd_launch_count(e->st, g, e->mask, e->planes, n_planes, e->d_tiles, e->n_tiles, cnt_r);
-    }
+    count_matrix(e, is_lead ? nullptr : e->d_M + (uint64_t)qr * n_blocks, is_lead ? 0 : mult_max[qr], n_blocks, block_size,
+                 d_cnt + (uint64_t)r * n_pairs);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev[4], e->st));

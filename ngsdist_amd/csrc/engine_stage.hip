@@ -61,11 +61,14 @@ void launch_plain_slices(ngd_engine *e, hipStream_t st, uint32_t ks0, uint32_t n
   if (e->kernel == NGD_KERNEL_EM_TABLE) {
     // beside a load ONE workgroup per CU (12 KB more LDS than its tables need): the chip is not full of workgroups that
     // last tens of milliseconds when the next piece's preparation kernel wants wave slots and registers
-    ngd_launch_accum_em_table_slices(st, g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64, ks0, n,
-                                     e->per_slice, e->slab, e->d_emcnt, beside_a_load ? 12u << 10 : 0u);
+    ngd_launch_accum_em_table_slices(st, emt_common(e), ks0, n, e->per_slice, e->slab, beside_a_load ? 12u << 10 : 0u);
   } else {
-    ngd_launch_accum_mfma(st, g, e->PA, e->congruent ? e->PA : e->QB, e->congruent ? e->d_wD : nullptr, nullptr, e->d_jobs, e->n_wg,
-                          e->exact_shapes, e->wg_waves, n, e->per_slice, g.n_kg, 0, 0, e->slab, e->d_clk, ks0);
+    ngd_mfma_launch l;
+    l.PA = e->PA; l.QB = e->congruent ? e->PA : e->QB;
+    l.d_wk = e->congruent ? e->d_wD : nullptr;
+    l.ks0 = ks0; l.n_ks = n; l.kg_per_slice = e->per_slice; l.n_kg_eff = g.n_kg;
+    l.slab = e->slab;
+    ngd_launch_accum_mfma(st, mfma_engine(e), l);
   }
 }
 

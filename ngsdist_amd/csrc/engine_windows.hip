@@ -394,11 +394,16 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
     HIPCHK(hipEventRecord(e->ev[1], e->st));
     if (em)
-      ngd_launch_accum_em_table_segs(e->st, g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64,
-                                     (uint32_t)n_seg, e->d_segtab, seg_sums, e->d_emcnt);
-    else
-      ngd_launch_accum_mfma(e->st, g, e->PA, e->congruent ? e->PA : e->QB, e->blk.wslice, nullptr, e->d_jobs, e->n_wg, e->exact_shapes,
-                            e->wg_waves, (uint32_t)n_ks, 0, g.n_kg, 0, 1, seg_sums, e->d_clk, 0, 0, e->d_segtab);
+      ngd_launch_accum_em_table_segs(e->st, emt_common(e), (uint32_t)n_seg, e->d_segtab, seg_sums);
+    else {
+      ngd_mfma_launch l;
+      l.PA = e->PA; l.QB = e->congruent ? e->PA : e->QB;
+      // every slice's own weights, at the offset its entry of the table names, with its k-group range
+      l.d_wk = e->blk.wslice; l.w_slice_stride = 1; l.d_seg = e->d_segtab;
+      l.n_ks = (uint32_t)n_ks; l.n_kg_eff = g.n_kg;
+      l.slab = seg_sums;
+      ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[2], e->st));
     double *bs = d_sum + a * n_mat * n_pairs;

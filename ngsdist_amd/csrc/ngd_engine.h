@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "kg_ranges.h"
 #include "ngd_buffers.h"
 #include "ngd_internal.h"
 #include "ngd_shard.h"
@@ -225,6 +226,14 @@ struct ngd_engine : ngd_mem {
   std::vector<ngd_em_exact_entry> exact_entries;  // of the last plain pass, sorted
 };
 
+// what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
+inline ngd_mfma_engine mfma_engine(const ngd_engine *e) {
+  return ngd_mfma_engine{e->g, e->d_jobs, e->n_wg, e->exact_shapes, e->wg_waves, e->d_clk};
+}
+inline ngd_emt_common emt_common(const ngd_engine *e) {
+  return ngd_emt_common{e->g, e->PA, e->sc, e->cfg.pairwise_del, e->em_shape, e->d_tiles64, e->n_tiles64, e->d_emcnt};
+}
+
 // The operand images and slabs (a GiB and more): an address range reserved at once, physical pieces of 256 MiB created,
 // mapped and zeroed behind it by a thread of the engine's own, in the order a load needs them.
 // [measured, round 6, tools/alloc_cost.hip, rocprofv3 --hip-trace of the C++ host, gpurun_out/r6/e2e_4.jsonl] On a box whose
@@ -275,7 +284,6 @@ int piece_start(ngd_engine *e);
 int piece_join(ngd_engine *e);
 int piece_wait_sites(ngd_engine *e, uint64_t s_end);
 // engine_create.hip
-uint64_t qb_piece(uint64_t kg_lim, uint32_t n_ks, uint64_t span, uint64_t *n_ranges);
 int spill_slot_map(ngd_engine *e, const std::vector<ngd_tile> &tiles64);  // d_rowpg, n_pg_spill, n_pg_live
 // engine_stage.hip
 void stage_reap(ngd_engine *e);

@@ -143,18 +143,33 @@ void ngd_launch_seg_weights(hipStream_t st, const uint64_t *d_seg, uint32_t n_se
                             double *d_W);
 
 // accum_mfma.hip : FP64 MFMA tiles, split over site slices into slabs
-// d_wk / d_kgl: bootstrap weights per contraction index and the list of k-groups to visit; with a list,
-// kg_per_slice and n_kg_eff count LIST entries.  k_per_slice != 0: slices are k_per_slice contraction indices
-// (not whole k-groups) and d_wk holds w_slice_stride k-groups of 0/1 weights PER SLICE (ngd_launch_slice_weights).
-void ngd_launch_accum_mfma(hipStream_t st, const ngd_geom &g, const double *PA, const double *QB,
-                           const double *d_wk, const uint32_t *d_kgl, const ngd_job *d_jobs, uint32_t n_wg,
-                           int exact_shapes, uint32_t wg_waves, uint32_t n_ks, uint64_t kg_per_slice, uint64_t n_kg_eff,
-                           uint64_t k_per_slice, uint32_t w_slice_stride, double *slab,
-                           unsigned long long *d_clk /* [2] or NULL: shader-cycle / constant-rate counter deltas of one wavefront */,
-                           uint32_t ks0 = 0 /* the launch covers slices ks0 .. ks0 + n_ks - 1 (multiples of 8) */,
-                           uint32_t resume = 0 /* 1: every block continues from its plane of the slab (a pass in ranges) */,
-                           const uint64_t *d_seg = nullptr /* slice table [n_ks][NGD_SEG_STRIDE] (windows): each slice's own   */
-                                                           /* k-group range and weight offset; needs d_ws and w_slice_stride != 0 */);
+// what ngd_create() fixes for the engine's lifetime
+struct ngd_mfma_engine {
+  const ngd_geom &g;
+  const ngd_job *d_jobs;
+  uint32_t n_wg;
+  int exact_shapes;  // 3: n_wg = 1 workgroup of wg_waves wavefronts per slice
+  uint32_t wg_waves;
+  unsigned long long *d_clk;  // [2] or NULL: shader-cycle / constant-rate counter deltas of one wavefront
+};
+// one launch; what it does not set is off
+struct ngd_mfma_launch {
+  const double *PA = nullptr, *QB = nullptr;  // the two operand images
+  // d_wk / d_kgl: bootstrap weights per contraction index and the list of k-groups to visit; with a list,
+  // kg_per_slice and n_kg_eff count LIST entries.  k_per_slice != 0: slices are k_per_slice contraction indices
+  // (not whole k-groups) and d_wk holds w_slice_stride k-groups of 0/1 weights PER SLICE (ngd_launch_slice_weights).
+  const double *d_wk = nullptr;
+  const uint32_t *d_kgl = nullptr;
+  uint32_t n_ks = 0;
+  uint64_t kg_per_slice = 0, n_kg_eff = 0, k_per_slice = 0;
+  uint32_t w_slice_stride = 0;
+  double *slab = nullptr;
+  uint32_t ks0 = 0;     // the launch covers slices ks0 .. ks0 + n_ks - 1 (multiples of 8)
+  uint32_t resume = 0;  // 1: every block continues from its plane of the slab (a pass in ranges)
+  // slice table [n_ks][NGD_SEG_STRIDE] (windows): each slice's own k-group range and weight offset; needs d_wk and w_slice_stride != 0
+  const uint64_t *d_seg = nullptr;
+};
+void ngd_launch_accum_mfma(hipStream_t st, const ngd_mfma_engine &en, const ngd_mfma_launch &l);
 
 // accum_em.hip : per-site EM, one thread per pair of a 16x16 tile
 void ngd_launch_accum_em(hipStream_t st, const ngd_geom &g, const double *PA, const uint32_t *d_ws,
@@ -163,10 +178,18 @@ void ngd_launch_accum_em(hipStream_t st, const ngd_geom &g, const double *PA, co
                          uint64_t sites_per_slice, double *slab);
 
 // accum_em_table.hip : per-site EM with per-individual tables shared by a 64 x 64 tile of pairs
-void ngd_launch_accum_em_table(hipStream_t st, const ngd_geom &g, const double *PA, const uint32_t *d_ws,
-                               uint64_t n_sites_eff, const ngd_score &score, int pairwise_del, int shape,
-                               const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice,
-                               double *slab, unsigned long long *d_counters /* [4]: += (tile, site) visits, table rounds; [2..3] = clock counters */);
+// what every launcher of the file is handed (`shape`: the batch and spilled-terms forms have one of their own)
+struct ngd_emt_common {
+  const ngd_geom &g;
+  const double *PA;
+  const ngd_score &score;
+  int pairwise_del, shape;
+  const ngd_tile *d_tiles64;
+  uint32_t n_tiles64;
+  unsigned long long *d_counters;  // [4]: += (tile, site) visits, table rounds; [2..3] = clock counters
+};
+void ngd_launch_accum_em_table(hipStream_t st, const ngd_emt_common &c, const uint32_t *d_ws, uint64_t n_sites_eff, uint32_t n_ks,
+                               uint64_t sites_per_slice, double *slab);
 
 // NGD_OPT_EM_EXACT: the noting form of the plain pass.  The rows' thresholds are widened by (1 + NGD_EM_EXACT_BETA), so
 // that no step before the one a pair stops at can be the reference's stopping step; a stop whose criterion is not below
@@ -178,9 +201,7 @@ void ngd_launch_accum_em_table(hipStream_t st, const ngd_geom &g, const double *
 #define NGD_EM_EXACT_BETA 0x1p-36
 #define NGD_NOTE_HEAD 4
 #define NGD_NOTE_WORDS 4
-void ngd_launch_accum_em_table_note(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score,
-                                    int pairwise_del, int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks,
-                                    uint64_t sites_per_slice, double *slab, unsigned long long *d_counters,
+void ngd_launch_accum_em_table_note(hipStream_t st, const ngd_emt_common &c, uint32_t n_ks, uint64_t sites_per_slice, double *slab,
                                     unsigned long long *d_note);
 // layout.hip: the six likelihoods of every noted (pair, site) out of the image: gl[6 e ..] = GL_i1[0..2], GL_i2[0..2]
 void ngd_launch_note_gather(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_tile *d_tiles64, uint32_t n_tiles64,
@@ -205,24 +226,19 @@ void ngd_launch_note_patch_w(hipStream_t st, const unsigned long long *d_pair, c
 
 // accum_em_table.hip, windows along the genome: slice ks = sites [s_lo, s_hi) of entry ks of the slice table (NGD_SEG_SLO /
 // NGD_SEG_SHI; any length from 1, any first site, all below g.n_sites), slab [n_seg][n_pad][n_pad]; every `shape` has the form
-void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,
-                                    int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_seg,
-                                    const uint64_t *d_seg, double *slab, unsigned long long *d_counters);
+void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_emt_common &c, uint32_t n_seg, const uint64_t *d_seg, double *slab);
 
 // accum_em_table.hip, rb (4 or 8) matrices in one pass: d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]
-void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_geom &g, const double *PA, const double *d_Wb, int rb,
-                                     uint64_t n_sites_eff, const ngd_score &score, int pairwise_del,
-                                     const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t n_ks,
-                                     uint64_t sites_per_slice, double *slab, unsigned long long *d_counters);
+void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_emt_common &c, const double *d_Wb, int rb, uint64_t n_sites_eff,
+                                     uint32_t n_ks, uint64_t sites_per_slice, double *slab);
 
 // accum_em_table.hip, terms not summed over the slice: sites [s_lo, s_hi) in units of q consecutive sites (one term per
 // pair slot and unit) into C (fragment-major: k-groups of 4 units x n_pg groups of 16 pair slots; d_rowpg[tile * 64 + row] + g =
-// slot group of the row's group g of 16 columns, for the groups that hold a pair); *d_nanflag = 1 if a term was not finite
-void ngd_launch_accum_em_table_spill(hipStream_t st, const ngd_geom &g, const double *PA, uint64_t s_lo, uint64_t s_hi,
-                                     const ngd_score &score, int pairwise_del, const ngd_tile *d_tiles64,
-                                     uint32_t n_tiles64, uint32_t n_ks, uint64_t sites_per_slice, uint32_t q,
-                                     const uint32_t *d_rowpg, uint32_t n_pg, double *C, unsigned long long *d_counters,
-                                     unsigned long long *d_nanflag, unsigned long long *d_note = nullptr);
+// slot group of the row's group g of 16 columns, for the groups that hold a pair); *d_nanflag = 1 if a term was not finite;
+// d_note != NULL: the noting form
+void ngd_launch_accum_em_table_spill(hipStream_t st, const ngd_emt_common &c, uint64_t s_lo, uint64_t s_hi, uint32_t n_ks,
+                                     uint64_t sites_per_slice, uint32_t q, const uint32_t *d_rowpg, uint32_t n_pg, double *C,
+                                     unsigned long long *d_nanflag, unsigned long long *d_note);
 
 // contract_mfma.hip : running sums D[matrix][pair slot] += W[matrix][unit] * C[unit][pair slot] over a chunk of sites
 // (a unit = q consecutive sites of one bootstrap block; site s_lo is the first site of the chunk's unit 0)
@@ -239,10 +255,10 @@ void ngd_launch_contract(hipStream_t st, const double *d_Wt, const double *C, ui
 void ngd_launch_spill_scatter(hipStream_t st, const double *D, uint32_t n_pg, const ngd_tile *d_tiles64, uint32_t n_tiles64,
                               const uint32_t *d_rowpg, uint64_t n_ind, uint32_t n_mat, double *d_sum);
 
-// rb (4, 8 or 16) replicates in one pass; d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]
-void ngd_launch_accum_em_table_slices(hipStream_t st, const ngd_geom &g, const double *PA, const ngd_score &score, int pairwise_del,
-                                      int shape, const ngd_tile *d_tiles64, uint32_t n_tiles64, uint32_t ks0, uint32_t n_sub,
-                                      uint64_t sites_per_slice, double *slab, unsigned long long *d_counters, uint32_t lds_pad);
+// accum_em_table.hip: slices ks0 .. ks0 + n_sub - 1 of a plain pass on their own, lds_pad more bytes of LDS per workgroup
+void ngd_launch_accum_em_table_slices(hipStream_t st, const ngd_emt_common &c, uint32_t ks0, uint32_t n_sub, uint64_t sites_per_slice,
+                                      double *slab, uint32_t lds_pad);
+// accum_em.hip: rb (4, 8 or 16) replicates in one pass; d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]
 void ngd_launch_accum_em_batch(hipStream_t st, const ngd_geom &g, const double *PA, const double *d_Wb, int rb,
                                uint64_t n_sites_eff, const ngd_score &score, int pairwise_del, int fast,
                                const ngd_tile *d_tiles16, uint32_t n_tiles16, uint32_t n_ks,

@@ -624,7 +624,7 @@ def test_mfma_exact_block_forms(n_ind, form):
 @pytest.mark.parametrize("n_ind,form", [(64, 0), (200, 0), (200, 2), (600, 0), (130, 1)])
 @pytest.mark.parametrize("scratch_bytes,resident", [(0, 0), (1, 0), (1, 6 << 20)])
 def test_mfma_single_image_engine(n_ind, form, scratch_bytes, resident):
-    """ngd_config.single_image (engine_plans.hip launch_accumulate): only p is resident, q = score . p is formed for a range of
+    """ngd_config.single_image (engine_plans.hip accumulate_single_image): only p is resident, q = score . p is formed for a range of
     k-groups at a time (layout.hip k_qb_range, with emit()'s own arithmetic) while the kernel works the range before.
     Per-block partial sums (blocks of 8 sites and of 6: masked slices) walk ranges of whole slices: the bits of the engine
     that holds both images.  A whole pass gives every slice a piece of every range (a block adds to its plane of the
