@@ -2,7 +2,6 @@
 // jobs that draw bootstrap replicates inside every window.
 #include <functional>
 #include <numeric>
-#include <iterator>
 
 #include "ngd_engine.h"
 
@@ -32,11 +31,7 @@
 //  * per window: one run_impl() per window on multiplicity vectors over blocks of gcd(lo, q, hi) sites counted from the
 //    engine's site 0 -- vector 0 is 1 on the window's sites, vector r the multiplicities of replicate r.  Serves every
 //    kernel, windows that do not fit the budget, and blocks so small that a slice per block loses.
-struct WinBoot {
-  uint32_t n_rep;
-  uint64_t n_blocks, q;
-  const uint32_t *mult;  // [n_rep][n_blocks]: draws of block b in replicate r
-};
+// What a slab plan tells the device -- the batches, their slices and tables -- is host arithmetic of its own: win_plan.h.
 
 static int windows_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const char *who) {
   if (!e) return fail(NGD_E_INVALID, std::string(who) + ": null engine");
@@ -240,230 +235,162 @@ static bool windows_slab_applies(const ngd_engine *e) {
   return (e->kernel == NGD_KERNEL_MFMA && !e->single_image) || e->kernel == NGD_KERNEL_EM_TABLE;
 }
 
-// bytes of one batch of the segment-slab plan: partial results (slices padded to the XCD deal's eights), counts, slice
-// weights and tables.  The EM kernel: a plane per segment, counts, tables -- no k-group weights, no padding slices.
-// A job (bt != NULL): + every window's table of block starts and the replicates' weights (doubles; uint32 for the counts).
-static uint64_t windows_batch_bytes(const ngd_engine *e, uint64_t n_seg, uint64_t span, uint64_t n_win, const WinBoot *bt = nullptr) {
-  const uint64_t plane = (uint64_t)e->g.n_pad * e->g.n_pad, n_ks = (n_seg + 7) / 8 * 8;
-  uint64_t job = 0;
-  if (bt) {
-    const uint64_t rb = ngd_reduce_chunk(bt->n_rep), stride = (bt->n_rep + rb - 1) / rb * rb;
-    job = n_win * (bt->n_blocks + 1) * 4 + bt->n_blocks * stride * (e->cfg.pairwise_del ? 12 : 8);
-  }
-  if (e->kernel == NGD_KERNEL_EM_TABLE)
-    return n_seg * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + n_seg * NGD_SEG_STRIDE * 8 + n_win * 16 + job;
-  const uint64_t wkg = 3 * span / 4 + n_ks * (3 + NGD_KG_TAIL) + 1 + NGD_KG_TAIL;
-  return n_ks * plane * 8 + (e->cfg.pairwise_del ? n_seg * plane * 4 : 0) + wkg * 32 + n_ks * NGD_SEG_STRIDE * 8 + n_win * 16 + job;
+// what the planner (win_plan.h) needs of the engine
+static win_env windows_env(const ngd_engine *e, const WinBoot *bt) {
+  return win_env{(uint64_t)e->g.n_pad * e->g.n_pad, e->kernel == NGD_KERNEL_EM_TABLE, e->cfg.pairwise_del != 0, e->n_ks,
+                 NGD_KG_TAIL, bt ? ngd_reduce_chunk(bt->n_rep) : 1};
 }
 
-// the segment-slab plan; *fits = false (nothing launched): some window alone does not fit the budget
+// a job's weights, the same for every window: Wt[b][r] (zero padded to whole chunks of replicates), as integers for the counts
+static int windows_job_weights(ngd_engine *e, const WinBoot &bt, uint32_t stride) {
+  std::vector<double> Wt(bt.n_blocks * stride, 0.0);
+  for (uint32_t r = 0; r < bt.n_rep; r++)
+    for (uint64_t b = 0; b < bt.n_blocks; b++) Wt[b * stride + r] = (double)bt.mult[(uint64_t)r * bt.n_blocks + b];
+  int rc = e->d_W.ensure(e, Wt.size());
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(e->d_W, Wt.data(), Wt.size() * 8, hipMemcpyHostToDevice));
+  if (!e->cfg.pairwise_del) return NGD_OK;
+  std::vector<uint32_t> M(Wt.size());
+  for (size_t k = 0; k < M.size(); k++) M[k] = (uint32_t)Wt[k];
+  if ((rc = e->d_M.ensure(e, M.size()))) return rc;
+  HIPCHK(hipMemcpy(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice));
+  return NGD_OK;
+}
+
+// What every batch of one slab plan shares on the device: the plan of the batch at hand, the scratch its slices' partial
+// results take, the output's matrices per window; a job: the weights' stride and the replicates of bt.  The batch's
+// matrices go to bs / bc, which the helpers take beside it.
+struct SlabCall {
+  const win_batch &p;
+  const WinBoot *bt;
+  DevBuf<double> &seg_sums;
+  DevBuf<uint32_t> &seg_cnt;
+  ngd_fix_flags ff;
+  uint32_t n_mat, stride;
+  uint32_t nb() const { return (uint32_t)(p.b - p.a); }
+};
+
+// the batch's tables to the device and its ONE accumulation pass: events 0 .. 2
+static int slab_accumulate(ngd_engine *e, const SlabCall &B) {
+  const win_batch &p = B.p;
+  const bool em = e->kernel == NGD_KERNEL_EM_TABLE;
+  const uint64_t plane = (uint64_t)e->g.n_pad * e->g.n_pad;
+  int rc = B.seg_sums.ensure(e, p.n_ks * plane);
+  if (!rc && B.bt) rc = e->d_winblk.ensure(e, p.blk.size());
+  if (!rc && e->cfg.pairwise_del) rc = B.seg_cnt.ensure(e, p.n_seg * plane);
+  if (!rc && !em) rc = e->blk.wslice.ensure(e, p.w_total * 4);
+  if (!rc) rc = e->d_segtab.ensure(e, p.tab.size());
+  if (!rc) rc = e->d_wintab.ensure(e, p.wt.size());
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(e->ev[0], e->st));
+  HIPCHK(hipMemcpyAsync(e->d_segtab, p.tab.data(), p.tab.size() * 8, hipMemcpyHostToDevice, e->st));
+  HIPCHK(hipMemcpyAsync(e->d_wintab, p.wt.data(), p.wt.size() * 8, hipMemcpyHostToDevice, e->st));
+  if (B.bt) HIPCHK(hipMemcpyAsync(e->d_winblk, p.blk.data(), p.blk.size() * 4, hipMemcpyHostToDevice, e->st));
+  if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)p.n_ks, p.max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
+  HIPCHK(hipEventRecord(e->ev[1], e->st));
+  if (em)
+    ngd_launch_accum_em_table_segs(e->st, emt_common(e), (uint32_t)p.n_seg, e->d_segtab, B.seg_sums);
+  else {
+    ngd_mfma_launch l;
+    l.PA = e->PA; l.QB = e->congruent ? e->PA : e->QB;
+    // every slice's own weights, at the offset its entry of the table names, with its k-group range
+    l.d_wk = e->blk.wslice; l.w_slice_stride = 1; l.d_seg = e->d_segtab;
+    l.n_ks = (uint32_t)p.n_ks; l.n_kg_eff = e->g.n_kg;
+    l.slab = B.seg_sums;
+    ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e->ev[2], e->st));
+  return NGD_OK;
+}
+
+// the slices' sums into the windows' matrices: the banded reduction; a job's replicates by the banded and weighted one
+// (a job: window w's full-data matrix is matrix w (n_rep + 1) of the output, its replicates follow it; matrix 0 is NOT
+// reduced from these slices -- windows_job_slab has filled it from the windows' own segments).  first: the launch that
+// also writes the counts without --pairwise_del and notes the pairs that want the fix-up
+static void slab_reduce_sums(ngd_engine *e, const SlabCall &B, double *bs, unsigned long long *bc, bool first) {
+  const bool pdel = e->cfg.pairwise_del != 0;
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
+  const ngd_fix_flags *ff = first && e->SM && !pdel ? &B.ff : nullptr;
+  if (!B.bt)
+    ngd_launch_reduce_band(e->st, e->g, B.seg_sums, nullptr, e->d_wintab, B.nb(), e->d_tiles, e->n_tiles, bs,
+                           first && !pdel ? bc : nullptr, ff, B.n_mat);
+  else {
+    const uint64_t n_vis = B.bt->n_blocks * B.bt->q;  // sites a replicate visits
+    ngd_launch_reduce_band_w(e->st, e->g, B.seg_sums, nullptr, e->d_winblk, B.nb(), (uint32_t)B.bt->n_blocks, e->d_W.get(), B.stride,
+                             B.bt->n_rep, B.n_mat, e->d_tiles, e->n_tiles, bs + n_pairs, first && !pdel ? bc + n_pairs : nullptr,
+                             n_vis, ff, NGD_FIX_MEAN * (double)n_vis);
+  }
+  e->win_info.band_launches++;
+}
+
+// --pairwise_del: the slices' popcounts into the windows' counts by the integer forms of both reductions; then the pairs
+// that want the fix-up noted from sums and counts
+static void slab_counts(ngd_engine *e, const SlabCall &B, double *bs, unsigned long long *bc) {
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
+  ngd_launch_count_blocks(e->st, e->g, e->mask, 0, (uint32_t)B.p.n_seg, e->d_tiles16, e->n_tiles16, B.seg_cnt, e->d_segtab);
+  if (!B.bt)
+    ngd_launch_reduce_band(e->st, e->g, nullptr, B.seg_cnt, e->d_wintab, B.nb(), e->d_tiles, e->n_tiles, nullptr, bc, nullptr, B.n_mat);
+  else
+    ngd_launch_reduce_band_w(e->st, e->g, nullptr, B.seg_cnt, e->d_winblk, B.nb(), (uint32_t)B.bt->n_blocks, e->d_M.get(), B.stride,
+                             B.bt->n_rep, B.n_mat, e->d_tiles, e->n_tiles, nullptr, bc + n_pairs, 0, nullptr, 0.0);
+  e->win_info.band_launches++;
+  if (!e->SM) return;
+  // (a job: over every matrix of the batch -- the windows' matrices 0 are in place already and hold their final sums)
+  if (B.bt) ngd_launch_fix_flag(e->st, e->g, bs, bc, B.nb() * B.n_mat, e->d_tiles, e->n_tiles, B.ff);
+  else ngd_launch_fix_flag(e->st, e->g, bs, bc, B.nb(), e->d_tiles, e->n_tiles, B.ff, B.n_mat);
+}
+
+// the segment-slab plan, batch by batch (win_plan.h); *fits = false (nothing launched): some window alone does not fit the budget
 // bt != NULL: the unit slab of a job, outputs [n_win][n_rep + 1][n_pairs] -- the replicates alone, matrix 0 is not written;
 // else window w's matrix is matrix w * out_stride of the outputs (a job's matrices 0: windows_job_slab)
 static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
                         unsigned long long *d_cnt, uint64_t budget, bool *fits, const WinBoot *bt = nullptr,
                         uint64_t out_stride = 1) {
-  const ngd_geom &g = e->g;
-  const uint64_t n_pairs = ngd_n_pairs(g.n_ind), plane = (uint64_t)g.n_pad * g.n_pad;
-  const bool pdel = e->cfg.pairwise_del != 0;
-  const bool fix = e->SM != nullptr;
-  const bool em = e->kernel == NGD_KERNEL_EM_TABLE;
+  const win_env v = windows_env(e, bt);
+  if (!(*fits = win_each_fits(v, lo, hi, n_win, bt, budget))) return NGD_OK;
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
+  const bool pdel = v.pdel, fix = e->SM != nullptr;
   const uint64_t n_mat = bt ? (uint64_t)bt->n_rep + 1 : out_stride;  // matrices of the output per window
-  *fits = true;
-  for (uint64_t w = 0; w < n_win; w++)
-    if (windows_batch_bytes(e, bt ? bt->n_blocks + 1 : 1, hi[w] - lo[w], 1, bt) > budget) {
-      *fits = false;
-      return NGD_OK;
-    }
-  // the boundaries a window brings to its batch, ascending: its ends, and in a job the starts of its blocks
-  std::vector<uint64_t> wb, merged;
-  auto win_bnd = [&](uint64_t w) {
-    wb.clear();
-    wb.push_back(lo[w]);
-    for (uint64_t b = 1; bt && b <= bt->n_blocks; b++) wb.push_back(lo[w] + b * bt->q);
-    if (wb.back() != hi[w]) wb.push_back(hi[w]);
-  };
-  // a job's weights, the same for every window: Wt[b][r] (zero padded to whole chunks of replicates), as integers for the counts
-  uint32_t stride = 0;
-  if (bt) {
-    const uint32_t rb = ngd_reduce_chunk(bt->n_rep);
-    stride = (bt->n_rep + rb - 1) / rb * rb;
-    std::vector<double> Wt(bt->n_blocks * stride, 0.0);
-    for (uint32_t r = 0; r < bt->n_rep; r++)
-      for (uint64_t b = 0; b < bt->n_blocks; b++) Wt[b * stride + r] = (double)bt->mult[(uint64_t)r * bt->n_blocks + b];
-    int rc = e->d_W.ensure(e, Wt.size());
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(e->d_W, Wt.data(), Wt.size() * 8, hipMemcpyHostToDevice));
-    if (pdel) {
-      std::vector<uint32_t> M(Wt.size());
-      for (size_t k = 0; k < M.size(); k++) M[k] = (uint32_t)Wt[k];
-      if ((rc = e->d_M.ensure(e, M.size()))) return rc;
-      HIPCHK(hipMemcpy(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice));
-    }
-  }
+  const uint32_t stride = bt ? win_weight_stride(v, *bt) : 0;
+  int rc = bt ? windows_job_weights(e, *bt, stride) : NGD_OK;
+  if (rc) return rc;
   // (the windowed call takes the scratch of the bootstrap's per-block partial results: their cache is dropped)
-  DevBuf<double> &seg_sums = e->blk.borrow_sums();
-  DevBuf<uint32_t> &seg_cnt = e->blk.borrow_counts();
-  const ngd_fix_flags ff{e->d_fixlist, e->d_fixcount, e->d_fixseen, e->fix_cap};
+  win_batch p;
+  const SlabCall B{p, bt, e->blk.borrow_sums(), e->blk.borrow_counts(),
+                   ngd_fix_flags{e->d_fixlist, e->d_fixcount, e->d_fixseen, e->fix_cap}, (uint32_t)n_mat, stride};
   uint64_t batch = 0;
-  for (uint64_t a = 0; a < n_win; batch++) {
-    // the batch: windows a .. b-1, as many as fit the budget (its segments bounded by its distinct boundaries - 1)
-    std::vector<uint64_t> x;  // the batch's boundaries, ascending: one merge of two sorted lists per window
-    uint64_t b = a, hi_max = 0;
-    while (b < n_win) {
-      win_bnd(b);
-      merged.clear();
-      std::set_union(x.begin(), x.end(), wb.begin(), wb.end(), std::back_inserter(merged));
-      const uint64_t n_seg_ub = merged.size() - 1, hm = std::max(hi_max, hi[b]);
-      if (b > a && (windows_batch_bytes(e, n_seg_ub, hm - lo[a], b + 1 - a, bt) > budget || n_seg_ub >= (1ull << 30))) break;
-      x.swap(merged);
-      hi_max = hm;
-      b++;
-    }
-    const uint64_t nb = b - a;
-    auto at = [&](uint64_t s) { return (uint64_t)(std::lower_bound(x.begin(), x.end(), s) - x.begin()); };
-    // interval k = [x[k], x[k + 1]) is a segment if some window of the batch covers it
-    std::vector<int64_t> cover(x.size(), 0);
-    for (uint64_t w = a; w < b; w++) { cover[at(lo[w])]++; cover[at(hi[w])]--; }
-    // EM kernel: an interval's slices are pieces of at most `piece` sites -- the covered sites over the slices of a plain
-    // pass, 64 sites or more (ngd_create's bound) -- unless the planes of the pieces would not fit the budget
-    uint64_t piece = ~0ull;
-    if (em) {
-      uint64_t covered = 0, n_cov = 0, n_cut = 0;
-      int64_t run = 0;
-      for (uint64_t k = 0; k + 1 < x.size(); k++)
-        if ((run += cover[k]) > 0) { covered += x[k + 1] - x[k]; n_cov++; }
-      piece = std::max<uint64_t>(64, (covered + e->n_ks - 1) / std::max<uint32_t>(1, e->n_ks));
-      run = 0;
-      for (uint64_t k = 0; k + 1 < x.size(); k++)
-        if ((run += cover[k]) > 0) n_cut += (x[k + 1] - x[k] - 1) / piece + 1;
-      if (n_cut > n_cov && (windows_batch_bytes(e, n_cut, hi_max - lo[a], nb, bt) > budget || n_cut >= (1ull << 30))) piece = ~0ull;
-    }
-    std::vector<uint32_t> seg_of(x.size(), 0), seg_end(x.size(), 0);  // interval k = slices [seg_of[k], seg_end[k])
-    std::vector<uint64_t> tab;
-    uint64_t n_seg = 0, wkg = 0, max_wkg = 0;
-    int64_t run = 0;
-    for (uint64_t k = 0; k + 1 < x.size(); k++) {
-      run += cover[k];
-      seg_of[k] = seg_end[k] = (uint32_t)n_seg;
-      if (run <= 0) continue;
-      if (em) {  // (the k-group entries are the MFMA kernel's: not read)
-        const uint64_t len = x[k + 1] - x[k], n_p = len <= piece ? 1 : (len - 1) / piece + 1, per = (len + n_p - 1) / n_p;
-        for (uint64_t s = x[k]; s < x[k + 1]; s += per, n_seg++) tab.insert(tab.end(), {0, 0, 0, s, std::min(s + per, x[k + 1])});
-      } else {
-        const uint64_t kg0 = 3 * x[k] / 4, kg1 = (3 * x[k + 1] + 3) / 4, n_wkg = kg1 - kg0 + 1 + NGD_KG_TAIL;
-        tab.insert(tab.end(), {kg0, kg1, wkg, x[k], x[k + 1]});
-        wkg += n_wkg;
-        max_wkg = std::max(max_wkg, n_wkg);
-        n_seg++;
-      }
-      seg_end[k] = (uint32_t)n_seg;
-    }
-    seg_of[x.size() - 1] = seg_end[x.size() - 1] = (uint32_t)n_seg;  // (the last boundary: where the slices end)
-    // (the XCD deal of accum_mfma.hip; padding slices have no k-group and no sites.  The EM launch needs none.)
-    const uint64_t n_ks = em ? n_seg : (n_seg + 7) / 8 * 8;
-    for (uint64_t q = n_seg; q < n_ks; q++) tab.insert(tab.end(), {0, 0, wkg, 0, 0});
-    const uint64_t w_total = wkg + 1 + NGD_KG_TAIL;
-    std::vector<unsigned long long> wt(2 * nb);
-    for (uint64_t w = a; w < b; w++) {
-      const uint64_t f = seg_of[at(lo[w])], l = seg_end[at(hi[w]) - 1];
-      wt[2 * (w - a)] = f | (l << 32);
-      wt[2 * (w - a) + 1] = hi[w] - lo[w];
-    }
-    std::vector<uint32_t> blk;  // a job: the first slice of each block of each window, and the end of its last block
-    if (bt) {
-      blk.resize(nb * (bt->n_blocks + 1));
-      for (uint64_t w = a; w < b; w++) {
-        uint64_t i = at(lo[w]);  // (the window's block starts ascend: one walk along the boundaries)
-        for (uint64_t k = 0; k <= bt->n_blocks; k++) {
-          while (x[i] < lo[w] + k * bt->q) i++;
-          blk[(w - a) * (bt->n_blocks + 1) + k] = seg_of[i];
-        }
-      }
-    }
-    int rc = seg_sums.ensure(e, n_ks * plane);
-    if (!rc && bt) rc = e->d_winblk.ensure(e, blk.size());
-    if (!rc && pdel) rc = seg_cnt.ensure(e, n_seg * plane);
-    if (!rc && !em) rc = e->blk.wslice.ensure(e, w_total * 4);
-    if (!rc) rc = e->d_segtab.ensure(e, tab.size());
-    if (!rc) rc = e->d_wintab.ensure(e, wt.size());
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(e->ev[0], e->st));
-    HIPCHK(hipMemcpyAsync(e->d_segtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, e->st));
-    HIPCHK(hipMemcpyAsync(e->d_wintab, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, e->st));
-    if (bt) HIPCHK(hipMemcpyAsync(e->d_winblk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, e->st));
-    if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)n_ks, max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
-    HIPCHK(hipEventRecord(e->ev[1], e->st));
-    if (em)
-      ngd_launch_accum_em_table_segs(e->st, emt_common(e), (uint32_t)n_seg, e->d_segtab, seg_sums);
-    else {
-      ngd_mfma_launch l;
-      l.PA = e->PA; l.QB = e->congruent ? e->PA : e->QB;
-      // every slice's own weights, at the offset its entry of the table names, with its k-group range
-      l.d_wk = e->blk.wslice; l.w_slice_stride = 1; l.d_seg = e->d_segtab;
-      l.n_ks = (uint32_t)n_ks; l.n_kg_eff = g.n_kg;
-      l.slab = seg_sums;
-      ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[2], e->st));
+  for (uint64_t a = 0; a < n_win; a = p.b, batch++) {
+    win_plan_batch(v, lo, hi, n_win, a, budget, bt, p);
     double *bs = d_sum + a * n_mat * n_pairs;
     unsigned long long *bc = d_cnt + a * n_mat * n_pairs;
+    if ((rc = slab_accumulate(e, B))) return rc;
     if (fix) {
       HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
       HIPCHK(hipMemsetAsync(e->d_fixseen, 0, (n_pairs / 32 + 1) * sizeof(uint32_t), e->st));
     }
-    // (a job: window w's full-data matrix is matrix w (n_rep + 1) of the output, its replicates follow it)
-    const uint32_t n_blk = bt ? (uint32_t)bt->n_blocks : 0, n_rep = bt ? bt->n_rep : 0;
-    const uint64_t n_vis = bt ? bt->n_blocks * bt->q : 0;  // sites a replicate visits
-    // (a job's matrix 0 is NOT reduced from these slices: windows_job_slab has filled it from the windows' own segments)
-    auto reduce_sums = [&](bool first) {
-      if (!bt) {
-        ngd_launch_reduce_band(e->st, g, seg_sums, nullptr, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, bs,
-                               first && !pdel ? bc : nullptr, first && fix && !pdel ? &ff : nullptr, (uint32_t)n_mat);
-        e->win_info.band_launches++;
-      } else {
-        ngd_launch_reduce_band_w(e->st, g, seg_sums, nullptr, e->d_winblk, (uint32_t)nb, n_blk, e->d_W.get(), stride, n_rep,
-                                 (uint32_t)n_mat, e->d_tiles, e->n_tiles, bs + n_pairs, first && !pdel ? bc + n_pairs : nullptr,
-                                 n_vis, first && fix && !pdel ? &ff : nullptr, NGD_FIX_MEAN * (double)n_vis);
-        e->win_info.band_launches++;
-      }
-    };
-    reduce_sums(true);
+    slab_reduce_sums(e, B, bs, bc, true);
     HIPCHK(hipEventRecord(e->ev[3], e->st));
-    if (pdel) {
-      ngd_launch_count_blocks(e->st, g, e->mask, 0, (uint32_t)n_seg, e->d_tiles16, e->n_tiles16, seg_cnt, e->d_segtab);
-      if (!bt) {
-        ngd_launch_reduce_band(e->st, g, nullptr, seg_cnt, e->d_wintab, (uint32_t)nb, e->d_tiles, e->n_tiles, nullptr, bc, nullptr,
-                               (uint32_t)n_mat);
-        e->win_info.band_launches++;
-      } else {
-        ngd_launch_reduce_band_w(e->st, g, nullptr, seg_cnt, e->d_winblk, (uint32_t)nb, n_blk, e->d_M.get(), stride, n_rep,
-                                 (uint32_t)n_mat, e->d_tiles, e->n_tiles, nullptr, bc + n_pairs, 0, nullptr, 0.0);
-        e->win_info.band_launches++;
-      }
-      // (a job: over every matrix of the batch -- the windows' matrices 0 are in place already and hold their final sums)
-      if (fix && bt) ngd_launch_fix_flag(e->st, g, bs, bc, (uint32_t)(nb * n_mat), e->d_tiles, e->n_tiles, ff);
-      if (fix && !bt) ngd_launch_fix_flag(e->st, g, bs, bc, (uint32_t)nb, e->d_tiles, e->n_tiles, ff, (uint32_t)n_mat);
-    }
+    if (pdel) slab_counts(e, B, bs, bc);
     if (fix) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[4], e->st));
-    HIPCHK(hipStreamSynchronize(e->st));  // (tab, wt are host temporaries)
-    read_timing(e, hi_max - lo[a], 1, batch > 0);
+    HIPCHK(hipStreamSynchronize(e->st));  // (the plan's tables are host memory)
+    read_timing(e, p.hi_max - lo[a], 1, batch > 0);
     if ((rc = mfma_fault(e))) return rc;
     float ms = 0;
     hipEventElapsedTime(&ms, e->ev[0], e->ev[4]);
     e->win_info.ms += ms;
-    e->win_info.segments += n_seg;
-    e->win_info.slab_bytes = std::max<uint64_t>(e->win_info.slab_bytes, n_ks * plane * 8 + (pdel ? n_seg * plane * 4 : 0));
+    e->win_info.segments += p.n_seg;
+    e->win_info.slab_bytes = std::max<uint64_t>(e->win_info.slab_bytes, (p.n_ks * 8 + (pdel ? p.n_seg * 4 : 0)) * v.plane);
     e->win_info.batches++;
-    if (fix && !bt && (rc = windows_fixup(e, lo + a, hi + a, nb, bs, n_mat))) return rc;
+    if (fix && !bt && (rc = windows_fixup(e, lo + a, hi + a, B.nb(), bs, n_mat))) return rc;
     if (fix && bt) {  // the noted pairs' slab entries exactly, then the weighted reductions of the batch again
       bool patched = false;
-      if ((rc = windows_job_fixup(e, tab, n_seg, seg_sums, nb * n_mat, &patched))) return rc;
+      if ((rc = windows_job_fixup(e, p.tab, p.n_seg, B.seg_sums, B.nb() * n_mat, &patched))) return rc;
       if (patched) {  // (timed like the recomputation: part of the fix-up and of the call)
         HIPCHK(hipEventRecord(e->ev[0], e->st));
-        reduce_sums(false);
+        slab_reduce_sums(e, B, bs, bc, false);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e->ev[1], e->st));
         HIPCHK(hipStreamSynchronize(e->st));
@@ -473,7 +400,6 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
         e->win_info.ms += ms2;
       }
     }
-    a = b;
   }
   return NGD_OK;
 }
@@ -485,12 +411,8 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
 // compared (windows_impl): a second pass over the covered sites and the banded reduction.
 static int windows_job_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
                             unsigned long long *d_cnt, uint64_t budget, bool *fits, const WinBoot *bt) {
-  *fits = true;
-  for (uint64_t w = 0; w < n_win; w++)  // (before anything is launched: the unit slab's own test)
-    if (windows_batch_bytes(e, bt->n_blocks + 1, hi[w] - lo[w], 1, bt) > budget) {
-      *fits = false;
-      return NGD_OK;
-    }
+  // (before anything is launched: the unit slab's own test)
+  if (!(*fits = win_each_fits(windows_env(e, bt), lo, hi, n_win, bt, budget))) return NGD_OK;
   bool fits0 = true;
   if (int rc = windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits0, nullptr, (uint64_t)bt->n_rep + 1)) return rc;
   if (!fits0) return fail(NGD_E_NOMEM, "ngd_run_windows_job: internal -- a window fits the unit slab and not its own segment");
@@ -521,10 +443,11 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     // window (~3/4 of a plain pass over its sites -- [measured] the EM kernel: 0.72, 37 windows of 10 000 sites in 1159 ms at
     // 1000 individuals, the sites before a window loaded and skipped -- + ~0.1 ms of launches and waits)
     uint64_t covered = 0, sum_len = 0, end = 0;
-    std::vector<uint64_t> bnd(lo, lo + n_win);
-    bnd.insert(bnd.end(), hi, hi + n_win);
-    for (uint64_t w = 0; bt && w < n_win; w++)  // (a job: + the starts of every window's blocks)
-      for (uint64_t b = 1; b <= bt->n_blocks; b++) bnd.push_back(lo[w] + b * bt->q);
+    std::vector<uint64_t> bnd, wb;  // (every window's boundaries: its ends, and in a job the starts of its blocks)
+    for (uint64_t w = 0; w < n_win; w++) {
+      win_boundaries(lo[w], hi[w], bt, wb);
+      bnd.insert(bnd.end(), wb.begin(), wb.end());
+    }
     std::sort(bnd.begin(), bnd.end());
     const uint64_t n_bnd = (uint64_t)(std::unique(bnd.begin(), bnd.end()) - bnd.begin());  // (segments < distinct boundaries)
     for (uint64_t w = 0; w < n_win; w++) {
@@ -536,7 +459,7 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     // 160 slices: 224.8 ms -- DESIGN.md section 6; the plain pass's 2.22e8)
     const double rate = em ? 2.22e8 : 1.05e10, np = (double)e->n_owned_pairs;
     const double plane_b = (double)e->g.n_pad * e->g.n_pad * 8;
-    const double need = (double)windows_batch_bytes(e, std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win, bt);
+    const double need = (double)win_batch_bytes(windows_env(e, bt), std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win, bt);
     const double have = (double)e->blk.bytes();
     if (!bt) {
       const double t_slab = np * (double)covered / rate + (double)(n_bnd + 2 * n_win) * np * 8 / 4e9 +
@@ -581,21 +504,21 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   return windows_by_pass(e, lo, hi, n_win, d_sum, d_cnt);
 }
 
-int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, void *d_sum,
-                           void *d_cnt) {
-  if (int rc = windows_check(e, win_lo, win_hi, n_win, "ngd_run_windows_device")) return rc;
-  if (!d_sum || !d_cnt) return fail(NGD_E_INVALID, "ngd_run_windows_device: null output");
+// the device-memory forms: [n_win][n_pairs] (a job, bt != NULL: [n_win][n_rep + 1][n_pairs]) where the caller says
+static int windows_device(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt, void *d_sum,
+                          void *d_cnt, const char *who) {
+  if (!d_sum || !d_cnt) return fail(NGD_E_INVALID, std::string(who) + ": null output");
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
   e->n_batch_valid = 0;
-  return windows_impl(e, win_lo, win_hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt);
+  return windows_impl(e, lo, hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, bt);
 }
 
 // the host-memory forms: windows in groups whose results fit ~2 GB of the engine's batch buffers; fn(first, count) takes
 // each group's results out of d_bsum / d_bcnt
 // (a job, bt != NULL: n_rep + 1 matrices per window, at least one window per group)
 static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win,
-                           const std::function<int(uint64_t, uint64_t)> &fn, const WinBoot *bt = nullptr) {
+                           const std::function<int(uint64_t, uint64_t)> &fn, const WinBoot *bt) {
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = bt ? (uint64_t)bt->n_rep + 1 : 1;
   const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (16 * n_mat * std::max<uint64_t>(1, n_pairs))));
   e->win_info = ngd_windows_info{};
@@ -611,42 +534,66 @@ static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
   return NGD_OK;
 }
 
-int ngd_run_windows(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, double *sum, uint64_t *cnt) {
-  if (int rc = windows_check(e, win_lo, win_hi, n_win, "ngd_run_windows")) return rc;
+// ... sums and counts (either may be NULL), bt == NULL: the windows alone
+static int windows_host(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt, double *sum,
+                        uint64_t *cnt) {
   HIPCHK(hipSetDevice(e->device));
-  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
-  return windows_chunked(e, win_lo, win_hi, n_win, [&](uint64_t w0, uint64_t n) {
-    int rc = copy_out(e, (uint32_t)n, e->d_bsum, e->d_bcnt, sum ? sum + w0 * n_pairs : nullptr, cnt ? cnt + w0 * n_pairs : nullptr);
+  const uint32_t n_mat = bt ? bt->n_rep + 1 : 1;
+  const uint64_t per_win = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
+  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
+    int rc = copy_out(e, (uint32_t)(n * n_mat), e->d_bsum, e->d_bcnt, sum ? sum + w0 * per_win : nullptr,
+                      cnt ? cnt + w0 * per_win : nullptr);
     e->n_batch_valid = 0;
     return rc;
-  });
+  }, bt);
+}
+
+// ... distances: the tail of gen_dist() on every matrix
+static int windows_host_dist(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt,
+                             uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who) {
+  const std::string w(who);
+  if (!dist) return fail(NGD_E_INVALID, w + ": null argument");
+  if (tot_sites && e->cfg.pairwise_del)
+    return fail(NGD_E_INVALID, w + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
+  if (evol_model > 2) return fail(NGD_E_MODEL, w + ": evolutionary model not supported (ngsDist.cpp:398-399)");
+  HIPCHK(hipSetDevice(e->device));
+  const uint32_t n_mat = bt ? bt->n_rep + 1 : 1;
+  const uint64_t per_win = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
+  std::vector<double> h_sum;
+  std::vector<uint64_t> h_cnt;
+  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
+    h_sum.resize(n * per_win);
+    h_cnt.resize(n * per_win);
+    int rc = copy_out(e, (uint32_t)(n * n_mat), e->d_bsum, e->d_bcnt, h_sum.data(), h_cnt.data());
+    e->n_batch_valid = 0;
+    if (rc) return rc;
+    // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
+    return ngd_finish(h_sum.data(), h_cnt.data(), n * per_win, tot_sites, evol_model, dist + w0 * per_win);
+  }, bt);
+}
+
+int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, void *d_sum,
+                           void *d_cnt) {
+  if (int rc = windows_check(e, win_lo, win_hi, n_win, "ngd_run_windows_device")) return rc;
+  return windows_device(e, win_lo, win_hi, n_win, nullptr, d_sum, d_cnt, "ngd_run_windows_device");
+}
+
+int ngd_run_windows(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, double *sum, uint64_t *cnt) {
+  if (int rc = windows_check(e, win_lo, win_hi, n_win, "ngd_run_windows")) return rc;
+  return windows_host(e, win_lo, win_hi, n_win, nullptr, sum, cnt);
 }
 
 int ngd_run_windows_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
                          uint64_t evol_model, double *dist) {
   if (int rc = windows_check(e, win_lo, win_hi, n_win, "ngd_run_windows_dist")) return rc;
-  if (!dist) return fail(NGD_E_INVALID, "ngd_run_windows_dist: null argument");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, "ngd_run_windows_dist: a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, "ngd_run_windows_dist: evolutionary model not supported (ngsDist.cpp:398-399)");
-  HIPCHK(hipSetDevice(e->device));
-  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
-  std::vector<double> h_sum;
-  std::vector<uint64_t> h_cnt;
-  return windows_chunked(e, win_lo, win_hi, n_win, [&](uint64_t w0, uint64_t n) {
-    h_sum.resize(n * n_pairs);
-    h_cnt.resize(n * n_pairs);
-    int rc = copy_out(e, (uint32_t)n, e->d_bsum, e->d_bcnt, h_sum.data(), h_cnt.data());
-    e->n_batch_valid = 0;
-    if (rc) return rc;
-    // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
-    return ngd_finish(h_sum.data(), h_cnt.data(), n * n_pairs, tot_sites, evol_model, dist + w0 * n_pairs);
-  });
+  return windows_host_dist(e, win_lo, win_hi, n_win, nullptr, tot_sites, evol_model, dist, "ngd_run_windows_dist");
 }
 
 // ---- ngd_run_windows_job*: the arguments of a job, and the replicates' multiplicities counted from the block maps ----
+// (bt: the job as the plans take it, its multiplicities in mult; n_rep == 0 -- the windows alone -- leaves both as they are)
 static int windows_job_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps,
-                             uint32_t n_rep, uint64_t n_blocks, uint64_t q, const char *who, std::vector<uint32_t> &mult) {
+                             uint32_t n_rep, uint64_t n_blocks, uint64_t q, const char *who, std::vector<uint32_t> &mult,
+                             WinBoot &bt) {
   if (int rc = windows_check(e, lo, hi, n_win, who)) return rc;
   if (!n_rep) return NGD_OK;  // (the windows alone: n_blocks and block_size are not read, as by ngd_run_job)
   const std::string w(who);
@@ -666,6 +613,7 @@ static int windows_job_check(const ngd_engine *e, const uint64_t *lo, const uint
       if (src >= n_blocks) return fail(NGD_E_INVALID, w + ": block_map entry out of range");
       mult[(uint64_t)r * n_blocks + src]++;
     }
+  bt = WinBoot{n_rep, n_blocks, q, mult.data()};
   return NGD_OK;
 }
 
@@ -673,59 +621,32 @@ int ngd_run_windows_job_device(ngd_engine *e, const uint64_t *win_lo, const uint
                                const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, void *d_sum,
                                void *d_cnt) {
   std::vector<uint32_t> mult;
-  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job_device", mult))
+  WinBoot bt{};
+  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job_device", mult, bt))
     return rc;
   if (!n_rep) return ngd_run_windows_device(e, win_lo, win_hi, n_win, d_sum, d_cnt);
-  if (!d_sum || !d_cnt) return fail(NGD_E_INVALID, "ngd_run_windows_job_device: null output");
-  const WinBoot bt{n_rep, n_blocks, block_size, mult.data()};
-  e->win_info = ngd_windows_info{};
-  e->fix_info = ngd_fixup_info{};
-  e->n_batch_valid = 0;
-  return windows_impl(e, win_lo, win_hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, &bt);
+  return windows_device(e, win_lo, win_hi, n_win, &bt, d_sum, d_cnt, "ngd_run_windows_job_device");
 }
 
 int ngd_run_windows_job(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, const uint64_t *block_maps,
                         uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, double *sum, uint64_t *cnt) {
   std::vector<uint32_t> mult;
-  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job", mult))
+  WinBoot bt{};
+  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job", mult, bt))
     return rc;
   if (!n_rep) return ngd_run_windows(e, win_lo, win_hi, n_win, sum, cnt);
-  HIPCHK(hipSetDevice(e->device));
-  const WinBoot bt{n_rep, n_blocks, block_size, mult.data()};
-  const uint64_t per_win = ((uint64_t)n_rep + 1) * ngd_n_pairs(e->g.n_ind);
-  return windows_chunked(e, win_lo, win_hi, n_win, [&](uint64_t w0, uint64_t n) {
-    int rc = copy_out(e, (uint32_t)(n * (n_rep + 1)), e->d_bsum, e->d_bcnt, sum ? sum + w0 * per_win : nullptr,
-                      cnt ? cnt + w0 * per_win : nullptr);
-    e->n_batch_valid = 0;
-    return rc;
-  }, &bt);
+  return windows_host(e, win_lo, win_hi, n_win, &bt, sum, cnt);
 }
 
 int ngd_run_windows_job_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                              const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                              uint64_t tot_sites, uint64_t evol_model, double *dist) {
   std::vector<uint32_t> mult;
-  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job_dist", mult))
+  WinBoot bt{};
+  if (int rc = windows_job_check(e, win_lo, win_hi, n_win, block_maps, n_rep, n_blocks, block_size, "ngd_run_windows_job_dist", mult, bt))
     return rc;
   if (!n_rep) return ngd_run_windows_dist(e, win_lo, win_hi, n_win, tot_sites, evol_model, dist);
-  if (!dist) return fail(NGD_E_INVALID, "ngd_run_windows_job_dist: null argument");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, "ngd_run_windows_job_dist: a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, "ngd_run_windows_job_dist: evolutionary model not supported (ngsDist.cpp:398-399)");
-  HIPCHK(hipSetDevice(e->device));
-  const WinBoot bt{n_rep, n_blocks, block_size, mult.data()};
-  const uint64_t per_win = ((uint64_t)n_rep + 1) * ngd_n_pairs(e->g.n_ind);
-  std::vector<double> h_sum;
-  std::vector<uint64_t> h_cnt;
-  return windows_chunked(e, win_lo, win_hi, n_win, [&](uint64_t w0, uint64_t n) {
-    h_sum.resize(n * per_win);
-    h_cnt.resize(n * per_win);
-    int rc = copy_out(e, (uint32_t)(n * (n_rep + 1)), e->d_bsum, e->d_bcnt, h_sum.data(), h_cnt.data());
-    e->n_batch_valid = 0;
-    if (rc) return rc;
-    // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
-    return ngd_finish(h_sum.data(), h_cnt.data(), n * per_win, tot_sites, evol_model, dist + w0 * per_win);
-  }, &bt);
+  return windows_host_dist(e, win_lo, win_hi, n_win, &bt, tot_sites, evol_model, dist, "ngd_run_windows_job_dist");
 }
 
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {

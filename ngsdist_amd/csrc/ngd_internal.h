@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/ngsdist_amd.h"
+#include "win_plan.h"
 
 #define NGD_TILE 128     // pair tile edge owned by one workgroup of the MFMA kernel
 #define NGD_IG 16        // individuals per fragment group (one MFMA operand edge)
@@ -128,16 +129,8 @@ void ngd_launch_accum_stream(hipStream_t st, const ngd_geom &g, const double *PI
                              uint64_t n_sites_eff, const ngd_score &score, int pairwise_del,
                              const uint64_t *d_pairs, uint64_t n_owned, double *d_sum);
 
-// Windows along the genome (engine.hip windows_slab): a slice table entry per segment of sites [s_lo, s_hi) --
-// k-groups [kg0, kg1) = [3 s_lo / 4, ceil(3 s_hi / 4)), its 0/1 weights (d3[k % 3] inside the segment, 0 outside) at k-group
-// woff of the weight array, kg1 - kg0 + 1 + NGD_KG_TAIL k-groups of them (the operand pipeline's run-ahead reads past kg1).
-// The table-driven EM kernel and k_count_blocks read s_lo / s_hi alone (an EM engine's table leaves the other entries 0).
-#define NGD_SEG_STRIDE 5
-#define NGD_SEG_KG0 0
-#define NGD_SEG_KG1 1
-#define NGD_SEG_WOFF 2
-#define NGD_SEG_SLO 3
-#define NGD_SEG_SHI 4
+// Windows along the genome (engine_windows.hip windows_slab): the slice table's layout NGD_SEG_* is win_plan.h's, where
+// the host builds the table.
 // layout.hip: the weights of every segment of the table (w_total k-groups in all)
 void ngd_launch_seg_weights(hipStream_t st, const uint64_t *d_seg, uint32_t n_seg, uint64_t max_wkg, const double *d3,
                             double *d_W);
