@@ -375,6 +375,17 @@ int ngd_drop_caches(ngd_engine *e);
                                  /*     nothing; the windowed calls stay refused.  Values above 2: NGD_E_INVALID                 */
 #define NGD_OPT_EM_EXACT_CAP 16   /* [0 = 2^20] entries the list of noted (pair, site)s holds, 32 bytes each.  A pass that notes */
                                  /*     more is counted in full, the list grows to the count and the pass runs ONCE more        */
+#define NGD_OPT_UNIT_SKIP 17      /* [1] one-image engines in congruent coordinates on the reference's matrices, no              */
+                                 /*     --pairwise_del: the plain full-data pass (ngd_run with no block map; the lead matrix    */
+                                 /*     of a job whose blocks do not cover every site) leaves out the k-groups of the           */
+                                 /*     coordinate p0 + p1 + p2 -- 1 for normalised input: a third of the pass multiplies ones  */
+                                 /*     by ones -- and adds their products as a constant per pair, n / 2 plus an exact          */
+                                 /*     per-individual correction ngd_commit derives.  Only for a data set ngd_commit found to  */
+                                 /*     be *unit* (every such sum finite and within 2^-40 of 1); else, and with 0, the pass     */
+                                 /*     visits every k-group.  The two agree to ~1e-14 relative, not bit for bit.  The          */
+                                 /*     skipping pass carries 2^-53 of n / 2 per rounding: if it finds a pair whose mean        */
+                                 /*     per-site term is below 1e-3 (nearly identical individuals) its sums are dropped, the    */
+                                 /*     pass runs whole, and so does every later one on this data set.                          */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -383,6 +394,9 @@ int ngd_drop_caches(ngd_engine *e);
 int ngd_set_option(ngd_engine *e, int option, uint64_t value);
 
 int ngd_last_timing(const ngd_engine *e, ngd_timing *t);
+/* k-groups (four contraction indices each) the last plain full-data pass of an MFMA engine visited: all of the image's, or
+ * two thirds of them where NGD_OPT_UNIT_SKIP applied; 0 for the other kernels. */
+int ngd_last_plain_pass(const ngd_engine *e, uint64_t *kgroups);
 /* What the engine holds (ngd_config.single_image resolved): 3 = two operand images, 1 = one image + the second formed a
  * range at a time, 2 = one image in congruent coordinates; 0 = not an MFMA engine.  *fixup (may be NULL) = 1 if the
  * engine recomputes the pairs its congruent arithmetic cannot hold to 1e-9 relative (the reference's score matrices). */

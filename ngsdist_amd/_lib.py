@@ -80,7 +80,7 @@ EXPORTS = [
     "ngd_upload_sites", "ngd_upload_ind_major", "ngd_commit", "ngd_stage_acquire", "ngd_stage_submit",
     "ngd_upload_raw_sites", "ngd_synth_fill", "ngd_synth_fill_range", "ngd_run", "ngd_run_mult", "ngd_run_mult_device",
     "ngd_run_device", "ngd_run_batch", "ngd_run_batch_device", "ngd_run_mult_batch",
-    "ngd_run_mult_batch_device", "ngd_run_job", "ngd_run_job_device", "ngd_run_job_dist", "ngd_run_batch_dist", "ngd_run_mult_batch_dist", "ngd_fetch_matrix", "ngd_drop_caches", "ngd_set_option", "ngd_last_timing", "ngd_last_spill_timing", "ngd_last_fixup", "ngd_image_mode", "ngd_last_shader_clock", "ngd_last_em_work", "ngd_finish", "ngd_finish_stream", "ngd_format_matrix", "ngd_taus_seed", "ngd_taus_get",
+    "ngd_run_mult_batch_device", "ngd_run_job", "ngd_run_job_device", "ngd_run_job_dist", "ngd_run_batch_dist", "ngd_run_mult_batch_dist", "ngd_fetch_matrix", "ngd_drop_caches", "ngd_set_option", "ngd_last_timing", "ngd_last_plain_pass", "ngd_last_spill_timing", "ngd_last_fixup", "ngd_image_mode", "ngd_last_shader_clock", "ngd_last_em_work", "ngd_finish", "ngd_finish_stream", "ngd_format_matrix", "ngd_taus_seed", "ngd_taus_get",
     "ngd_taus_uniform", "ngd_boot_block_map", "ngd_n_pairs", "ngd_pair_index", "ngd_device_bytes", "ngd_device_memory", "ngd_shard_of_pair", "ngd_shard_map",
     "ngd_score_congruence", "ngd_run_windows", "ngd_run_windows_device", "ngd_run_windows_dist", "ngd_last_windows",
     "ngd_window_ranges", "ngd_run_windows_job", "ngd_run_windows_job_device", "ngd_run_windows_job_dist",
@@ -143,6 +143,8 @@ def load():
     L.ngd_drop_caches.argtypes = [vp]
     L.ngd_set_option.argtypes = [vp, C.c_int, u64]
     L.ngd_last_timing.argtypes = [vp, C.POINTER(NgdTiming)]
+    if hasattr(L, "ngd_last_plain_pass"):  # (an A/B build of an engine from before the symbol: NGSDIST_AMD_LIB)
+        L.ngd_last_plain_pass.argtypes = [vp, u64p]
     L.ngd_last_spill_timing.argtypes = [vp, C.POINTER(NgdSpillTiming)]
     L.ngd_last_fixup.argtypes = [vp, C.POINTER(NgdFixupInfo)]
     L.ngd_image_mode.argtypes = [vp, C.POINTER(C.c_int)]

@@ -153,6 +153,7 @@ int ngd_set_option(ngd_engine *e, int option, uint64_t value) {
         e->opt_stage_piece_mib = value;
       }
       break;
+    case NGD_OPT_UNIT_SKIP: e->opt_unit_skip = value != 0; break;
     case NGD_OPT_DEBUG_FORGE_JOB: {  // tests only: the first block of the MFMA job list gets another shape
       // (an engine with a forged job list computes nothing right ever after: refused unless the process says it is a test)
       const char *hook = getenv("NGD_ENABLE_TEST_HOOKS");
@@ -207,6 +208,12 @@ int ngd_image_mode(const ngd_engine *e, int *fixup) {
 int ngd_last_spill_timing(const ngd_engine *e, ngd_spill_timing *t) {
   if (!e || !t) return fail(NGD_E_INVALID, "ngd_last_spill_timing: null argument");
   *t = e->spill_timing;
+  return NGD_OK;
+}
+
+int ngd_last_plain_pass(const ngd_engine *e, uint64_t *kgroups) {
+  if (!e || !kgroups) return fail(NGD_E_INVALID, "ngd_last_plain_pass: null argument");
+  *kgroups = e->plain_kg;
   return NGD_OK;
 }
 

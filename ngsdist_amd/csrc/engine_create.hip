@@ -399,6 +399,20 @@ static int create_images(ngd_engine *e) {
     TRY(e->d_wD.alloc(e, 4 * (g.n_kg + NGD_KG_TAIL), false));
     ngd_launch_index_weights(e->st, 4 * (g.n_kg + NGD_KG_TAIL), e->sc.d, e->d_wD);
   }
+  if (e->congruent && e->sc.fix && !cfg->pairwise_del && g.n_kg < (1ull << 32)) {
+    // the k-groups a plain pass walks when it leaves the unit-sum coordinate out (ngd_engine.h): all but every third,
+    // padded as ngd_launch_kg_compact pads a list -- entries that point at the first zeroed tail k-group
+    std::vector<uint32_t> list;
+    list.reserve(g.n_kg / 3 * 2 + NGD_KG_LIST_PAD);
+    for (uint64_t kg = 0; kg < g.n_kg; kg++)
+      if (kg % 3) list.push_back((uint32_t)kg);
+    e->n_kgskip = list.size();
+    list.insert(list.end(), NGD_KG_LIST_PAD, (uint32_t)g.n_kg);
+    TRY(e->d_kgskip.alloc(e, list.size(), false));
+    if (hipMemcpy(e->d_kgskip, list.data(), list.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return fail(NGD_E_HIP, "ngd_create: k-group list upload failed");
+    TRY(e->d_unitE.alloc(e, g.n_ind + 1, true));
+  }
   if (e->congruent && e->sc.fix) {
     TRY(dev_alloc_pieces(e, e->SM, g.n_sites * g.n_ind, true, PIECE_SITE_MAJOR, g.n_ind * 8));
     e->fix_cap = (uint32_t)std::min<uint64_t>(n_pairs, NGD_FIX_LIST);
@@ -492,6 +506,9 @@ static int create_slices(ngd_engine *e, const std::vector<ngd_tile> &tiles64) {
     ks = std::max<uint64_t>(8, (ks + 7) / 8 * 8);
     e->n_ks = (uint32_t)ks;
     e->per_slice = ((g.n_kg + ks - 1) / ks + 3) / 4 * 4;  // whole pipeline trips (accum_mfma.hip DEPTH)
+    // (the pass over the list of ngd_engine.h: the same slices -- a slice count fills its dispatch rounds as well or as
+    // badly whatever the slices' length -- of equal shares of the list)
+    e->skip_per_slice = ((e->n_kgskip + ks - 1) / ks + 3) / 4 * 4;
     TRY(dev_alloc_pieces(e, e->slab, ks * (uint64_t)g.n_pad * g.n_pad, false));
     // ([0..1] the clock sample; [2] set by a block whose shape the kernel does not list: mfma_fault())
     if (e->h_clk.alloc(4, hipHostMallocMapped) || hipHostGetDevicePointer((void **)&e->d_clk, e->h_clk, 0) != hipSuccess)

@@ -10,7 +10,7 @@
 static int fixup_by_pass(ngd_engine *e, const uint32_t *ws, uint64_t s_hi, double *d_sum, const unsigned long long *d_cnt, double thr) {
   const ngd_geom &g = e->g;
   const uint64_t kstride = (uint64_t)g.n_ig * 64;
-  const uint64_t kg_lim = std::min<uint64_t>(g.n_kg, (3 * s_hi + 3) / 4);
+  const uint64_t kg_lim = std::min<uint64_t>(g.n_kg, (3 * s_hi + 3) / 4);  // (the scratch images: k = 3 s + g, layout.hip k_pq_range)
   // ranges of about 1 GiB per scratch image (two of them), every slice a piece of every range
   const kg_pass_ranges pr(kg_lim, e->n_ks, std::max<uint64_t>(256, ((uint64_t)1 << 30) / (kstride * 8)), 0);
   const uint64_t need = (std::min<uint64_t>(kg_lim, pr.piece * e->n_ks) + NGD_KG_TAIL) * kstride;

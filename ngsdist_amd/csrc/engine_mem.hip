@@ -90,7 +90,9 @@ int piece_wait_sites(ngd_engine *e, uint64_t s_end) {
   for (auto &q : e->piece_ranges) {
     size_t need = q->size;
     if (s_end < e->g.n_sites) {
-      if (q->kind == PIECE_FRAG) need = std::min<size_t>(q->size, ((3 * s_end + 3) / 4 + 1) * (size_t)e->g.n_ig * 512);
+      // (every k-group a site below s_end has an index in -- rounded outwards to whole periods of four sites, which bounds
+      // both layouts of ngd_layout.h -- and one more)
+      if (q->kind == PIECE_FRAG) need = std::min<size_t>(q->size, (ngd_kg_hi(s_end, 1) + 1) * (size_t)e->g.n_ig * 512);
       else if (q->kind == PIECE_SITE_MAJOR) need = std::min<size_t>(q->size, (size_t)(s_end * q->bytes_per_site));
       else if (q.get() == e->slab.range()) continue;  // (nothing of a load goes there)
     } else if (q.get() == e->slab.range()) {

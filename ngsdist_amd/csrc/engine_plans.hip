@@ -17,6 +17,9 @@ struct pass_slices {
   uint64_t k_per_slice = 0;
   uint32_t w_stride = 0;
   bool note = false;  // NGD_OPT_EM_EXACT, table-driven EM kernel, a plain pass: the noting form, into e->d_note
+  // ... in the congruent image, whose blocks are rounded outwards to whole periods of four sites (ngd_layout.h): the slices'
+  // k-group ranges and weight offsets by table instead (the windows' NGD_SEG_* table, win_plan.h), weights in e->blk.wslice
+  const uint64_t *seg = nullptr;
 };
 
 // the MFMA launch over the pass's slices as they are, but for the second image and the k-group list
@@ -26,6 +29,7 @@ static ngd_mfma_launch slices_launch(const ngd_engine *e, const pass_slices &p, 
   l.d_wk = p.k_per_slice ? e->blk.wslice : (p.w ? e->d_wk : d_w_plain);
   l.n_ks = p.n_ks; l.kg_per_slice = p.per_slice; l.n_kg_eff = p.kg_lim;
   l.k_per_slice = p.k_per_slice; l.w_slice_stride = p.w_stride;
+  if (p.seg) { l.d_wk = e->blk.wslice; l.d_seg = p.seg; l.w_slice_stride = 1; l.k_per_slice = 0; }
   l.slab = p.slab;
   return l;
 }
@@ -117,7 +121,7 @@ static void accumulate_em(ngd_engine *e, const pass_slices &p) {
 static void accumulate_two_images(ngd_engine *e, const pass_slices &p) {
   ngd_mfma_launch l = slices_launch(e, p, e->congruent ? e->d_wD.get() : nullptr);
   l.QB = e->congruent ? e->PA : e->QB;
-  l.d_kgl = (p.w && !p.k_per_slice) ? p.kgl : nullptr;
+  l.d_kgl = (!p.k_per_slice && !p.seg) ? p.kgl : nullptr;  // (a replicate's list, or the plain pass's without the unit-sum coordinate)
   ngd_launch_accum_mfma(e->st, mfma_engine(e), l);
 }
 
@@ -200,6 +204,7 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
   uint64_t n_eff = g.n_sites;
   const uint32_t *ws = nullptr;
   uint32_t n_list = 0;
+  bool unit_skip = false;
   const bool list_pass = mult && e->kernel == NGD_KERNEL_MFMA && !e->single_image;
   HIPCHK(hipEventRecord(e->ev[0], e->st));
   if (mult) {
@@ -229,6 +234,12 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
   int rc_acc = NGD_OK;
   pass_slices ps;
   ps.w = ws; ps.sites_eff = n_eff; ps.n_ks = e->n_ks; ps.slab = e->slab;
+  // a congruent image of a *unit* data set (ngd_commit): the k-groups of t0 = p0 + p1 + p2 multiply ones by ones -- the
+  // plain pass walks the list of the others, a third shorter, and the reduction adds d_0 (n + E_i + E_j) (NGD_OPT_UNIT_SKIP)
+  unit_skip = !mult && e->kernel == NGD_KERNEL_MFMA && e->d_kgskip && e->unit_ok && e->opt_unit_skip && !e->single_image;
+  const double fix_mean = unit_skip ? NGD_FIX_MEAN_UNIT : NGD_FIX_MEAN;
+  if (!mult && e->eager_valid && e->eager_slices && e->eager_skip != unit_skip)
+    if (int rc = eager_discard(e)) return rc;  // (slices of the other kind of plain pass)
   if (e->kernel == NGD_KERNEL_STREAM)
     ngd_launch_accum_stream(e->st, g, e->PI, ws, n_eff, e->sc, e->cfg.pairwise_del,
                             e->cfg.shard_world > 1 ? e->d_pairs : nullptr, e->n_owned_pairs, d_sum);
@@ -238,13 +249,15 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
   } else if (!mult && e->eager_valid && e->eager_slices) {
     // the leading slices were accumulated beside the load (eager_advance): what is left, behind them
     HIPCHK(hipStreamWaitEvent(e->st, e->ev_eager, 0));
-    if (e->eager_slices < e->n_ks) launch_plain_slices(e, e->st, e->eager_slices, e->n_ks - e->eager_slices, false);
+    if (e->eager_slices < e->n_ks) launch_plain_slices(e, e->st, e->eager_slices, e->n_ks - e->eager_slices, false, unit_skip);
     e->eager_valid = false;
     e->eager_slices = 0;
   } else {
     ps.per_slice = e->per_slice; ps.kg_lim = g.n_kg; ps.note = note;
+    if (unit_skip) { ps.kgl = e->d_kgskip; ps.per_slice = e->skip_per_slice; ps.kg_lim = e->n_kgskip; }
     rc_acc = launch_accumulate(e, ps);
   }
+  if (!mult) e->plain_kg = e->kernel != NGD_KERNEL_MFMA ? 0 : unit_skip ? e->n_kgskip : g.n_kg;
   if (rc_acc) return rc_acc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev[2], e->st));
@@ -257,7 +270,8 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
   if (fix) HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
   if (e->kernel != NGD_KERNEL_STREAM)
     ngd_launch_reduce(e->st, g, e->slab, e->n_ks, 1, e->d_tiles, e->n_tiles, d_sum, cnt_in_reduce ? d_cnt : nullptr,
-                      mult ? n_drawn : n_eff, fix_in_reduce ? &ff : nullptr, NGD_FIX_MEAN * (double)(mult ? n_drawn : n_eff));
+                      mult ? n_drawn : n_eff, fix_in_reduce ? &ff : nullptr, fix_mean * (double)(mult ? n_drawn : n_eff),
+                      unit_skip ? e->d_unitE.get() : nullptr, e->sc.d[0] * (double)g.n_sites, e->sc.d[0]);
   if (fix_in_reduce) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
   HIPCHK(hipEventRecord(e->ev[3], e->st));
   if (e->cfg.pairwise_del) {
@@ -276,9 +290,17 @@ static int pass_once(ngd_engine *e, const uint32_t *mult, uint32_t mult_max, uin
   HIPCHK(hipStreamSynchronize(e->st));
   read_timing(e, n_eff, 1, add_timing);
   if (int rc = mfma_fault(e)) return rc;
+  if (unit_skip && *(volatile uint32_t *)e->h_fixcount) {
+    // Without the +1/2 of every site the accumulators run to -(sites of a slice) / 2, and a sum carries 2^-53 of that per
+    // rounding: fine for every sum above NGD_FIX_MEAN_UNIT per site, not for the tiny sums of nearly identical individuals
+    // -- which the fix-up pass, and a caller who budgets it, are promised at the full pass's 4e-17 per site.  A data set
+    // that holds such a pair is not one for this pass: it is run whole, now and from now on (until the next ngd_commit).
+    e->unit_ok = false;
+    return pass_once(e, mult, mult_max, n_blocks, block_size, n_drawn, d_sum, d_cnt, true, note);
+  }
   if (fix)
     return fixup_pass(e, ws, n_eff, d_sum, 0, 0, nullptr, e->cfg.pairwise_del ? d_cnt : nullptr,
-                      NGD_FIX_MEAN * (double)(mult ? n_drawn : n_eff));
+                      fix_mean * (double)(mult ? n_drawn : n_eff));
   return NGD_OK;
 }
 
@@ -396,11 +418,33 @@ static int partials_impl(ngd_engine *e, const uint32_t *mult /*[n_rep][n_blocks]
     e->blk.per_slice = unit / sub;
     pass_slices ps;  // a slice = a block (or an equal part of one)
     ps.sites_eff = n_eff; ps.n_ks = e->blk.nks; ps.slab = e->blk.sums();
-    if (unaligned) {
+    if (unaligned && e->congruent) {
+      // the congruent image: a block's sites occupy whole periods of four sites (ngd_layout.h), which the kernel's own
+      // k_per_slice arithmetic does not know -- the slices go by table, as the windows' segments do (win_plan.h): slice b =
+      // the k-groups of block b, its weights d[coordinate] on the block's sites and 0 on the others the periods hold
+      std::vector<uint64_t> tab;
+      tab.reserve((size_t)e->blk.nks * NGD_SEG_STRIDE);
+      uint64_t wkg = 0, max_wkg = 0;
+      for (uint64_t b = 0; b < n_blocks; b++) {
+        const uint64_t s_lo = b * block_size, s_hi = s_lo + block_size;
+        const uint64_t kg0 = ngd_kg_lo(s_lo, 1), kg1 = ngd_kg_hi(s_hi, 1), n_wkg = kg1 - kg0 + 1 + NGD_KG_TAIL;
+        tab.insert(tab.end(), {kg0, kg1, wkg, s_lo, s_hi});
+        wkg += n_wkg;
+        max_wkg = std::max(max_wkg, n_wkg);
+      }
+      for (uint64_t k = n_blocks; k < e->blk.nks; k++) tab.insert(tab.end(), {0, 0, wkg, 0, 0});  // (the XCD deal's padding slices)
+      max_wkg = std::max<uint64_t>(max_wkg, 1 + NGD_KG_TAIL);
+      rc = e->blk.wslice.ensure(e, (wkg + 1 + NGD_KG_TAIL) * 4);
+      if (!rc) rc = e->d_segtab.ensure(e, tab.size());
+      if (rc) return rc;
+      HIPCHK(hipMemcpy(e->d_segtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+      ngd_launch_seg_weights(e->st, e->d_segtab, e->blk.nks, max_wkg, e->sc.d, e->blk.wslice);
+      ps.kg_lim = g.n_kg; ps.seg = e->d_segtab;
+    } else if (unaligned) {
       const uint32_t w_stride = (uint32_t)((3 * block_size + 3) / 4 + 1 + NGD_KG_TAIL);
       rc = e->blk.wslice.ensure(e, (uint64_t)e->blk.nks * w_stride * 4);
       if (rc) return rc;
-      ngd_launch_slice_weights(e->st, e->blk.nks, w_stride, 3 * block_size, 3 * n_eff, e->blk.wslice, e->congruent ? e->sc.d : nullptr);
+      ngd_launch_slice_weights(e->st, e->blk.nks, w_stride, 3 * block_size, 3 * n_eff, e->blk.wslice);
       ps.kg_lim = (3 * n_eff + 3) / 4; ps.k_per_slice = 3 * block_size; ps.w_stride = w_stride;
     } else {
       if (note && (rc = em_exact_begin(e))) return rc;

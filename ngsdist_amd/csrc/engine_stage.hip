@@ -56,7 +56,7 @@ bool eager_supported(const ngd_engine *e) {
 }
 
 // slices [ks0, ks0 + n) of the plain pass on `st` (results: their planes of e->slab, as a whole launch leaves them)
-void launch_plain_slices(ngd_engine *e, hipStream_t st, uint32_t ks0, uint32_t n, bool beside_a_load) {
+void launch_plain_slices(ngd_engine *e, hipStream_t st, uint32_t ks0, uint32_t n, bool beside_a_load, bool unit_skip) {
   const ngd_geom &g = e->g;
   if (e->kernel == NGD_KERNEL_EM_TABLE) {
     // beside a load ONE workgroup per CU (12 KB more LDS than its tables need): the chip is not full of workgroups that
@@ -67,9 +67,17 @@ void launch_plain_slices(ngd_engine *e, hipStream_t st, uint32_t ks0, uint32_t n
     l.PA = e->PA; l.QB = e->congruent ? e->PA : e->QB;
     l.d_wk = e->congruent ? e->d_wD : nullptr;
     l.ks0 = ks0; l.n_ks = n; l.kg_per_slice = e->per_slice; l.n_kg_eff = g.n_kg;
+    if (unit_skip) { l.d_kgl = e->d_kgskip; l.kg_per_slice = e->skip_per_slice; l.n_kg_eff = e->n_kgskip; }  // (pass_once)
     l.slab = e->slab;
     ngd_launch_accum_mfma(st, mfma_engine(e), l);
   }
+}
+
+// which plain pass the slices started beside a load belong to: the one ngd_run() will want if the data set turns out *unit*
+// (every data set a staged load prepares is: K0 normalises)
+static bool eager_unit_skip(const ngd_engine *e) {
+  if (e->eager_slices) return e->eager_skip;
+  return e->d_kgskip && e->opt_unit_skip;
 }
 
 // after the piece of sites [s0, s0 + n) has been submitted (its preparation kernel is on e->st, k0_done[b] recorded)
@@ -83,9 +91,13 @@ static int eager_advance(ngd_engine *e, uint64_t s0, uint64_t n, int b) {
   if (e->kernel == NGD_KERNEL_EM_TABLE) {
     done = (uint32_t)std::min<uint64_t>(e->n_ks, e->stage_prefix / e->per_slice);
   } else {
-    // a slice's k-groups + the NGD_KG_TAIL groups its operand pipeline runs ahead: index 4 kg + 3 belongs to site (4 kg + 3) / 3
-    const uint64_t kg_ready = 3 * e->stage_prefix / 4;  // k-groups whose every index is below 3 * prefix
-    const uint64_t full = kg_ready > NGD_KG_TAIL ? (kg_ready - NGD_KG_TAIL) / e->per_slice : 0;
+    // a slice's k-groups + the NGD_KG_TAIL groups its operand pipeline runs ahead: every index of theirs belongs to a site
+    // below the prefix (ngd_layout.h: whole periods of four sites in the congruent image)
+    uint64_t kg_ready = ngd_kg_whole(e->stage_prefix, e->congruent), per_slice = e->per_slice;
+    // the pass that leaves the unit-sum coordinate out walks a list: entry 2 q + r is k-group 3 q + 1 + r, so the list's
+    // first 2 kg_ready / 3 entries are the listed k-groups below kg_ready (a multiple of 3 in the congruent image)
+    if (eager_unit_skip(e)) { kg_ready = kg_ready / 3 * 2; per_slice = e->skip_per_slice; }
+    const uint64_t full = kg_ready > NGD_KG_TAIL ? (kg_ready - NGD_KG_TAIL) / per_slice : 0;
     done = (uint32_t)std::min<uint64_t>(e->n_ks, full) / 8 * 8;  // (launches of whole eights of slices: the XCD deal)
   }
   const uint32_t batch = e->kernel == NGD_KERNEL_EM_TABLE ? std::max(1u, e->n_ks / 32) : std::max(8u, e->n_ks / 8 / 8 * 8);
@@ -114,7 +126,8 @@ static int eager_advance(ngd_engine *e, uint64_t s0, uint64_t n, int b) {
     HIPCHK(hipEventCreateWithFlags(&e->ev_eager, hipEventDisableTiming));
   }
   HIPCHK(hipStreamWaitEvent(e->st_eager, e->ring[b].k0_done, 0));  // this piece's preparation -- and every earlier one's -- is done
-  launch_plain_slices(e, e->st_eager, e->eager_slices, done - e->eager_slices, true);
+  if (!e->eager_slices) e->eager_skip = eager_unit_skip(e);  // (one kind of slices per load)
+  launch_plain_slices(e, e->st_eager, e->eager_slices, done - e->eager_slices, true, e->eager_skip);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(e->ev_eager, e->st_eager));
   e->eager_slices = done;
@@ -253,6 +266,24 @@ int ngd_upload_raw_sites(ngd_engine *e, const double *raw, uint64_t s0, uint64_t
   return NGD_OK;
 }
 
+// The data set is fixed from here on: what the plain pass needs to leave the unit-sum coordinate out (engine_plans.hip,
+// NGD_OPT_UNIT_SKIP) is derived once, as part of the load -- E_i = SUM_s (t0_i(s) - 1) per individual, and the *unit* mark:
+// every t0 finite and within 2^-40 of 1 (prepared, normalised input is; values a caller uploads need not be).  One pass
+// over the t0 k-groups of the image, a third of it.
+static int unit_scan(ngd_engine *e) {
+  e->unit_ok = false;
+  if (!e->d_unitE) return NGD_OK;
+  HIPCHK(hipMemsetAsync(e->d_unitE, 0, (e->g.n_ind + 1) * sizeof(long long), e->st));  // (the last word: the mark's flag)
+  int *d_flag = (int *)(e->d_unitE.get() + e->g.n_ind);
+  ngd_launch_unit_scan(e->st, e->g, e->PA, e->d_unitE, d_flag);
+  HIPCHK(hipGetLastError());
+  int flag = 1;
+  HIPCHK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, e->st));
+  HIPCHK(hipStreamSynchronize(e->st));
+  e->unit_ok = flag == 0;
+  return NGD_OK;
+}
+
 int ngd_commit(ngd_engine *e) {
   if (!e) return fail(NGD_E_INVALID, "ngd_commit: null engine");
   HIPCHK(hipSetDevice(e->device));
@@ -296,6 +327,7 @@ int ngd_commit(ngd_engine *e) {
   if (e->QB_res)  // single-image engine: the part of the second image it keeps (stream order: before any pass)
     ngd_launch_qb_range(e->st, e->g, e->sc, e->PA, 0, std::min<uint64_t>(e->qb_res_kg + NGD_KG_TAIL, e->g.n_kg + NGD_KG_TAIL),
                         e->QB_res);
+  if (int rc = unit_scan(e)) return rc;
   e->committed = true;
   return NGD_OK;
 }

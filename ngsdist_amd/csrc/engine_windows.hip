@@ -238,7 +238,7 @@ static bool windows_slab_applies(const ngd_engine *e) {
 // what the planner (win_plan.h) needs of the engine
 static win_env windows_env(const ngd_engine *e, const WinBoot *bt) {
   return win_env{(uint64_t)e->g.n_pad * e->g.n_pad, e->kernel == NGD_KERNEL_EM_TABLE, e->cfg.pairwise_del != 0, e->n_ks,
-                 NGD_KG_TAIL, bt ? ngd_reduce_chunk(bt->n_rep) : 1};
+                 NGD_KG_TAIL, bt ? ngd_reduce_chunk(bt->n_rep) : 1, e->congruent};
 }
 
 // a job's weights, the same for every window: Wt[b][r] (zero padded to whole chunks of replicates), as integers for the counts

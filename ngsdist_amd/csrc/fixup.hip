@@ -47,9 +47,8 @@ __global__ __launch_bounds__(64) void k_fixup(ngd_geom g, ngd_score sc, const do
 #pragma unroll
     for (int w = 0; w < 2; w++) {
       const uint32_t x = w ? j : i;
-      const uint64_t k = 3 * s;
-      const double d = sc.fix_sign * T[ngd_frag_off(k + 1, x, g.n_ig)];  // p2 - p0
-      const double m = T[ngd_frag_off(k + 2, x, g.n_ig)];
+      const double d = sc.fix_sign * T[ngd_frag_off(ngd_k_of(s, 1, 1), x, g.n_ig)];  // p2 - p0 (the congruent image's layout)
+      const double m = T[ngd_frag_off(ngd_k_of(s, 2, 1), x, g.n_ig)];
       const double sm = SM[s * g.n_ind + x];
       p[w][1] = m;
       p[w][0] = d >= 0 ? sm : sm - d;
@@ -100,9 +99,8 @@ __global__ __launch_bounds__(256) void k_fixup_tile(ngd_geom g, ngd_score sc, co
       double p0 = 0, p1 = 0, p2 = 0;
       const uint64_t s = s4 + su;
       if (s < b && x < g.n_ind) {
-        const uint64_t k = 3 * s;
-        const double d = sc.fix_sign * T[ngd_frag_off(k + 1, x, g.n_ig)];  // p2 - p0
-        const double m = T[ngd_frag_off(k + 2, x, g.n_ig)];
+        const double d = sc.fix_sign * T[ngd_frag_off(ngd_k_of(s, 1, 1), x, g.n_ig)];  // p2 - p0 (the congruent image's layout)
+        const double m = T[ngd_frag_off(ngd_k_of(s, 2, 1), x, g.n_ig)];
         const double sm = SM[s * g.n_ind + x];
         p1 = m;
         p0 = d >= 0 ? sm : sm - d;

@@ -3,14 +3,19 @@
 // the missing-site masks (reference gen_func.cpp:862-868) and, for bootstrap,
 // expands a block map (reference ngsDist.cpp:416-437) into per-site
 // multiplicities instead of moving any data.
+#include <algorithm>
+
 #include "ngd_internal.h"
 
 namespace {
 
+// the weight of a coordinate and the layout of the image it is for: a congruence's diagonal goes with the congruent
+// engine's ONE image (quad, ngd_layout.h), plain ones with every other image
 struct ngd_d3 {
   double v[3];
+  int quad;
 };
-inline ngd_d3 d3_of(const double *d3) { return d3 ? ngd_d3{{d3[0], d3[1], d3[2]}} : ngd_d3{{1.0, 1.0, 1.0}}; }
+inline ngd_d3 d3_of(const double *d3) { return d3 ? ngd_d3{{d3[0], d3[1], d3[2]}, 1} : ngd_d3{{1.0, 1.0, 1.0}, 0}; }
 
 // One (individual, site): write every image that is allocated.
 __device__ __forceinline__ void emit(const ngd_geom &g, const ngd_score &sc, int pairwise_del,
@@ -38,7 +43,7 @@ __device__ __forceinline__ void emit(const ngd_geom &g, const ngd_score &sc, int
       double t = sc.c[3 * r] * p0;
       t = t + sc.c[3 * r + 1] * p1;
       t = t + sc.c[3 * r + 2] * p2;
-      PA[ngd_frag_off(k + r, i, g.n_ig)] = t;
+      PA[ngd_frag_off(ngd_k_of(s, r, 1), i, g.n_ig)] = t;
     }
   } else if (PA) {
     PA[ngd_frag_off(k, i, g.n_ig)] = p0;
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(256) void k_qb_range(ngd_geom g, ngd_score sc, cons
 
 // Both operand images of the two-image arithmetic for a RANGE of k-groups, out of a congruent one-image engine's image T and
 // its side array SM = min(p0, p2) (fixup.hip has the recovery: p1 = t2, delta = +-t1, the smaller of p0 / p2 beside the
-// larger): Ps = p, Qs = score . p with emit()'s arithmetic, per-site weight folded into p (a bootstrap multiplicity: a small
+// larger; T in the congruent image's own layout, the scratch images in the plain one, k = 3 s + g): Ps = p, Qs = score . p with emit()'s arithmetic, per-site weight folded into p (a bootstrap multiplicity: a small
 // integer).  One thread per (site, padded individual) of the sites that reach into [kg_lo, kg_end); scratch entries of
 // padding individuals, of sites past the data set and of the tail groups are written as zeros.
 __global__ void k_pq_range(ngd_geom g, ngd_score sc, const double *__restrict__ T, const double *__restrict__ SM,
@@ -116,9 +121,8 @@ __global__ void k_pq_range(ngd_geom g, ngd_score sc, const double *__restrict__ 
   const uint32_t i = (uint32_t)(e % g.n_pad);
   double p0 = 0, p1 = 0, p2 = 0;
   if (s < g.n_sites && i < g.n_ind) {
-    const uint64_t k = 3 * s;
-    const double d = sc.fix_sign * T[ngd_frag_off(k + 1, i, g.n_ig)];  // p2 - p0
-    const double m = T[ngd_frag_off(k + 2, i, g.n_ig)];
+    const double d = sc.fix_sign * T[ngd_frag_off(ngd_k_of(s, 1, 1), i, g.n_ig)];  // p2 - p0
+    const double m = T[ngd_frag_off(ngd_k_of(s, 2, 1), i, g.n_ig)];
     const double sm = SM[s * g.n_ind + i];
     p1 = m;
     p0 = d >= 0 ? sm : sm - d;
@@ -245,15 +249,19 @@ __global__ void k_expand(const uint32_t *__restrict__ mult, uint64_t n_eff, uint
   const uint32_t m = s < n_eff ? mult[s / block_size] : 0u;
   ws[s] = m;
   if (wk) {  // (d3: 1, 1, 1 -- or the congruence's diagonal, single_image = 2)
-    wk[3 * s] = (double)m * d3.v[0];
-    wk[3 * s + 1] = (double)m * d3.v[1];
-    wk[3 * s + 2] = (double)m * d3.v[2];
+    wk[ngd_k_of(s, 0, d3.quad)] = (double)m * d3.v[0];
+    wk[ngd_k_of(s, 1, d3.quad)] = (double)m * d3.v[1];
+    wk[ngd_k_of(s, 2, d3.quad)] = (double)m * d3.v[2];
   }
 }
 
 __global__ void k_index_weights(uint64_t n_k, ngd_d3 d3, double *W) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n_k) W[k] = d3.v[k % 3];
+  if (k >= n_k) return;
+  uint64_t s;
+  uint32_t c;
+  ngd_site_of(k, d3.quad, &s, &c);
+  W[k] = d3.v[c];
 }
 
 // W[s][RB] for the EM batch kernel: replicate r's multiplicity of site s (mult is [n_rep][n_blocks]); rows
@@ -276,28 +284,30 @@ __global__ void k_expand_batch(const uint32_t *__restrict__ mult, uint32_t n_rep
   }
 }
 
-// 0/1 weights per slice for bootstrap blocks that are not whole k-groups (accum_mfma.hip, k_per_slice)
-__global__ void k_slice_weights(uint32_t n_slices, uint32_t stride, uint64_t k_per_slice, uint64_t k_total, double *W,
-                                ngd_d3 d3) {
+// 0/1 weights per slice for bootstrap blocks that are not whole k-groups (accum_mfma.hip, k_per_slice; images with
+// k = 3 s + g -- the congruent image's blocks go by slice table: k_seg_weights, engine_plans.hip partials_impl)
+__global__ void k_slice_weights(uint32_t n_slices, uint32_t stride, uint64_t k_per_slice, uint64_t k_total, double *W) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (uint64_t)n_slices * stride * 4) return;
   const uint64_t slice = t / ((uint64_t)stride * 4), r = t % ((uint64_t)stride * 4);
   const uint64_t k = (((slice * k_per_slice) >> 2) << 2) + r;
   const uint64_t lo = slice * k_per_slice, hi = lo + k_per_slice < k_total ? lo + k_per_slice : k_total;
-  W[t] = (k >= lo && k < hi) ? d3.v[k % 3] : 0.0;
+  W[t] = (k >= lo && k < hi) ? 1.0 : 0.0;
 }
 
-// Windows along the genome: the weights of segment q (grid.x) -- d3[k % 3] for the contraction indices of its sites
+// Windows along the genome: the weights of segment q (grid.x) -- d3[coordinate] for the contraction indices of its sites
 // [s_lo, s_hi), 0 for those its first and last k-group share with the neighbouring segments and for the run-ahead past
 // them -- written at k-group woff of W (vector stores; a segment's k-groups are disjoint from every other's)
 __global__ void k_seg_weights(const uint64_t *__restrict__ seg, double *__restrict__ W, ngd_d3 d3) {
   const uint64_t *t = seg + (uint64_t)blockIdx.x * NGD_SEG_STRIDE;
   const uint64_t kg0 = t[NGD_SEG_KG0], kg1 = t[NGD_SEG_KG1], woff = t[NGD_SEG_WOFF];
-  const uint64_t k_lo = 3 * t[NGD_SEG_SLO], k_hi = 3 * t[NGD_SEG_SHI];
+  const uint64_t s_lo = t[NGD_SEG_SLO], s_hi = t[NGD_SEG_SHI];
   const uint64_t n = (kg1 - kg0 + 1 + NGD_KG_TAIL) * 4;
   for (uint64_t r = blockIdx.y * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.y * blockDim.x) {
-    const uint64_t k = kg0 * 4 + r;
-    W[woff * 4 + r] = (k >= k_lo && k < k_hi) ? d3.v[k % 3] : 0.0;
+    uint64_t s;
+    uint32_t c;
+    ngd_site_of(kg0 * 4 + r, d3.quad, &s, &c);
+    W[woff * 4 + r] = (s >= s_lo && s < s_hi) ? d3.v[c] : 0.0;
   }
 }
 
@@ -399,7 +409,44 @@ __global__ void k_kg_pad(uint32_t *list, const uint32_t *total, uint32_t n_pad_e
   if (t < n_pad_entries) list[*total + t] = tail_kg;
 }
 
+// The unit-sum coordinate of a congruent image on the reference's matrices, t0 = fl(p0 + p1 + p2): whole fragments of the
+// k-groups 3 q (lane = site 4 q + lane / 16, individual 16 ig + lane % 16).  A wavefront takes one group of 16
+// individuals through per_wg periods; t0 - 1 is exact and a multiple of 2^-53 wherever |t0 - 1| <= 2^-40, so the sums
+// are 64-bit integers: a lane's own, then the four sites of a fragment by shuffles, then ONE integer atomic per
+// (individual, workgroup) -- the same bits in any order.
+__global__ __launch_bounds__(256) void k_unit_scan(ngd_geom g, const double *__restrict__ T, uint64_t per_wg,
+                                                   long long *__restrict__ E, int *__restrict__ flag) {
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t ig = blockIdx.x * 4 + wave;  // (n_ig is a multiple of 8)
+  const uint32_t i = ig * 16 + (lane & 15);
+  const uint64_t n_q = g.n_sites_pad >> 2;
+  const uint64_t q0 = (uint64_t)blockIdx.y * per_wg, q1 = q0 + per_wg < n_q ? q0 + per_wg : n_q;
+  long long acc = 0;
+  bool bad = false;
+#pragma unroll 4
+  for (uint64_t q = q0; q < q1; q++) {  // (k-group 3 q < n_kg, ig < n_ig: inside the image)
+    const double v = T[(3 * q * g.n_ig + ig) * 64 + lane];
+    const uint64_t s = 4 * q + (lane >> 4);
+    if (s < g.n_sites && i < g.n_ind) {
+      const double d = v - 1.0;
+      if (!(__builtin_fabs(d) <= 0x1p-40)) bad = true;  // (NaN and infinities too)
+      else acc += (long long)(d * 0x1p53);
+    }
+  }
+  acc += __shfl_xor(acc, 16, 64);
+  acc += __shfl_xor(acc, 32, 64);
+  if (lane < 16 && i < g.n_ind && acc) atomicAdd((unsigned long long *)&E[i], (unsigned long long)acc);
+  if (bad) atomicOr(flag, 1);
+}
+
 }  // namespace
+
+void ngd_launch_unit_scan(hipStream_t st, const ngd_geom &g, const double *T, long long *d_E, int *d_flag) {
+  const uint64_t n_q = g.n_sites_pad >> 2;
+  const uint64_t per_wg = std::max<uint64_t>(64, (n_q + 32767) / 32768);  // (grid.y below 65536)
+  hipLaunchKernelGGL(k_unit_scan, dim3(g.n_ig / 4, (unsigned)((n_q + per_wg - 1) / per_wg)), dim3(256), 0, st, g, T, per_wg, d_E,
+                     d_flag);
+}
 
 uint32_t ngd_kg_count_blocks(uint64_t n_kg) { return (uint32_t)((n_kg + CPB - 1) / CPB); }
 
@@ -478,11 +525,11 @@ void ngd_launch_weights_batch(hipStream_t st, const uint32_t *d_mult, uint32_t n
 }
 
 void ngd_launch_slice_weights(hipStream_t st, uint32_t n_slices, uint32_t stride, uint64_t k_per_slice, uint64_t k_total,
-                              double *d_W, const double *d3) {
+                              double *d_W) {
   const uint64_t n = (uint64_t)n_slices * stride * 4;
   if (!n) return;
   hipLaunchKernelGGL(k_slice_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n_slices, stride, k_per_slice,
-                     k_total, d_W, d3_of(d3));
+                     k_total, d_W);
 }
 
 void ngd_launch_planes(hipStream_t st, const uint32_t *d_ws, uint64_t n_sites, uint32_t n_words,

@@ -62,7 +62,17 @@ struct ngd_engine : ngd_mem {
   // ngd_config.single_image (MFMA kernel): QB is not resident; a launch forms it for a range of k-groups at a time
   bool single_image = false;    // (ngd_config.single_image = 1: q is formed range by range)
   bool congruent = false;       // ngd_config.single_image = 2: the image holds t (sc.c, sc.d), read for both operands
-  DevBuf<double> d_wD;          // ... and these are the weights of a plain pass: sc.d[k % 3] per contraction index
+  DevBuf<double> d_wD;          // ... and these are the weights of a plain pass: sc.d[coordinate] per contraction index
+  // ... on the reference's matrices without --pairwise_del (sc.fix: t0 = p0 + p1 + p2, 1 for normalised input) the plain
+  // pass leaves the t0 k-groups out -- kg % 3 == 0 in the image's layout, ngd_layout.h -- and the reduction adds their
+  // products as a constant (NGD_OPT_UNIT_SKIP): the list of the other k-groups (+ NGD_KG_LIST_PAD), made by ngd_create;
+  // E_i = SUM_s (t0_i(s) - 1) in units of 2^-53 (+ one word: the scan's flag) and the *unit* mark, made by ngd_commit
+  DevBuf<uint32_t> d_kgskip;
+  uint64_t n_kgskip = 0, skip_per_slice = 0;
+  DevBuf<long long> d_unitE;
+  bool unit_ok = false;
+  uint64_t opt_unit_skip = 1;
+  uint64_t plain_kg = 0;  // k-groups the last plain pass visited (ngd_last_plain_pass)
   // ... and, for the reference's matrices (sc.fix), the fix-up pass of the pairs its arithmetic cannot hold to 1e-9
   // relative (fixup.hip): SM[site][individual] = min(p0, p2) beside the image, the pairs a reduction noted, scratch
   DevBuf<double> SM;
@@ -166,6 +176,8 @@ struct ngd_engine : ngd_mem {
   bool stage_in_order = true;
   uint32_t eager_slices = 0;   // slices [0, eager_slices) of the plain pass have been launched on st_eager
   bool eager_valid = false;
+  bool eager_skip = false;     // ... as slices of the pass that leaves the unit-sum coordinate out (d_kgskip): the data set is not
+                               // known to be *unit* before ngd_commit -- a plain pass of the other kind drops them
   hipStream_t st_copy[2] = {nullptr, nullptr};
   uint64_t n_staged = 0;
   int ring_slots = 0;
@@ -289,7 +301,7 @@ int spill_slot_map(ngd_engine *e, const std::vector<ngd_tile> &tiles64);  // d_r
 void stage_reap(ngd_engine *e);
 void ring_maker_join(ngd_engine *e);
 bool eager_supported(const ngd_engine *e);
-void launch_plain_slices(ngd_engine *e, hipStream_t st, uint32_t ks0, uint32_t n, bool beside_a_load);
+void launch_plain_slices(ngd_engine *e, hipStream_t st, uint32_t ks0, uint32_t n, bool beside_a_load, bool unit_skip);
 int eager_discard(ngd_engine *e);
 // engine_fixup.hip
 int fix_collect(ngd_engine *e, uint32_t n, bool all, std::vector<ngd_fix_tile> &tiles, std::vector<unsigned long long> &singles);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/ngsdist_amd.h"
+#include "ngd_layout.h"
 #include "win_plan.h"
 
 #define NGD_TILE 128     // pair tile edge owned by one workgroup of the MFMA kernel
@@ -32,7 +33,9 @@ struct ngd_score {
 // Geometry of the resident data set.
 //
 // Fragment-major operand layout ("PA", and "QB" = score-weighted copy):
-//   the contraction index is k = 3*s + g  (site s, genotype g);
+//   the contraction index is k = 3*s + g  (site s, genotype g) -- except in the ONE image of a congruent engine
+//   (single_image = 2), where twelve indices are still four whole sites but the four t0 of a period fill a k-group of
+//   their own: k = ngd_k_of(s, coordinate, 1), ngd_layout.h (which also turns site ranges into k-group ranges);
 //   element (i, k) lives at  ((k/4)*n_ig + i/16)*64 + (k%4)*16 + i%16.
 // One 64-double group (512 B) is exactly the per-lane operand image of
 // v_mfma_f64_16x16x4_f64 (lane l <-> individual l&15, k-offset l>>4), so a
@@ -105,6 +108,7 @@ void ngd_launch_prep_layout(hipStream_t st, const ngd_geom &g, const double *raw
 void ngd_launch_synth(hipStream_t st, const ngd_geom &g, uint64_t seed, double miss_frac, uint64_t site0,
                       const ngd_score &score, int pairwise_del, double *PA, double *QB, double *PI,
                       unsigned long long *mask);
+// (d3 != NULL: the congruence's diagonal per coordinate, and the image's layout is the congruent one -- quad, ngd_layout.h)
 void ngd_launch_weights(hipStream_t st, uint64_t n_blocks, uint64_t block_size, uint64_t n_sites,
                         const uint32_t *d_mult, uint32_t *d_ws, double *d_wk, const double *d3 = nullptr);
 // list of the k-groups with a non-zero bootstrap weight (ascending), NGD_KG_LIST_PAD entries of padding;
@@ -116,11 +120,16 @@ void ngd_launch_weights_batch(hipStream_t st, const uint32_t *d_mult, uint32_t n
                               uint64_t n_blocks, uint64_t block_size, uint64_t n_sites, uint64_t n_sites_alloc,
                               double *d_W);
 // W[slice][j][c] = 1 if contraction index 4 (kg0(slice) + j) + c lies in [slice k_per_slice, (slice+1) k_per_slice)
-// and below k_total, else 0; kg0(slice) = slice * k_per_slice / 4; j < stride
+// and below k_total, else 0; kg0(slice) = slice * k_per_slice / 4; j < stride.  Images with k = 3 s + g only: the blocks of
+// a congruent engine's image go by slice table (ngd_launch_seg_weights)
 void ngd_launch_slice_weights(hipStream_t st, uint32_t n_slices, uint32_t stride, uint64_t k_per_slice, uint64_t k_total,
-                              double *d_W, const double *d3 = nullptr /* weight of index k inside a slice: d3[k % 3], not 1 */);
-// single_image = 2: the weights of a plain pass, d3[k % 3] for every contraction index of the images (+ tail)
+                              double *d_W);
+// single_image = 2: the weights of a plain pass, d3[coordinate of k] for every contraction index of the image (+ tail)
 void ngd_launch_index_weights(hipStream_t st, uint64_t n_k, const double *d3, double *d_W);
+// single_image = 2 on the reference's matrices: E[i] += SUM_s (t0_i(s) - 1) in units of 2^-53 (exact: 64-bit integers, so
+// the result does not depend on the order) over the t0 k-groups of the image; *d_flag |= 1 if some t0 is not finite or
+// |t0 - 1| > 2^-40 (the data set is then not *unit*: no pass may take the coordinate's products as a constant)
+void ngd_launch_unit_scan(hipStream_t st, const ngd_geom &g, const double *T, long long *d_E, int *d_flag);
 void ngd_launch_planes(hipStream_t st, const uint32_t *d_ws, uint64_t n_sites, uint32_t n_words,
                        uint32_t n_planes, unsigned long long *d_planes);
 
@@ -129,8 +138,8 @@ void ngd_launch_accum_stream(hipStream_t st, const ngd_geom &g, const double *PI
                              uint64_t n_sites_eff, const ngd_score &score, int pairwise_del,
                              const uint64_t *d_pairs, uint64_t n_owned, double *d_sum);
 
-// Windows along the genome (engine_windows.hip windows_slab): the slice table's layout NGD_SEG_* is win_plan.h's, where
-// the host builds the table.
+// Windows along the genome (engine_windows.hip windows_slab) and, in a congruent engine's image, bootstrap blocks that are
+// not whole periods of four sites (engine_plans.hip partials_impl): the slice table's layout NGD_SEG_* is win_plan.h's.
 // layout.hip: the weights of every segment of the table (w_total k-groups in all)
 void ngd_launch_seg_weights(hipStream_t st, const uint64_t *d_seg, uint32_t n_seg, uint64_t max_wkg, const double *d3,
                             double *d_W);
@@ -261,6 +270,13 @@ void ngd_launch_accum_em_batch(hipStream_t st, const ngd_geom &g, const double *
 // (mean per-site term below NGD_FIX_MEAN: nearly identical individuals) recomputed with two-operand arithmetic from
 // p recovered out of the image T and the side array SM[site][individual] = min(p0, p2).
 #define NGD_FIX_MEAN 1e-6  // flag a pair whose sum is below this x the sites its matrix visits (error bound: 4e-17 per site)
+// The plain pass that leaves the unit-sum coordinate out (NGD_OPT_UNIT_SKIP) delivers its sums only if NONE is below this x
+// the sites: without the +1/2 of every site its accumulators run to -(sites of a slice) / 2 and the constant cancels them at
+// the end, so a sum carries ~2^-53 of n / 2 per rounding -- [measured] 7e-13 absolute at 3000 sites, 5e-10 at 1e6 -- instead
+// of 4e-17 per site: relative error <= 1e-10 above this mean (worst case, every rounding of a 4000-site slice aligned:
+// 2^-53 x 4000 / 4 / 1e-3), and only nearly identical individuals lie below it.  A data set with such a pair takes the full
+// pass (engine_plans.hip pass_once), whose sums the fix-up rule above is written for
+#define NGD_FIX_MEAN_UNIT 1e-3
 #define NGD_FIX_CAP 4096u  // pairs (or tiles) recomputed per LAUNCH of the fix-up kernels (the size of their scratch)
 // The reductions note up to NGD_FIX_LIST pairs (ngd_engine::fix_cap: the capacity of the list) and the pass recomputes
 // every one of them (more than the list holds: every pair of the engine, tile by tile).  Its cost in pair-sites of work --
@@ -306,10 +322,13 @@ void ngd_launch_fixup_finish(hipStream_t st, const ngd_geom &g, const unsigned l
 // the first slice's plane of the wanted result
 // d_cnt != NULL: every pair's count is set to cnt_value in the same launch (no --pairwise_del)
 // fix != NULL (single_image = 2 engines): pairs whose sum is below fix_thr are noted for the fix-up pass
+// unit_E != NULL (a pass that left the unit-sum coordinate's k-groups out): pair (i, j) takes
+// (unit_c + S) + unit_d0 * 2^-53 * (unit_E[i] + unit_E[j]), S the slab sum -- unit_c = d_0 x the sites the pass visited
 void ngd_launch_reduce(hipStream_t st, const ngd_geom &g, const double *slab, uint32_t n_ks,
                        uint32_t planes_per_slice, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
                        unsigned long long *d_cnt = nullptr, unsigned long long cnt_value = 0,
-                       const ngd_fix_flags *fix = nullptr, double fix_thr = 0);
+                       const ngd_fix_flags *fix = nullptr, double fix_thr = 0, const long long *unit_E = nullptr,
+                       double unit_c = 0, double unit_d0 = 0);
 // --pairwise_del: the pairs of d_sum / d_cnt ([n_rep][n_pairs]) that want the fix-up pass, decided with their valid-site
 // counts in hand (a pair with no valid site in a matrix is exactly 0 there and is not noted); fix.count zeroed by the caller
 // layout.hip / reduce.hip : the fix-up pass as ONE two-operand pass over scratch images formed a range of k-groups at a time

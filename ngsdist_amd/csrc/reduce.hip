@@ -26,7 +26,8 @@ __global__ __launch_bounds__(128) void k_reduce(const double *__restrict__ slab,
                                                  uint32_t planes_per_slice, const ngd_tile *__restrict__ tiles,
                                                  uint32_t n_pad, uint64_t n_ind, double *__restrict__ d_sum,
                                                  unsigned long long *__restrict__ d_cnt, unsigned long long cnt_value,
-                                                 ngd_fix_flags fix, double fix_thr) {
+                                                 ngd_fix_flags fix, double fix_thr, const long long *__restrict__ unit_E,
+                                                 double unit_c, double unit_d0) {
   const uint32_t tile = blockIdx.x >> 7, row = blockIdx.x & 127;
   const uint32_t i = tiles[tile].ti * NGD_TILE + row;
   const uint32_t j = tiles[tile].tj * NGD_TILE + threadIdx.x;
@@ -41,7 +42,11 @@ __global__ __launch_bounds__(128) void k_reduce(const double *__restrict__ slab,
   }
   for (int u = 0; ks < n_ks; ks++, u++) s[u] += p[(uint64_t)ks * plane];
   const uint64_t idx = ngd_pair_idx(n_ind, i, j);
-  const double sum = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+  double sum = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+  // a pass that left the unit-sum coordinate's k-groups out (engine_plans.hip): its products are d_0 (n + E_i + E_j) to
+  // within n 2^-106.  The constant first -- it cancels nearly exactly against the slab sum -- so that the correction is
+  // rounded at the result's own magnitude (E in units of 2^-53: an exact integer sum, converted once)
+  if (unit_E) sum = (unit_c + sum) + unit_d0 * ((double)(unit_E[i] + unit_E[j]) * 0x1p-53);
   d_sum[idx] = sum;
   if (d_cnt) d_cnt[idx] = cnt_value;
   // single_image = 2 engines: a sum this small is not held to 1e-9 relative by the congruent arithmetic -- noted for the
@@ -556,10 +561,12 @@ void reduce_cb(hipStream_t st, const ngd_geom &g, const uint32_t *C, uint32_t n_
 
 void ngd_launch_reduce(hipStream_t st, const ngd_geom &g, const double *slab, uint32_t n_ks,
                        uint32_t planes_per_slice, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
-                       unsigned long long *d_cnt, unsigned long long cnt_value, const ngd_fix_flags *fix, double fix_thr) {
+                       unsigned long long *d_cnt, unsigned long long cnt_value, const ngd_fix_flags *fix, double fix_thr,
+                       const long long *unit_E, double unit_c, double unit_d0) {
   if (!n_tiles) return;
   hipLaunchKernelGGL(k_reduce, dim3(n_tiles * NGD_TILE), dim3(128), 0, st, slab, n_ks, planes_per_slice, d_tiles,
-                     g.n_pad, g.n_ind, d_sum, d_cnt, cnt_value, fix ? *fix : ngd_fix_flags{nullptr, nullptr, nullptr, 0}, fix_thr);
+                     g.n_pad, g.n_ind, d_sum, d_cnt, cnt_value, fix ? *fix : ngd_fix_flags{nullptr, nullptr, nullptr, 0}, fix_thr,
+                     unit_E, unit_c, unit_d0);
 }
 
 void ngd_launch_fix_flag(hipStream_t st, const ngd_geom &g, const double *d_sum, const unsigned long long *d_cnt,

@@ -9,8 +9,11 @@
 #include <iterator>
 #include <vector>
 
-// The slice table: an entry per segment of sites [s_lo, s_hi) -- k-groups [kg0, kg1) = [3 s_lo / 4, ceil(3 s_hi / 4)), its
-// 0/1 weights (d3[k % 3] inside the segment, 0 outside) at k-group woff of the weight array, kg1 - kg0 + 1 + NGD_KG_TAIL
+#include "ngd_layout.h"
+
+// The slice table: an entry per segment of sites [s_lo, s_hi) -- k-groups [kg0, kg1) = [3 s_lo / 4, ceil(3 s_hi / 4)), or
+// rounded outwards to whole periods of four sites in a congruent engine's image (win_env::quad, ngd_layout.h) -- its
+// 0/1 weights (d3[coordinate] inside the segment, 0 outside) at k-group woff of the weight array, kg1 - kg0 + 1 + NGD_KG_TAIL
 // k-groups of them (the operand pipeline's run-ahead reads past kg1).  The table-driven EM kernel and k_count_blocks read
 // s_lo / s_hi alone (an EM engine's table leaves the other entries 0).
 #define NGD_SEG_STRIDE 5
@@ -34,6 +37,7 @@ struct win_env {
   uint32_t n_ks;   // slices of a plain pass (the EM kernel's piece rule)
   uint64_t tail;   // NGD_KG_TAIL
   uint32_t chunk;  // a job: ngd_reduce_chunk(n_rep)
+  bool quad = false;  // the MFMA kernel on the congruent image: its layout (ngd_layout.h)
 };
 
 // a job's weights Wt[b][r]: replicates per block, zero padded to whole chunks
@@ -54,7 +58,8 @@ inline uint64_t win_batch_bytes(const win_env &v, uint64_t n_seg, uint64_t span,
   const uint64_t n_ks = (n_seg + 7) / 8 * 8, cnt = v.pdel ? n_seg * v.plane * 4 : 0;
   const uint64_t job = bt ? n_win * (bt->n_blocks + 1) * 4 + bt->n_blocks * win_weight_stride(v, *bt) * (v.pdel ? 12 : 8) : 0;
   if (v.em) return n_seg * v.plane * 8 + cnt + n_seg * NGD_SEG_STRIDE * 8 + n_win * 16 + job;
-  const uint64_t wkg = 3 * span / 4 + n_ks * (3 + v.tail) + 1 + v.tail;
+  // (a segment's k-groups: at most 3 len / 4 + 2, or + 6 rounded outwards to periods, + 1 + tail of run-ahead)
+  const uint64_t wkg = 3 * span / 4 + n_ks * ((v.quad ? 7 : 3) + v.tail) + 1 + v.tail;
   return n_ks * v.plane * 8 + cnt + wkg * 32 + n_ks * NGD_SEG_STRIDE * 8 + n_win * 16 + job;
 }
 
@@ -130,7 +135,7 @@ inline void win_plan_batch(const win_env &v, const uint64_t *lo, const uint64_t 
       const uint64_t len = x[k + 1] - x[k], n_p = len <= piece ? 1 : (len - 1) / piece + 1, per = (len + n_p - 1) / n_p;
       for (uint64_t s = x[k]; s < x[k + 1]; s += per, n_seg++) p.tab.insert(p.tab.end(), {0, 0, 0, s, std::min(s + per, x[k + 1])});
     } else {
-      const uint64_t kg0 = 3 * x[k] / 4, kg1 = (3 * x[k + 1] + 3) / 4, n_wkg = kg1 - kg0 + 1 + v.tail;
+      const uint64_t kg0 = ngd_kg_lo(x[k], v.quad), kg1 = ngd_kg_hi(x[k + 1], v.quad), n_wkg = kg1 - kg0 + 1 + v.tail;
       p.tab.insert(p.tab.end(), {kg0, kg1, wkg, x[k], x[k + 1]});
       wkg += n_wkg;
       p.max_wkg = std::max(p.max_wkg, n_wkg);
