@@ -273,9 +273,15 @@ void ngd_launch_accum_em_batch(hipStream_t st, const ngd_geom &g, const double *
 // The plain pass that leaves the unit-sum coordinate out (NGD_OPT_UNIT_SKIP) delivers its sums only if NONE is below this x
 // the sites: without the +1/2 of every site its accumulators run to -(sites of a slice) / 2 and the constant cancels them at
 // the end, so a sum carries ~2^-53 of n / 2 per rounding -- [measured] 7e-13 absolute at 3000 sites, 5e-10 at 1e6 -- instead
-// of 4e-17 per site: relative error <= 1e-10 above this mean (worst case, every rounding of a 4000-site slice aligned:
-// 2^-53 x 4000 / 4 / 1e-3), and only nearly identical individuals lie below it.  A data set with such a pair takes the full
-// pass (engine_plans.hip pass_once), whose sums the fix-up rule above is written for
+// of 4e-17 per site.  Were every rounding of a slice aligned, a sum at this mean would be off by 2^-53 x (sites of a slice)
+// / 4 / 1e-3 relative: 1e-10 at 4000 sites (cfg 3's slices), 1e-9 at 36 000 -- and create_slices plans up to ~137 000 for the
+// largest data sets that fit the device (tools/unit_skip_slices.py).  The roundings are not aligned, and the formula is not
+// approached: [measured] a pair at 1.2e-3 per site is within 1.9e-14 relative of the full pass's sum with slices of a few
+// hundred sites, 1.4e-13 with 32 768, 2e-12 with 262 144 (oracle: 2.6e-14, 1.6e-13, 2e-12); one at 2e-3 3.4e-13 and 3.7e-13
+// (profiles/unit_skip/threshold_edges.txt, tests/test_gpu_unit_skip_edges.py) -- fifty times inside 1e-10 at twice the
+// longest slice the engine plans, so the rule does not follow the slice length.  Only nearly identical individuals lie
+// below this mean.  A data set with such a pair takes the full pass (engine_plans.hip pass_once), whose sums the fix-up rule
+// above is written for
 #define NGD_FIX_MEAN_UNIT 1e-3
 #define NGD_FIX_CAP 4096u  // pairs (or tiles) recomputed per LAUNCH of the fix-up kernels (the size of their scratch)
 // The reductions note up to NGD_FIX_LIST pairs (ngd_engine::fix_cap: the capacity of the list) and the pass recomputes
