@@ -372,7 +372,8 @@ int ngd_drop_caches(ngd_engine *e);
                                  /*     leaves the engine.  ngd_last_em_exact() / ngd_em_exact_entries() then report the call:  */
                                  /*     each noted (pair, site) once.  A call neither plan can serve (ngd_config.variant != 0 or */
                                  /*     NGD_OPT_EM_SPILL = 0 where partials do not apply) fails with NGD_E_INVALID and computes  */
-                                 /*     nothing; the windowed calls stay refused.  Values above 2: NGD_E_INVALID                 */
+                                 /*     nothing; the windowed calls stay refused, unless NGD_OPT_EM_EXACT_WIN lets them through. */
+                                 /*     Values above 2: NGD_E_INVALID                                                            */
 #define NGD_OPT_EM_EXACT_CAP 16   /* [0 = 2^20] entries the list of noted (pair, site)s holds, 32 bytes each.  A pass that notes */
                                  /*     more is counted in full, the list grows to the count and the pass runs ONCE more        */
 #define NGD_OPT_UNIT_SKIP 17      /* [1] one-image engines in congruent coordinates on the reference's matrices, no              */
@@ -386,6 +387,23 @@ int ngd_drop_caches(ngd_engine *e);
                                  /*     skipping pass carries 2^-53 of n / 2 per rounding: if it finds a pair whose mean        */
                                  /*     per-site term is below 1e-3 (nearly identical individuals) its sums are dropped, the    */
                                  /*     pass runs whole, and so does every later one on this data set.                          */
+#define NGD_OPT_EM_EXACT_WIN 18   /* [0] 1: while NGD_OPT_EM_EXACT is 1 or 2 the windowed calls are served instead of refused,   */
+                                 /*     every window at the reference's stopping steps; it does nothing while NGD_OPT_EM_EXACT   */
+                                 /*     is 0, and with 0 every call does what NGD_OPT_EM_EXACT alone says.  The segment-slab     */
+                                 /*     plan's one accumulation pass per batch notes (the slice-table form of the noting kernel), */
+                                 /*     the host rechecks the list behind the banded reductions, and every matrix of every window */
+                                 /*     of the batch takes its weight of the site -- 1 inside the window; a replicate: the        */
+                                 /*     multiplicity of block (site - lo) / block_size, 0 in the tail -- times (c_ref - c_dev),   */
+                                 /*     in site order, before any sum leaves the engine (_device, host and _dist forms alike).    */
+                                 /*     ngd_last_em_exact() / ngd_em_exact_entries() report the call: the union over batches and  */
+                                 /*     passes, each (pair, site) once; passes the maximum, ms the sum.                           */
+                                 /*     NGD_OPT_EM_EXACT = 1: ngd_run_windows* by the segment-slab plan only -- NGD_OPT_WIN_PLAN   */
+                                 /*     = 1 fails with NGD_E_INVALID, a window beyond NGD_OPT_WIN_MAX_BYTES with NGD_E_NOMEM,      */
+                                 /*     nothing computed; ngd_run_windows_job* stay refused (replicates need value 2).            */
+                                 /*     NGD_OPT_EM_EXACT = 2: both plans and the jobs; the per-window plan goes window by window  */
+                                 /*     through the noting plans of value 2 and fails as they do where none applies.              */
+                                 /*     NGD_E_INVALID for values above 1, and for 1 on the engines that refuse NGD_OPT_EM_EXACT   */
+                                 /*     (--indep_geno, an explicit kernel other than NGD_KERNEL_EM_TABLE)                         */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */

@@ -441,6 +441,9 @@ constexpr int PACK_DENSE = NGD_PACK_DENSE;
 // SPILL && NOTE (NGD_OPT_EM_EXACT = 2: the spilled-terms plan of a job under the option): the note is per SITE -- the site's
 // own term c, before it joins its unit's running sum, under the absolute site index -- and the buffer arrives in `segtab`
 // (nanlist is the flag word there).  The buffer's count runs on from chunk to chunk of the plan: the engine zeroes it once.
+// SEGS && NOTE (NGD_OPT_EM_EXACT_WIN: the windows' segment slab under the option): the slice-table form that notes.  The
+// table stays in `segtab`, the buffer arrives in `nanlist` as in the plain noting form, and an entry is the plain noting
+// form's: word 0 the workgroup (tile = blockIdx.x % n_tiles here too), word 1 the absolute site of the segment walk.
 template <int NW, int CH, int WPS, bool WEIGHTED, bool PDEL, bool PACK, int RB, bool SPILL = false, bool SEGS = false,
           bool NOTE = false>
 __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
@@ -457,8 +460,9 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
   static_assert(RB == 1 || (PACK && WEIGHTED), "several matrices per pass: the packed form, weighted");
   static_assert(!SPILL || (PACK && !WEIGHTED && RB == 1), "spilled terms: the packed form, unweighted");
   static_assert(!SEGS || (!WEIGHTED && RB == 1 && !SPILL), "a slice table: one matrix per segment, unweighted");
-  static_assert(!NOTE || (!WEIGHTED && RB == 1 && !SEGS), "the noting form: the plain one-matrix pass, or its spilled terms");
-  // (SPILL && NOTE: `nanlist` is the non-finite flag word there; the note buffer arrives in `segtab`, which SPILL never reads)
+  static_assert(!NOTE || (!WEIGHTED && RB == 1), "the noting form: the plain one-matrix pass, its slice-table form, or its spilled terms");
+  // (SPILL && NOTE: `nanlist` is the non-finite flag word there; the note buffer arrives in `segtab`, which SPILL never reads.
+  // SEGS && NOTE: the slice table stays in `segtab`, the note buffer arrives in `nanlist`, which SEGS never reads)
   unsigned long long *const note_buf =
       (SPILL && NOTE) ? const_cast<unsigned long long *>(reinterpret_cast<const unsigned long long *>(segtab)) : nanlist;
   (void)note_buf;
@@ -899,6 +903,18 @@ void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_emt_common &c, uin
     hipLaunchKernelGGL((k_accum_em_table<T::NW, T::CH, T::WPS, false, decltype(P)::value, T::PACK, 1, false, true>),
                        dim3(c.n_tiles64 * n_seg), dim3(T::NW * 64), 0, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64,
                        c.g.n_ig, c.g.n_pad, c.g.n_ind, c.g.n_sites, 0, slab, c.d_counters, 0, nullptr, 1, nullptr, d_seg);
+  });
+}
+
+// The noting form of the same launch (NGD_OPT_EM_EXACT_WIN): d_note as ngd_launch_accum_em_table_note takes it.
+void ngd_launch_accum_em_table_segs_note(hipStream_t st, const ngd_emt_common &c, uint32_t n_seg, const uint64_t *d_seg, double *slab,
+                                         unsigned long long *d_note) {
+  if (!c.n_tiles64 || !n_seg) return;
+  with_shape(c, [&](auto S, auto P) {
+    using T = decltype(S);
+    hipLaunchKernelGGL((k_accum_em_table<T::NW, T::CH, T::WPS, false, decltype(P)::value, T::PACK, 1, false, true, true>),
+                       dim3(c.n_tiles64 * n_seg), dim3(T::NW * 64), 0, st, c.PA, nullptr, nullptr, c.score, c.d_tiles64, c.n_tiles64,
+                       c.g.n_ig, c.g.n_pad, c.g.n_ind, c.g.n_sites, 0, slab, c.d_counters, 0, d_note, 1, nullptr, d_seg);
   });
 }
 

@@ -187,6 +187,63 @@ int em_exact_finish_w(ngd_engine *e, double *d_sum, const ngd_note_weights &w, b
   return NGD_OK;
 }
 
+// NGD_OPT_EM_EXACT_WIN: the switch that lets the windowed calls through while NGD_OPT_EM_EXACT is on.  Off, every call does
+// what it did before the switch existed, refusals and their words included.
+int em_exact_win_set(ngd_engine *e, uint64_t value) {
+  if (value > 1) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT_WIN is 0 or 1");
+  if (value) {  // (the engines on which NGD_OPT_EM_EXACT itself is refused)
+    if (e->cfg.indep_geno) return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT_WIN belongs to the EM path (no --indep_geno)");
+    if (e->cfg.kernel != NGD_KERNEL_AUTO && e->cfg.kernel != NGD_KERNEL_EM_TABLE)
+      return fail(NGD_E_INVALID, "ngd_set_option: NGD_OPT_EM_EXACT_WIN needs the table-driven EM kernel (kernel = auto or NGD_KERNEL_EM_TABLE)");
+  }
+  e->opt_em_exact_win = value != 0;
+  return NGD_OK;
+}
+
+int em_exact_refuse_windows(const ngd_engine *e, const char *who, bool job) {
+  if (!e || !e->opt_em_exact) return NGD_OK;
+  if (!e->opt_em_exact_win) return em_exact_refuse(e, who);
+  if (job && !e->opt_em_exact_boot)
+    return fail(NGD_E_INVALID, std::string("NGD_OPT_EM_EXACT_WIN is on beside NGD_OPT_EM_EXACT = 1: ") + who +
+                                   " is not served -- the replicates of a job need NGD_OPT_EM_EXACT = 2");
+  return NGD_OK;
+}
+
+int em_exact_finish_win(ngd_engine *e, double *d_sum, const uint64_t *lo, const uint64_t *hi, ngd_note_win w, bool *again) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t np = 0;
+  if (int rc = em_exact_recheck(e, true, again, &np)) return rc;
+  if (*again || !np) return NGD_OK;
+  if ((uint64_t)np * w.n_win * w.n_mat >= NGD_NOTE_WIN_MAX)
+    return fail(NGD_E_NOMEM, "NGD_OPT_EM_EXACT_WIN: noted pairs x windows x matrices of one batch reach 2^39 (a smaller NGD_OPT_WIN_MAX_BYTES makes smaller batches)");
+  std::vector<unsigned long long> lohi(2ull * w.n_win);
+  for (uint32_t k = 0; k < w.n_win; k++) {
+    lohi[2ull * k] = lo[k];
+    lohi[2ull * k + 1] = hi[k];
+  }
+  if (int rc = e->d_note_win.ensure(e, lohi.size())) return rc;
+  HIPCHK(hipMemcpy(e->d_note_win, lohi.data(), lohi.size() * 8, hipMemcpyHostToDevice));
+  w.lohi = e->d_note_win;
+  ngd_launch_note_patch_win(e->st, e->d_note_pair, e->d_note_first, e->d_note_delta, e->d_note_site, np, w, ngd_n_pairs(e->g.n_ind), d_sum);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(e->st));
+  e->exact_info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return NGD_OK;
+}
+
+void em_exact_call_begin(ngd_engine *e) {
+  e->exact_info = e->call_info = ngd_em_exact_info{};
+  e->exact_entries.clear();
+  e->call_entries.clear();
+}
+
+// (any number of lists: each joins the union of those before it -- em_exact_merge, fold by fold)
+void em_exact_call_add(ngd_engine *e) {
+  em_exact_merge(e, e->call_entries, e->call_info);
+  e->call_entries = e->exact_entries;
+  e->call_info = e->exact_info;
+}
+
 // Two noting launches of one call (the replicates' per-block partials and the lead matrix's own plain pass): the call's
 // list is their union, each (pair, site) once.  `first` / `info1` are the earlier launch's, e->exact_* the later one's.
 void em_exact_merge(ngd_engine *e, const std::vector<ngd_em_exact_entry> &first, const ngd_em_exact_info &info1) {

@@ -33,11 +33,12 @@
 //    kernel, windows that do not fit the budget, and blocks so small that a slice per block loses.
 // What a slab plan tells the device -- the batches, their slices and tables -- is host arithmetic of its own: win_plan.h.
 
-static int windows_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const char *who) {
+// (job: the call draws replicates -- under NGD_OPT_EM_EXACT_WIN those need NGD_OPT_EM_EXACT = 2)
+static int windows_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const char *who, bool job = false) {
   if (!e) return fail(NGD_E_INVALID, std::string(who) + ": null engine");
   if (!lo || !hi || !n_win) return fail(NGD_E_INVALID, std::string(who) + ": no windows");
   if (!e->committed) return fail(NGD_E_INVALID, std::string(who) + ": call ngd_commit() first");
-  if (int rc = em_exact_refuse(e, who)) return rc;
+  if (int rc = em_exact_refuse_windows(e, who, job)) return rc;
   if (e->cfg.shard_world > 1)
     return fail(NGD_E_INVALID, std::string(who) + ": windows on an engine that owns a share of the pairs are not supported");
   if (n_win >= (1ull << 31)) return fail(NGD_E_INVALID, std::string(who) + ": too many windows in one call");
@@ -58,6 +59,15 @@ static int windows_by_pass(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
     const uint64_t B = std::gcd(lo[w], hi[w]), n_blocks = hi[w] / B;
     mult.assign(n_blocks, 0u);
     std::fill(mult.begin() + lo[w] / B, mult.end(), 1u);
+    if (em_exact_win(e)) {
+      // NGD_OPT_EM_EXACT_WIN (value 2 of NGD_OPT_EM_EXACT; windows_impl has refused value 1): the weighted pass does not
+      // note, so the window goes through the noting plans run_impl has for a multiplicity vector, or fails there
+      if (int rc = run_impl(e, nullptr, mult.data(), 1, false, n_blocks, B, d_sum + w * n_pairs, d_cnt + w * n_pairs)) return rc;
+      e->win_info.ms += e->timing.ms_total + e->fix_info.ms + e->exact_info.ms;
+      em_exact_call_add(e);
+      e->win_info.windows_by_pass++;
+      continue;
+    }
     const double fix_ms = e->fix_info.ms;
     const uint64_t fixed = e->fix_info.recomputed;
     int rc = pass_impl(e, mult.data(), 1, n_blocks, B, hi[w] - lo[w], d_sum + w * n_pairs, d_cnt + w * n_pairs, false);
@@ -89,6 +99,10 @@ static int windows_job_by_pass(ngd_engine *e, const uint64_t *lo, const uint64_t
     if (rc) return rc;
     e->win_info.ms += e->timing.ms_total + e->fix_info.ms;
     e->win_info.fixup_pairs += e->fix_info.recomputed;
+    if (em_exact_win(e)) {  // (run_impl has noted, rechecked and patched this window's matrices: its list joins the call's)
+      e->win_info.ms += e->exact_info.ms;
+      em_exact_call_add(e);
+    }
     // (run_impl reports its own call: the job's report is the sum over its windows)
     e->fix_info.flagged += fi.flagged; e->fix_info.recomputed += fi.recomputed; e->fix_info.skipped += fi.skipped;
     e->fix_info.ms += fi.ms; e->fix_info.by_pass += fi.by_pass;
@@ -282,13 +296,17 @@ static int slab_accumulate(ngd_engine *e, const SlabCall &B) {
   if (!rc) rc = e->d_segtab.ensure(e, p.tab.size());
   if (!rc) rc = e->d_wintab.ensure(e, p.wt.size());
   if (rc) return rc;
+  const bool note = em && em_exact_win(e);  // NGD_OPT_EM_EXACT_WIN: the noting slice-table form, into e->d_note
+  if (note && (rc = em_exact_begin(e))) return rc;
   HIPCHK(hipEventRecord(e->ev[0], e->st));
   HIPCHK(hipMemcpyAsync(e->d_segtab, p.tab.data(), p.tab.size() * 8, hipMemcpyHostToDevice, e->st));
   HIPCHK(hipMemcpyAsync(e->d_wintab, p.wt.data(), p.wt.size() * 8, hipMemcpyHostToDevice, e->st));
   if (B.bt) HIPCHK(hipMemcpyAsync(e->d_winblk, p.blk.data(), p.blk.size() * 4, hipMemcpyHostToDevice, e->st));
   if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)p.n_ks, p.max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
   HIPCHK(hipEventRecord(e->ev[1], e->st));
-  if (em)
+  if (note)
+    ngd_launch_accum_em_table_segs_note(e->st, emt_common(e), (uint32_t)p.n_seg, e->d_segtab, B.seg_sums, e->d_note);
+  else if (em)
     ngd_launch_accum_em_table_segs(e->st, emt_common(e), (uint32_t)p.n_seg, e->d_segtab, B.seg_sums);
   else {
     ngd_mfma_launch l;
@@ -341,6 +359,30 @@ static void slab_counts(ngd_engine *e, const SlabCall &B, double *bs, unsigned l
   else ngd_launch_fix_flag(e->st, e->g, bs, bc, B.nb(), e->d_tiles, e->n_tiles, B.ff, B.n_mat);
 }
 
+// one batch: its accumulation pass, its reductions and counts, and the wait for them (the plan's tables are host memory)
+static int slab_batch(ngd_engine *e, const SlabCall &B, double *bs, unsigned long long *bc, uint64_t span, bool add_timing) {
+  const bool pdel = e->cfg.pairwise_del != 0, fix = e->SM != nullptr;
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
+  if (int rc = slab_accumulate(e, B)) return rc;
+  if (fix) {
+    HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
+    HIPCHK(hipMemsetAsync(e->d_fixseen, 0, (n_pairs / 32 + 1) * sizeof(uint32_t), e->st));
+  }
+  slab_reduce_sums(e, B, bs, bc, true);
+  HIPCHK(hipEventRecord(e->ev[3], e->st));
+  if (pdel) slab_counts(e, B, bs, bc);
+  if (fix) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e->ev[4], e->st));
+  HIPCHK(hipStreamSynchronize(e->st));
+  read_timing(e, span, 1, add_timing);
+  if (int rc = mfma_fault(e)) return rc;
+  float ms = 0;
+  hipEventElapsedTime(&ms, e->ev[0], e->ev[4]);
+  e->win_info.ms += ms;
+  return NGD_OK;
+}
+
 // the segment-slab plan, batch by batch (win_plan.h); *fits = false (nothing launched): some window alone does not fit the budget
 // bt != NULL: the unit slab of a job, outputs [n_win][n_rep + 1][n_pairs] -- the replicates alone, matrix 0 is not written;
 // else window w's matrix is matrix w * out_stride of the outputs (a job's matrices 0: windows_job_slab)
@@ -364,23 +406,23 @@ static int windows_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     win_plan_batch(v, lo, hi, n_win, a, budget, bt, p);
     double *bs = d_sum + a * n_mat * n_pairs;
     unsigned long long *bc = d_cnt + a * n_mat * n_pairs;
-    if ((rc = slab_accumulate(e, B))) return rc;
-    if (fix) {
-      HIPCHK(hipMemsetAsync(e->d_fixcount, 0, sizeof(uint32_t), e->st));
-      HIPCHK(hipMemsetAsync(e->d_fixseen, 0, (n_pairs / 32 + 1) * sizeof(uint32_t), e->st));
+    if ((rc = slab_batch(e, B, bs, bc, p.hi_max - lo[a], batch > 0))) return rc;
+    if (em_exact_win(e)) {
+      // NGD_OPT_EM_EXACT_WIN: the accumulation has noted; the batch's sums take the host's verdict here, behind the reductions
+      // and before they can leave the engine.  A list that was too short has grown to the count: the batch runs once more
+      const ngd_note_win nw = bt ? ngd_note_win{nullptr, B.nb(), bt->n_rep, 1, (uint32_t)n_mat, e->d_W.get(), stride, bt->n_blocks, bt->q}
+                                 : ngd_note_win{nullptr, B.nb(), 1, 0, (uint32_t)n_mat, nullptr, 0, 0, 0};
+      bool again = false;
+      if ((rc = em_exact_finish_win(e, bs, lo + a, hi + a, nw, &again))) return rc;
+      if (again) {
+        if ((rc = slab_batch(e, B, bs, bc, p.hi_max - lo[a], true))) return rc;
+        if ((rc = em_exact_finish_win(e, bs, lo + a, hi + a, nw, &again))) return rc;
+        if (again) return fail(NGD_E_HIP, "NGD_OPT_EM_EXACT: internal -- the second pass noted more than the first counted");
+        e->exact_info.passes = 2;
+      }
+      e->win_info.ms += e->exact_info.ms;
+      em_exact_call_add(e);
     }
-    slab_reduce_sums(e, B, bs, bc, true);
-    HIPCHK(hipEventRecord(e->ev[3], e->st));
-    if (pdel) slab_counts(e, B, bs, bc);
-    if (fix) HIPCHK(hipMemcpyAsync(e->h_fixcount, e->d_fixcount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[4], e->st));
-    HIPCHK(hipStreamSynchronize(e->st));  // (the plan's tables are host memory)
-    read_timing(e, p.hi_max - lo[a], 1, batch > 0);
-    if ((rc = mfma_fault(e))) return rc;
-    float ms = 0;
-    hipEventElapsedTime(&ms, e->ev[0], e->ev[4]);
-    e->win_info.ms += ms;
     e->win_info.segments += p.n_seg;
     e->win_info.slab_bytes = std::max<uint64_t>(e->win_info.slab_bytes, (p.n_ks * 8 + (pdel ? p.n_seg * 4 : 0)) * v.plane);
     e->win_info.batches++;
@@ -430,6 +472,13 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   if (e->opt_win_plan == 2 && !slab_ok)
     return fail(NGD_E_INVALID, "ngd_run_windows: the segment-slab plan needs the MFMA kernel with both operand images resident "
                                "or the one congruent image, or the table-driven EM kernel (NGD_OPT_WIN_PLAN = 2)");
+  // NGD_OPT_EM_EXACT_WIN under NGD_OPT_EM_EXACT = 1: the segment slab or nothing (the per-window plan's weighted pass does not
+  // note, and the plans that note for a multiplicity vector belong to value 2)
+  const bool slab_only = em_exact_win(e) && !e->opt_em_exact_boot;
+  if (slab_only && (e->opt_win_plan == 1 || !slab_ok))
+    return fail(NGD_E_INVALID, "ngd_run_windows: NGD_OPT_EM_EXACT = 1 with NGD_OPT_EM_EXACT_WIN serves the windows by the segment-slab plan "
+                               "only, and NGD_OPT_WIN_PLAN = 1 asks for the per-window plan (that one needs NGD_OPT_EM_EXACT = 2); "
+                               "nothing was computed");
   bool slab = slab_ok && e->opt_win_plan != 1;
   uint64_t budget = e->opt_win_max_bytes;
   if (slab && !budget) {  // the rule of the bootstrap's per-block partial results
@@ -437,7 +486,7 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     budget = (uint64_t)((free_b + e->blk.bytes()) / 100 * 85);
   }
-  if (slab && e->opt_win_plan == 0) {
+  if (slab && e->opt_win_plan == 0 && !slab_only) {
     // auto: the cheaper plan by estimate (the rates partials_impl uses) -- one pass over the sites the
     // windows cover + the banded reduction's reads and writes + allocating a larger slab, against one weighted pass per
     // window (~3/4 of a plain pass over its sites -- [measured] the EM kernel: 0.72, 37 windows of 10 000 sites in 1159 ms at
@@ -499,6 +548,10 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     if (rc || fits) return rc;
     if (e->opt_win_plan == 2)
       return fail(NGD_E_NOMEM, "ngd_run_windows: a window does not fit the segment-slab plan's budget (NGD_OPT_WIN_MAX_BYTES)");
+    if (slab_only)
+      return fail(NGD_E_NOMEM, "ngd_run_windows: a window does not fit the segment-slab plan's budget (NGD_OPT_WIN_MAX_BYTES), and "
+                               "NGD_OPT_EM_EXACT = 1 with NGD_OPT_EM_EXACT_WIN has no other plan (the per-window plan needs "
+                               "NGD_OPT_EM_EXACT = 2); nothing was computed");
   }
   if (bt) return windows_job_by_pass(e, lo, hi, n_win, *bt, d_sum, d_cnt);
   return windows_by_pass(e, lo, hi, n_win, d_sum, d_cnt);
@@ -511,6 +564,7 @@ static int windows_device(ngd_engine *e, const uint64_t *lo, const uint64_t *hi,
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
   e->n_batch_valid = 0;
+  if (e->opt_em_exact_win) em_exact_call_begin(e);
   return windows_impl(e, lo, hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, bt);
 }
 
@@ -523,6 +577,7 @@ static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
   const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (16 * n_mat * std::max<uint64_t>(1, n_pairs))));
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
+  if (e->opt_em_exact_win) em_exact_call_begin(e);
   int rc = batch_buffers(e, (uint32_t)(per * n_mat));
   if (rc) return rc;
   for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
@@ -594,7 +649,7 @@ int ngd_run_windows_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *
 static int windows_job_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps,
                              uint32_t n_rep, uint64_t n_blocks, uint64_t q, const char *who, std::vector<uint32_t> &mult,
                              WinBoot &bt) {
-  if (int rc = windows_check(e, lo, hi, n_win, who)) return rc;
+  if (int rc = windows_check(e, lo, hi, n_win, who, n_rep != 0)) return rc;
   if (!n_rep) return NGD_OK;  // (the windows alone: n_blocks and block_size are not read, as by ngd_run_job)
   const std::string w(who);
   if (!q) return fail(NGD_E_INVALID, w + ": block size 0");

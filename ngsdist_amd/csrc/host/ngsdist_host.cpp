@@ -114,6 +114,9 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // --em_exact_boot: the same, and allowed together with --n_boot_rep: every replicate's matrix is patched from the same
   // list, weighted by its block multiplicities (NGD_OPT_EM_EXACT = 2).  --em_exact itself keeps refusing replicates.
   bool em_exact_boot = false;
+  // --em_exact_win: the same for the windows of --win_size, and for the replicates inside them with --win_boot_rep
+  // (NGD_OPT_EM_EXACT = 1, or 2 with replicates, and NGD_OPT_EM_EXACT_WIN).  The two flags above keep refusing windows.
+  bool em_exact_win = false;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -158,7 +161,7 @@ static void die_engine(const char *func, int rc) {
 // fix-up pass of nearly identical pairs did in the last engine call.  Pairs it had to leave alone (more of them than its
 // budget covers: a large data set of copies of one individual) keep an ABSOLUTE error bound -- far below what "%.10f"
 // prints, but the user should know; said once.  --verbose 2: the pairs recomputed, every call.
-static uint64_t g_exact_noted = 0, g_exact_changed = 0;  // --em_exact / --em_exact_boot: over every engine and call (site ranges add up)
+static uint64_t g_exact_noted = 0, g_exact_changed = 0;  // --em_exact / --em_exact_boot / --em_exact_win: over every engine and call (site ranges add up)
 static void report_fixup(ngd_engine *h, uint64_t verbose) {
   ngd_em_exact_info x;
   if (ngd_last_em_exact && ngd_last_em_exact(h, &x) == NGD_OK) {
@@ -221,6 +224,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"win_boot_rep", required_argument, nullptr, 1013},
                                  {"em_exact", no_argument, nullptr, 1014},
                                  {"em_exact_boot", no_argument, nullptr, 1015},
+                                 {"em_exact_win", no_argument, nullptr, 1016},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -258,6 +262,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1013: p.win_boot = true; p.win_boot_rep = strtoull(optarg, nullptr, 10); break;
       case 1014: p.em_exact = true; break;
       case 1015: p.em_exact_boot = true; break;
+      case 1016: p.em_exact_win = true; break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -302,6 +307,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.win_boot) fprintf(stderr, "\twin_boot_rep: %lu\n\n", p.win_boot_rep);
     if (p.em_exact) fprintf(stderr, "\tem_exact: true\n\n");
     if (p.em_exact_boot) fprintf(stderr, "\tem_exact_boot: true\n\n");
+    if (p.em_exact_win) fprintf(stderr, "\tem_exact_win: true\n\n");
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -335,6 +341,12 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.indep_geno || p.call_geno || !p.in_probs)
       die(__FUNCTION__, "the reference's EM stopping step (--em_exact_boot) belongs to the EM path: not with --indep_geno / --call_geno or genotype input!");
     if (p.win) die(__FUNCTION__, "the reference's EM stopping step (--em_exact_boot) cannot be combined with windows (--win_size)!");
+    p.eager = 0;
+  }
+  if (p.em_exact_win) {  // (beside either flag above, that flag's own check has died already)
+    if (p.indep_geno || p.call_geno || !p.in_probs)
+      die(__FUNCTION__, "the reference's EM stopping step (--em_exact_win) belongs to the EM path: not with --indep_geno / --call_geno or genotype input!");
+    if (!p.win) die(__FUNCTION__, "the reference's EM stopping step inside windows (--em_exact_win) needs windows (--win_size)!");
     p.eager = 0;
   }
   if (p.win) {
@@ -1213,6 +1225,9 @@ int main(int argc, char **argv) {
       die_engine("ngd_set_option", rc);
     if ((p.em_exact || p.em_exact_boot) && (rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT, p.em_exact_boot ? 2 : 1)))
       die_engine("ngd_set_option", rc);
+    if (p.em_exact_win && ((rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT, p.win_boot_rep ? 2 : 1)) ||
+                           (rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT_WIN, 1))))
+      die_engine("ngd_set_option", rc);
     if (p.stage_piece && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_PIECE_MIB, p.stage_piece))) die_engine("ngd_set_option", rc);
     if (p.stage_ring && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_RING, p.stage_ring))) die_engine("ngd_set_option", rc);
   };
@@ -1696,7 +1711,7 @@ int main(int argc, char **argv) {
     g_phases.add("of_matrices_format_write", t_write);
     g_phases.print();
   }
-  if ((p.em_exact || p.em_exact_boot) && p.verbose >= 1)
+  if ((p.em_exact || p.em_exact_boot || p.em_exact_win) && p.verbose >= 1)
     fprintf(stderr, "==> em_exact: %lu (pair, site)s within rounding of the EM's tolerance rechecked, %lu moved to the reference's step\n",
             (unsigned long)g_exact_noted, (unsigned long)g_exact_changed);
   if (p.verbose >= 1) fprintf(stderr, "==> Freeing memory...\n");

@@ -227,6 +227,7 @@ struct ngd_engine : ngd_mem {
   // is within 2^-36 of the tolerance; the host reruns them the reference's way and the pairs' sums are patched
   bool opt_em_exact = false;
   bool opt_em_exact_boot = false;      // value 2: the calls that weight sites are served too (run_impl: noting plans only)
+  bool opt_em_exact_win = false;       // NGD_OPT_EM_EXACT_WIN: while opt_em_exact is on, the windowed calls are served too
   uint64_t note_cap = 1ull << 20;      // entries the list is to hold (NGD_OPT_EM_EXACT_CAP; grown by a pass that noted more)
   DevBuf<unsigned long long> d_note;   // the note buffer (ngd_internal.h): count, capacity, the entries
   unsigned long long note_head[NGD_NOTE_HEAD] = {0, 0, 0, 0};  // what a pass starts from (alive while its copy is in flight)
@@ -234,8 +235,13 @@ struct ngd_engine : ngd_mem {
   DevBuf<unsigned long long> d_note_pair;  // ... the distinct pairs' indices
   DevBuf<uint32_t> d_note_first;           // ... and where each pair's corrections start (+ one past the last)
   DevBuf<unsigned long long> d_note_site;  // ... and the corrections' sites (value 2: a matrix weights each by its block)
+  DevBuf<unsigned long long> d_note_win;   // NGD_OPT_EM_EXACT_WIN: [window of the batch][2] = lo, hi (k_note_patch_win)
   ngd_em_exact_info exact_info{};
   std::vector<ngd_em_exact_entry> exact_entries;  // of the last plain pass, sorted
+  // a windowed call under NGD_OPT_EM_EXACT_WIN notes batch by batch, pass by pass (window by window in the per-window
+  // plan): what the call has gathered so far, while exact_info / exact_entries hold the launch at hand
+  ngd_em_exact_info call_info{};
+  std::vector<ngd_em_exact_entry> call_entries;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
@@ -323,6 +329,14 @@ int em_exact_refuse_weighted(const ngd_engine *e, const char *who);  // as em_ex
 // value 2, after a plan's noting launch (stream idle): recheck + the weighted patch of every matrix of d_sum, or grow the list
 int em_exact_finish_w(ngd_engine *e, double *d_sum, const ngd_note_weights &w, bool *again);
 void em_exact_merge(ngd_engine *e, const std::vector<ngd_em_exact_entry> &first, const ngd_em_exact_info &info1);
+// NGD_OPT_EM_EXACT_WIN
+int em_exact_win_set(ngd_engine *e, uint64_t value);
+inline bool em_exact_win(const ngd_engine *e) { return e->opt_em_exact && e->opt_em_exact_win; }  // windowed calls note
+int em_exact_refuse_windows(const ngd_engine *e, const char *who, bool job);  // em_exact_refuse, unless the option serves `who`
+// after a batch's noting launch and its banded reductions (stream idle): recheck + k_note_patch_win, or grow the list
+int em_exact_finish_win(ngd_engine *e, double *d_sum, const uint64_t *lo, const uint64_t *hi, ngd_note_win w, bool *again);
+void em_exact_call_begin(ngd_engine *e);  // a windowed call starts: nothing gathered
+void em_exact_call_add(ngd_engine *e);    // exact_info / exact_entries join the call's union, which both then hold
 // engine_out.hip
 bool out_trace();
 double out_now();

@@ -225,10 +225,29 @@ struct ngd_note_weights {
 void ngd_launch_note_patch_w(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
                              const unsigned long long *d_site, uint32_t n_pairs_noted, const ngd_note_weights &w,
                              uint64_t n_sites, uint64_t n_pairs, double *d_sum);
+// reduce.hip, NGD_OPT_EM_EXACT_WIN: the same corrections into the matrices of a batch of windows (engine_windows.hip, the slab
+// plans).  Window w of the batch is sites [lohi[2 w], lohi[2 w + 1]); the launch patches matrices mat0 .. mat0 + n_mat - 1 of
+// every window, window w's matrix m at d_sum[(w * out_stride + m) * n_pairs ..].  W == NULL: full-data matrices, weight 1 on the
+// window's sites.  Else matrix mat0 + r weights a site of block b = (site - lo) / q by W[b * w_stride + r] where b < n_blocks,
+// and by 0 behind the last whole block.  pairs x n_win x n_mat must be below NGD_NOTE_WIN_MAX.
+struct ngd_note_win {
+  const unsigned long long *lohi;
+  uint32_t n_win, n_mat, mat0, out_stride;
+  const double *W;
+  uint32_t w_stride;
+  uint64_t n_blocks, q;
+};
+#define NGD_NOTE_WIN_MAX (1ull << 39)
+void ngd_launch_note_patch_win(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
+                               const unsigned long long *d_site, uint32_t n_pairs_noted, const ngd_note_win &w, uint64_t n_pairs,
+                               double *d_sum);
 
 // accum_em_table.hip, windows along the genome: slice ks = sites [s_lo, s_hi) of entry ks of the slice table (NGD_SEG_SLO /
 // NGD_SEG_SHI; any length from 1, any first site, all below g.n_sites), slab [n_seg][n_pad][n_pad]; every `shape` has the form
 void ngd_launch_accum_em_table_segs(hipStream_t st, const ngd_emt_common &c, uint32_t n_seg, const uint64_t *d_seg, double *slab);
+// ... and its noting form (NGD_OPT_EM_EXACT_WIN): entries as ngd_launch_accum_em_table_note leaves them, sites absolute
+void ngd_launch_accum_em_table_segs_note(hipStream_t st, const ngd_emt_common &c, uint32_t n_seg, const uint64_t *d_seg, double *slab,
+                                         unsigned long long *d_note);
 
 // accum_em_table.hip, rb (4 or 8) matrices in one pass: d_Wb is [n_sites][rb] doubles, slab [n_ks][rb][n_pad][n_pad]
 void ngd_launch_accum_em_table_batch(hipStream_t st, const ngd_emt_common &c, const double *d_Wb, int rb, uint64_t n_sites_eff,

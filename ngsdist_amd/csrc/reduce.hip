@@ -714,7 +714,48 @@ __global__ __launch_bounds__(256) void k_note_patch_w(const unsigned long long *
   }
   *out = s;
 }
+// NGD_OPT_EM_EXACT_WIN: one thread per (noted pair, window of the batch, matrix of the launch); the pair's corrections in
+// site order, each weighted by what the matrix makes of the site -- 1 inside [lo, hi) for a window's full-data matrix, the
+// multiplicity of block (site - lo) / q for a replicate, 0 in the tail behind the last whole block (ngsDist.cpp:236) --
+// product first, then the sum, like k_note_patch_w.  A cell no correction reaches is not written.
+__global__ __launch_bounds__(256) void k_note_patch_win(const unsigned long long *__restrict__ pair, const uint32_t *__restrict__ first,
+                                                        const double *__restrict__ delta, const unsigned long long *__restrict__ site,
+                                                        uint32_t n, ngd_note_win w, uint64_t n_pairs, double *__restrict__ d_sum) {
+  const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (uint64_t)n * w.n_win * w.n_mat) return;
+  const uint32_t q = (uint32_t)(idx % n);
+  const uint64_t wm = idx / n;
+  const uint32_t win = (uint32_t)(wm % w.n_win), r = (uint32_t)(wm / w.n_win);
+  const uint64_t lo = w.lohi[2 * (uint64_t)win], hi = w.lohi[2 * (uint64_t)win + 1];
+  double *out = d_sum + ((uint64_t)win * w.out_stride + w.mat0 + r) * n_pairs + pair[q];
+  double s = *out;
+  bool touched = false;
+  for (uint32_t k = first[q]; k < first[q + 1]; k++) {
+    const uint64_t st = site[k];
+    if (st < lo || st >= hi) continue;
+    double m = 1.0;
+    if (w.W) {
+      const uint64_t b = (st - lo) / w.q;
+      m = b < w.n_blocks ? w.W[b * w.w_stride + r] : 0.0;
+    }
+    if (m != 0.0) {
+      s = s + m * delta[k];
+      touched = true;
+    }
+  }
+  if (touched) *out = s;
+}
 }  // namespace
+
+void ngd_launch_note_patch_win(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
+                               const unsigned long long *d_site, uint32_t n_pairs_noted, const ngd_note_win &w, uint64_t n_pairs,
+                               double *d_sum) {
+  if (!n_pairs_noted || !w.n_win || !w.n_mat || (w.W && !w.q)) return;
+  const uint64_t n = (uint64_t)n_pairs_noted * w.n_win * w.n_mat;
+  // (n < NGD_NOTE_WIN_MAX threads: the caller has checked)
+  hipLaunchKernelGGL(k_note_patch_win, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pair, d_first, d_delta, d_site,
+                     n_pairs_noted, w, n_pairs, d_sum);
+}
 
 void ngd_launch_note_patch_w(hipStream_t st, const unsigned long long *d_pair, const uint32_t *d_first, const double *d_delta,
                              const unsigned long long *d_site, uint32_t n_pairs_noted, const ngd_note_weights &w,

@@ -17,7 +17,7 @@ KERNELS = {"auto": 0, "stream": 1, "mfma": 2, "em_faithful": 3, "em_fast": 4, "e
 OPTIONS = {"boot_partials": 1, "boot_max_bytes": 2, "boot_wg": 3, "boot_unaligned": 4, "em_batch": 5,
            "em_spill": 6, "em_spill_bytes": 7, "single_image_bytes": 8, "fixup_work": 9, "stage_piece_mib": 10,
            "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "em_exact": 15, "em_exact_cap": 16,
-           "unit_skip": 17,
+           "unit_skip": 17, "em_exact_win": 18,
            "debug_forge_job": 100}
 # ngd_em_exact_entry
 EM_EXACT_ENTRY = np.dtype([("i1", np.uint32), ("i2", np.uint32), ("site", np.uint64), ("t_dev", np.uint32),
@@ -329,7 +329,8 @@ class Engine:
         """plan selection for the replicate loop (ngd_set_option): boot_partials, boot_max_bytes, boot_wg, boot_unaligned,
         em_batch, em_spill, em_spill_bytes, single_image_bytes, fixup_work, win_plan, win_max_bytes; em_exact (the plain
         pass of the table-driven EM kernel stops where the reference does: last_em_exact(), em_exact_entries(); 2: block
-        maps, multiplicities, batches and jobs are served that way too) and em_exact_cap; unit_skip (0: the plain pass of a
+        maps, multiplicities, batches and jobs are served that way too) and em_exact_cap; em_exact_win (1: while em_exact is on the windowed calls
+        are served too -- run_windows* under 1 or 2, run_windows_job* under 2); unit_skip (0: the plain pass of a
         one-image engine in congruent coordinates visits the k-groups of p0 + p1 + p2 too: plain_pass_kgroups())"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self

@@ -24,7 +24,20 @@ The option-off figure is the comparison: that instantiation of the kernel is the
                              engine buys the partials' slab only once the calls it would have saved add up to its allocation)
   terms_off_all / _on_all    every timed step's EM pass under the spilled-terms plan, ms (0 under per-block partials)
   noted, changed, recheck_ms, passes   ngd_last_em_exact() of the last option-2 step
-  max_rel_diff, cells_patched          over every (matrix, pair) cell of the finished distances"""
+  max_rel_diff, cells_patched          over every (matrix, pair) cell of the finished distances
+
+--windows: the windowed EM shape of tools/bench_windows.py -- 37 windows of 10 000 sites every 2 500 at 1000 x 1e5, segment slab
+(NGD_OPT_WIN_PLAN = 2), results in device memory -- with NGD_OPT_EM_EXACT 0 / 1 alternating (NGD_OPT_EM_EXACT_WIN on throughout:
+it does nothing while the other is 0), and a plain-pass off / on pair in the same process to read the windowed ratio against:
+
+  plain                      the plain leg's figures (ms_off, ms_on, on_over_off, their spread)
+  accum_off_ms / accum_on_ms median of the slab's ONE accumulation launch (ngd_last_timing ms_accum): per pair-site the plain
+                             noting form's work
+  call_off_ms / call_on_ms   median of ngd_last_windows().ms: the call on the device, option on: + recheck and patch
+  wall_off_ms / wall_on_ms   median host wall clock of the call
+  accum_on_over_off, call_on_over_off, wall_on_over_off;  *_all: every timed step;  spread_*: (max - min) / median of them
+  excess_over_plain          accum_on_over_off - plain.on_over_off, to be read against twice the spreads
+  noted, changed, recheck_ms, passes   ngd_last_em_exact() of the last option-on call (the call's union)"""
 import argparse
 import json
 import os
@@ -77,6 +90,80 @@ def job(N, a, res):
     print(json.dumps(res))
 
 
+def plain(e, a):
+    """the plain full-data pass, option 0 / 1 alternating: accumulation kernel alone, the run call, host wall clock"""
+    t = {0: {"accum": [], "total": [], "wall": []}, 1: {"accum": [], "total": [], "wall": []}}
+    sums, info = {}, None
+    for step in range(a.warmup + a.steps):
+        for on in (0, 1):  # alternating: both see the same clock and the same neighbours
+            e.set_option("em_exact", on)
+            w0 = time.perf_counter()
+            s, c = e.run()
+            wall = (time.perf_counter() - w0) * 1e3
+            if step >= a.warmup:
+                tm = e.timing()
+                t[on]["accum"].append(tm["ms_accum"])
+                t[on]["total"].append(tm["ms_total"])
+                t[on]["wall"].append(wall)
+            sums[on] = s
+            if on:
+                info = e.last_em_exact()
+    e.set_option("em_exact", 0)
+    return t, sums, info
+
+
+def spread(xs):
+    return (max(xs) - min(xs)) / statistics.median(xs)
+
+
+def windows(N, a, res):
+    import torch
+    med = statistics.median
+    with N.Engine(a.n_ind, a.n_sites, indep_geno=False, kernel="em_table", pairwise_del=a.pairwise_del,
+                  variant=a.variant) as e:
+        e.synth_fill(a.seed, 0.05 if a.pairwise_del else 0.0)
+        tp, _, _ = plain(e, a)
+        res["plain"] = dict(ms_off=med(tp[0]["accum"]), ms_on=med(tp[1]["accum"]), ms_off_all=tp[0]["accum"],
+                            ms_on_all=tp[1]["accum"], on_over_off=med(tp[1]["accum"]) / med(tp[0]["accum"]),
+                            spread_off=spread(tp[0]["accum"]), spread_on=spread(tp[1]["accum"]),
+                            wall_off_ms=med(tp[0]["wall"]), wall_on_ms=med(tp[1]["wall"]))
+        lo, hi = N.window_ranges(a.n_sites, a.win_size, a.win_step)
+        res.update(win_size=a.win_size, win_step=a.win_step, n_win=int(len(lo)))
+        e.set_option("win_plan", 2)
+        e.set_option("em_exact_win", 1)
+        d_sum = {on: torch.empty((len(lo), e.n_pairs), dtype=torch.float64, device="cuda") for on in (0, 1)}
+        d_cnt = torch.empty((len(lo), e.n_pairs), dtype=torch.int64, device="cuda")
+        t = {on: {"accum": [], "call": [], "wall": []} for on in (0, 1)}
+        info = wi = None
+        for step in range(a.warmup + a.steps):
+            for on in (0, 1):
+                e.set_option("em_exact", on)
+                w0 = time.perf_counter()
+                e.run_windows(lo, hi, d_sum[on].data_ptr(), d_cnt.data_ptr())
+                wall = (time.perf_counter() - w0) * 1e3
+                wi = e.windows_info()
+                if step >= a.warmup:
+                    t[on]["accum"].append(e.timing()["ms_accum"])
+                    t[on]["call"].append(wi["ms"])
+                    t[on]["wall"].append(wall)
+                if on:
+                    info = e.last_em_exact()
+        torch.cuda.synchronize()
+        res["shader_clock_mhz"] = e.shader_clock_mhz()
+        res.update(segments=int(wi["segments"]), batches=int(wi["batches"]), slab_bytes=int(wi["slab_bytes"]))
+        d = (d_sum[1] - d_sum[0]).abs()
+        res["cells_patched"] = int(torch.count_nonzero(d).item())
+        res["max_rel_diff"] = float(torch.nan_to_num(d / d_sum[0].abs(), nan=0.0).max().item())
+    for k in ("accum", "call", "wall"):
+        res["%s_off_ms" % k], res["%s_on_ms" % k] = med(t[0][k]), med(t[1][k])
+        res["%s_off_all" % k], res["%s_on_all" % k] = t[0][k], t[1][k]
+        res["%s_on_over_off" % k] = med(t[1][k]) / med(t[0][k])
+        res["spread_%s_off" % k], res["spread_%s_on" % k] = spread(t[0][k]), spread(t[1][k])
+    res["excess_over_plain"] = res["accum_on_over_off"] - res["plain"]["on_over_off"]
+    res.update(noted=int(info["noted"]), changed=int(info["changed"]), recheck_ms=info["ms"], passes=int(info["passes"]))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_ind", type=int, default=1000)
@@ -88,6 +175,9 @@ def main():
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--job", type=int, default=0, help="R: time the full data + R replicates (option 0 / 2) instead of the plain pass")
     ap.add_argument("--block_size", type=int, default=1)
+    ap.add_argument("--windows", action="store_true", help="time the windowed call (option 0 / 1) beside a plain-pass pair")
+    ap.add_argument("--win_size", type=int, default=10000)
+    ap.add_argument("--win_step", type=int, default=2500)
     a = ap.parse_args()
     import ngsdist_amd as N
     if N.device_count() < 1:
@@ -96,25 +186,12 @@ def main():
            "pairwise_del": bool(a.pairwise_del), "variant": a.variant}
     if a.job:
         return job(N, a, res)
+    if a.windows:
+        return windows(N, a, res)
     with N.Engine(a.n_ind, a.n_sites, indep_geno=False, kernel="em_table", pairwise_del=a.pairwise_del,
                   variant=a.variant) as e:
         e.synth_fill(a.seed, 0.05 if a.pairwise_del else 0.0)
-        t = {0: {"accum": [], "total": [], "wall": []}, 1: {"accum": [], "total": [], "wall": []}}
-        sums = {}
-        for step in range(a.warmup + a.steps):
-            for on in (0, 1):  # alternating: both see the same clock and the same neighbours
-                e.set_option("em_exact", on)
-                w0 = time.perf_counter()
-                s, c = e.run()
-                wall = (time.perf_counter() - w0) * 1e3
-                if step >= a.warmup:
-                    tm = e.timing()
-                    t[on]["accum"].append(tm["ms_accum"])
-                    t[on]["total"].append(tm["ms_total"])
-                    t[on]["wall"].append(wall)
-                sums[on] = s
-                if on:
-                    info = e.last_em_exact()
+        t, sums, info = plain(e, a)
         res["shader_clock_mhz"] = e.shader_clock_mhz()
         res["pair_sites"] = e.timing()["pair_sites"]
     med = statistics.median
