@@ -214,6 +214,41 @@ def test_jobs_agree_with_run_job_on_an_engine_of_the_window_alone(kernel, kw, in
             assert np.all(np.isfinite(s))
 
 
+BAND_ENGINES = [("mfma", {"single_image": 3}, 40, True), ("mfma", {"single_image": 2, "exact_shapes": 1}, 40, True),
+                ("em_table", {}, 12, False)]
+
+
+@pytest.mark.parametrize("kernel,kw,n_ind,indep", BAND_ENGINES, ids=["two-images", "congruent", "em_table"])
+@pytest.mark.parametrize("pdel", [False, True])
+@pytest.mark.parametrize("q", [4, 7])
+@pytest.mark.parametrize("n_rep", [1, 2, 4, 16, 17, 32, 64, 65])
+def test_every_group_size_of_the_band_reduction(kernel, kw, n_ind, indep, pdel, q, n_rep):
+    """k_reduce_band_w<RB, CNT> (reduce.hip): RB = ngd_reduce_chunk(n_rep) = 1, 4, 16 or 32 replicates per group, with counts
+    (--pairwise_del) and without -- one replicate, a full group of 4, 16 and 32, one more than a group (17, 65), two groups
+    of 32.  240 sites, windows of 80 every 40; q = 4 divides the step (a block is one slice of the slab), q = 7 does not.
+    The slab plan forced and read back; every matrix of every window against the oracle on the window's sites with the
+    window's map, counts exact; matrix 0 the bits of run_windows()."""
+    p, lo, hi, maps, (so, co) = synth_case(29, n_ind, 240, 0.2 if pdel else 0.0, 80, 40, q, 65, 13, pdel, indep)
+    assert len(lo) == 5 and maps.shape == (65, 80 // q)
+    maps, so, co = maps[:n_rep], so[:, :n_rep + 1], co[:, :n_rep + 1]  # (a generator draws map after map: a prefix)
+    with engine(p, kernel, pairwise_del=pdel, indep_geno=indep, **kw) as e:
+        e.set_option("win_plan", 2)
+        s, c = e.run_windows_job(lo, hi, maps, q)
+        info = e.windows_info()
+        assert info["windows_by_pass"] == 0 and info["batches"] >= 1 and info["segments"] >= 1, info
+        s0, c0 = e.run_windows(lo, hi)
+        assert e.windows_info()["windows_by_pass"] == 0
+    assert s.shape == (5, n_rep + 1, e.n_pairs) and c.shape == s.shape
+    assert np.array_equal(c, co)
+    assert np.all(np.isfinite(s))
+    for w in range(5):
+        for m in range(n_rep + 1):  # every matrix of every window
+            err = rel_err(s[w, m], so[w, m])
+            assert err < RTOL, (w, m, err)
+    assert np.array_equal(c[:, 0], c0)
+    assert np.array_equal(s[:, 0].view(np.uint64), s0.view(np.uint64))
+
+
 def test_matrix_0_and_no_replicates_are_run_windows_bit_for_bit():
     """Under the slab plan matrix 0 of every window is run_windows()' matrix under the slab plan, bit for bit, whatever the
     block size: it is reduced from the windows' own segments, not from the replicates' finer slices (whose additions come in
