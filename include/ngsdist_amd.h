@@ -556,6 +556,37 @@ int ngd_run_windows_job_device(ngd_engine *e, const uint64_t *win_lo, const uint
 int ngd_run_windows_job_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                              const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                              uint64_t tot_sites, uint64_t evol_model, double *dist);
+/* The same over windows of UNEQUAL length (windows in coordinates, ngd_window_ranges_bp): the meaning of ngd_run_windows_job*
+ * window by window, with n_blocks_w = (hi_w - lo_w) / block_size rounded down.  Window w's maps are [n_rep][n_blocks_w] at
+ * block_maps + map_off[w] (ngd_window_boot_maps draws them as the cut-down runs would; windows may share an offset), maps_len
+ * the entries of block_maps.  Outputs are [n_win][n_rep + 1][n_pairs]: matrix 0 of a window is its ngd_run_windows matrix,
+ * matrix r visits blocks block_maps[map_off[w] + (r - 1) n_blocks_w + b]; a replicate's count is n_blocks_w * block_size,
+ * under --pairwise_del the multiplicity-weighted number of valid sites, exactly.  A window shorter than one block
+ * (n_blocks_w = 0) has replicates with sum 0 and count 0 -- what the reference's truncation (ngsDist.cpp:236) leaves; the
+ * _dist form prints ngd_finish's 0 / 0 there.  n_rep = 0 is ngd_run_windows*, bit for bit.
+ * NGD_E_INVALID, before anything is launched: anything ngd_run_windows refuses, block_size 0, a null table,
+ * map_off[w] + n_rep n_blocks_w > maps_len, a map entry >= n_blocks_w; and while NGD_OPT_EM_EXACT is on (either value, with
+ * or without NGD_OPT_EM_EXACT_WIN) the call is refused in the words of every other call that option does not serve.
+ * The plans are those of ngd_run_windows_job (NGD_OPT_WIN_PLAN, NGD_OPT_WIN_MAX_BYTES):
+ *  - unit slab: as there -- the block boundaries lo_w + b q and the ends hi_w of a batch cut the sites into the slices of
+ *    ONE accumulation pass, matrix 0 comes from the plain segment slab with ngd_run_windows_device()'s bits -- and the
+ *    replicates from the descriptor form of the banded and weighted reduction: every workgroup first reads four words of
+ *    its window (where its row of block starts begins, n_blocks_w, where its weight table begins, the sites a replicate
+ *    visits), so the count and the fix-up threshold are the window's own.  Windows that share map_off and n_blocks_w share
+ *    a weight table; a batch holds the tables of its own classes only.  The slices of a batch are cut by the boundaries of
+ *    every window of the call inside its span, so the MFMA kernel's replicates carry the same bits under any
+ *    NGD_OPT_WIN_MAX_BYTES (matrix 0 is ngd_run_windows_device()'s at the same budget);
+ *  - per window: one ngd_run_windows_job of one window each, with that window's maps.
+ * Windows of one length through this call give ngd_run_windows_job*'s bits in both plans. */
+int ngd_run_windows_job_var(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                            const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                            uint64_t block_size, double *sum, uint64_t *cnt);
+int ngd_run_windows_job_var_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                   const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                   uint64_t block_size, void *d_sum, void *d_cnt);
+int ngd_run_windows_job_var_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                 const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                 uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *dist);
 /* What the last ngd_run_windows* call did */
 typedef struct ngd_windows_info {
   uint64_t segments;       /* slices of the segment-slab plan's accumulation passes, summed over its batches          */
@@ -574,6 +605,27 @@ int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info);
  * shows up again after another one (a positions file not grouped by chromosome). */
 int64_t ngd_window_ranges(const uint32_t *chrom_id, uint64_t n_sites, uint64_t size, uint64_t step, uint64_t *lo, uint64_t *hi,
                           uint64_t cap);
+/* The window list of --win_bp / --win_bp_step (pure host arithmetic): chromosomes as above; in a chromosome whose sites have
+ * positions p_0 <= ... <= p_{m-1}, all >= 1, window k = 0, 1, ... covers the coordinates [1 + k step_bp, 1 + k step_bp +
+ * size_bp) for every k with 1 + k step_bp <= p_{m-1} (trailing partial windows are kept: the chromosome's length is not
+ * known).  Its sites are those whose position lies in the interval, a range [lo, hi); a window with fewer than
+ * max(1, min_sites) sites is left out and the kept ones are numbered in output order, so that lo does not decrease and
+ * lo < hi, as ngd_run_windows* wants.  bp_start (may be NULL) receives 1 + k step_bp of each kept window.  Returns the
+ * count and writes the first min(count, cap) windows.  NGD_E_INVALID: size_bp or step_bp 0, pos == NULL, a position of 0, a
+ * position or size >= 2^62, positions that descend inside a chromosome (equal ones are allowed), a chromosome id that shows
+ * up again after another one.  Time is proportional to sites + kept windows: runs of windows that cannot be kept are
+ * jumped over. */
+int64_t ngd_window_ranges_bp(const uint32_t *chrom_id, const uint64_t *pos, uint64_t n_sites, uint64_t size_bp, uint64_t step_bp,
+                             uint64_t min_sites, uint64_t *lo, uint64_t *hi, uint64_t *bp_start, uint64_t cap);
+/* The block maps ngd_run_windows_job_var* takes, drawn as the reference would on every window's cut-down file: each such
+ * run seeds its generator anew, so a window of L sites draws its n_rep maps of n_blocks = L / block_size blocks from a
+ * fresh ngd_taus_seed(seed) (ngd_boot_block_map, n_rep times) -- a sequence that depends on n_blocks alone: windows with
+ * one n_blocks, those of one length among them, share one set of maps and one offset.  Window w's maps are
+ * [n_rep][n_blocks_w] at block_maps + map_off[w]; a window shorter than one block has no entries (map_off[w] = 0).
+ * Returns the number of entries needed and writes map_off[0 .. n_win); nothing is written beyond block_maps[cap)
+ * (block_maps may be NULL with cap 0).  NGD_E_INVALID: block_size 0, a null lo / hi / map_off, hi < lo. */
+int64_t ngd_window_boot_maps(uint64_t seed, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint32_t n_rep,
+                             uint64_t block_size, uint64_t *block_maps, uint64_t cap, uint64_t *map_off);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

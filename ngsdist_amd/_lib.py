@@ -84,6 +84,8 @@ EXPORTS = [
     "ngd_taus_uniform", "ngd_boot_block_map", "ngd_n_pairs", "ngd_pair_index", "ngd_device_bytes", "ngd_device_memory", "ngd_shard_of_pair", "ngd_shard_map",
     "ngd_score_congruence", "ngd_run_windows", "ngd_run_windows_device", "ngd_run_windows_dist", "ngd_last_windows",
     "ngd_window_ranges", "ngd_run_windows_job", "ngd_run_windows_job_device", "ngd_run_windows_job_dist",
+    "ngd_window_ranges_bp", "ngd_window_boot_maps", "ngd_run_windows_job_var", "ngd_run_windows_job_var_device",
+    "ngd_run_windows_job_var_dist",
     "ngd_last_em_exact", "ngd_em_exact_entries", "ngd_em2_site",
 ]
 
@@ -183,6 +185,13 @@ def load():
     L.ngd_run_windows_job_dist.argtypes = [vp, u64p, u64p, u64, u64p, C.c_uint32, u64, u64, u64, u64, dp]
     L.ngd_window_ranges.argtypes = [u32p, u64, u64, u64, u64p, u64p, u64]
     L.ngd_window_ranges.restype = C.c_int64
+    L.ngd_window_ranges_bp.argtypes = [u32p, u64p, u64, u64, u64, u64, u64p, u64p, u64p, u64]
+    L.ngd_window_ranges_bp.restype = C.c_int64
+    L.ngd_window_boot_maps.argtypes = [u64, u64p, u64p, u64, C.c_uint32, u64, u64p, u64, u64p]
+    L.ngd_window_boot_maps.restype = C.c_int64
+    L.ngd_run_windows_job_var.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, dp, u64p]
+    L.ngd_run_windows_job_var_device.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, vp, vp]
+    L.ngd_run_windows_job_var_dist.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, u64, u64, dp]
     L.ngd_last_em_exact.argtypes = [vp, C.POINTER(NgdEmExactInfo)]
     L.ngd_em_exact_entries.argtypes = [vp, C.POINTER(NgdEmExactEntry), u64]
     L.ngd_em_exact_entries.restype = C.c_int64

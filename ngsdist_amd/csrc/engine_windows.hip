@@ -1,6 +1,7 @@
 // engine_windows.hip -- the windowed calls: their two plans, the fix-up of a batch of windows, the host-memory forms; and the
 // jobs that draw bootstrap replicates inside every window.
 #include <functional>
+#include <map>
 #include <numeric>
 
 #include "ngd_engine.h"
@@ -250,9 +251,10 @@ static bool windows_slab_applies(const ngd_engine *e) {
 }
 
 // what the planner (win_plan.h) needs of the engine
-static win_env windows_env(const ngd_engine *e, const WinBoot *bt) {
+// (n_rep: the replicates of a job over windows of unequal length, which has no WinBoot)
+static win_env windows_env(const ngd_engine *e, const WinBoot *bt, uint32_t n_rep = 0) {
   return win_env{(uint64_t)e->g.n_pad * e->g.n_pad, e->kernel == NGD_KERNEL_EM_TABLE, e->cfg.pairwise_del != 0, e->n_ks,
-                 NGD_KG_TAIL, bt ? ngd_reduce_chunk(bt->n_rep) : 1, e->congruent};
+                 NGD_KG_TAIL, bt ? ngd_reduce_chunk(bt->n_rep) : n_rep ? ngd_reduce_chunk(n_rep) : 1, e->congruent};
 }
 
 // a job's weights, the same for every window: Wt[b][r] (zero padded to whole chunks of replicates), as integers for the counts
@@ -281,6 +283,9 @@ struct SlabCall {
   DevBuf<uint32_t> &seg_cnt;
   ngd_fix_flags ff;
   uint32_t n_mat, stride;
+  // a job over windows of unequal length (bt == NULL then): p is this batch's plan too, with its descriptors and classes
+  const WinBootVar *bv = nullptr;
+  const win_batch_var *pv = nullptr;
   uint32_t nb() const { return (uint32_t)(p.b - p.a); }
 };
 
@@ -290,7 +295,8 @@ static int slab_accumulate(ngd_engine *e, const SlabCall &B) {
   const bool em = e->kernel == NGD_KERNEL_EM_TABLE;
   const uint64_t plane = (uint64_t)e->g.n_pad * e->g.n_pad;
   int rc = B.seg_sums.ensure(e, p.n_ks * plane);
-  if (!rc && B.bt) rc = e->d_winblk.ensure(e, p.blk.size());
+  if (!rc && (B.bt || B.bv)) rc = e->d_winblk.ensure(e, p.blk.size());
+  if (!rc && B.bv) rc = e->d_windesc.ensure(e, B.pv->desc.size());
   if (!rc && e->cfg.pairwise_del) rc = B.seg_cnt.ensure(e, p.n_seg * plane);
   if (!rc && !em) rc = e->blk.wslice.ensure(e, p.w_total * 4);
   if (!rc) rc = e->d_segtab.ensure(e, p.tab.size());
@@ -301,7 +307,8 @@ static int slab_accumulate(ngd_engine *e, const SlabCall &B) {
   HIPCHK(hipEventRecord(e->ev[0], e->st));
   HIPCHK(hipMemcpyAsync(e->d_segtab, p.tab.data(), p.tab.size() * 8, hipMemcpyHostToDevice, e->st));
   HIPCHK(hipMemcpyAsync(e->d_wintab, p.wt.data(), p.wt.size() * 8, hipMemcpyHostToDevice, e->st));
-  if (B.bt) HIPCHK(hipMemcpyAsync(e->d_winblk, p.blk.data(), p.blk.size() * 4, hipMemcpyHostToDevice, e->st));
+  if (B.bt || B.bv) HIPCHK(hipMemcpyAsync(e->d_winblk, p.blk.data(), p.blk.size() * 4, hipMemcpyHostToDevice, e->st));
+  if (B.bv) HIPCHK(hipMemcpyAsync(e->d_windesc, B.pv->desc.data(), B.pv->desc.size() * 8, hipMemcpyHostToDevice, e->st));
   if (!em) ngd_launch_seg_weights(e->st, e->d_segtab, (uint32_t)p.n_ks, p.max_wkg, e->congruent ? e->sc.d : nullptr, e->blk.wslice);
   HIPCHK(hipEventRecord(e->ev[1], e->st));
   if (note)
@@ -330,7 +337,10 @@ static void slab_reduce_sums(ngd_engine *e, const SlabCall &B, double *bs, unsig
   const bool pdel = e->cfg.pairwise_del != 0;
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
   const ngd_fix_flags *ff = first && e->SM && !pdel ? &B.ff : nullptr;
-  if (!B.bt)
+  if (B.bv)  // (count and threshold are the window's own: the sites its replicates visit, from its descriptor)
+    ngd_launch_reduce_band_wv(e->st, e->g, B.seg_sums, nullptr, e->d_winblk, e->d_windesc, B.nb(), e->d_W.get(), B.stride, B.bv->n_rep,
+                              B.n_mat, e->d_tiles, e->n_tiles, bs + n_pairs, first && !pdel ? bc + n_pairs : nullptr, ff);
+  else if (!B.bt)
     ngd_launch_reduce_band(e->st, e->g, B.seg_sums, nullptr, e->d_wintab, B.nb(), e->d_tiles, e->n_tiles, bs,
                            first && !pdel ? bc : nullptr, ff, B.n_mat);
   else {
@@ -347,7 +357,10 @@ static void slab_reduce_sums(ngd_engine *e, const SlabCall &B, double *bs, unsig
 static void slab_counts(ngd_engine *e, const SlabCall &B, double *bs, unsigned long long *bc) {
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
   ngd_launch_count_blocks(e->st, e->g, e->mask, 0, (uint32_t)B.p.n_seg, e->d_tiles16, e->n_tiles16, B.seg_cnt, e->d_segtab);
-  if (!B.bt)
+  if (B.bv)
+    ngd_launch_reduce_band_wv(e->st, e->g, nullptr, B.seg_cnt, e->d_winblk, e->d_windesc, B.nb(), e->d_M.get(), B.stride, B.bv->n_rep,
+                              B.n_mat, e->d_tiles, e->n_tiles, nullptr, bc + n_pairs, nullptr);
+  else if (!B.bt)
     ngd_launch_reduce_band(e->st, e->g, nullptr, B.seg_cnt, e->d_wintab, B.nb(), e->d_tiles, e->n_tiles, nullptr, bc, nullptr, B.n_mat);
   else
     ngd_launch_reduce_band_w(e->st, e->g, nullptr, B.seg_cnt, e->d_winblk, B.nb(), (uint32_t)B.bt->n_blocks, e->d_M.get(), B.stride,
@@ -355,7 +368,7 @@ static void slab_counts(ngd_engine *e, const SlabCall &B, double *bs, unsigned l
   e->win_info.band_launches++;
   if (!e->SM) return;
   // (a job: over every matrix of the batch -- the windows' matrices 0 are in place already and hold their final sums)
-  if (B.bt) ngd_launch_fix_flag(e->st, e->g, bs, bc, B.nb() * B.n_mat, e->d_tiles, e->n_tiles, B.ff);
+  if (B.bt || B.bv) ngd_launch_fix_flag(e->st, e->g, bs, bc, B.nb() * B.n_mat, e->d_tiles, e->n_tiles, B.ff);
   else ngd_launch_fix_flag(e->st, e->g, bs, bc, B.nb(), e->d_tiles, e->n_tiles, B.ff, B.n_mat);
 }
 
@@ -461,10 +474,108 @@ static int windows_job_slab(ngd_engine *e, const uint64_t *lo, const uint64_t *h
   return windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, fits, bt);
 }
 
-// one call's windows into device memory [n_win][n_pairs] (a job, bt != NULL: [n_win][n_rep + 1][n_pairs]); the plan by
+// ---- jobs over windows of unequal length (ngd_run_windows_job_var*) ----
+// Window w has its own n_blocks_w = (hi - lo) / q and the maps of its class (WinBootVar, win_plan.h).  The two plans again:
+// per window, one job of one window each; and the unit slab, whose replicates come from the descriptor form of the banded
+// and weighted reduction (reduce.hip k_reduce_band_wv) -- the slices, the pass, matrix 0 and the fix-up are the job's.
+
+// the weight tables of the classes one batch holds, one after the other: Wt[row][r], as integers for the counts
+static int windows_var_weights(ngd_engine *e, const WinBootVar &bv, const win_batch_var &p, uint32_t stride) {
+  if (!p.wt_rows) return NGD_OK;
+  std::vector<double> Wt(p.wt_rows * stride, 0.0);
+  for (uint32_t c : p.cls_list) {
+    const uint64_t n_blocks = bv.cls_blocks[c];
+    const uint32_t *mult = bv.mult + bv.cls_mult[c];
+    for (uint32_t r = 0; r < bv.n_rep; r++)
+      for (uint64_t b = 0; b < n_blocks; b++) Wt[(p.cls_row[c] + b) * stride + r] = (double)mult[(uint64_t)r * n_blocks + b];
+  }
+  int rc = e->d_W.ensure(e, Wt.size());
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(e->d_W, Wt.data(), Wt.size() * 8, hipMemcpyHostToDevice));
+  if (!e->cfg.pairwise_del) return NGD_OK;
+  std::vector<uint32_t> M(Wt.size());
+  for (size_t k = 0; k < M.size(); k++) M[k] = (uint32_t)Wt[k];
+  if ((rc = e->d_M.ensure(e, M.size()))) return rc;
+  HIPCHK(hipMemcpy(e->d_M, M.data(), M.size() * 4, hipMemcpyHostToDevice));
+  return NGD_OK;
+}
+
+// the unit slab, batch by batch: the replicates alone into [n_win][n_rep + 1][n_pairs] (matrix 0: windows_job_slab_var)
+static int windows_slab_var(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
+                            unsigned long long *d_cnt, uint64_t budget, const WinBootVar &bv) {
+  const win_env v = windows_env(e, nullptr, bv.n_rep);
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = (uint64_t)bv.n_rep + 1;
+  const uint32_t stride = win_weight_stride_var(v, bv.n_rep);
+  win_batch_var p;
+  std::vector<uint64_t> all;  // (the call's boundaries: a batch's slices do not depend on where the budget cuts the call)
+  win_call_boundaries_var(lo, hi, n_win, bv.q, all);
+  const SlabCall B{p, nullptr, e->blk.borrow_sums(), e->blk.borrow_counts(),
+                   ngd_fix_flags{e->d_fixlist, e->d_fixcount, e->d_fixseen, e->fix_cap}, (uint32_t)n_mat, stride, &bv, &p};
+  uint64_t batch = 0;
+  for (uint64_t a = 0; a < n_win; a = p.b, batch++) {
+    win_plan_batch_var(v, lo, hi, n_win, a, budget, bv, all, p);
+    double *bs = d_sum + a * n_mat * n_pairs;
+    unsigned long long *bc = d_cnt + a * n_mat * n_pairs;
+    int rc = windows_var_weights(e, bv, p, stride);
+    if (!rc) rc = slab_batch(e, B, bs, bc, p.hi_max - lo[a], batch > 0);
+    if (rc) return rc;
+    e->win_info.segments += p.n_seg;
+    e->win_info.slab_bytes = std::max<uint64_t>(e->win_info.slab_bytes, (p.n_ks * 8 + (v.pdel ? p.n_seg * 4 : 0)) * v.plane);
+    e->win_info.batches++;
+    if (!e->SM) continue;
+    // one-image engines: the noted pairs' slab entries exactly, then the weighted reductions of the batch again
+    bool patched = false;
+    if ((rc = windows_job_fixup(e, p.tab, p.n_seg, B.seg_sums, B.nb() * n_mat, &patched))) return rc;
+    if (patched) {
+      HIPCHK(hipEventRecord(e->ev[0], e->st));
+      slab_reduce_sums(e, B, bs, bc, false);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(e->ev[1], e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
+      float ms2 = 0;
+      hipEventElapsedTime(&ms2, e->ev[0], e->ev[1]);
+      e->fix_info.ms += ms2;
+      e->win_info.ms += ms2;
+    }
+  }
+  return NGD_OK;
+}
+
+// the slab plan: matrix 0 of every window from the windows' own segments (as windows_job_slab), the replicates from the unit slab
+static int windows_job_slab_var(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
+                                unsigned long long *d_cnt, uint64_t budget, bool *fits, const WinBootVar &bv) {
+  if (!(*fits = win_each_fits_var(windows_env(e, nullptr, bv.n_rep), lo, hi, n_win, bv, budget))) return NGD_OK;
+  bool fits0 = true;
+  if (int rc = windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits0, nullptr, (uint64_t)bv.n_rep + 1)) return rc;
+  if (!fits0) return fail(NGD_E_NOMEM, "ngd_run_windows_job_var: internal -- a window fits the unit slab and not its own segment");
+  return windows_slab_var(e, lo, hi, n_win, d_sum, d_cnt, budget, bv);
+}
+
+// the per-window plan: the job of one window, with that window's maps; a window shorter than one block: its matrix 0 by a
+// pass of its own, its replicates sum 0 and count 0 (ngsDist.cpp:236)
+static int windows_job_by_pass_var(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBootVar &bv,
+                                   double *d_sum, unsigned long long *d_cnt) {
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = (uint64_t)bv.n_rep + 1;
+  for (uint64_t w = 0; w < n_win; w++) {
+    double *ws = d_sum + w * n_mat * n_pairs;
+    unsigned long long *wc = d_cnt + w * n_mat * n_pairs;
+    if (bv.cls[w] == NGD_WIN_NO_CLASS) {
+      if (int rc = windows_by_pass(e, lo + w, hi + w, 1, ws, wc)) return rc;
+      HIPCHK(hipMemsetAsync(ws + n_pairs, 0, (size_t)bv.n_rep * n_pairs * 8, e->st));
+      HIPCHK(hipMemsetAsync(wc + n_pairs, 0, (size_t)bv.n_rep * n_pairs * 8, e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
+      continue;
+    }
+    const WinBoot bt{bv.n_rep, bv.cls_blocks[bv.cls[w]], bv.q, bv.mult + bv.cls_mult[bv.cls[w]]};
+    if (int rc = windows_job_by_pass(e, lo + w, hi + w, 1, bt, ws, wc)) return rc;
+  }
+  return NGD_OK;
+}
+
+// one call's windows into device memory [n_win][n_pairs] (a job, bt or bv != NULL: [n_win][n_rep + 1][n_pairs]); the plan by
 // NGD_OPT_WIN_PLAN
 static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, double *d_sum,
-                        unsigned long long *d_cnt, const WinBoot *bt = nullptr) {
+                        unsigned long long *d_cnt, const WinBoot *bt = nullptr, const WinBootVar *bv = nullptr) {
   HIPCHK(hipSetDevice(e->device));
   if (int rc = eager_discard(e)) return rc;
   e->spill_timing = ngd_spill_timing{};
@@ -493,8 +604,11 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     // 1000 individuals, the sites before a window loaded and skipped -- + ~0.1 ms of launches and waits)
     uint64_t covered = 0, sum_len = 0, end = 0;
     std::vector<uint64_t> bnd, wb;  // (every window's boundaries: its ends, and in a job the starts of its blocks)
+    uint64_t blk_entries = 0;       // (a job over windows of unequal length: its rows of block starts)
     for (uint64_t w = 0; w < n_win; w++) {
-      win_boundaries(lo[w], hi[w], bt, wb);
+      const WinBoot one{0, bv ? (hi[w] - lo[w]) / bv->q : 0, bv ? bv->q : 0, nullptr};
+      blk_entries += one.n_blocks + 1;
+      win_boundaries(lo[w], hi[w], bv ? &one : bt, wb);
       bnd.insert(bnd.end(), wb.begin(), wb.end());
     }
     std::sort(bnd.begin(), bnd.end());
@@ -508,9 +622,29 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
     // 160 slices: 224.8 ms -- DESIGN.md section 6; the plain pass's 2.22e8)
     const double rate = em ? 2.22e8 : 1.05e10, np = (double)e->n_owned_pairs;
     const double plane_b = (double)e->g.n_pad * e->g.n_pad * 8;
-    const double need = (double)win_batch_bytes(windows_env(e, bt), std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1), end, n_win, bt);
+    const uint64_t seg_ub = std::min<uint64_t>(n_bnd, budget / (uint64_t)plane_b + 1);
+    const double need = bv ? (double)win_batch_bytes_var(windows_env(e, nullptr, bv->n_rep), seg_ub, end, n_win, blk_entries, 0, bv->n_rep)
+                           : (double)win_batch_bytes(windows_env(e, bt), seg_ub, end, n_win, bt);
     const double have = (double)e->blk.bytes();
-    if (!bt) {
+    if (bv) {
+      // A job over windows of unequal length.  [predicted -- the legs of the equal-length job below with every window's own
+      // length and blocks.  tools/bench_windows_boot.py --bp (1000 x 1e5, 96 windows of ~990 sites,
+      // 100 replicates) ranks the plans as this estimate does -- unit slab 42 .. 351 ms, per window 2.6 .. 3.7 s -- but
+      // gives no rates yet; where blocks of 10 sites of overlapping windows interleave, a slab per window beats both]
+      const double n_mat = (double)bv->n_rep + 1, chunks = (double)((bv->n_rep + 31) / 32);
+      const double t_slab = np * (2.0 * (double)covered + (em ? 0.0 : 12.0) * (double)n_bnd) / rate + (double)n_bnd * plane_b / 4e9 +
+                            (double)(4 * n_win) * np * 8 / 4e9 +
+                            ((double)n_bnd + chunks * (double)blk_entries + (double)n_win * 2 * n_mat) * np * 8 / 4e9 +
+                            (need > have ? (need - have) * 12e-9 : 0.0);
+      double t_pass = 0;
+      for (uint64_t w = 0; w < n_win; w++) {
+        const uint64_t B = std::gcd(std::gcd(lo[w], bv->q), hi[w]);
+        const double by_matrix = n_mat * np * (double)(hi[w] - lo[w]) / (0.75 * rate);
+        const double shared = np * (double)hi[w] / rate * (em ? 1.1 : 1.0) + (em ? 0.0 : chunks * (double)(hi[w] / B) * np * 8 / 4e9);
+        t_pass += ((em || B % 4 == 0) ? std::min(by_matrix, shared) : by_matrix) + 0.1 + n_mat * np * 16 / 4e9;
+      }
+      slab = t_slab < t_pass;
+    } else if (!bt) {
       const double t_slab = np * (double)covered / rate + (double)(n_bnd + 2 * n_win) * np * 8 / 4e9 +
                             (need > have ? (need - have) * 12e-9 : 0.0);
       const double t_pass = np * (double)sum_len / (0.75 * rate) + 0.1 * (double)n_win;
@@ -543,7 +677,8 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   }
   if (slab) {
     bool fits = true;
-    int rc = bt ? windows_job_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits, bt)
+    int rc = bv ? windows_job_slab_var(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits, *bv)
+           : bt ? windows_job_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits, bt)
                 : windows_slab(e, lo, hi, n_win, d_sum, d_cnt, budget, &fits);
     if (rc || fits) return rc;
     if (e->opt_win_plan == 2)
@@ -553,27 +688,28 @@ static int windows_impl(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
                                "NGD_OPT_EM_EXACT = 1 with NGD_OPT_EM_EXACT_WIN has no other plan (the per-window plan needs "
                                "NGD_OPT_EM_EXACT = 2); nothing was computed");
   }
+  if (bv) return windows_job_by_pass_var(e, lo, hi, n_win, *bv, d_sum, d_cnt);
   if (bt) return windows_job_by_pass(e, lo, hi, n_win, *bt, d_sum, d_cnt);
   return windows_by_pass(e, lo, hi, n_win, d_sum, d_cnt);
 }
 
 // the device-memory forms: [n_win][n_pairs] (a job, bt != NULL: [n_win][n_rep + 1][n_pairs]) where the caller says
 static int windows_device(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt, void *d_sum,
-                          void *d_cnt, const char *who) {
+                          void *d_cnt, const char *who, const WinBootVar *bv = nullptr) {
   if (!d_sum || !d_cnt) return fail(NGD_E_INVALID, std::string(who) + ": null output");
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
   e->n_batch_valid = 0;
   if (e->opt_em_exact_win) em_exact_call_begin(e);
-  return windows_impl(e, lo, hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, bt);
+  return windows_impl(e, lo, hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, bt, bv);
 }
 
 // the host-memory forms: windows in groups whose results fit ~2 GB of the engine's batch buffers; fn(first, count) takes
 // each group's results out of d_bsum / d_bcnt
-// (a job, bt != NULL: n_rep + 1 matrices per window, at least one window per group)
+// (a job, bt or bv != NULL: n_rep + 1 matrices per window, at least one window per group)
 static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win,
-                           const std::function<int(uint64_t, uint64_t)> &fn, const WinBoot *bt) {
-  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = bt ? (uint64_t)bt->n_rep + 1 : 1;
+                           const std::function<int(uint64_t, uint64_t)> &fn, const WinBoot *bt, const WinBootVar *bv) {
+  const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = bv ? (uint64_t)bv->n_rep + 1 : bt ? (uint64_t)bt->n_rep + 1 : 1;
   const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (16 * n_mat * std::max<uint64_t>(1, n_pairs))));
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
@@ -582,7 +718,8 @@ static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
   if (rc) return rc;
   for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
     const uint64_t n = std::min(per, n_win - w0);
-    if ((rc = windows_impl(e, lo + w0, hi + w0, n, e->d_bsum, e->d_bcnt, bt))) return rc;
+    const WinBootVar from = bv ? bv->from(w0) : WinBootVar{};
+    if ((rc = windows_impl(e, lo + w0, hi + w0, n, e->d_bsum, e->d_bcnt, bt, bv ? &from : nullptr))) return rc;
     if ((rc = fn(w0, n))) return rc;
   }
   e->n_batch_valid = 0;
@@ -591,28 +728,29 @@ static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
 
 // ... sums and counts (either may be NULL), bt == NULL: the windows alone
 static int windows_host(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt, double *sum,
-                        uint64_t *cnt) {
+                        uint64_t *cnt, const WinBootVar *bv = nullptr) {
   HIPCHK(hipSetDevice(e->device));
-  const uint32_t n_mat = bt ? bt->n_rep + 1 : 1;
+  const uint32_t n_mat = bv ? bv->n_rep + 1 : bt ? bt->n_rep + 1 : 1;
   const uint64_t per_win = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
   return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
     int rc = copy_out(e, (uint32_t)(n * n_mat), e->d_bsum, e->d_bcnt, sum ? sum + w0 * per_win : nullptr,
                       cnt ? cnt + w0 * per_win : nullptr);
     e->n_batch_valid = 0;
     return rc;
-  }, bt);
+  }, bt, bv);
 }
 
 // ... distances: the tail of gen_dist() on every matrix
 static int windows_host_dist(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt,
-                             uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who) {
+                             uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who,
+                             const WinBootVar *bv = nullptr) {
   const std::string w(who);
   if (!dist) return fail(NGD_E_INVALID, w + ": null argument");
   if (tot_sites && e->cfg.pairwise_del)
     return fail(NGD_E_INVALID, w + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
   if (evol_model > 2) return fail(NGD_E_MODEL, w + ": evolutionary model not supported (ngsDist.cpp:398-399)");
   HIPCHK(hipSetDevice(e->device));
-  const uint32_t n_mat = bt ? bt->n_rep + 1 : 1;
+  const uint32_t n_mat = bv ? bv->n_rep + 1 : bt ? bt->n_rep + 1 : 1;
   const uint64_t per_win = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
   std::vector<double> h_sum;
   std::vector<uint64_t> h_cnt;
@@ -624,7 +762,7 @@ static int windows_host_dist(ngd_engine *e, const uint64_t *lo, const uint64_t *
     if (rc) return rc;
     // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
     return ngd_finish(h_sum.data(), h_cnt.data(), n * per_win, tot_sites, evol_model, dist + w0 * per_win);
-  }, bt);
+  }, bt, bv);
 }
 
 int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, void *d_sum,
@@ -702,6 +840,88 @@ int ngd_run_windows_job_dist(ngd_engine *e, const uint64_t *win_lo, const uint64
     return rc;
   if (!n_rep) return ngd_run_windows_dist(e, win_lo, win_hi, n_win, tot_sites, evol_model, dist);
   return windows_host_dist(e, win_lo, win_hi, n_win, &bt, tot_sites, evol_model, dist, "ngd_run_windows_job_dist");
+}
+
+// ---- ngd_run_windows_job_var*: the arguments, and every class's multiplicities counted from its block maps ----
+// (a class: the windows that share map_off and n_blocks -- one set of maps, checked and counted once, one weight table)
+struct WinVarStore {
+  std::vector<uint32_t> cls, mult;
+  std::vector<uint64_t> cls_blocks, cls_mult;
+};
+
+static int windows_job_var_check(const ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps,
+                                 uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep, uint64_t q, const char *who,
+                                 WinVarStore &st, WinBootVar &bv) {
+  if (!e) return fail(NGD_E_INVALID, std::string(who) + ": null engine");
+  if (int rc = em_exact_refuse(e, who)) return rc;  // (per-window weights are not patched: neither value of the option serves it)
+  if (int rc = windows_check(e, lo, hi, n_win, who)) return rc;
+  if (!n_rep) return NGD_OK;  // (the windows alone: the maps and block_size are not read)
+  const std::string w(who);
+  if (!q) return fail(NGD_E_INVALID, w + ": block size 0");
+  if (!map_off) return fail(NGD_E_INVALID, w + ": null map offsets");
+  if (n_win * ((uint64_t)n_rep + 1) >= (1ull << 31)) return fail(NGD_E_INVALID, w + ": too many matrices in one call");
+  if (n_rep > (1u << 20)) return fail(NGD_E_INVALID, w + ": more than 2^20 replicates in one call");  // (grid.y: chunks of 32)
+  std::map<std::pair<uint64_t, uint64_t>, uint32_t> ids;
+  st.cls.assign(n_win, NGD_WIN_NO_CLASS);
+  for (uint64_t k = 0; k < n_win; k++) {
+    const uint64_t n_blocks = (hi[k] - lo[k]) / q;
+    if (!n_blocks) continue;  // (no block: no entries, the offset is not read)
+    if (!maps) return fail(NGD_E_INVALID, w + ": null block maps");
+    const auto ins = ids.emplace(std::make_pair(map_off[k], n_blocks), (uint32_t)st.cls_blocks.size());
+    st.cls[k] = ins.first->second;
+    if (!ins.second) continue;
+    const uint64_t len = (uint64_t)n_rep * n_blocks;
+    if (map_off[k] > maps_len || len > maps_len - map_off[k])
+      return fail(NGD_E_INVALID, w + ": the block maps of window " + std::to_string(k) + " reach past maps_len");
+    const uint64_t at = st.mult.size();
+    st.cls_blocks.push_back(n_blocks);
+    st.cls_mult.push_back(at);
+    st.mult.resize(at + len, 0u);
+    for (uint32_t r = 0; r < n_rep; r++)
+      for (uint64_t b = 0; b < n_blocks; b++) {
+        const uint64_t src = maps[map_off[k] + (uint64_t)r * n_blocks + b];
+        if (src >= n_blocks) return fail(NGD_E_INVALID, w + ": block_map entry out of range (window " + std::to_string(k) + ")");
+        st.mult[at + (uint64_t)r * n_blocks + src]++;
+      }
+  }
+  bv = WinBootVar{n_rep, q, (uint32_t)st.cls_blocks.size(), st.cls.data(), st.cls_blocks.data(), st.cls_mult.data(), st.mult.data()};
+  return NGD_OK;
+}
+
+int ngd_run_windows_job_var_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                   const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                   uint64_t block_size, void *d_sum, void *d_cnt) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = windows_job_var_check(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size,
+                                     "ngd_run_windows_job_var_device", st, bv))
+    return rc;
+  if (!n_rep) return ngd_run_windows_device(e, win_lo, win_hi, n_win, d_sum, d_cnt);
+  return windows_device(e, win_lo, win_hi, n_win, nullptr, d_sum, d_cnt, "ngd_run_windows_job_var_device", &bv);
+}
+
+int ngd_run_windows_job_var(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, const uint64_t *block_maps,
+                            uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, double *sum,
+                            uint64_t *cnt) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = windows_job_var_check(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size,
+                                     "ngd_run_windows_job_var", st, bv))
+    return rc;
+  if (!n_rep) return ngd_run_windows(e, win_lo, win_hi, n_win, sum, cnt);
+  return windows_host(e, win_lo, win_hi, n_win, nullptr, sum, cnt, &bv);
+}
+
+int ngd_run_windows_job_var_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                 const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                 uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *dist) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = windows_job_var_check(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size,
+                                     "ngd_run_windows_job_var_dist", st, bv))
+    return rc;
+  if (!n_rep) return ngd_run_windows_dist(e, win_lo, win_hi, n_win, tot_sites, evol_model, dist);
+  return windows_host_dist(e, win_lo, win_hi, n_win, nullptr, tot_sites, evol_model, dist, "ngd_run_windows_job_var_dist", &bv);
 }
 
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {

@@ -69,6 +69,7 @@
 #pragma weak ngd_run_windows_dist
 #pragma weak ngd_last_windows
 #pragma weak ngd_run_windows_job_dist  // (--win_boot_rep)
+#pragma weak ngd_run_windows_job_var_dist  // (--win_boot_rep under --win_bp: windows of unequal length)
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -108,6 +109,11 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // per window what the reference prints for the cut-down file with --n_boot_rep.  Not --n_boot_rep, which resamples the genome.
   bool win_boot = false;
   uint64_t win_boot_rep = 0;
+  // --win_bp / --win_bp_step / --win_min_sites: the same windows in coordinates -- window k of a chromosome covers the
+  // positions [1 + k step, 1 + k step + size) of the positions file's second column, kept if it holds --win_min_sites sites.
+  // Turns on --win_size's flow (win is set): its refusals, plans and files; --win_boot_rep draws per-window maps.
+  bool win_bp = false, win_bp_step_set = false, win_min_sites_set = false;
+  long long win_bp_size = 0, win_bp_step = 0, win_min_sites = 1;
   // --em_exact: on the EM path the full-data pass stops every (pair, site) at the reference's EM step (NGD_OPT_EM_EXACT: the
   // stops within rounding of the tolerance are rerun on the host).  Not in the reference.
   bool em_exact = false;
@@ -225,6 +231,9 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"em_exact", no_argument, nullptr, 1014},
                                  {"em_exact_boot", no_argument, nullptr, 1015},
                                  {"em_exact_win", no_argument, nullptr, 1016},
+                                 {"win_bp", required_argument, nullptr, 1017},
+                                 {"win_bp_step", required_argument, nullptr, 1018},
+                                 {"win_min_sites", required_argument, nullptr, 1019},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -263,6 +272,9 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1014: p.em_exact = true; break;
       case 1015: p.em_exact_boot = true; break;
       case 1016: p.em_exact_win = true; break;
+      case 1017: p.win_bp = true; p.win_bp_size = strtoll(optarg, nullptr, 10); break;
+      case 1018: p.win_bp_step_set = true; p.win_bp_step = strtoll(optarg, nullptr, 10); break;
+      case 1019: p.win_min_sites_set = true; p.win_min_sites = strtoll(optarg, nullptr, 10); break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -304,6 +316,9 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
             p.boot_block_size, p.out, p.n_threads, p.verbose, p.seed, kVersion);
     if (p.win || p.win_step_set)
       fprintf(stderr, "\twin_size: %lu\n\twin_step: %lu\n\n", p.win_size, p.win_step_set ? p.win_step : p.win_size);
+    if (p.win_bp || p.win_bp_step_set || p.win_min_sites_set)
+      fprintf(stderr, "\twin_bp: %lld\n\twin_bp_step: %lld\n\twin_min_sites: %lld\n\n", p.win_bp_size,
+              p.win_bp_step_set ? p.win_bp_step : p.win_bp_size, p.win_min_sites);
     if (p.win_boot) fprintf(stderr, "\twin_boot_rep: %lu\n\n", p.win_boot_rep);
     if (p.em_exact) fprintf(stderr, "\tem_exact: true\n\n");
     if (p.em_exact_boot) fprintf(stderr, "\tem_exact_boot: true\n\n");
@@ -325,6 +340,18 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
   if (p.n_threads < 1) die(__FUNCTION__, "number of threads cannot be less than 1!");
   if (p.n_gpus < 1) die(__FUNCTION__, "number of GPUs cannot be less than 1!");
   if (p.boot_block_size < 1) die(__FUNCTION__, "bootstrap block size cannot be less than 1!");
+  if (p.win_bp && p.win) die(__FUNCTION__, "windows in base pairs (--win_bp) cannot be combined with windows in sites (--win_size)!");
+  if (p.win_bp_step_set && !p.win_bp) die(__FUNCTION__, "window step in base pairs (--win_bp_step) requires a window size in base pairs (--win_bp)!");
+  if (p.win_min_sites_set && !p.win_bp) die(__FUNCTION__, "minimum number of sites per window (--win_min_sites) requires a window size in base pairs (--win_bp)!");
+  if (p.win_bp) {
+    if (!p.win_bp_step_set) p.win_bp_step = p.win_bp_size;
+    if (p.win_bp_size < 1) die(__FUNCTION__, "window size in base pairs (--win_bp) cannot be less than 1!");
+    if (p.win_bp_step < 1) die(__FUNCTION__, "window step in base pairs (--win_bp_step) cannot be less than 1!");
+    if (p.win_min_sites < 1) die(__FUNCTION__, "minimum number of sites per window (--win_min_sites) cannot be less than 1!");
+    if (!p.in_pos) die(__FUNCTION__, "windows in base pairs (--win_bp) require a positions file (--pos / --posH)!");
+    if (p.win_step_set) die(__FUNCTION__, "window step (--win_step) requires a window size (--win_size)!");
+    p.win = true;  // from here on --win_size's flow, with its refusals
+  }
   if (p.win_step_set && !p.win) die(__FUNCTION__, "window step (--win_step) requires a window size (--win_size)!");
   if (p.win_boot && !p.win) die(__FUNCTION__, "bootstrap replicates inside windows (--win_boot_rep) require a window size (--win_size)!");
   if (p.win_boot && p.n_boot_rep > 0)
@@ -347,12 +374,16 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.indep_geno || p.call_geno || !p.in_probs)
       die(__FUNCTION__, "the reference's EM stopping step (--em_exact_win) belongs to the EM path: not with --indep_geno / --call_geno or genotype input!");
     if (!p.win) die(__FUNCTION__, "the reference's EM stopping step inside windows (--em_exact_win) needs windows (--win_size)!");
+    if (p.win_bp && p.win_boot_rep)
+      die(__FUNCTION__, "the reference's EM stopping step inside windows (--em_exact_win) serves plain windows in base pairs (--win_bp) only: not with --win_boot_rep!");
     p.eager = 0;
   }
   if (p.win) {
-    if (!p.win_step_set) p.win_step = p.win_size;
-    if (p.win_size < 1) die(__FUNCTION__, "window size (--win_size) cannot be less than 1!");
-    if (p.win_step < 1) die(__FUNCTION__, "window step (--win_step) cannot be less than 1!");
+    if (!p.win_bp) {
+      if (!p.win_step_set) p.win_step = p.win_size;
+      if (p.win_size < 1) die(__FUNCTION__, "window size (--win_size) cannot be less than 1!");
+      if (p.win_step < 1) die(__FUNCTION__, "window step (--win_step) cannot be less than 1!");
+    }
     if (p.n_boot_rep > 0) die(__FUNCTION__, "windows (--win_size) cannot be combined with bootstrap replicates (--n_boot_rep)!");
     if (p.n_gpus > 1) die(__FUNCTION__, "windows (--win_size) are computed on one GPU (--n_gpus 1)!");
   }
@@ -1153,6 +1184,7 @@ int main(int argc, char **argv) {
   // and coordinates of --win_size's windows
   std::vector<uint32_t> win_chrom;
   std::vector<std::string> win_pos_txt;
+  std::vector<uint64_t> win_pos;  // --win_bp: the coordinates as numbers
   std::unordered_map<uint32_t, std::string> win_chr_name;
   if (p.in_pos) {
     if (p.verbose >= 1) fprintf(stderr, "==> Reading positions file\n");
@@ -1177,11 +1209,37 @@ int main(int argc, char **argv) {
         win_pos_txt[s] = l.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
         if (s == 0 || win_chrom[s] != win_chrom[s - 1]) win_chr_name.emplace(win_chrom[s], chr);
       }
+      if (p.win_bp) {  // whole numbers from 1 (below 2^62: ngd_window_ranges_bp) that do not descend inside a chromosome
+        win_pos.resize(p.n_sites);
+        for (uint64_t s = 0; s < p.n_sites; s++) {
+          const std::string &t = win_pos_txt[s];
+          const bool digits = !t.empty() && t.size() <= 18 && t.find_first_not_of("0123456789") == std::string::npos;
+          win_pos[s] = digits ? strtoull(t.c_str(), nullptr, 10) : 0;
+          if (!win_pos[s]) die(__FUNCTION__, "invalid position in POS file: windows in base pairs (--win_bp) need whole numbers from 1!");
+          if (s && win_chrom[s] == win_chrom[s - 1] && win_pos[s] < win_pos[s - 1])
+            die(__FUNCTION__, "positions descend inside a chromosome of the POS file: windows in base pairs (--win_bp) need them in ascending order!");
+        }
+      }
     }
   }
   // the windows (--win_size / --win_step): the list the Python package makes too (host_util.cpp ngd_window_ranges)
-  std::vector<uint64_t> win_lo, win_hi;
-  if (p.win) {
+  std::vector<uint64_t> win_lo, win_hi, win_bp_start;
+  if (p.win_bp) {
+    const uint64_t B = (uint64_t)p.win_bp_size, T = (uint64_t)p.win_bp_step, M = (uint64_t)p.win_min_sites;
+    const int64_t n_win = ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, nullptr, nullptr, nullptr, 0);
+    if (n_win < 0) die(__FUNCTION__, "positions file not grouped by chromosome!");
+    if (n_win == 0) die(__FUNCTION__, "no window is kept (--win_min_sites larger than every window's number of sites)!");
+    win_lo.resize((size_t)n_win);
+    win_hi.resize((size_t)n_win);
+    win_bp_start.resize((size_t)n_win);
+    ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, win_lo.data(), win_hi.data(), win_bp_start.data(),
+                         (uint64_t)n_win);
+    if (!ngd_run_windows_dist)
+      die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
+    if (p.win_boot_rep && !ngd_run_windows_job_var_dist)
+      die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!");
+    if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu bp every %lu bp\n", (unsigned long)n_win, (unsigned long)B, (unsigned long)T);
+  } else if (p.win) {
     const uint32_t *ids = win_chrom.empty() ? nullptr : win_chrom.data();
     const int64_t n_win = ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, nullptr, nullptr, 0);
     if (n_win < 0) die(__FUNCTION__, "positions file not grouped by chromosome!");
@@ -1541,8 +1599,20 @@ int main(int argc, char **argv) {
     // concatenation of the cut-down runs' files.  Every cut-down run seeds the generator anew and the windows have one
     // length, so ONE set of block maps, drawn from a fresh state, serves them all (ngsDist.cpp:179-180, :235-238, :416-437)
     const uint64_t R = p.win_boot_rep, n_mat = R + 1;
-    const uint64_t wb_blocks = R ? p.win_size / p.boot_block_size : 0;
+    const uint64_t wb_blocks = R && !p.win_bp ? p.win_size / p.boot_block_size : 0;
     std::vector<uint64_t> wb_maps(R * wb_blocks);
+    // --win_bp: the windows differ in length, every one draws the maps of its own cut-down run (ngd_window_boot_maps); a
+    // window shorter than one block comes back as sum 0 and count 0, printed as 0 / 0 by the call itself
+    std::vector<uint64_t> wb_off;
+    if (R && p.win_bp) {
+      wb_off.resize(n_win);
+      const int64_t len = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0,
+                                               wb_off.data());
+      if (len < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
+      wb_maps.resize((size_t)len + 1);  // (+ 1: never a null table, even where no window holds a block)
+      ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, wb_maps.data(), (uint64_t)len,
+                           wb_off.data());
+    }
     if (R && wb_blocks) {
       uint32_t wrng[3];
       ngd_taus_seed(wrng, p.seed);
@@ -1557,14 +1627,18 @@ int main(int argc, char **argv) {
       if (ngd_finish(zs.data(), zc.data(), n_comb, p.tot_sites, p.evol_model, wb_empty.data()))
         die("gen_dist", "invalid evolutionary model specified!");
     }
-    const bool job = R && wb_blocks;
+    const bool job = R && (wb_blocks || p.win_bp);
     const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * (job ? n_mat : 1) * std::max<uint64_t>(1, n_comb))));
     std::vector<double> wd;
     for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
       const uint64_t n = std::min(per, n_win - w0);
       const auto t_c0 = std::chrono::steady_clock::now();
       wd.resize(n * (job ? n_mat : 1) * n_comb);
-      if (job) {
+      if (job && p.win_bp) {
+        const int rc = ngd_run_windows_job_var_dist(eng.h, &win_lo[w0], &win_hi[w0], n, wb_maps.data(), wb_maps.size() - 1, &wb_off[w0],
+                                                    (uint32_t)R, p.boot_block_size, p.tot_sites, p.evol_model, wd.data());
+        if (rc) die_engine("ngd_run_windows_job_var_dist", rc);
+      } else if (job) {
         const int rc = ngd_run_windows_job_dist(eng.h, &win_lo[w0], &win_hi[w0], n, wb_maps.data(), (uint32_t)R, wb_blocks,
                                                 p.boot_block_size, p.tot_sites, p.evol_model, wd.data());
         if (rc) die_engine("ngd_run_windows_job_dist", rc);
@@ -1593,10 +1667,13 @@ int main(int argc, char **argv) {
     const std::string wpath = std::string(p.out) + ".windows";
     FILE *wf = fopen(wpath.c_str(), "w");
     if (!wf) die(__FUNCTION__, "cannot open windows output file!");
-    fprintf(wf, "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
+    fprintf(wf, p.win_bp ? "window\tchr\tstart\tend\tfirst_site\tn_sites\twin_start\twin_end\n" : "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
     for (uint64_t w = 0; w < n_win; w++) {
       const uint64_t lo = win_lo[w], hi = win_hi[w];
-      if (win_chrom.empty())
+      if (p.win_bp)  // (+ the window's own coordinates, inclusive: 1 + k T and k T + B)
+        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
+                win_pos_txt[hi - 1].c_str(), lo, hi - lo, win_bp_start[w], win_bp_start[w] + (uint64_t)p.win_bp_size - 1);
+      else if (win_chrom.empty())
         fprintf(wf, "%lu\t.\t%lu\t%lu\t%lu\t%lu\n", w, lo + 1, hi, lo, hi - lo);
       else
         fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),

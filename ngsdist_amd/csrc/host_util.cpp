@@ -593,6 +593,91 @@ int64_t ngd_window_ranges(const uint32_t *chrom_id, uint64_t n_sites, uint64_t s
   return (int64_t)count;
 }
 
+// Windows in coordinates: window k of a chromosome covers [1 + k step_bp, 1 + k step_bp + size_bp).  Positions ascend inside
+// a chromosome, so the sites of a window are a range [a, b) and both ends only move forwards.  A window that holds fewer than
+// `need` sites can reach `need` only by gaining the site at b: the walk goes straight to the first window that does, so its
+// time is sites + kept windows, whatever the coordinate span.
+int64_t ngd_window_ranges_bp(const uint32_t *chrom_id, const uint64_t *pos, uint64_t n_sites, uint64_t size_bp, uint64_t step_bp,
+                             uint64_t min_sites, uint64_t *lo, uint64_t *hi, uint64_t *bp_start, uint64_t cap) {
+  const uint64_t lim = 1ull << 62;
+  if (!size_bp || !step_bp || !pos || size_bp >= lim) return NGD_E_INVALID;
+  const uint64_t need = std::max<uint64_t>(1, min_sites);
+  std::unordered_set<uint32_t> seen;
+  uint64_t count = 0;
+  for (uint64_t c0 = 0; c0 < n_sites;) {
+    uint64_t c1 = c0 + 1;
+    if (chrom_id) {
+      while (c1 < n_sites && chrom_id[c1] == chrom_id[c0]) c1++;
+      if (!seen.insert(chrom_id[c0]).second) return NGD_E_INVALID;
+    } else {
+      c1 = n_sites;
+    }
+    for (uint64_t s = c0; s < c1; s++)
+      if (!pos[s] || pos[s] >= lim || (s > c0 && pos[s] < pos[s - 1])) return NGD_E_INVALID;
+    const uint64_t k_max = (pos[c1 - 1] - 1) / step_bp;
+    uint64_t a = c0, b = c0;
+    for (uint64_t k = 0; k <= k_max;) {
+      const uint64_t start = 1 + k * step_bp;
+      while (a < c1 && pos[a] < start) a++;
+      if (b < a) b = a;
+      while (b < c1 && pos[b] < start + size_bp) b++;
+      if (b - a >= need) {
+        if (count < cap) {
+          if (lo) lo[count] = a;
+          if (hi) hi[count] = b;
+          if (bp_start) bp_start[count] = start;
+        }
+        count++;
+        k++;
+        continue;
+      }
+      if (b == c1) break;  // (nothing left to gain)
+      // the first window whose end passes pos[b]: 1 + k' step + size > pos[b]
+      const uint64_t gain = pos[b] > size_bp ? (pos[b] - size_bp - 1) / step_bp + 1 : 0;
+      k = std::max(k + 1, gain);
+    }
+    c0 = c1;
+  }
+  return (int64_t)count;
+}
+
+// The block maps of windows of unequal length.  A run of the reference on a window's cut-down file seeds its generator
+// anew (ngsDist.cpp:179-180) and draws n_rep maps of n_blocks = L / block_size blocks (:236, :416-437): what it draws
+// depends on n_blocks alone, so windows with one n_blocks -- those of one length among them -- share one set of maps.
+int64_t ngd_window_boot_maps(uint64_t seed, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint32_t n_rep,
+                             uint64_t block_size, uint64_t *block_maps, uint64_t cap, uint64_t *map_off) {
+  if (!block_size || (n_win && (!lo || !hi || !map_off))) return NGD_E_INVALID;
+  for (uint64_t w = 0; w < n_win; w++)
+    if (hi[w] < lo[w]) return NGD_E_INVALID;
+  std::vector<uint64_t> order(n_win);  // windows by n_blocks, then by index: a class's offset is set where it first appears
+  for (uint64_t w = 0; w < n_win; w++) order[w] = w;
+  auto nb = [&](uint64_t w) { return (hi[w] - lo[w]) / block_size; };
+  std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return nb(x) != nb(y) ? nb(x) < nb(y) : x < y; });
+  std::vector<uint64_t> first;  // the first window of every class, then in call order
+  for (uint64_t k = 0; k < n_win; k++)
+    if (!k || nb(order[k]) != nb(order[k - 1])) first.push_back(order[k]);
+  std::sort(first.begin(), first.end());
+  uint64_t total = 0;
+  std::vector<uint64_t> m;
+  for (uint64_t w : first) {
+    const uint64_t n_blocks = nb(w);
+    map_off[w] = n_blocks && n_rep ? total : 0;
+    if (!n_blocks || !n_rep) continue;
+    if (block_maps && total < cap) {
+      uint32_t st[3];
+      ngd_taus_seed(st, seed);
+      m.resize((uint64_t)n_rep * n_blocks);
+      for (uint32_t r = 0; r < n_rep; r++) ngd_boot_block_map(st, n_blocks, &m[(uint64_t)r * n_blocks]);
+      std::copy_n(m.begin(), std::min<uint64_t>(m.size(), cap - total), block_maps + total);
+    }
+    total += (uint64_t)n_rep * n_blocks;
+  }
+  // (every other window: the offset of its class's first window, which precedes it in `order`)
+  for (uint64_t k = 1; k < n_win; k++)
+    if (nb(order[k]) == nb(order[k - 1])) map_off[order[k]] = map_off[order[k - 1]];
+  return (int64_t)total;
+}
+
 }  // extern "C"
 
 // The same for the engine's own use (engine.hip run_dist: a job's tail inside the call), over n_mat matrices of n_pairs cells:

@@ -221,6 +221,7 @@ struct ngd_engine : ngd_mem {
   DevBuf<uint64_t> d_segtab;
   DevBuf<unsigned long long> d_wintab;
   DevBuf<uint32_t> d_winblk;  // a job's replicates (ngd_run_windows_job*): [window][block] first slice of the block
+  DevBuf<uint64_t> d_windesc;  // ... over windows of unequal length (ngd_run_windows_job_var*): [window][NGD_WIN_DESC]
   uint64_t opt_win_plan = 0, opt_win_max_bytes = 0;  // NGD_OPT_WIN_PLAN, NGD_OPT_WIN_MAX_BYTES
   ngd_windows_info win_info{};
   // NGD_OPT_EM_EXACT (engine_em_exact.hip): the plain pass of the table-driven EM kernel notes the (pair, site)s whose stop

@@ -395,6 +395,13 @@ void ngd_launch_reduce_band_w(hipStream_t st, const ngd_geom &g, const double *s
                               uint32_t n_win, uint32_t n_blocks, const void *d_Wt, uint32_t w_stride, uint32_t n_rep,
                               uint32_t mat_stride, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
                               unsigned long long *d_cnt, unsigned long long cnt_value, const ngd_fix_flags *fix, double fix_thr);
+// ... over windows of unequal length (k_reduce_band_wv): d_desc[w] = the window's NGD_WIN_DESC words (win_plan.h) -- its row
+// of d_blk, its n_blocks, its table of d_Wt, the sites a replicate visits: the count a sum launch writes when d_cnt != NULL,
+// and x NGD_FIX_MEAN the threshold below which a pair is noted when fix != NULL
+void ngd_launch_reduce_band_wv(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
+                               const uint64_t *d_desc, uint32_t n_win, const void *d_Wt, uint32_t w_stride, uint32_t n_rep,
+                               uint32_t mat_stride, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
+                               unsigned long long *d_cnt, const ngd_fix_flags *fix);
 void ngd_launch_count(hipStream_t st, const ngd_geom &g, const unsigned long long *mask,
                       const unsigned long long *planes, uint32_t n_planes, const ngd_tile *d_tiles,
                       uint32_t n_tiles, unsigned long long *d_cnt);  // owned 128-tiles

@@ -519,6 +519,138 @@ __global__ __launch_bounds__(128) void k_reduce_band_w(const void *__restrict__ 
   }
 }
 
+// k_reduce_band_w's walk for one window whose row of block starts (bf), n_blocks, weight table at replicate r0 (Wt), count
+// and threshold arrive as arguments -- all uniform across the workgroup.  It restates that kernel's body statement for
+// statement: routing k_reduce_band_w itself through this function changes the code the compiler emits for it (every
+// instantiation, 2 % to 19 % in instruction count either way), and the equal-length job keeps the kernel it was measured with.
+template <int RB, bool CNT, typename T>
+__device__ __forceinline__ void band_w_window(const void *__restrict__ slab_v, uint32_t i, uint32_t j, uint32_t w, uint32_t r0,
+                                              const uint32_t *bf, uint32_t n_blocks, const T *Wt,
+                                              uint32_t w_stride, uint32_t n_rep, uint32_t mat_stride, uint32_t n_pad,
+                                              uint64_t n_ind, uint64_t n_pairs, double *__restrict__ d_sum,
+                                              unsigned long long *__restrict__ d_cnt, unsigned long long cnt_value,
+                                              ngd_fix_flags fix, double fix_thr) {
+  typedef typename std::conditional<CNT, unsigned long long, double>::type A;
+  const uint64_t plane = (uint64_t)n_pad * n_pad;
+  const T *p = reinterpret_cast<const T *>(slab_v) + (uint64_t)i * n_pad + j;
+  A acc[RB];
+#pragma unroll
+  for (int r = 0; r < RB; r++) acc[r] = 0;
+  const uint32_t s_begin = bf[0], s_end = bf[n_blocks];
+  constexpr int U = 4;  // slices in flight per thread
+  uint32_t s = s_begin, b = 0, next = n_blocks ? bf[1] : s_end;  // slice s lies in block b, which ends before slice `next`
+  bool bad = false;  // a non-finite partial among this pair's slices
+  for (; s + U <= s_end; s += U) {
+    T v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) v[u] = p[(uint64_t)(s + u) * plane];
+    if (!CNT) {
+#pragma unroll
+      for (int u = 0; u < U; u++) bad |= !ngd_finite((double)v[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      while (s + u >= next) next = bf[++b + 1];
+      const T *wb = Wt + (uint64_t)b * w_stride;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        if (CNT) acc[r] += (A)wb[r] * (A)v[u];
+        else acc[r] = (A)__builtin_fma((double)wb[r], (double)v[u], (double)acc[r]);
+      }
+    }
+  }
+  for (; s < s_end; s++) {
+    const T v = p[(uint64_t)s * plane];
+    if (!CNT) bad |= !ngd_finite((double)v);
+    while (s >= next) next = bf[++b + 1];
+    const T *wb = Wt + (uint64_t)b * w_stride;
+#pragma unroll
+    for (int r = 0; r < RB; r++) {
+      if (CNT) acc[r] += (A)wb[r] * (A)v;
+      else acc[r] = (A)__builtin_fma((double)wb[r], (double)v, (double)acc[r]);
+    }
+  }
+  if (!CNT && __builtin_expect(bad, 0)) {  // again, slices in the same order, blocks that are not drawn left out
+#pragma unroll
+    for (int r = 0; r < RB; r++) acc[r] = 0;
+    for (b = 0; b < n_blocks; b++) {
+      const T *wb = Wt + (uint64_t)b * w_stride;
+      for (s = bf[b]; s < bf[b + 1]; s++) {
+        const T v = p[(uint64_t)s * plane];
+#pragma unroll
+        for (int r = 0; r < RB; r++)
+          if (wb[r] != 0) acc[r] = (A)__builtin_fma((double)wb[r], (double)v, (double)acc[r]);
+      }
+    }
+  }
+  const uint64_t idx = ngd_pair_idx(n_ind, i, j);
+  bool small = false;
+#pragma unroll
+  for (int r = 0; r < RB; r++)
+    if (r0 + r < n_rep) {
+      const uint64_t o = ((uint64_t)w * mat_stride + r0 + r) * n_pairs + idx;
+      if (CNT) {
+        d_cnt[o] = (unsigned long long)acc[r];
+      } else {
+        d_sum[o] = (double)acc[r];
+        if (d_cnt) d_cnt[o] = cnt_value;
+        if (fix.list) small = small || (double)acc[r] < fix_thr;
+      }
+    }
+  // single_image = 2 engines (see k_reduce): noted once, whichever window, matrix or launch of the batch sees a small sum first
+  if (!CNT && small && !((atomicOr(&fix.seen[idx >> 5], 1u << (idx & 31)) >> (idx & 31)) & 1u)) {
+    const uint32_t slot = atomicAdd(fix.count, 1u);
+    if (slot < fix.cap) fix.list[slot] = ((unsigned long long)i << 32) | j;
+  }
+}
+
+// Windows of UNEQUAL length (ngd_run_windows_job_var*): the same reduction, but what k_reduce_band_w takes once per launch --
+// n_blocks, the weight table, the count, the fix-up threshold -- is the window's own.  desc[w] = {where the window's row of
+// block starts begins in blk, n_blocks_w, where its weight table [n_blocks_w][w_stride] begins in Wt (elements), the sites a
+// replicate visits n_blocks_w q} (win_plan.h NGD_WIN_DESC_*): four words indexed by blockIdx.y alone, so uniform across the
+// workgroup -- scalar loads, nothing per lane.  Windows of one class point at one table.  A window with no block reads no
+// slice and writes sum 0, count 0.
+template <int RB, bool CNT>
+__global__ __launch_bounds__(128) void k_reduce_band_wv(const void *__restrict__ slab_v, const uint32_t *__restrict__ blk,
+                                                         const uint64_t *__restrict__ desc, const void *__restrict__ Wt_v,
+                                                         uint32_t w_stride, uint32_t n_rep, uint32_t n_chunks, uint32_t mat_stride,
+                                                         const ngd_tile *__restrict__ tiles, uint32_t n_pad, uint64_t n_ind,
+                                                         uint64_t n_pairs, double *__restrict__ d_sum,
+                                                         unsigned long long *__restrict__ d_cnt, ngd_fix_flags fix, double fix_mean) {
+  typedef typename std::conditional<CNT, uint32_t, double>::type T;
+  const uint32_t tile = blockIdx.x >> 7, row = blockIdx.x & 127;
+  const uint32_t i = tiles[tile].ti * NGD_TILE + row;
+  const uint32_t j = tiles[tile].tj * NGD_TILE + threadIdx.x;
+  if (!(i < j && j < n_ind)) return;
+  const uint32_t w = blockIdx.y / n_chunks, r0 = (blockIdx.y % n_chunks) * RB;
+  const uint64_t *d = desc + (uint64_t)w * NGD_WIN_DESC;
+  const uint64_t n_vis = d[NGD_WIN_DESC_VIS];
+  band_w_window<RB, CNT, T>(slab_v, i, j, w, r0, blk + d[NGD_WIN_DESC_BLK], (uint32_t)d[NGD_WIN_DESC_NB],
+                            reinterpret_cast<const T *>(Wt_v) + d[NGD_WIN_DESC_WT] + r0, w_stride, n_rep, mat_stride, n_pad, n_ind,
+                            n_pairs, d_sum, d_cnt, n_vis, fix, fix_mean * (double)n_vis);
+}
+
+template <int RB>
+void reduce_band_wv(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
+                    const uint64_t *d_desc, uint32_t n_win, const void *d_Wt, uint32_t w_stride, uint32_t n_rep, uint32_t mat_stride,
+                    const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum, unsigned long long *d_cnt, const ngd_fix_flags &f) {
+  const uint64_t n_pairs = g.n_ind * (g.n_ind - 1) / 2;
+  const uint32_t n_chunks = (n_rep + RB - 1) / RB, per = 65535u / n_chunks;  // (grid.y holds 65 535)
+  for (uint32_t w0 = 0; w0 < n_win; w0 += per) {
+    const uint32_t n = n_win - w0 < per ? n_win - w0 : per;
+    const dim3 grid(n_tiles * NGD_TILE, n * n_chunks);
+    const uint64_t *desc = d_desc + (uint64_t)w0 * NGD_WIN_DESC;  // (its offsets count from the batch's tables)
+    const uint64_t off = (uint64_t)w0 * mat_stride * n_pairs;
+    if (C)
+      hipLaunchKernelGGL((k_reduce_band_wv<RB, true>), grid, dim3(128), 0, st, (const void *)C, d_blk, desc, d_Wt, w_stride, n_rep,
+                         n_chunks, mat_stride, d_tiles, g.n_pad, g.n_ind, n_pairs, nullptr, d_cnt + off, f, 0.0);
+    else
+      hipLaunchKernelGGL((k_reduce_band_wv<RB, false>), grid, dim3(128), 0, st, (const void *)slab, d_blk, desc, d_Wt, w_stride,
+                         n_rep, n_chunks, mat_stride, d_tiles, g.n_pad, g.n_ind, n_pairs, d_sum + off,
+                         d_cnt ? d_cnt + off : nullptr, f, NGD_FIX_MEAN);
+  }
+}
+
 template <int RB>
 void reduce_band_w(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
                    uint32_t n_win, uint32_t n_blocks, const void *d_Wt, uint32_t w_stride, uint32_t n_rep, uint32_t mat_stride,
@@ -654,6 +786,20 @@ void ngd_launch_reduce_band_w(hipStream_t st, const ngd_geom &g, const double *s
     case 4: reduce_band_w<4>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr); break;
     case 16: reduce_band_w<16>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr); break;
     default: reduce_band_w<32>(st, g, slab, C, d_blk, n_win, n_blocks, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, cnt_value, f, fix_thr);
+  }
+}
+
+void ngd_launch_reduce_band_wv(hipStream_t st, const ngd_geom &g, const double *slab, const uint32_t *C, const uint32_t *d_blk,
+                               const uint64_t *d_desc, uint32_t n_win, const void *d_Wt, uint32_t w_stride, uint32_t n_rep,
+                               uint32_t mat_stride, const ngd_tile *d_tiles, uint32_t n_tiles, double *d_sum,
+                               unsigned long long *d_cnt, const ngd_fix_flags *fix) {
+  if (!n_tiles || !n_win || !n_rep) return;
+  const ngd_fix_flags f = fix ? *fix : ngd_fix_flags{nullptr, nullptr, nullptr, 0};
+  switch (ngd_reduce_chunk(n_rep)) {  // (the weights' stride is a multiple of it)
+    case 1: reduce_band_wv<1>(st, g, slab, C, d_blk, d_desc, n_win, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, f); break;
+    case 4: reduce_band_wv<4>(st, g, slab, C, d_blk, d_desc, n_win, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, f); break;
+    case 16: reduce_band_wv<16>(st, g, slab, C, d_blk, d_desc, n_win, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, f); break;
+    default: reduce_band_wv<32>(st, g, slab, C, d_blk, d_desc, n_win, d_Wt, w_stride, n_rep, mat_stride, d_tiles, n_tiles, d_sum, d_cnt, f);
   }
 }
 

@@ -84,23 +84,12 @@ struct win_batch {
   std::vector<uint32_t> seg_of, seg_end;
 };
 
-// The next batch of windows lo[] / hi[] (starts not decreasing, each alone within the budget): from window `a` on as many
-// as fit the budget, their segments bounded by their distinct boundaries - 1.
-inline void win_plan_batch(const win_env &v, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint64_t a, uint64_t budget,
-                           const WinBoot *bt, win_batch &p) {
-  std::vector<uint64_t> &x = p.x, &wb = p.wb, &merged = p.merged;  // (one merge of two sorted lists per window)
-  x.clear();
-  uint64_t b = a, hi_max = 0;
-  while (b < n_win) {
-    win_boundaries(lo[b], hi[b], bt, wb);
-    merged.clear();
-    std::set_union(x.begin(), x.end(), wb.begin(), wb.end(), std::back_inserter(merged));
-    const uint64_t n_seg_ub = merged.size() - 1, hm = std::max(hi_max, hi[b]);
-    if (b > a && (win_batch_bytes(v, n_seg_ub, hm - lo[a], b + 1 - a, bt) > budget || n_seg_ub >= (1ull << 30))) break;
-    x.swap(merged);
-    hi_max = hm;
-    b++;
-  }
+// The tables of the batch [a, b) whose distinct boundaries are p.x, ascending: its slice table and every window's range of
+// slices.  bytes(n_seg): what the batch takes with n_seg slices (the EM kernel's pieces must fit the budget too).
+template <class Bytes>
+inline void win_plan_slices(const win_env &v, const uint64_t *lo, const uint64_t *hi, uint64_t a, uint64_t b, uint64_t hi_max,
+                            uint64_t budget, Bytes bytes, win_batch &p) {
+  std::vector<uint64_t> &x = p.x;
   const uint64_t nb = b - a, n_x = x.size();
   auto at = [&](uint64_t s) { return (uint64_t)(std::lower_bound(x.begin(), x.end(), s) - x.begin()); };
   // interval k = [x[k], x[k + 1]) is a segment if some window of the batch covers it
@@ -119,7 +108,7 @@ inline void win_plan_batch(const win_env &v, const uint64_t *lo, const uint64_t 
     piece = std::max<uint64_t>(64, (sites + v.n_ks - 1) / std::max<uint32_t>(1, v.n_ks));
     for (uint64_t k = 0; k + 1 < n_x; k++)
       if (covered(k)) n_cut += (x[k + 1] - x[k] - 1) / piece + 1;
-    if (n_cut > n_cov && (win_batch_bytes(v, n_cut, hi_max - lo[a], nb, bt) > budget || n_cut >= (1ull << 30))) piece = ~0ull;
+    if (n_cut > n_cov && (bytes(n_cut) > budget || n_cut >= (1ull << 30))) piece = ~0ull;
   }
   // the slice table; interval k = slices [seg_of[k], seg_end[k]), none where no window covers it
   std::vector<uint32_t> &seg_of = p.seg_of, &seg_end = p.seg_end;
@@ -155,14 +144,141 @@ inline void win_plan_batch(const win_env &v, const uint64_t *lo, const uint64_t 
     p.wt[2 * (w - a)] = f | (l << 32);
     p.wt[2 * (w - a) + 1] = hi[w] - lo[w];
   }
+}
+
+// The next batch of windows lo[] / hi[] (starts not decreasing, each alone within the budget): from window `a` on as many
+// as fit the budget, their segments bounded by their distinct boundaries - 1.
+inline void win_plan_batch(const win_env &v, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint64_t a, uint64_t budget,
+                           const WinBoot *bt, win_batch &p) {
+  std::vector<uint64_t> &x = p.x, &wb = p.wb, &merged = p.merged;  // (one merge of two sorted lists per window)
+  x.clear();
+  uint64_t b = a, hi_max = 0;
+  while (b < n_win) {
+    win_boundaries(lo[b], hi[b], bt, wb);
+    merged.clear();
+    std::set_union(x.begin(), x.end(), wb.begin(), wb.end(), std::back_inserter(merged));
+    const uint64_t n_seg_ub = merged.size() - 1, hm = std::max(hi_max, hi[b]);
+    if (b > a && (win_batch_bytes(v, n_seg_ub, hm - lo[a], b + 1 - a, bt) > budget || n_seg_ub >= (1ull << 30))) break;
+    x.swap(merged);
+    hi_max = hm;
+    b++;
+  }
+  win_plan_slices(v, lo, hi, a, b, hi_max, budget,
+                  [&](uint64_t n_seg) { return win_batch_bytes(v, n_seg, hi_max - lo[a], b - a, bt); }, p);
+  const std::vector<uint32_t> &seg_of = p.seg_of;
+  auto at = [&](uint64_t s) { return (uint64_t)(std::lower_bound(x.begin(), x.end(), s) - x.begin()); };
   p.blk.clear();
   if (!bt) return;
+  const uint64_t nb = b - a;
   p.blk.resize(nb * (bt->n_blocks + 1));
   for (uint64_t w = a; w < b; w++) {
     uint64_t i = at(lo[w]);  // (the window's block starts ascend: one walk along the boundaries)
     for (uint64_t k = 0; k <= bt->n_blocks; k++) {
       while (x[i] < lo[w] + k * bt->q) i++;
       p.blk[(w - a) * (bt->n_blocks + 1) + k] = seg_of[i];
+    }
+  }
+}
+
+// ---- a job over windows of UNEQUAL length (ngd_run_windows_job_var*) ----
+// Window w has n_blocks_w = (hi - lo) / q blocks and draws the maps of its class: windows that share map_off and n_blocks_w
+// share one weight table.  k_reduce_band_wv reads a descriptor per window instead of one n_blocks / table / count per call.
+#define NGD_WIN_DESC 4       // words of a window's descriptor:
+#define NGD_WIN_DESC_BLK 0   //  where its row of block starts begins in blk (n_blocks_w + 1 entries)
+#define NGD_WIN_DESC_NB 1    //  n_blocks_w
+#define NGD_WIN_DESC_WT 2    //  where its weight table begins (elements: rows of `stride` weights)
+#define NGD_WIN_DESC_VIS 3   //  the sites a replicate visits, n_blocks_w q
+#define NGD_WIN_NO_CLASS 0xffffffffu
+
+struct WinBootVar {
+  uint32_t n_rep;
+  uint64_t q;
+  uint32_t n_cls;
+  const uint32_t *cls;         // [n_win] the window's class, NGD_WIN_NO_CLASS for a window shorter than one block
+  const uint64_t *cls_blocks;  // [n_cls] n_blocks of the class
+  const uint64_t *cls_mult;    // [n_cls] where `mult` holds the class's [n_rep][n_blocks] draws
+  const uint32_t *mult;
+  WinBootVar from(uint64_t w0) const { WinBootVar t = *this; t.cls += w0; return t; }  // the same job, windows w0 on
+};
+
+inline uint32_t win_weight_stride_var(const win_env &v, uint32_t n_rep) { return (n_rep + v.chunk - 1) / v.chunk * v.chunk; }
+
+// bytes of one batch: the plain batch's + the rows of block starts, the descriptors, and wt_rows rows of weights
+inline uint64_t win_batch_bytes_var(const win_env &v, uint64_t n_seg, uint64_t span, uint64_t n_win, uint64_t blk_entries,
+                                    uint64_t wt_rows, uint32_t n_rep) {
+  return win_batch_bytes(v, n_seg, span, n_win, nullptr) + blk_entries * 4 + n_win * NGD_WIN_DESC * 8 +
+         wt_rows * win_weight_stride_var(v, n_rep) * (v.pdel ? 12 : 8);
+}
+
+inline bool win_each_fits_var(const win_env &v, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBootVar &bv,
+                              uint64_t budget) {
+  for (uint64_t w = 0; w < n_win; w++) {
+    const uint64_t n_blocks = (hi[w] - lo[w]) / bv.q;
+    if (win_batch_bytes_var(v, n_blocks + 1, hi[w] - lo[w], 1, n_blocks + 1, n_blocks, bv.n_rep) > budget) return false;
+  }
+  return true;
+}
+
+struct win_batch_var : win_batch {
+  // blk: every window's row of block starts, one after the other (a window with no block: its first slice alone)
+  std::vector<uint64_t> desc;            // [b - a][NGD_WIN_DESC]
+  std::vector<uint32_t> cls_list;        // the classes the batch holds, in the order its windows bring them
+  std::vector<uint64_t> cls_row;         // [n_cls] the first row of the class's weights in the batch's table, ~0: not held
+  uint64_t wt_rows = 0;                  // rows of the batch's weight table
+};
+
+// every boundary the windows of one call bring, ascending and distinct: their block starts and ends
+inline void win_call_boundaries_var(const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint64_t q, std::vector<uint64_t> &all) {
+  all.clear();
+  for (uint64_t w = 0; w < n_win; w++) {
+    if (w && lo[w] == lo[w - 1] && hi[w] == hi[w - 1]) continue;  // (a window that comes again brings nothing new)
+    for (uint64_t s = lo[w]; s + q <= hi[w]; s += q) all.push_back(s);
+    all.push_back(lo[w] + (hi[w] - lo[w]) / q * q);
+    all.push_back(hi[w]);
+  }
+  std::sort(all.begin(), all.end());
+  all.erase(std::unique(all.begin(), all.end()), all.end());
+}
+
+// The next batch, as win_plan_batch -- but its slices are cut by the boundaries of EVERY window of the call (`all`,
+// win_call_boundaries_var) that fall inside its span, not by its own windows' alone: a block is then added up from the same
+// slices whatever the budget makes of the batches, and the MFMA kernel's replicates carry the same bits under any
+// NGD_OPT_WIN_MAX_BYTES.  (The EM kernel's pieces of a long slice still follow the batch.)  A window of a neighbouring batch
+// that reaches into this one costs it a few more slices; with no budget `all` is what the windows' own merge gives.
+inline void win_plan_batch_var(const win_env &v, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint64_t a, uint64_t budget,
+                               const WinBootVar &bv, const std::vector<uint64_t> &all, win_batch_var &p) {
+  std::vector<uint64_t> &x = p.x;
+  p.cls_row.assign(bv.n_cls, ~0ull);
+  p.cls_list.clear();
+  const auto first = std::lower_bound(all.begin(), all.end(), lo[a]);
+  uint64_t b = a, hi_max = 0, blk_entries = 0, wt_rows = 0;
+  while (b < n_win) {
+    const uint64_t n_blocks = (hi[b] - lo[b]) / bv.q, hm = std::max(hi_max, hi[b]);
+    const uint64_t n_seg_ub = (uint64_t)(std::upper_bound(first, all.end(), hm) - first) - 1;
+    const bool fresh = n_blocks && p.cls_row[bv.cls[b]] == ~0ull;
+    const uint64_t be = blk_entries + n_blocks + 1, wr = wt_rows + (fresh ? n_blocks : 0);
+    if (b > a && (win_batch_bytes_var(v, n_seg_ub, hm - lo[a], b + 1 - a, be, wr, bv.n_rep) > budget || n_seg_ub >= (1ull << 30))) break;
+    if (fresh) { p.cls_row[bv.cls[b]] = wt_rows; p.cls_list.push_back(bv.cls[b]); }
+    blk_entries = be;
+    wt_rows = wr;
+    hi_max = hm;
+    b++;
+  }
+  x.assign(first, std::upper_bound(first, all.end(), hi_max));
+  p.wt_rows = wt_rows;
+  win_plan_slices(v, lo, hi, a, b, hi_max, budget,
+                  [&](uint64_t n_seg) { return win_batch_bytes_var(v, n_seg, hi_max - lo[a], b - a, blk_entries, wt_rows, bv.n_rep); }, p);
+  auto at = [&](uint64_t s) { return (uint64_t)(std::lower_bound(x.begin(), x.end(), s) - x.begin()); };
+  const uint32_t stride = win_weight_stride_var(v, bv.n_rep);
+  p.blk.clear();
+  p.desc.clear();
+  for (uint64_t w = a; w < b; w++) {
+    const uint64_t n_blocks = (hi[w] - lo[w]) / bv.q;
+    p.desc.insert(p.desc.end(), {p.blk.size(), n_blocks, n_blocks ? p.cls_row[bv.cls[w]] * stride : 0, n_blocks * bv.q});
+    uint64_t i = at(lo[w]);
+    for (uint64_t k = 0; k <= n_blocks; k++) {
+      while (x[i] < lo[w] + k * bv.q) i++;
+      p.blk.push_back(p.seg_of[i]);
     }
   }
 }

@@ -299,6 +299,59 @@ class Engine:
                                                 int(evol_model), d.ctypes.data_as(C.POINTER(C.c_double))))
         return d
 
+    @staticmethod
+    def _var_maps(block_maps, map_off, n_win):
+        """flat block maps and one offset per window (window_boot_maps) -> (arrays kept alive, pointers, entries)"""
+        m = np.ascontiguousarray(block_maps if block_maps is not None else [], dtype=np.uint64)
+        off = np.ascontiguousarray(map_off, dtype=np.uint64)
+        if m.ndim != 1 or off.shape != (n_win,):
+            raise ValueError("block_maps: expected a flat array; map_off: one offset per window")
+        u64p = C.POINTER(C.c_uint64)
+        return (m, off), m.ctypes.data_as(u64p) if m.size else None, off.ctypes.data_as(u64p), m.size
+
+    def run_windows_job_var(self, lo, hi, block_maps, map_off, block_size=1, d_sum_ptr=None, d_cnt_ptr=None, n_rep=None):
+        """bootstrap replicates inside windows of UNEQUAL length (ngd_run_windows_job_var): window w draws the maps
+        [n_rep][(hi[w] - lo[w]) // block_size] at block_maps[map_off[w]:] (n_rep: read off window_boot_maps()'s layout when
+        not given; any other layout must name it); -> (sum, cnt) of shape (n_win, n_rep + 1, n_pairs), a
+        window shorter than one block with replicates of sum 0 and count 0; with device pointers
+        (ngd_run_windows_job_var_device) the results go there and None is returned"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
+        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        if d_sum_ptr is not None:
+            _check(self._L.ngd_run_windows_job_var_device(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size),
+                                                          C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr)))
+            return None
+        s = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.float64)
+        c = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.uint64)
+        _check(self._L.ngd_run_windows_job_var(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size),
+                                               s.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return s, c
+
+    def run_windows_job_var_dist(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None):
+        """the job and the tail of gen_dist() on every matrix (ngd_run_windows_job_var_dist): float64 (n_win, n_rep + 1,
+        n_pairs); the replicates of a window shorter than one block are ngd_finish's 0 / 0"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
+        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        d = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.float64)
+        _check(self._L.ngd_run_windows_job_var_dist(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size),
+                                                    int(tot_sites), int(evol_model), d.ctypes.data_as(C.POINTER(C.c_double))))
+        return d
+
+    @staticmethod
+    def _var_n_rep(lo, hi, off, n_ent, block_size):
+        """replicates of a layout window_boot_maps() made: the classes lie one after the other, so the first class's maps
+        end where the next offset above its own begins (or where the table ends)"""
+        nb = (hi - lo) // np.uint64(max(1, int(block_size)))
+        has = np.flatnonzero(nb > 0)
+        if has.size == 0:
+            raise ValueError("n_rep: no window has a block to tell it from; pass n_rep")
+        w = has[np.argmin(off[has])]
+        above = off[has][off[has] > off[w]]
+        end = int(above.min()) if above.size else int(n_ent)
+        return (end - int(off[w])) // int(nb[w])
+
     def windows_info(self):
         """what the last windowed call did (ngd_last_windows): segments, slab_bytes, batches, band_launches,
         windows_by_pass, fixup_pairs, ms"""
@@ -450,6 +503,55 @@ def window_ranges(n_sites, size, step=None, chrom=None):
     L.ngd_window_ranges(idp, int(n_sites), int(size), int(step), lo.ctypes.data_as(C.POINTER(C.c_uint64)),
                         hi.ctypes.data_as(C.POINTER(C.c_uint64)), n)
     return lo, hi
+
+
+def window_ranges_bp(pos, size, step=None, chrom=None, min_sites=1):
+    """the window list of --win_bp / --win_bp_step (ngd_window_ranges_bp): -> (lo, hi, bp_start) uint64 arrays.  pos: one
+    coordinate >= 1 per site, not descending inside a chromosome; window k of a chromosome covers the coordinates
+    [1 + k step, 1 + k step + size), its sites are [lo, hi), and windows with fewer than max(1, min_sites) sites are left
+    out.  chrom: as window_ranges()."""
+    L = _lib.load()
+    step = size if step is None else step
+    pos = np.ascontiguousarray(pos, dtype=np.uint64)
+    if pos.ndim != 1:
+        raise ValueError("pos: expected one coordinate per site")
+    n_sites = pos.size
+    ids = None
+    if chrom is not None:
+        if len(chrom) != n_sites:
+            raise ValueError("chrom: expected one id per site")
+        codes = {}
+        ids = np.fromiter((codes.setdefault(c, len(codes)) for c in chrom), dtype=np.uint32, count=n_sites)
+    u64p = C.POINTER(C.c_uint64)
+    idp = ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None
+    args = (idp, pos.ctypes.data_as(u64p), n_sites, int(size), int(step), int(min_sites))
+    n = L.ngd_window_ranges_bp(*args, None, None, None, 0)
+    if n < 0:
+        raise NgdError(int(n), "window_ranges_bp: size and step must be positive, positions whole numbers from 1 to 2^62 that "
+                               "do not descend inside a chromosome, and chromosomes grouped")
+    lo, hi, start = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+    L.ngd_window_ranges_bp(*args, lo.ctypes.data_as(u64p), hi.ctypes.data_as(u64p), start.ctypes.data_as(u64p), n)
+    return lo, hi, start
+
+
+def window_boot_maps(seed, lo, hi, n_rep, block_size):
+    """the block maps of run_windows_job_var() (ngd_window_boot_maps), drawn as the reference would on every window's
+    cut-down file: -> (block_maps uint64[entries], map_off uint64[n_win]); window w's maps are
+    block_maps[map_off[w]:][:n_rep * n_blocks_w].reshape(n_rep, n_blocks_w), n_blocks_w = (hi[w] - lo[w]) // block_size"""
+    L = _lib.load()
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    hi = np.ascontiguousarray(hi, dtype=np.uint64)
+    if lo.ndim != 1 or lo.shape != hi.shape:
+        raise ValueError("lo, hi: expected two 1-D arrays of the same length")
+    u64p = C.POINTER(C.c_uint64)
+    off = np.zeros(lo.size, dtype=np.uint64)
+    args = (int(seed), lo.ctypes.data_as(u64p), hi.ctypes.data_as(u64p), lo.size, int(n_rep), int(block_size))
+    n = L.ngd_window_boot_maps(*args, None, 0, off.ctypes.data_as(u64p))
+    if n < 0:
+        raise NgdError(int(n), "window_boot_maps: block_size must be positive and no window end before its start")
+    maps = np.zeros(n, dtype=np.uint64)
+    L.ngd_window_boot_maps(*args, maps.ctypes.data_as(u64p), n, off.ctypes.data_as(u64p))
+    return maps, off
 
 
 def score_congruence(score):

@@ -13,6 +13,16 @@ of the same engine in the same process, and the bytes of results.  Not bench.py:
 
     python tools/bench_windows_boot.py [--n_ind 1000] [--n_sites 100000] [--win_size 10000] [--win_step 2500]
                                        [--block 100] [--n_rep 100] [--reps 2] [--skip_indep] [--skip_em] [--legs ...]
+
+--bp: windows in base pairs, of unequal length (Engine.run_windows_job_var).  Synthetic positions -- gaps of 1 .. 39 bp
+between sites, every 50th stretch of 100 sites twelve times sparser -- and windows of --win_bp every --win_bp_step (20 000
+every 4 000: about 1000 sites, 5 x overlap), blocks of 10 and of 100 sites.  The results of all windows do not fit a device
+(500 windows x 101 matrices x 8 MB at 1000 individuals), so the windows go through in groups of --group whose results share
+one buffer; --max_windows takes the first so many.  Legs, one JSON line each, the MEDIAN device time of --reps calls after
+one warm-up call:
+  unit_slab   run_windows_job_var under NGD_OPT_WIN_PLAN = 2;      per_window  the same under NGD_OPT_WIN_PLAN = 1;
+  auto        the same under NGD_OPT_WIN_PLAN = 0 (which plan it took: windows_by_pass);
+  baseline    the only route before the call existed: one run_windows_job per window, in a Python loop (auto plan).
 """
 import argparse
 import json
@@ -38,7 +48,15 @@ def main():
     ap.add_argument("--skip_em", action="store_true")
     ap.add_argument("--skip_indep", action="store_true")
     ap.add_argument("--legs", default="unit_slab,per_window,baseline")
+    ap.add_argument("--bp", action="store_true", help="windows in base pairs through run_windows_job_var")
+    ap.add_argument("--win_bp", type=int, default=20000)
+    ap.add_argument("--win_bp_step", type=int, default=4000)
+    ap.add_argument("--blocks", default="10,100", help="--bp: block sizes, one set of lines each")
+    ap.add_argument("--group", type=int, default=16, help="--bp: windows per call (their results share one device buffer)")
+    ap.add_argument("--max_windows", type=int, default=0, help="--bp: only the first so many windows (0: all)")
     args = ap.parse_args()
+    if args.bp:
+        return main_bp(args)
     import numpy as np
     import torch
 
@@ -112,6 +130,85 @@ def main():
                         "ratio_to_plain": round(best / t_plain, 3) if t_plain else None})
             out.update(extra)
             print(json.dumps(out), flush=True)
+
+    if not args.skip_indep:
+        with N.Engine(args.n_ind, args.n_sites, indep_geno=True, kernel="mfma") as e:
+            e.synth_fill(3, 0.0)
+            lines(e, "indep_mfma_image_mode_%d" % e.image_mode()[0])
+    if not args.skip_em:
+        with N.Engine(args.n_ind, args.n_sites, indep_geno=False, kernel="auto") as e:
+            e.synth_fill(3, 0.0)
+            lines(e, "em_auto")
+
+
+def main_bp(args):
+    import statistics
+
+    import numpy as np
+    import torch
+
+    import ngsdist_amd as N
+
+    R = args.n_rep
+    rng = np.random.default_rng(3)
+    gaps = rng.integers(1, 40, args.n_sites)
+    sparse = (np.arange(args.n_sites) // 100) % 50 == 49
+    gaps[sparse] *= 12
+    pos = np.cumsum(gaps)
+    lo, hi, _ = N.window_ranges_bp(pos, args.win_bp, args.win_bp_step)
+    if args.max_windows:
+        lo, hi = lo[:args.max_windows], hi[:args.max_windows]
+    legs = args.legs.split(",") if args.legs != "unit_slab,per_window,baseline" else ["unit_slab", "per_window", "auto", "baseline"]
+
+    def one_call(e, leg, q, maps, off, d_sum, d_cnt):
+        """all windows, group by group -> (device ms, what the plans did)"""
+        ms, took = 0.0, {"segments": 0, "batches": 0, "windows_by_pass": 0, "fixup_pairs": 0}
+        e.set_option("win_plan", {"unit_slab": 2, "per_window": 1}.get(leg, 0))
+        for g0 in range(0, len(lo), args.group):
+            l, h, o = lo[g0:g0 + args.group], hi[g0:g0 + args.group], off[g0:g0 + args.group]
+            if leg != "baseline":
+                e.run_windows_job_var(l, h, maps, o, q, d_sum.data_ptr(), d_cnt.data_ptr(), n_rep=R)
+                info = e.windows_info()
+                ms += info["ms"]
+                for k in took:
+                    took[k] += info[k]
+                continue
+            per = (R + 1) * e.n_pairs * 8
+            for w in range(len(l)):
+                nb = int(h[w] - l[w]) // q
+                if not nb:  # (the old call refuses a window without a block: its matrix 0 alone)
+                    e.run_windows(l[w:w + 1], h[w:w + 1], d_sum.data_ptr() + w * per, d_cnt.data_ptr() + w * per)
+                else:
+                    m = maps[int(o[w]):int(o[w]) + R * nb].reshape(R, nb)
+                    e.run_windows_job(l[w:w + 1], h[w:w + 1], m, q, d_sum.data_ptr() + w * per, d_cnt.data_ptr() + w * per)
+                info = e.windows_info()
+                ms += info["ms"]
+                took["windows_by_pass"] += info["windows_by_pass"]
+                took["batches"] += info["batches"]
+        return ms, took
+
+    def lines(e, path):
+        d_sum = torch.empty((args.group, R + 1, e.n_pairs), dtype=torch.float64, device="cuda")
+        d_cnt = torch.empty((args.group, R + 1, e.n_pairs), dtype=torch.int64, device="cuda")
+        L = (hi - lo).astype(np.int64)
+        for q in [int(x) for x in args.blocks.split(",")]:
+            maps, off = N.window_boot_maps(args.seed, lo, hi, R, q)
+            for leg in legs:
+                one_call(e, leg, q, maps, off, d_sum, d_cnt)  # warm-up: allocations, code objects
+                runs = []
+                for _ in range(args.reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    ms, took = one_call(e, leg, q, maps, off, d_sum, d_cnt)
+                    torch.cuda.synchronize()
+                    runs.append((ms, (time.perf_counter() - t0) * 1e3))
+                out = {"path": path, "leg": leg, "n_ind": e.n_ind, "n_sites": e.n_sites, "win_bp": args.win_bp,
+                       "win_bp_step": args.win_bp_step, "n_win": int(len(lo)), "sites_per_window_min_median_max":
+                       [int(L.min()), int(np.median(L)), int(L.max())], "distinct_lengths": int(len(set(L.tolist()))), "block": q,
+                       "n_rep": R, "group": args.group, "device_ms_median": round(statistics.median(r[0] for r in runs), 3),
+                       "device_ms_runs": [round(r[0], 3) for r in runs], "wall_ms_median": round(statistics.median(r[1] for r in runs), 3)}
+                out.update(took)
+                print(json.dumps(out), flush=True)
 
     if not args.skip_indep:
         with N.Engine(args.n_ind, args.n_sites, indep_geno=True, kernel="mfma") as e:
