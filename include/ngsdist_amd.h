@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define NGD_ABI_VERSION 6 /* 6: ngd_run_job_dist, ngd_run_batch_dist, ngd_run_mult_batch_dist (and, added under 6: ngd_run_windows*, ngd_last_windows, ngd_window_ranges, ngd_run_windows_job / _job_device / _job_dist; NGD_OPT_EM_EXACT / _EM_EXACT_CAP, ngd_last_em_exact, ngd_em_exact_entries, ngd_em2_site); 5: ngd_finish_stream, ngd_fixup_info.by_pass, NGD_OPT_STAGE_PIECE_MIB / _STAGE_RING / _EAGER_FULL, NGD_OPT_FIXUP_WORK 0 = no budget (every noted pair is recomputed); 4: ngd_last_spill_timing, ngd_last_fixup, ngd_image_mode, ngd_config.single_image 0 = auto / 3 = two images; 3: ngd_config.single_image / second_image_mib (were reserved, zero), ngd_fetch_matrix, ngd_score_congruence */
+#define NGD_ABI_VERSION 6 /* 6: ngd_run_job_dist, ngd_run_batch_dist, ngd_run_mult_batch_dist (and, added under 6: ngd_run_windows*, ngd_last_windows, ngd_window_ranges, ngd_run_windows_job / _job_device / _job_dist; NGD_OPT_EM_EXACT / _EM_EXACT_CAP, ngd_last_em_exact, ngd_em_exact_entries, ngd_em2_site; ngd_set_groups, ngd_group_means_device, ngd_run_job_groups, ngd_run_windows_groups, ngd_run_windows_job_var_groups, ngd_last_groups_ms, ngd_n_group_pairs, ngd_group_pair_index, ngd_group_cells); 5: ngd_finish_stream, ngd_fixup_info.by_pass, NGD_OPT_STAGE_PIECE_MIB / _STAGE_RING / _EAGER_FULL, NGD_OPT_FIXUP_WORK 0 = no budget (every noted pair is recomputed); 4: ngd_last_spill_timing, ngd_last_fixup, ngd_image_mode, ngd_config.single_image 0 = auto / 3 = two images; 3: ngd_config.single_image / second_image_mib (were reserved, zero), ngd_fetch_matrix, ngd_score_congruence */
 
 #define NGD_OK 0
 #define NGD_E_INVALID (-1)  /* bad argument / bad state                    */
@@ -626,6 +626,47 @@ int64_t ngd_window_ranges_bp(const uint32_t *chrom_id, const uint64_t *pos, uint
  * (block_maps may be NULL with cap 0).  NGD_E_INVALID: block_size 0, a null lo / hi / map_off, hi < lo. */
 int64_t ngd_window_boot_maps(uint64_t seed, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, uint32_t n_rep,
                              uint64_t block_size, uint64_t *block_maps, uint64_t cap, uint64_t *map_off);
+
+/* Group-mean distance matrices, reduced on the device: per matrix the G x G table of mean distances within and between
+ * groups of individuals (populations) instead of the n x n matrix -- n_gp = G (G + 1) / 2 numbers cross the host link.
+ * A grouping is group_of[i] for every individual: a value in [0, n_groups) names its group, -1 leaves it out of every
+ * group.  Group pairs (a, b), a <= b, are numbered as the row-major upper triangle with the diagonal:
+ * gp = a G - a (a - 1) / 2 + (b - a).  The cells of (a, b) are the pairs i1 < i2 with one individual in a and the other in
+ * b, whichever has the lower index (a == b: both in a).  A cell's value d is ngd_finish()'s, operation by operation, from
+ * the matrix's (sum, cnt) and (tot_sites, evol_model); the division and the products carry the host's bits (no fast-math),
+ * log is the device's.  used[m][gp] = the cells whose d is finite, mean[m][gp] = their sum / used, a positive quiet NaN
+ * where used is 0 (a group of one on the diagonal, an empty group, no shared valid site under --pairwise_del): cells that
+ * are not finite are left out and counted, cells - used of them (ngd_group_cells).  No floating-point atomics: the order
+ * of additions is a function of (n_ind, group_of) alone -- not of the matrices a call or a launch holds. */
+uint64_t ngd_n_group_pairs(uint32_t n_groups);
+uint64_t ngd_group_pair_index(uint32_t n_groups, uint32_t a, uint32_t b); /* a <= b */
+/* cells[n_gp]: the cells of every group pair.  Pure host arithmetic, needs no device.  NGD_E_INVALID: a null argument,
+ * n_groups 0, an entry of group_of outside [-1, n_groups). */
+int ngd_group_cells(const int32_t *group_of, uint64_t n_ind, uint32_t n_groups, uint64_t *cells);
+/* The engine's grouping (group_of: n_ind entries): the member lists, their offsets and the launch's work list go to device
+ * memory of the engine's.  NULL / 0 clears it and frees that memory.  NGD_E_INVALID: an entry outside
+ * [-1, n_groups), n_groups 0 with a list, a list with n_groups 0; a refused call leaves the grouping as it was. */
+int ngd_set_groups(ngd_engine *e, const int32_t *group_of, uint32_t n_groups);
+/* mean / used [n_mat][n_gp] (host memory; used may be NULL) of any [n_mat][n_pairs] matrices in device memory -- the
+ * caller's, as a *_device call wrote them; whatever wrote them has finished.  d_cnt is not read when tot_sites > 0.
+ * NGD_E_INVALID, before anything is launched: no grouping set, a null pointer, n_mat 0, tot_sites with --pairwise_del, an
+ * engine that owns a share of the pairs; NGD_E_MODEL for evol_model > 2.  A failed call leaves grouping and engine usable. */
+int ngd_group_means_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                           uint64_t evol_model, double *mean, uint64_t *used);
+/* ngd_run_job_device / ngd_run_windows_device / ngd_run_windows_job_var_device into the engine's batch buffers (the windows
+ * in groups of ~2 GB of results) followed by that reduction: plans, fix-up, NGD_OPT_EM_EXACT* and refusals are the sibling's,
+ * and the means are ngd_group_means_device()'s on the sibling's output bit for bit at the same options.  Outputs:
+ * [n_rep + 1][n_gp], [n_win][n_gp], [n_win][n_rep + 1][n_gp].  Windows of one length go through the _var form (whose bits
+ * are ngd_run_windows_job*'s).  The refusals of ngd_group_means_device come first, before anything is launched. */
+int ngd_run_job_groups(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                       uint64_t tot_sites, uint64_t evol_model, double *mean, uint64_t *used);
+int ngd_run_windows_groups(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
+                           uint64_t evol_model, double *mean, uint64_t *used);
+int ngd_run_windows_job_var_groups(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                   const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                   uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *mean, uint64_t *used);
+/* device time (HIP events) of the group reduction's kernels in the last of these calls, summed over its launches */
+int ngd_last_groups_ms(const ngd_engine *e, double *ms);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

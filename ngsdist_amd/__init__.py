@@ -6,7 +6,9 @@ the library; the first Engine()/finish()/Taus() does, and fails loudly if the
 HIP engine was not built.
 """
 from .engine import (DEFAULT_SCORE, KERNELS, Engine, NgdError, Taus, device_count, em2_site, finish, format_matrix, n_pairs,
-                     score_congruence, score_matrix, window_boot_maps, window_ranges, window_ranges_bp)
+                     score_congruence, score_matrix, window_boot_maps, window_ranges, window_ranges_bp, n_group_pairs,
+                     group_pair_index, group_cells, expand_groups)
 
 __all__ = ["Engine", "NgdError", "Taus", "finish", "format_matrix", "device_count", "n_pairs", "score_matrix",
-           "score_congruence", "window_ranges", "window_ranges_bp", "window_boot_maps", "em2_site", "DEFAULT_SCORE", "KERNELS"]
+           "score_congruence", "window_ranges", "window_ranges_bp", "window_boot_maps", "em2_site", "DEFAULT_SCORE", "KERNELS",
+           "n_group_pairs", "group_pair_index", "group_cells", "expand_groups"]

@@ -87,6 +87,8 @@ EXPORTS = [
     "ngd_window_ranges_bp", "ngd_window_boot_maps", "ngd_run_windows_job_var", "ngd_run_windows_job_var_device",
     "ngd_run_windows_job_var_dist",
     "ngd_last_em_exact", "ngd_em_exact_entries", "ngd_em2_site",
+    "ngd_n_group_pairs", "ngd_group_pair_index", "ngd_group_cells", "ngd_set_groups", "ngd_group_means_device",
+    "ngd_run_job_groups", "ngd_run_windows_groups", "ngd_run_windows_job_var_groups", "ngd_last_groups_ms",
 ]
 
 _lib = None
@@ -197,6 +199,17 @@ def load():
     L.ngd_em_exact_entries.restype = C.c_int64
     L.ngd_em2_site.argtypes = [dp, dp, dp, C.POINTER(C.c_int)]
     L.ngd_em2_site.restype = None
+    L.ngd_n_group_pairs.argtypes = [C.c_uint32]
+    L.ngd_n_group_pairs.restype = u64
+    L.ngd_group_pair_index.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.ngd_group_pair_index.restype = u64
+    L.ngd_group_cells.argtypes = [C.POINTER(C.c_int32), u64, C.c_uint32, u64p]
+    L.ngd_set_groups.argtypes = [vp, C.POINTER(C.c_int32), C.c_uint32]
+    L.ngd_group_means_device.argtypes = [vp, vp, vp, u64, u64, u64, dp, u64p]
+    L.ngd_run_job_groups.argtypes = [vp, u64p, C.c_uint32, u64, u64, u64, u64, dp, u64p]
+    L.ngd_run_windows_groups.argtypes = [vp, u64p, u64p, u64, u64, u64, dp, u64p]
+    L.ngd_run_windows_job_var_groups.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, u64, u64, dp, u64p]
+    L.ngd_last_groups_ms.argtypes = [vp, dp]
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

@@ -924,6 +924,25 @@ int ngd_run_windows_job_var_dist(ngd_engine *e, const uint64_t *win_lo, const ui
   return windows_host_dist(e, win_lo, win_hi, n_win, nullptr, tot_sites, evol_model, dist, "ngd_run_windows_job_var_dist", &bv);
 }
 
+// ... group means (ngd_run_windows_groups, ngd_run_windows_job_var_groups; engine_groups.hip has checked what is the
+// grouping's): the sibling's checks, then every group of windows from the batch buffers through the group reduction --
+// n_gp means and counts per matrix leave the device instead of n_pairs sums and counts
+int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
+                        const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
+                        double *mean, uint64_t *used, const char *who) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = n_rep ? windows_job_var_check(e, lo, hi, n_win, maps, maps_len, map_off, n_rep, block_size, who, st, bv)
+                     : windows_check(e, lo, hi, n_win, who))
+    return rc;
+  HIPCHK(hipSetDevice(e->device));
+  const uint64_t n_mat = (uint64_t)n_rep + 1, n_gp = e->grp.n_gp;
+  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
+    return groups_reduce(e, e->d_bsum, e->d_bcnt, n * n_mat, tot_sites, evol_model, mean + w0 * n_mat * n_gp,
+                         used ? used + w0 * n_mat * n_gp : nullptr);
+  }, nullptr, n_rep ? &bv : nullptr);
+}
+
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {
   if (!e || !info) return fail(NGD_E_INVALID, "ngd_last_windows: null argument");
   *info = e->win_info;

@@ -33,7 +33,9 @@
 //    device, except host when genotypes are called so that calls are decided by glibc),
 //    --eager 0|1|2 (1, the default: on the EM path without bootstrap the full-data pass starts beside the load,
 //    NGD_OPT_EAGER_FULL; 2: on the --indep_geno path too; 0: never), --stage piece_MiB,ring[,share_MiB[,drop]] (the load
-//    pipeline's geometry, for measurements: tools/r6_stage_sweep.sh);
+//    pipeline's geometry, for measurements: tools/r6_stage_sweep.sh), --groups FILE (the group of every individual: <out>
+//    holds the G x G table of mean distances within and between groups of every matrix, <out>.used the cells behind them;
+//    one GPU, the whole data set resident);
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
@@ -70,6 +72,11 @@
 #pragma weak ngd_last_windows
 #pragma weak ngd_run_windows_job_dist  // (--win_boot_rep)
 #pragma weak ngd_run_windows_job_var_dist  // (--win_boot_rep under --win_bp: windows of unequal length)
+// (--groups: the group means of every matrix, reduced on the device)
+#pragma weak ngd_set_groups
+#pragma weak ngd_run_job_groups
+#pragma weak ngd_run_windows_groups
+#pragma weak ngd_run_windows_job_var_groups
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -123,6 +130,10 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // --em_exact_win: the same for the windows of --win_size, and for the replicates inside them with --win_boot_rep
   // (NGD_OPT_EM_EXACT = 1, or 2 with replicates, and NGD_OPT_EM_EXACT_WIN).  The two flags above keep refusing windows.
   bool em_exact_win = false;
+  // --groups FILE: one line per individual, its first field the name of the individual's group (NA, - or an empty line: in
+  // no group).  <out> then holds, per matrix, the G x G table of mean distances within and between groups -- the engine
+  // reduces every matrix on the device (ngd_run_*_groups) -- and <out>.used the cells behind each mean.  Not in the reference.
+  const char *in_groups = nullptr;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -234,6 +245,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"win_bp", required_argument, nullptr, 1017},
                                  {"win_bp_step", required_argument, nullptr, 1018},
                                  {"win_min_sites", required_argument, nullptr, 1019},
+                                 {"groups", required_argument, nullptr, 1020},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -275,6 +287,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1017: p.win_bp = true; p.win_bp_size = strtoll(optarg, nullptr, 10); break;
       case 1018: p.win_bp_step_set = true; p.win_bp_step = strtoll(optarg, nullptr, 10); break;
       case 1019: p.win_min_sites_set = true; p.win_min_sites = strtoll(optarg, nullptr, 10); break;
+      case 1020: p.in_groups = optarg; break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -323,6 +336,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.em_exact) fprintf(stderr, "\tem_exact: true\n\n");
     if (p.em_exact_boot) fprintf(stderr, "\tem_exact_boot: true\n\n");
     if (p.em_exact_win) fprintf(stderr, "\tem_exact_win: true\n\n");
+    if (p.in_groups) fprintf(stderr, "\tgroups: %s\n\n", p.in_groups);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -387,6 +401,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.n_boot_rep > 0) die(__FUNCTION__, "windows (--win_size) cannot be combined with bootstrap replicates (--n_boot_rep)!");
     if (p.n_gpus > 1) die(__FUNCTION__, "windows (--win_size) are computed on one GPU (--n_gpus 1)!");
   }
+  if (p.in_groups && p.n_gpus > 1) die(__FUNCTION__, "group means (--groups) are computed on one GPU (--n_gpus 1)!");
 }
 
 // ---------------------------------------------------------------------------
@@ -422,6 +437,53 @@ static std::vector<std::string> read_lines(const char *path, uint64_t offset) {
   }
   gzclose(fh);
   return out;
+}
+
+// --groups: every line of the file (empty ones too: an individual in no group), its first field the group's name; groups
+// are numbered in order of first appearance, "NA", "-" and an empty field are -1
+static void read_groups(const char *path, std::vector<int32_t> &group_of, std::vector<std::string> &names) {
+  gzFile fh = open_gz(path, "r");
+  if (!fh) die("read_file", "cannot open file!");
+  std::unordered_map<std::string, int32_t> ids;
+  std::vector<char> buf(kLineBuf);
+  while (gzgets(fh, buf.data(), (int)buf.size())) {
+    std::string l(buf.data());
+    while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+    l.resize(std::min(l.size(), l.find_first_of("\t ")));
+    if (l.empty() || l == "NA" || l == "-") {
+      group_of.push_back(-1);
+      continue;
+    }
+    const auto ins = ids.emplace(l, (int32_t)names.size());
+    if (ins.second) names.push_back(l);
+    group_of.push_back(ins.first->second);
+  }
+  gzclose(fh);
+}
+
+// --groups: the print block of one matrix's group means, in the layout of a distance matrix's block (ngsDist.cpp:282-287):
+// "\n<G>\n", then per group its name and G cells "\t%.10f" -- the within-group mean on the diagonal, "nan" where no cell
+// was finite --; `cnt` takes the same block with the numbers of cells behind the means.  mean / used: [n_gp], a <= b
+static void format_groups(const std::vector<std::string> &names, const double *mean, const uint64_t *used, std::string &txt,
+                          std::string &cnt) {
+  const uint32_t G = (uint32_t)names.size();
+  char cell[64];
+  txt += "\n" + std::to_string(G) + "\n";
+  cnt += "\n" + std::to_string(G) + "\n";
+  for (uint32_t a = 0; a < G; a++) {
+    txt += names[a];
+    cnt += names[a];
+    for (uint32_t b = 0; b < G; b++) {
+      const uint64_t lo = std::min(a, b), hi = std::max(a, b);
+      const uint64_t gp = lo * G - lo * (lo ? lo - 1 : 0) / 2 + (hi - lo);  // (ngd_group_pair_index)
+      snprintf(cell, sizeof(cell), "\t%.10f", mean[gp]);
+      txt += cell;
+      snprintf(cell, sizeof(cell), "\t%lu", (unsigned long)used[gp]);
+      cnt += cell;
+    }
+    txt += "\n";
+    cnt += "\n";
+  }
 }
 
 // strtod for the common spelling [-+]digits[.digits][e[-+]digits], exactly: up to 19 significant digits are
@@ -1180,6 +1242,18 @@ int main(int argc, char **argv) {
   }
   if (p.verbose >= 4) for (auto &l : labels) fprintf(stderr, "%s\n", l.c_str());
 
+  // --groups: the group of every individual, in input order
+  std::vector<int32_t> group_of;
+  std::vector<std::string> group_names;
+  if (p.in_groups) {
+    if (p.verbose >= 1) fprintf(stderr, "==> Reading groups\n");
+    read_groups(p.in_groups, group_of, group_names);
+    if (group_of.size() != p.n_ind || group_names.empty()) die(__FUNCTION__, "invalid GROUPS file!");
+    if (!ngd_set_groups || !ngd_run_job_groups || !ngd_run_windows_groups || !ngd_run_windows_job_var_groups)
+      die(__FUNCTION__, "this build of the engine has no group means (--groups)!");
+    if (p.verbose >= 1) fprintf(stderr, "==> %lu groups\n", (unsigned long)group_names.size());
+  }
+
   // positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149 -- except for the chromosomes
   // and coordinates of --win_size's windows
   std::vector<uint32_t> win_chrom;
@@ -1234,9 +1308,9 @@ int main(int argc, char **argv) {
     win_bp_start.resize((size_t)n_win);
     ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, win_lo.data(), win_hi.data(), win_bp_start.data(),
                          (uint64_t)n_win);
-    if (!ngd_run_windows_dist)
+    if (!p.in_groups && !ngd_run_windows_dist)  // (--groups: its own entry points, checked above)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (p.win_boot_rep && !ngd_run_windows_job_var_dist)
+    if (!p.in_groups && p.win_boot_rep && !ngd_run_windows_job_var_dist)
       die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu bp every %lu bp\n", (unsigned long)n_win, (unsigned long)B, (unsigned long)T);
   } else if (p.win) {
@@ -1247,9 +1321,9 @@ int main(int argc, char **argv) {
     win_lo.resize((size_t)n_win);
     win_hi.resize((size_t)n_win);
     ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win_lo.data(), win_hi.data(), (uint64_t)n_win);
-    if (!ngd_run_windows_dist)
+    if (!p.in_groups && !ngd_run_windows_dist)  // (--groups: its own entry points, checked above)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (p.win_boot_rep && !ngd_run_windows_job_dist)
+    if (!p.in_groups && p.win_boot_rep && !ngd_run_windows_job_dist)
       die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows (--win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
   }
@@ -1315,6 +1389,8 @@ int main(int argc, char **argv) {
   eager_ranges = in_parts;
   if (p.win && in_parts)
     die(__FUNCTION__, "windows (--win_size) need the whole data set on one GPU; it does not fit the device budget!");
+  if (p.in_groups && in_parts)
+    die(__FUNCTION__, "group means (--groups) need the whole data set on one GPU; it does not fit the device budget!");
 
   if (p.verbose >= 2) fprintf(stderr, "==> Setting seed for random number generator\n");
   uint32_t rng[3];
@@ -1591,7 +1667,109 @@ int main(int argc, char **argv) {
     fprintf(stderr, "> read + prepare + upload: %.3f s (%.2f GB of prepared input resident on the device)\n", t_load,
             (double)p.n_ind * p.n_sites * 24 / 1e9);
 
-  if (p.win) {
+  // <out>.windows: where each window lies
+  auto write_windows_file = [&]() {
+    const uint64_t n_win = win_lo.size();
+    const std::string wpath = std::string(p.out) + ".windows";
+    FILE *wf = fopen(wpath.c_str(), "w");
+    if (!wf) die(__FUNCTION__, "cannot open windows output file!");
+    fprintf(wf, p.win_bp ? "window\tchr\tstart\tend\tfirst_site\tn_sites\twin_start\twin_end\n" : "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
+    for (uint64_t w = 0; w < n_win; w++) {
+      const uint64_t lo = win_lo[w], hi = win_hi[w];
+      if (p.win_bp)  // (+ the window's own coordinates, inclusive: 1 + k T and k T + B)
+        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
+                win_pos_txt[hi - 1].c_str(), lo, hi - lo, win_bp_start[w], win_bp_start[w] + (uint64_t)p.win_bp_size - 1);
+      else if (win_chrom.empty())
+        fprintf(wf, "%lu\t.\t%lu\t%lu\t%lu\t%lu\n", w, lo + 1, hi, lo, hi - lo);
+      else
+        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
+                win_pos_txt[hi - 1].c_str(), lo, hi - lo);
+    }
+    if (fclose(wf) != 0) die(__FUNCTION__, "cannot write windows output file!");
+  };
+  if (p.in_groups) {
+    // ---- group means: every matrix of the run -- the full data set and its replicates, or the windows and theirs -- leaves
+    // the engine as its G x G table (ngd_run_*_groups): one block per matrix in <out>, in the order of the run without
+    // --groups, and the same blocks with the numbers of cells behind the means in <out>.used ----
+    int rc = ngd_set_groups(eng.h, group_of.data(), (uint32_t)group_names.size());
+    if (rc) die_engine("ngd_set_groups", rc);
+    const uint64_t G = group_names.size(), n_gp = G * (G + 1) / 2;
+    const std::string upath = std::string(p.out) + ".used";
+    FILE *uf = fopen(upath.c_str(), "w");
+    if (!uf) die(__FUNCTION__, "cannot open used output file!");
+    std::string txt, cnt;
+    auto write_blocks = [&](const double *mean, const uint64_t *used, uint64_t n_mat) {
+      const auto t_w0 = std::chrono::steady_clock::now();
+      txt.clear();
+      cnt.clear();
+      for (uint64_t m = 0; m < n_mat; m++) format_groups(group_names, mean + m * n_gp, used + m * n_gp, txt, cnt);
+      if (fwrite(txt.data(), 1, txt.size(), out_fh) != txt.size() || fwrite(cnt.data(), 1, cnt.size(), uf) != cnt.size())
+        die(__FUNCTION__, "cannot write output file!");
+      t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_w0).count();
+    };
+    std::vector<double> gmean;
+    std::vector<uint64_t> gused;
+    const auto t_c0 = std::chrono::steady_clock::now();
+    if (p.win) {
+      const uint64_t n_win = win_lo.size(), R = p.win_boot_rep, n_mat = R + 1;
+      gmean.resize(n_win * n_mat * n_gp);
+      gused.resize(n_win * n_mat * n_gp);
+      if (R) {
+        // every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length share them); a
+        // window shorter than one block has replicates of 0 / 0, whose means are nan
+        std::vector<uint64_t> off(n_win);
+        const int64_t len = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0,
+                                                 off.data());
+        if (len < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
+        std::vector<uint64_t> maps((size_t)len + 1);
+        ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, maps.data(), (uint64_t)len,
+                             off.data());
+        rc = ngd_run_windows_job_var_groups(eng.h, win_lo.data(), win_hi.data(), n_win, maps.data(), (uint64_t)len, off.data(), (uint32_t)R,
+                                            p.boot_block_size, p.tot_sites, p.evol_model, gmean.data(), gused.data());
+        if (rc) die_engine("ngd_run_windows_job_var_groups", rc);
+      } else {
+        rc = ngd_run_windows_groups(eng.h, win_lo.data(), win_hi.data(), n_win, p.tot_sites, p.evol_model, gmean.data(), gused.data());
+        if (rc) die_engine("ngd_run_windows_groups", rc);
+      }
+      report_fixup(eng.h, p.verbose);
+      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
+      if (p.verbose >= 1) fprintf(stderr, "==> %lu windows, %lu matrices each\n", (unsigned long)n_win, (unsigned long)n_mat);
+      write_blocks(gmean.data(), gused.data(), n_win * n_mat);
+    } else {
+      // the full data set, then the replicates in batches (their maps drawn in the reference's order); a batch after the
+      // first goes through the same call and its leading full-data matrix is dropped
+      const uint64_t n_sites_b = p.n_sites - p.n_sites % p.boot_block_size, n_blocks = n_sites_b / p.boot_block_size;
+      std::vector<uint64_t> maps;
+      for (uint64_t rep = 0; rep <= p.n_boot_rep;) {
+        const auto t_b0 = std::chrono::steady_clock::now();
+        const uint64_t n_here = std::min<uint64_t>(kBatch - 1, p.n_boot_rep - (rep ? rep - 1 : 0));  // replicates of this call
+        gmean.assign((n_here + 1) * n_gp, std::nan(""));
+        gused.assign((n_here + 1) * n_gp, 0);
+        if (n_here && n_blocks) {
+          maps.resize(n_here * n_blocks);
+          for (uint64_t r = 0; r < n_here; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
+        }
+        // (fewer sites than one block: the replicates visit no site, ngsDist.cpp:236 -- their means stay nan, used 0)
+        const uint32_t n_call = n_blocks ? (uint32_t)n_here : 0;
+        if (rep == 0 || n_call) {
+          rc = ngd_run_job_groups(eng.h, maps.data(), n_call, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, gmean.data(),
+                                  gused.data());
+          if (rc) die_engine("ngd_run_job_groups", rc);
+          report_fixup(eng.h, p.verbose);
+        }
+        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_b0).count();
+        if (p.verbose >= 1 && rep == 0) fprintf(stderr, "==> Analyzing full dataset...\n");
+        if (p.verbose >= 1 && n_here) fprintf(stderr, "==> Bootstrap replicates # %lu to %lu ...\n", rep ? rep : 1, (rep ? rep : 1) + n_here - 1);
+        const uint64_t skip = rep ? 1 : 0;
+        write_blocks(gmean.data() + skip * n_gp, gused.data() + skip * n_gp, n_here + 1 - skip);
+        rep = (rep ? rep : 1) + n_here;
+      }
+    }
+    if (fclose(uf) != 0) die(__FUNCTION__, "cannot write used output file!");
+  }
+  if (p.in_groups) {
+    if (p.win) write_windows_file();  // (the windows' own file: as without --groups)
+  } else if (p.win) {
     // ---- windows along the genome: one matrix per window, in window order, a group of windows per engine call (their
     // distances in ~2 GB of host memory), each window's block formatted and written like the full data set's ----
     const uint64_t n_win = win_lo.size();
@@ -1663,23 +1841,7 @@ int main(int argc, char **argv) {
       }
       writer.wait_idle();  // (the last block's text is written before the next group's call)
     }
-    // <out>.windows: where each window lies
-    const std::string wpath = std::string(p.out) + ".windows";
-    FILE *wf = fopen(wpath.c_str(), "w");
-    if (!wf) die(__FUNCTION__, "cannot open windows output file!");
-    fprintf(wf, p.win_bp ? "window\tchr\tstart\tend\tfirst_site\tn_sites\twin_start\twin_end\n" : "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
-    for (uint64_t w = 0; w < n_win; w++) {
-      const uint64_t lo = win_lo[w], hi = win_hi[w];
-      if (p.win_bp)  // (+ the window's own coordinates, inclusive: 1 + k T and k T + B)
-        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
-                win_pos_txt[hi - 1].c_str(), lo, hi - lo, win_bp_start[w], win_bp_start[w] + (uint64_t)p.win_bp_size - 1);
-      else if (win_chrom.empty())
-        fprintf(wf, "%lu\t.\t%lu\t%lu\t%lu\t%lu\n", w, lo + 1, hi, lo, hi - lo);
-      else
-        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
-                win_pos_txt[hi - 1].c_str(), lo, hi - lo);
-    }
-    if (fclose(wf) != 0) die(__FUNCTION__, "cannot write windows output file!");
+    write_windows_file();
   } else {
   // Matrices go to the engine in batches: the first batch is the full-data matrix plus the first replicates
   // (ngd_run_job, which lets the engine share work between them), later ones replicates only (ngd_run_batch).

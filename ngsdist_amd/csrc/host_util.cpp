@@ -678,6 +678,28 @@ int64_t ngd_window_boot_maps(uint64_t seed, const uint64_t *lo, const uint64_t *
   return (int64_t)total;
 }
 
+// ---- groups of individuals (--groups): pairs of groups (a, b), a <= b, numbered as the row-major upper triangle WITH the
+// diagonal; a group pair's cells are the pairs of individuals i1 < i2 with one in a and one in b (a == b: both in a) ----
+uint64_t ngd_n_group_pairs(uint32_t n_groups) { return (uint64_t)n_groups * ((uint64_t)n_groups + 1) / 2; }
+
+uint64_t ngd_group_pair_index(uint32_t n_groups, uint32_t a, uint32_t b) {
+  const uint64_t G = n_groups, A = a;
+  return A * G - (A ? A * (A - 1) / 2 : 0) + (b - a);
+}
+
+int ngd_group_cells(const int32_t *group_of, uint64_t n_ind, uint32_t n_groups, uint64_t *cells) {
+  if (!group_of || !n_groups || !cells) return NGD_E_INVALID;
+  std::vector<uint64_t> size(n_groups, 0);
+  for (uint64_t i = 0; i < n_ind; i++) {
+    if (group_of[i] < -1 || group_of[i] >= (int64_t)n_groups) return NGD_E_INVALID;
+    if (group_of[i] >= 0) size[group_of[i]]++;
+  }
+  for (uint32_t a = 0; a < n_groups; a++)
+    for (uint32_t b = a; b < n_groups; b++)
+      cells[ngd_group_pair_index(n_groups, a, b)] = a == b ? size[a] * (size[a] - (size[a] ? 1 : 0)) / 2 : size[a] * size[b];
+  return NGD_OK;
+}
+
 }  // extern "C"
 
 // The same for the engine's own use (engine.hip run_dist: a job's tail inside the call), over n_mat matrices of n_pairs cells:

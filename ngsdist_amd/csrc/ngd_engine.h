@@ -243,6 +243,17 @@ struct ngd_engine : ngd_mem {
   // plan): what the call has gathered so far, while exact_info / exact_entries hold the launch at hand
   ngd_em_exact_info call_info{};
   std::vector<ngd_em_exact_entry> call_entries;
+  // groups of individuals (ngd_set_groups): the grouping as group_reduce.hip reads it, and the reduction's scratch and
+  // results -- everything here goes when the grouping is cleared
+  struct Groups {
+    uint32_t n_groups = 0, n_work = 0;  // n_groups 0: no grouping set
+    uint64_t n_gp = 0;
+    DevBuf<uint32_t> d_members, d_off, d_gp_first;
+    DevBuf<ngd_group_work> d_work;
+    DevBuf<double> d_part_sum, d_mean;
+    DevBuf<unsigned long long> d_part_cnt, d_used;
+    double ms = 0;  // ngd_last_groups_ms
+  } grp;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
@@ -352,4 +363,12 @@ int run_to_host(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult,
                 uint64_t n_blocks, uint64_t block_size, uint32_t n_batch, double *sum, uint64_t *cnt);
 int run_dist(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, uint32_t n_rep, bool lead_full,
              uint64_t n_blocks, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who);
+// engine_groups.hip: [n_mat][n_pairs] device matrices -> mean / used [n_mat][n_gp] in host memory (the arguments are checked)
+int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                  uint64_t evol_model, double *mean, uint64_t *used);
+// engine_windows.hip: the windowed calls through the batch buffers, every group of windows reduced by groups_reduce
+// (n_rep == 0, or maps NULL with it: the windows alone)
+int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
+                        const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
+                        double *mean, uint64_t *used, const char *who);
 #pragma GCC visibility pop

@@ -408,3 +408,24 @@ void ngd_launch_count(hipStream_t st, const ngd_geom &g, const unsigned long lon
 void ngd_launch_fill_cnt(hipStream_t st, const ngd_geom &g, const ngd_tile *d_tiles, uint32_t n_tiles,
                          unsigned long long value, const unsigned long long *d_values, uint32_t n_rep,
                          unsigned long long *d_cnt);
+
+// group_reduce.hip : group-mean distance matrices (ngd_set_groups, ngd_group_means_device, ngd_run_*_groups)
+// One work item: rows [r0, r1) of group pair (a, b) -- positions in group a's member list --, every column of group b
+#define NGD_GROUP_WG_CELLS 4096  // cells of a work item's rectangle, about: whole rows, at least one
+struct ngd_group_work {
+  uint32_t a, b, r0, r1;
+};
+// a grouping on the device: members sorted by group and ascending inside one, goff[g] .. goff[g + 1] the members of group g,
+// the work items sorted by group pair, gp_first[gp] .. gp_first[gp + 1] those of group pair gp (none: no cell)
+struct ngd_group_launch {
+  uint64_t n_ind;
+  const uint32_t *members, *goff;
+  const ngd_group_work *work;
+  const uint32_t *gp_first;
+  uint32_t n_work, n_gp;
+};
+// [n_mat][n_pairs] sums and counts -> mean / used [n_mat][n_gp]; part_sum / part_cnt: n_mat * n_work entries of scratch;
+// n_mat * max(n_work, n_gp / 256 + 1) below 2^31 (grid.x).  tot_sites > 0: d_cnt is not read
+void ngd_launch_group_means(hipStream_t st, const ngd_group_launch &l, const double *d_sum, const unsigned long long *d_cnt,
+                            uint64_t n_mat, uint64_t tot_sites, uint32_t model, double *part_sum, unsigned long long *part_cnt,
+                            double *mean, unsigned long long *used);

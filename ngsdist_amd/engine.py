@@ -359,6 +359,69 @@ class Engine:
         _check(self._L.ngd_last_windows(self._h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_}
 
+    # -- group means: the G x G table of mean distances instead of the n x n matrix -------------------------------
+    def set_groups(self, group_of, n_groups=None):
+        """the engine's grouping (ngd_set_groups): group_of[i] in [0, n_groups) names individual i's group, -1 leaves it out;
+        n_groups: max + 1 when not given; set_groups(None) clears the grouping and frees its device memory"""
+        if group_of is None:
+            _check(self._L.ngd_set_groups(self._h, None, 0))
+            self.n_groups = 0
+            return self
+        g = np.ascontiguousarray(group_of, dtype=np.int32)
+        if g.shape != (self.n_ind,):
+            raise ValueError("group_of: expected one entry per individual")
+        n_groups = int(g.max()) + 1 if n_groups is None else int(n_groups)
+        _check(self._L.ngd_set_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int32)), n_groups))
+        self.n_groups = n_groups
+        return self
+
+    def _group_out(self, *lead):
+        n_gp = n_group_pairs(getattr(self, "n_groups", 0))
+        mean = np.empty(lead + (n_gp,), dtype=np.float64)
+        used = np.empty(lead + (n_gp,), dtype=np.uint64)
+        return mean, used, mean.ctypes.data_as(C.POINTER(C.c_double)), used.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    def group_means(self, d_sum_ptr, d_cnt_ptr, n_mat, evol_model=1, tot_sites=0):
+        """the group reduction of n_mat device matrices (ngd_group_means_device; raw addresses of [n_mat][n_pairs] sums and
+        counts, as a *_device call wrote them): -> (mean float64[n_mat][n_gp], used uint64[n_mat][n_gp]), the mean of the
+        finite cells of every pair of groups (NaN where there is none) and their number"""
+        mean, used, mp, up = self._group_out(int(n_mat))
+        _check(self._L.ngd_group_means_device(self._h, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr), int(n_mat), int(tot_sites),
+                                              int(evol_model), mp, up))
+        return mean, used
+
+    def run_job_groups(self, block_maps=None, block_size=1, evol_model=1, tot_sites=0):
+        """run_job() and the group reduction of its matrices on the device (ngd_run_job_groups): -> (mean, used) of shape
+        (n_rep + 1, n_gp)"""
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        mean, used, mp, up = self._group_out(n_rep + 1)
+        _check(self._L.ngd_run_job_groups(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model), mp, up))
+        return mean, used
+
+    def run_windows_groups(self, lo, hi, evol_model=1, tot_sites=0):
+        """run_windows() and the group reduction of every window (ngd_run_windows_groups): -> (mean, used) of shape (n_win, n_gp)"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        mean, used, mp, up = self._group_out(lo.size)
+        _check(self._L.ngd_run_windows_groups(self._h, lp, hp, lo.size, int(tot_sites), int(evol_model), mp, up))
+        return mean, used
+
+    def run_windows_job_var_groups(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None):
+        """run_windows_job_var() and the group reduction of every matrix (ngd_run_windows_job_var_groups): -> (mean, used) of
+        shape (n_win, n_rep + 1, n_gp)"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        keep, mp_, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
+        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        mean, used, mp, up = self._group_out(lo.size, n_rep + 1)
+        _check(self._L.ngd_run_windows_job_var_groups(self._h, lp, hp, lo.size, mp_, n_ent, op, n_rep, int(block_size),
+                                                      int(tot_sites), int(evol_model), mp, up))
+        return mean, used
+
+    def groups_ms(self):
+        """device time of the group reduction's kernels in the last *_groups / group_means call (ngd_last_groups_ms)"""
+        v = C.c_double(0.0)
+        _check(self._L.ngd_last_groups_ms(self._h, C.byref(v)))
+        return float(v.value)
+
     def run_job_keep(self, block_maps, block_size=1):
         """ngd_run_job with the matrices left in the engine; fetch_matrix(r) copies them out one at a time"""
         a = np.ascontiguousarray(block_maps, dtype=np.uint64)
@@ -552,6 +615,44 @@ def window_boot_maps(seed, lo, hi, n_rep, block_size):
     maps = np.zeros(n, dtype=np.uint64)
     L.ngd_window_boot_maps(*args, maps.ctypes.data_as(u64p), n, off.ctypes.data_as(u64p))
     return maps, off
+
+
+def n_group_pairs(n_groups):
+    """pairs of groups (a, b), a <= b (ngd_n_group_pairs): G (G + 1) / 2"""
+    return int(_lib.load().ngd_n_group_pairs(int(n_groups)))
+
+
+def group_pair_index(n_groups, a, b):
+    """the place of group pair (a, b), a <= b, in the row-major upper triangle with the diagonal (ngd_group_pair_index)"""
+    if not 0 <= a <= b < n_groups:
+        raise ValueError("expected 0 <= a <= b < n_groups")
+    return int(_lib.load().ngd_group_pair_index(int(n_groups), int(a), int(b)))
+
+
+def group_cells(group_of, n_groups=None):
+    """the cells -- pairs of individuals -- of every group pair (ngd_group_cells): uint64[n_gp]; needs no device"""
+    g = np.ascontiguousarray(group_of, dtype=np.int32)
+    if g.ndim != 1:
+        raise ValueError("group_of: expected one entry per individual")
+    n_groups = int(g.max()) + 1 if n_groups is None else int(n_groups)
+    cells = np.zeros(n_group_pairs(n_groups), dtype=np.uint64)
+    rc = _lib.load().ngd_group_cells(g.ctypes.data_as(C.POINTER(C.c_int32)), g.size, n_groups,
+                                     cells.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc:
+        raise NgdError(int(rc), "group_cells: n_groups must be positive and every entry in [-1, n_groups)")
+    return cells
+
+
+def expand_groups(mean, n_groups):
+    """[..., n_gp] in group-pair order -> the symmetric [..., G, G] table (the within-group value on the diagonal)"""
+    m = np.asarray(mean)
+    if m.shape[-1] != n_group_pairs(n_groups):
+        raise ValueError("the last axis must hold n_groups * (n_groups + 1) / 2 entries")
+    a, b = np.triu_indices(n_groups)
+    out = np.empty(m.shape[:-1] + (n_groups, n_groups), dtype=m.dtype)
+    out[..., a, b] = m
+    out[..., b, a] = m
+    return out
 
 
 def score_congruence(score):
