@@ -668,6 +668,61 @@ int ngd_run_windows_job_var_groups(ngd_engine *e, const uint64_t *win_lo, const 
 /* device time (HIP events) of the group reduction's kernels in the last of these calls, summed over its launches */
 int ngd_last_groups_ms(const ngd_engine *e, double *ms);
 
+/* Bootstrap summaries per cell, reduced on the device (added under ABI 6): per cell of a set an estimate, a standard
+ * error and a percentile interval leave the device instead of R + 1 sums and counts.
+ * A *set* is one window's (or the whole run's) n_mat = R + 1 matrices over n_cells cells -- n_pairs pairs, or n_gp group
+ * pairs.  A cell's values are v_0 .. v_R; F = the replicates r >= 1 with v_r finite, m = |F|, s_(0) <= .. <= s_(m-1)
+ * those values sorted by numeric value (ties in any order).  Per cell:
+ *   stat 0  est   v_0, whatever it is (nan / inf pass through)
+ *   stat 1  mean  (SUM_{r in F} v_r) / m, the terms added one by one in ascending r starting from 0.0; a positive quiet
+ *                 NaN if m = 0
+ *   stat 2  sd    sqrt(SUM_{r in F} (v_r - mean)^2 / (m - 1)), same order, no contraction; a positive quiet NaN if m < 2
+ *   stat 3  lo    s_(k_lo), k_lo = floor(p_lo * (double)(m - 1)); NaN if m = 0
+ *   stat 4  hi    s_(k_hi), k_hi = ceil(p_hi * (double)(m - 1)); NaN if m = 0
+ *           used  m
+ * p_lo = (1 - ci) / 2 and p_hi = 1 - p_lo are computed once on the host in double from the caller's ci in (0, 1).  Order
+ * statistics, not interpolation: lo and hi are values the engine computed.  Replicates that are not finite are left out
+ * and counted, as the group means leave cells out; a window shorter than one block has replicates 0 / 0 and so m = 0.
+ * From sums and counts a cell's value is ngd_finish()'s, operation by operation (the division and the products carry the
+ * host's bits, log is the device's).  Outputs, in host memory: stats[n_set][NGD_BOOT_NSTAT][n_cells] doubles and
+ * used[n_set][n_cells].  A cell's bits depend on its own values alone, never on the launch or the set it shares a call with.
+ * The device keeps a cell's n_mat values in on-chip memory: R <= ngd_boot_stats_max_rep(), more is refused. */
+#define NGD_BOOT_NSTAT 5
+uint32_t ngd_boot_stats_max_rep(void);
+/* The definitions above in plain host arithmetic on val[n_set][n_mat][n_cells], for callers of the *_dist forms; needs no
+ * device, any n_mat >= 2.  NGD_E_INVALID: a null pointer, n_set 0, n_mat < 2, ci outside (0, 1). */
+int ngd_boot_stats_host(const double *val, uint64_t n_set, uint64_t n_mat, uint64_t n_cells, double ci, double *stats,
+                        uint64_t *used);
+/* ... on the device, of [n_set][n_mat][n_pairs] sums and counts in device memory -- the caller's, as a *_device call wrote
+ * them (d_cnt is not read when tot_sites > 0) --, or of [n_set][n_mat][n_cells] values as they are.  NGD_E_INVALID, before
+ * anything is launched: a null pointer, n_set 0, n_mat < 2, ci outside (0, 1) (NaN included), n_mat - 1 above
+ * ngd_boot_stats_max_rep(), tot_sites with --pairwise_del, an engine that owns a share of the pairs; NGD_E_MODEL for
+ * evol_model > 2.  A refused call leaves outputs and engine as they were. */
+int ngd_boot_stats_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
+                          uint64_t evol_model, double ci, double *stats, uint64_t *used);
+int ngd_boot_stats_values_device(ngd_engine *e, const void *d_val, uint64_t n_set, uint64_t n_mat, uint64_t n_cells, double ci,
+                                 double *stats, uint64_t *used);
+/* ngd_run_job_device (one set) / ngd_run_windows_job_var_device (one set per window; windows of one length go through it
+ * too) into the engine's batch buffers, followed by that reduction: plans, fix-up, NGD_OPT_EM_EXACT* and refusals are the
+ * sibling's, and the statistics are ngd_boot_stats_device()'s on the sibling's output bit for bit at the same options.
+ * The _groups forms run the group reduction first and summarise the n_gp means of every matrix while they are still in
+ * device memory (NGD_E_INVALID without a grouping).  n_rep 0 is refused.  Outputs: stats [5][n_cells] / [n_win][5][n_cells],
+ * used [n_cells] / [n_win][n_cells], n_cells = n_pairs or n_gp. */
+int ngd_run_job_stats(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                      uint64_t tot_sites, uint64_t evol_model, double ci, double *stats, uint64_t *used);
+int ngd_run_windows_job_var_stats(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                  const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                  uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double ci, double *stats,
+                                  uint64_t *used);
+int ngd_run_job_groups_stats(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                             uint64_t tot_sites, uint64_t evol_model, double ci, double *stats, uint64_t *used);
+int ngd_run_windows_job_var_groups_stats(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                         const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                         uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double ci, double *stats,
+                                         uint64_t *used);
+/* device time (HIP events) of the summary kernels in the last of these calls, summed over its launches */
+int ngd_last_boot_stats_ms(const ngd_engine *e, double *ms);
+
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:
  *   cnt = tot_sites if tot_sites > 0; d = sum/cnt;

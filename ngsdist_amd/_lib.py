@@ -89,7 +89,12 @@ EXPORTS = [
     "ngd_last_em_exact", "ngd_em_exact_entries", "ngd_em2_site",
     "ngd_n_group_pairs", "ngd_group_pair_index", "ngd_group_cells", "ngd_set_groups", "ngd_group_means_device",
     "ngd_run_job_groups", "ngd_run_windows_groups", "ngd_run_windows_job_var_groups", "ngd_last_groups_ms",
+    "ngd_boot_stats_max_rep", "ngd_boot_stats_host", "ngd_boot_stats_device", "ngd_boot_stats_values_device",
+    "ngd_run_job_stats", "ngd_run_windows_job_var_stats", "ngd_run_job_groups_stats", "ngd_run_windows_job_var_groups_stats",
+    "ngd_last_boot_stats_ms",
 ]
+
+NSTAT = 5  # NGD_BOOT_NSTAT: est, mean, sd, lo, hi
 
 _lib = None
 
@@ -210,6 +215,16 @@ def load():
     L.ngd_run_windows_groups.argtypes = [vp, u64p, u64p, u64, u64, u64, dp, u64p]
     L.ngd_run_windows_job_var_groups.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, u64, u64, dp, u64p]
     L.ngd_last_groups_ms.argtypes = [vp, dp]
+    L.ngd_boot_stats_max_rep.argtypes = []
+    L.ngd_boot_stats_max_rep.restype = C.c_uint32
+    L.ngd_boot_stats_host.argtypes = [dp, u64, u64, u64, C.c_double, dp, u64p]
+    L.ngd_boot_stats_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, C.c_double, dp, u64p]
+    L.ngd_boot_stats_values_device.argtypes = [vp, vp, u64, u64, u64, C.c_double, dp, u64p]
+    L.ngd_run_job_stats.argtypes = [vp, u64p, C.c_uint32, u64, u64, u64, u64, C.c_double, dp, u64p]
+    L.ngd_run_job_groups_stats.argtypes = L.ngd_run_job_stats.argtypes
+    L.ngd_run_windows_job_var_stats.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, u64, u64, C.c_double, dp, u64p]
+    L.ngd_run_windows_job_var_groups_stats.argtypes = L.ngd_run_windows_job_var_stats.argtypes
+    L.ngd_last_boot_stats_ms.argtypes = [vp, dp]
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

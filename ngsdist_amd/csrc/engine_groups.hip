@@ -21,6 +21,7 @@ static void groups_clear(ngd_engine *e) {
   auto &g = e->grp;
   g.d_members.release(); g.d_off.release(); g.d_gp_first.release(); g.d_work.release();
   g.d_part_sum.release(); g.d_part_cnt.release(); g.d_mean.release(); g.d_used.release();
+  g.d_keep_mean.release(); g.d_keep_used.release();
   g.n_groups = g.n_work = 0;
   g.n_gp = 0;
 }
@@ -87,15 +88,16 @@ int ngd_set_groups(ngd_engine *e, const int32_t *group_of, uint32_t n_groups) {
 // The matrices in chunks whose partial results and outputs stay small (2^22 entries each) and whose launches fit grid.x; a
 // matrix's bits do not depend on the chunk it falls into.  Events 0 and 1 time each chunk's kernels (grp.ms: the entry
 // points start it at 0, a windowed call adds up its groups of windows).
-int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
-                  uint64_t evol_model, double *mean, uint64_t *used) {
+// keep: the chunks' results go one after the other into grp.d_keep_mean / d_keep_used and stay there, nothing is copied.
+static int groups_reduce_impl(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                              uint64_t evol_model, double *mean, uint64_t *used, bool keep) {
   auto &g = e->grp;
   const uint64_t per_mat = std::max<uint64_t>(std::max<uint64_t>(1, g.n_work), g.n_gp);
   const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n_mat, (1ull << 22) / per_mat));
   int rc = g.d_part_sum.ensure(e, chunk * std::max<uint64_t>(1, g.n_work));
   if (!rc) rc = g.d_part_cnt.ensure(e, chunk * std::max<uint64_t>(1, g.n_work));
-  if (!rc) rc = g.d_mean.ensure(e, chunk * g.n_gp);
-  if (!rc) rc = g.d_used.ensure(e, chunk * g.n_gp);
+  if (!rc) rc = keep ? g.d_keep_mean.ensure(e, n_mat * g.n_gp) : g.d_mean.ensure(e, chunk * g.n_gp);
+  if (!rc) rc = keep ? g.d_keep_used.ensure(e, n_mat * g.n_gp) : g.d_used.ensure(e, chunk * g.n_gp);
   if (rc) return rc;
   const ngd_group_launch l{e->g.n_ind, g.d_members, g.d_off, g.d_work, g.d_gp_first, g.n_work, (uint32_t)g.n_gp};
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
@@ -103,17 +105,30 @@ int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *
     const uint64_t n = std::min(chunk, n_mat - m0);
     HIPCHK(hipEventRecord(e->ev[0], e->st));
     ngd_launch_group_means(e->st, l, d_sum + m0 * n_pairs, d_cnt + m0 * n_pairs, n, tot_sites, (uint32_t)evol_model, g.d_part_sum,
-                           g.d_part_cnt, g.d_mean, g.d_used);
+                           g.d_part_cnt, keep ? g.d_keep_mean + m0 * g.n_gp : g.d_mean.get(),
+                           keep ? g.d_keep_used + m0 * g.n_gp : g.d_used.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[1], e->st));
-    HIPCHK(hipMemcpyAsync(mean + m0 * g.n_gp, g.d_mean, n * g.n_gp * sizeof(double), hipMemcpyDeviceToHost, e->st));
-    if (used) HIPCHK(hipMemcpyAsync(used + m0 * g.n_gp, g.d_used, n * g.n_gp * sizeof(uint64_t), hipMemcpyDeviceToHost, e->st));
+    if (!keep) {
+      HIPCHK(hipMemcpyAsync(mean + m0 * g.n_gp, g.d_mean, n * g.n_gp * sizeof(double), hipMemcpyDeviceToHost, e->st));
+      if (used) HIPCHK(hipMemcpyAsync(used + m0 * g.n_gp, g.d_used, n * g.n_gp * sizeof(uint64_t), hipMemcpyDeviceToHost, e->st));
+    }
     HIPCHK(hipStreamSynchronize(e->st));
     float ms = 0;
     hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
     g.ms += ms;
   }
   return NGD_OK;
+}
+
+int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                  uint64_t evol_model, double *mean, uint64_t *used) {
+  return groups_reduce_impl(e, d_sum, d_cnt, n_mat, tot_sites, evol_model, mean, used, false);
+}
+
+int groups_reduce_keep(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                       uint64_t evol_model) {
+  return groups_reduce_impl(e, d_sum, d_cnt, n_mat, tot_sites, evol_model, nullptr, nullptr, true);
 }
 
 int ngd_group_means_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_mat, uint64_t tot_sites,

@@ -943,6 +943,26 @@ int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, u
   }, nullptr, n_rep ? &bv : nullptr);
 }
 
+// ... bootstrap summaries (ngd_run_windows_job_var_stats, ngd_run_windows_job_var_groups_stats; engine_boot_stats.hip has
+// checked what is the summaries'): the sibling's checks, then every group of windows -- whole sets: n_rep + 1 matrices per
+// window -- from the batch buffers through boot_reduce; 5 doubles and a count per cell leave the device
+int windows_host_stats(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
+                       const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
+                       BootCi ci, bool groups, double *stats, uint64_t *used, const char *who) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = windows_job_var_check(e, lo, hi, n_win, maps, maps_len, map_off, n_rep, block_size, who, st, bv)) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  const uint64_t n_mat = (uint64_t)n_rep + 1, n_cells = groups ? e->grp.n_gp : ngd_n_pairs(e->g.n_ind);
+  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
+    double *s = stats + w0 * NGD_BOOT_NSTAT * n_cells;
+    uint64_t *u = used + w0 * n_cells;
+    if (!groups) return boot_reduce(e, e->d_bsum, e->d_bcnt, false, n, n_mat, n_cells, tot_sites, evol_model, ci, s, u);
+    if (int rc = groups_reduce_keep(e, e->d_bsum, e->d_bcnt, n * n_mat, tot_sites, evol_model)) return rc;
+    return boot_reduce(e, e->grp.d_keep_mean, nullptr, true, n, n_mat, n_cells, 0, 0, ci, s, u);
+  }, nullptr, &bv);
+}
+
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {
   if (!e || !info) return fail(NGD_E_INVALID, "ngd_last_windows: null argument");
   *info = e->win_info;

@@ -14,15 +14,7 @@
 
 #define NGD_GROUP_THREADS 256
 
-// d = sum / cnt, then the model's transform: ngd_finish's operations in its order (host_util.cpp finish_range), compiled
-// without fast-math and with -ffp-contract=off like it -- the division and the products carry the host's bits, log is the
-// device's
-__device__ inline double group_cell(double s, double c, uint32_t model) {
-  double d = s / c;
-  if (model == 1) d = -log(1 - d);
-  else if (model == 2) d = -log(1 - (d * 4 / 3)) * 3 / 4;
-  return d;
-}
+// (a cell's value: group_cell, ngd_internal.h)
 
 __global__ __launch_bounds__(NGD_GROUP_THREADS) void k_group_means(const double *__restrict__ d_sum,
                                                                    const unsigned long long *__restrict__ d_cnt,

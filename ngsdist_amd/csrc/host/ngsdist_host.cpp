@@ -35,7 +35,9 @@
 //    NGD_OPT_EAGER_FULL; 2: on the --indep_geno path too; 0: never), --stage piece_MiB,ring[,share_MiB[,drop]] (the load
 //    pipeline's geometry, for measurements: tools/r6_stage_sweep.sh), --groups FILE (the group of every individual: <out>
 //    holds the G x G table of mean distances within and between groups of every matrix, <out>.used the cells behind them;
-//    one GPU, the whole data set resident);
+//    one GPU, the whole data set resident), --boot_stats [--boot_ci X] (with --n_boot_rep or --win_boot_rep: the replicates
+//    stay on the device, <out> holds the estimates and <out>.boot_mean / _sd / _lo / _hi / _used the replicates' summaries
+//    per cell; one GPU, the whole data set resident);
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
@@ -77,6 +79,12 @@
 #pragma weak ngd_run_job_groups
 #pragma weak ngd_run_windows_groups
 #pragma weak ngd_run_windows_job_var_groups
+// (--boot_stats: the summaries over a set's replicates, reduced on the device)
+#pragma weak ngd_boot_stats_max_rep
+#pragma weak ngd_run_job_stats
+#pragma weak ngd_run_windows_job_var_stats
+#pragma weak ngd_run_job_groups_stats
+#pragma weak ngd_run_windows_job_var_groups_stats
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -134,6 +142,13 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // no group).  <out> then holds, per matrix, the G x G table of mean distances within and between groups -- the engine
   // reduces every matrix on the device (ngd_run_*_groups) -- and <out>.used the cells behind each mean.  Not in the reference.
   const char *in_groups = nullptr;
+  // --boot_stats [--boot_ci X]: with --n_boot_rep R or --win_boot_rep R the replicates stay on the device, which reduces
+  // every cell of a set (the run's, or a window's R + 1 matrices) to its estimate, the replicates' mean, standard deviation
+  // and a percentile interval of coverage X (ngd_run_*_stats).  <out> holds matrix 0 of every set -- the run without
+  // replicates --, <out>.boot_mean / .boot_sd / .boot_lo / .boot_hi the same blocks of the other statistics and
+  // <out>.boot_used the finite replicates behind them.  With --groups the cells are the group pairs.  Not in the reference.
+  bool boot_stats = false, boot_ci_set = false;
+  double boot_ci = 0.95;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -246,6 +261,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"win_bp_step", required_argument, nullptr, 1018},
                                  {"win_min_sites", required_argument, nullptr, 1019},
                                  {"groups", required_argument, nullptr, 1020},
+                                 {"boot_stats", no_argument, nullptr, 1021},
+                                 {"boot_ci", required_argument, nullptr, 1022},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -288,6 +305,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1018: p.win_bp_step_set = true; p.win_bp_step = strtoll(optarg, nullptr, 10); break;
       case 1019: p.win_min_sites_set = true; p.win_min_sites = strtoll(optarg, nullptr, 10); break;
       case 1020: p.in_groups = optarg; break;
+      case 1021: p.boot_stats = true; break;
+      case 1022: p.boot_ci_set = true; p.boot_ci = atof(optarg); break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -337,6 +356,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.em_exact_boot) fprintf(stderr, "\tem_exact_boot: true\n\n");
     if (p.em_exact_win) fprintf(stderr, "\tem_exact_win: true\n\n");
     if (p.in_groups) fprintf(stderr, "\tgroups: %s\n\n", p.in_groups);
+    if (p.boot_stats) fprintf(stderr, "\tboot_stats: true\n\tboot_ci: %f\n\n", p.boot_ci);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -402,6 +422,13 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.n_gpus > 1) die(__FUNCTION__, "windows (--win_size) are computed on one GPU (--n_gpus 1)!");
   }
   if (p.in_groups && p.n_gpus > 1) die(__FUNCTION__, "group means (--groups) are computed on one GPU (--n_gpus 1)!");
+  if (p.boot_ci_set && !p.boot_stats) die(__FUNCTION__, "interval coverage (--boot_ci) requires bootstrap summaries (--boot_stats)!");
+  if (p.boot_stats) {
+    if (!(p.boot_ci > 0.0 && p.boot_ci < 1.0)) die(__FUNCTION__, "interval coverage (--boot_ci) must lie between 0 and 1!");
+    if (p.n_boot_rep < 1 && p.win_boot_rep < 1)
+      die(__FUNCTION__, "bootstrap summaries (--boot_stats) require bootstrap replicates (--n_boot_rep or --win_boot_rep)!");
+    if (p.n_gpus > 1) die(__FUNCTION__, "bootstrap summaries (--boot_stats) are computed on one GPU (--n_gpus 1)!");
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1253,6 +1280,13 @@ int main(int argc, char **argv) {
       die(__FUNCTION__, "this build of the engine has no group means (--groups)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu groups\n", (unsigned long)group_names.size());
   }
+  if (p.boot_stats) {
+    if (!ngd_boot_stats_max_rep || !ngd_run_job_stats || !ngd_run_windows_job_var_stats || !ngd_run_job_groups_stats ||
+        !ngd_run_windows_job_var_groups_stats)
+      die(__FUNCTION__, "this build of the engine has no bootstrap summaries (--boot_stats)!");
+    if (std::max<uint64_t>(p.n_boot_rep, p.win_boot_rep) > ngd_boot_stats_max_rep())
+      die(__FUNCTION__, "too many bootstrap replicates for bootstrap summaries (--boot_stats): a cell's replicates stay in on-chip memory!");
+  }
 
   // positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149 -- except for the chromosomes
   // and coordinates of --win_size's windows
@@ -1308,9 +1342,9 @@ int main(int argc, char **argv) {
     win_bp_start.resize((size_t)n_win);
     ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, win_lo.data(), win_hi.data(), win_bp_start.data(),
                          (uint64_t)n_win);
-    if (!p.in_groups && !ngd_run_windows_dist)  // (--groups: its own entry points, checked above)
+    if (!p.in_groups && !p.boot_stats && !ngd_run_windows_dist)  // (--groups, --boot_stats: their own entry points, checked above)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (!p.in_groups && p.win_boot_rep && !ngd_run_windows_job_var_dist)
+    if (!p.in_groups && !p.boot_stats && p.win_boot_rep && !ngd_run_windows_job_var_dist)
       die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu bp every %lu bp\n", (unsigned long)n_win, (unsigned long)B, (unsigned long)T);
   } else if (p.win) {
@@ -1321,9 +1355,9 @@ int main(int argc, char **argv) {
     win_lo.resize((size_t)n_win);
     win_hi.resize((size_t)n_win);
     ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win_lo.data(), win_hi.data(), (uint64_t)n_win);
-    if (!p.in_groups && !ngd_run_windows_dist)  // (--groups: its own entry points, checked above)
+    if (!p.in_groups && !p.boot_stats && !ngd_run_windows_dist)  // (--groups, --boot_stats: their own entry points, checked above)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (!p.in_groups && p.win_boot_rep && !ngd_run_windows_job_dist)
+    if (!p.in_groups && !p.boot_stats && p.win_boot_rep && !ngd_run_windows_job_dist)
       die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows (--win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
   }
@@ -1389,6 +1423,8 @@ int main(int argc, char **argv) {
   eager_ranges = in_parts;
   if (p.win && in_parts)
     die(__FUNCTION__, "windows (--win_size) need the whole data set on one GPU; it does not fit the device budget!");
+  if (p.boot_stats && in_parts)
+    die(__FUNCTION__, "bootstrap summaries (--boot_stats) need the whole data set on one GPU; it does not fit the device budget!");
   if (p.in_groups && in_parts)
     die(__FUNCTION__, "group means (--groups) need the whole data set on one GPU; it does not fit the device budget!");
 
@@ -1472,7 +1508,7 @@ int main(int argc, char **argv) {
                   b * p.boot_block_size + s, bm[b], bm[b] * p.boot_block_size + s);
     }
     if (p.verbose >= 2) fprintf(stderr, "> Calculating pairwise genetic distances...\n");
-    if (p.verbose >= 3 && !window) {  // the per-pair line of ngsDist.cpp:366-367
+    if (p.verbose >= 3 && !window && rs) {  // the per-pair line of ngsDist.cpp:366-367
       uint64_t k = 0;
       for (uint64_t i1 = 0; i1 < p.n_ind; i1++)
         for (uint64_t i2 = i1 + 1; i2 < p.n_ind; i2++, k++)
@@ -1687,7 +1723,105 @@ int main(int argc, char **argv) {
     }
     if (fclose(wf) != 0) die(__FUNCTION__, "cannot write windows output file!");
   };
-  if (p.in_groups) {
+  if (p.boot_stats) {
+    // ---- bootstrap summaries: the replicates of every set -- the run's, or a window's -- stay on the device, which reduces
+    // each cell to five statistics and a count (ngd_run_*_stats).  <out> takes the estimates (matrix 0 of every set: the
+    // bytes of the run without replicates), <out>.boot_mean / _sd / _lo / _hi the other statistics in the same blocks and
+    // <out>.boot_used the finite replicates behind them, as integers; with --groups the blocks are G x G ----
+    int rc = 0;
+    const bool grp = p.in_groups != nullptr;
+    if (grp && (rc = ngd_set_groups(eng.h, group_of.data(), (uint32_t)group_names.size()))) die_engine("ngd_set_groups", rc);
+    const uint64_t G = group_names.size(), n_cells = grp ? G * (G + 1) / 2 : n_comb;
+    static const char *const kSuffix[NGD_BOOT_NSTAT + 1] = {"", ".boot_mean", ".boot_sd", ".boot_lo", ".boot_hi", ".boot_used"};
+    FILE *sf[NGD_BOOT_NSTAT + 1] = {out_fh};
+    for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
+      if (!(sf[k] = fopen((std::string(p.out) + kSuffix[k]).c_str(), "w"))) die(__FUNCTION__, "cannot open bootstrap summaries output file!");
+    std::vector<char> text;
+    std::string txt, cnt, skip;
+    // one set's blocks: est through emit() (pairs: the progress lines and the writer of any matrix), the rest formatted here
+    auto write_set = [&](uint64_t w, const char *name, const double *st, const uint64_t *us) {
+      if (grp) {
+        for (int k = 0; k < NGD_BOOT_NSTAT; k++) {
+          txt.clear();
+          (k ? skip : cnt).clear();
+          format_groups(group_names, st + k * n_cells, us, txt, k ? skip : cnt);
+          if (fwrite(txt.data(), 1, txt.size(), sf[k]) != txt.size()) die(__FUNCTION__, "cannot write output file!");
+        }
+      } else {
+        emit(w, nullptr, nullptr, nullptr, 0, st, 0, name);
+        if (text.empty()) text.resize(64 + p.n_ind * (p.n_ind * 16 + 64));
+        for (int k = 1; k < NGD_BOOT_NSTAT; k++) {
+          int64_t need = ngd_format_matrix(st + k * n_cells, p.n_ind, label_ptr.data(), text.data(), text.size(), p.n_threads);
+          if (need > (int64_t)text.size()) {
+            text.resize((size_t)need);
+            need = ngd_format_matrix(st + k * n_cells, p.n_ind, label_ptr.data(), text.data(), text.size(), p.n_threads);
+          }
+          if (need < 0 || fwrite(text.data(), 1, (size_t)need, sf[k]) != (size_t)need) die(__FUNCTION__, "cannot write output file!");
+        }
+        // the counts in a matrix's layout: "\n<n_ind>\n", per individual its label and n_ind cells "\t<m>" (0 on the diagonal)
+        cnt = "\n" + std::to_string(p.n_ind) + "\n";
+        for (uint64_t i = 0; i < p.n_ind; i++) {
+          cnt += labels[i];
+          for (uint64_t j = 0; j < p.n_ind; j++) {
+            const uint64_t a = std::min(i, j), b = std::max(i, j);
+            cnt += "\t" + std::to_string(i == j ? 0 : (unsigned long)us[a * p.n_ind - a * (a + 1) / 2 + (b - a - 1)]);
+          }
+          cnt += "\n";
+        }
+      }
+      if (fwrite(cnt.data(), 1, cnt.size(), sf[NGD_BOOT_NSTAT]) != cnt.size()) die(__FUNCTION__, "cannot write output file!");
+    };
+    std::vector<double> st;
+    std::vector<uint64_t> us;
+    if (p.win) {
+      // every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length share them); a
+      // window shorter than one block has replicates of 0 / 0: no finite replicate
+      const uint64_t n_win = win_lo.size(), R = p.win_boot_rep;
+      std::vector<uint64_t> off(n_win);
+      const int64_t len = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0,
+                                               off.data());
+      if (len < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
+      std::vector<uint64_t> maps((size_t)len + 1);
+      ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, maps.data(), (uint64_t)len, off.data());
+      // a group of windows per call: their statistics in ~2 GB of host memory
+      const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * (NGD_BOOT_NSTAT + 1) * std::max<uint64_t>(1, n_cells))));
+      for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
+        const uint64_t n = std::min(per, n_win - w0);
+        const auto t_c0 = std::chrono::steady_clock::now();
+        st.resize(n * NGD_BOOT_NSTAT * n_cells);
+        us.resize(n * n_cells);
+        rc = (grp ? ngd_run_windows_job_var_groups_stats : ngd_run_windows_job_var_stats)(
+            eng.h, &win_lo[w0], &win_hi[w0], n, maps.data(), (uint64_t)len, &off[w0], (uint32_t)R, p.boot_block_size, p.tot_sites,
+            p.evol_model, p.boot_ci, st.data(), us.data());
+        if (rc) die_engine(grp ? "ngd_run_windows_job_var_groups_stats" : "ngd_run_windows_job_var_stats", rc);
+        report_fixup(eng.h, p.verbose);
+        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
+        for (uint64_t k = 0; k < n; k++) {
+          const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
+          write_set(w0 + k, name.c_str(), &st[k * NGD_BOOT_NSTAT * n_cells], &us[k * n_cells]);
+        }
+        if (!grp) writer.wait_idle();  // (the last block's text is written before the next group's call)
+      }
+      write_windows_file();
+    } else {
+      // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
+      const uint64_t R = p.n_boot_rep, n_blocks = (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size;
+      if (!n_blocks) die(__FUNCTION__, "bootstrap summaries (--boot_stats) need at least one bootstrap block of sites!");
+      const auto t_c0 = std::chrono::steady_clock::now();
+      std::vector<uint64_t> maps(R * n_blocks);
+      for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
+      st.resize(NGD_BOOT_NSTAT * n_cells);
+      us.resize(n_cells);
+      rc = (grp ? ngd_run_job_groups_stats : ngd_run_job_stats)(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites,
+                                                                 p.evol_model, p.boot_ci, st.data(), us.data());
+      if (rc) die_engine(grp ? "ngd_run_job_groups_stats" : "ngd_run_job_stats", rc);
+      report_fixup(eng.h, p.verbose);
+      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
+      write_set(0, nullptr, st.data(), us.data());
+    }
+    for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
+      if (fclose(sf[k]) != 0) die(__FUNCTION__, "cannot write bootstrap summaries output file!");
+  } else if (p.in_groups) {
     // ---- group means: every matrix of the run -- the full data set and its replicates, or the windows and theirs -- leaves
     // the engine as its G x G table (ngd_run_*_groups): one block per matrix in <out>, in the order of the run without
     // --groups, and the same blocks with the numbers of cells behind the means in <out>.used ----
@@ -1767,7 +1901,9 @@ int main(int argc, char **argv) {
     }
     if (fclose(uf) != 0) die(__FUNCTION__, "cannot write used output file!");
   }
-  if (p.in_groups) {
+  if (p.boot_stats) {
+    // (written above)
+  } else if (p.in_groups) {
     if (p.win) write_windows_file();  // (the windows' own file: as without --groups)
   } else if (p.win) {
     // ---- windows along the genome: one matrix per window, in window order, a group of windows per engine call (their

@@ -751,3 +751,48 @@ int ngd_finish_matrices_stream(const double *sum, const uint64_t *cnt, const uin
   }
   return NGD_OK;
 }
+
+// ---- bootstrap summaries (--boot_stats): the definitions of include/ngsdist_amd.h "Bootstrap summaries" in plain host
+// arithmetic, cell by cell: est, then the finite replicates' mean and standard deviation in ascending r (no contraction:
+// -ffp-contract=off), then two order statistics of their sorted values ----
+int ngd_boot_stats_host(const double *val, uint64_t n_set, uint64_t n_mat, uint64_t n_cells, double ci, double *stats,
+                        uint64_t *used) {
+  if (!val || !stats || !used || !n_set || n_mat < 2 || !(ci > 0.0 && ci < 1.0)) return NGD_E_INVALID;
+  const double p_lo = (1.0 - ci) / 2.0, p_hi = 1.0 - p_lo;
+  const uint64_t nan_bits = 0x7FF8000000000000ull;
+  double nan;
+  memcpy(&nan, &nan_bits, 8);
+  std::vector<double> f;
+  f.reserve(n_mat);
+  for (uint64_t s = 0; s < n_set; s++)
+    for (uint64_t c = 0; c < n_cells; c++) {
+      const double *v = val + s * n_mat * n_cells + c;
+      double *out = stats + s * NGD_BOOT_NSTAT * n_cells + c;
+      f.clear();
+      double acc = 0.0;
+      for (uint64_t r = 1; r < n_mat; r++) {
+        const double x = v[r * n_cells];
+        if (std::isfinite(x)) { acc += x; f.push_back(x); }
+      }
+      const uint64_t m = f.size();
+      const double mean = m ? acc / (double)m : nan;
+      double ss = 0.0;
+      for (double x : f) {
+        const double d = x - mean;
+        ss += d * d;
+      }
+      out[0] = v[0];
+      out[n_cells] = mean;
+      out[2 * n_cells] = m >= 2 ? std::sqrt(ss / (double)(m - 1)) : nan;
+      out[3 * n_cells] = out[4 * n_cells] = nan;
+      if (m) {
+        std::sort(f.begin(), f.end());
+        const uint64_t k_lo = (uint64_t)std::floor(p_lo * (double)(m - 1));
+        const uint64_t k_hi = std::min<uint64_t>(m - 1, (uint64_t)std::ceil(p_hi * (double)(m - 1)));
+        out[3 * n_cells] = f[std::min(k_lo, k_hi)];
+        out[4 * n_cells] = f[k_hi];
+      }
+      used[s * n_cells + c] = m;
+    }
+  return NGD_OK;
+}

@@ -252,8 +252,16 @@ struct ngd_engine : ngd_mem {
     DevBuf<ngd_group_work> d_work;
     DevBuf<double> d_part_sum, d_mean;
     DevBuf<unsigned long long> d_part_cnt, d_used;
+    DevBuf<double> d_keep_mean;              // the means of a call's every matrix, kept for the summaries (groups_reduce_keep)
+    DevBuf<unsigned long long> d_keep_used;
     double ms = 0;  // ngd_last_groups_ms
   } grp;
+  // bootstrap summaries (engine_boot_stats.hip): a chunk of sets' statistics and counts on their way to the host
+  struct BootStats {
+    DevBuf<double> d_stats;
+    DevBuf<unsigned long long> d_used;
+    double ms = 0;  // ngd_last_boot_stats_ms
+  } bst;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
@@ -366,6 +374,21 @@ int run_dist(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, ui
 // engine_groups.hip: [n_mat][n_pairs] device matrices -> mean / used [n_mat][n_gp] in host memory (the arguments are checked)
 int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
                   uint64_t evol_model, double *mean, uint64_t *used);
+// ... the same reduction with the means left in device memory: grp.d_keep_mean / d_keep_used [n_mat][n_gp]
+int groups_reduce_keep(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                       uint64_t evol_model);
+// engine_boot_stats.hip: the summaries of [n_set][n_mat][n_cells] device matrices -> stats / used in host memory; d_cnt and
+// the two arguments of ngd_finish for sums and counts, `values` for cells as they are (the arguments are checked)
+struct BootCi {
+  double p_lo, p_hi;
+};
+int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
+                uint64_t n_cells, uint64_t tot_sites, uint64_t evol_model, BootCi ci, double *stats, uint64_t *used);
+// engine_windows.hip: ngd_run_windows_job_var_device through the batch buffers, every group of windows -- whole sets --
+// summarised by boot_reduce; groups: the group reduction first, the means' summaries (n_cells = n_gp)
+int windows_host_stats(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
+                       const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
+                       BootCi ci, bool groups, double *stats, uint64_t *used, const char *who);
 // engine_windows.hip: the windowed calls through the batch buffers, every group of windows reduced by groups_reduce
 // (n_rep == 0, or maps NULL with it: the windows alone)
 int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,

@@ -409,6 +409,35 @@ void ngd_launch_fill_cnt(hipStream_t st, const ngd_geom &g, const ngd_tile *d_ti
                          unsigned long long value, const unsigned long long *d_values, uint32_t n_rep,
                          unsigned long long *d_cnt);
 
+// d = sum / cnt, then the model's transform: ngd_finish's operations in its order (host_util.cpp finish_range), compiled
+// without fast-math and with -ffp-contract=off like it -- the division and the products carry the host's bits, log is the
+// device's (group_reduce.hip, boot_stats.hip)
+#ifdef __HIPCC__
+__device__ inline double group_cell(double s, double c, uint32_t model) {
+  double d = s / c;
+  if (model == 1) d = -log(1 - d);
+  else if (model == 2) d = -log(1 - (d * 4 / 3)) * 3 / 4;
+  return d;
+}
+#endif
+
+// boot_stats.hip : per-cell summaries over the n_mat = R + 1 matrices of a set (include/ngsdist_amd.h "Bootstrap summaries")
+#define NGD_BOOT_LDS_BYTES 163840u  // the LDS a workgroup may have on gfx950 (160 KiB, the CU's)
+#define NGD_BOOT_MIN_TILE 16u       // the narrowest tile of cells: it sets the largest n_mat
+#define NGD_BOOT_MAX_MAT (NGD_BOOT_LDS_BYTES / (NGD_BOOT_MIN_TILE * 8u))
+// cells per workgroup at n_mat matrices: the widest of 64, 32, 16 whose [n_mat][C] doubles fit (0: none does)
+inline uint32_t ngd_boot_tile(uint64_t n_mat) {
+  for (uint32_t c = 64; c >= NGD_BOOT_MIN_TILE; c >>= 1)
+    if (n_mat * c * 8 <= NGD_BOOT_LDS_BYTES) return c;
+  return 0;
+}
+// [n_set][n_mat][n_cells] sums and counts (d_cnt is not read when tot_sites > 0) or, `values`, the cells' values as they
+// are (d_cnt, tot_sites and model unused) -> d_stats [n_set][5][n_cells], d_used [n_set][n_cells].  2 <= n_mat <=
+// NGD_BOOT_MAX_MAT and n_set * ceil(n_cells / tile) below 2^31 (grid.x): the caller's to see to.  Returns a hipError_t.
+int ngd_launch_boot_stats(hipStream_t st, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set,
+                          uint32_t n_mat, uint64_t n_cells, uint64_t tot_sites, uint32_t model, double p_lo, double p_hi,
+                          double *d_stats, unsigned long long *d_used);
+
 // group_reduce.hip : group-mean distance matrices (ngd_set_groups, ngd_group_means_device, ngd_run_*_groups)
 // One work item: rows [r0, r1) of group pair (a, b) -- positions in group a's member list --, every column of group b
 #define NGD_GROUP_WG_CELLS 4096  // cells of a work item's rectangle, about: whole rows, at least one

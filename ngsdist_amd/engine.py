@@ -422,6 +422,75 @@ class Engine:
         _check(self._L.ngd_last_groups_ms(self._h, C.byref(v)))
         return float(v.value)
 
+    # -- bootstrap summaries: per cell est, mean, sd, lo, hi over a set's replicates instead of its R + 1 matrices ------
+    @staticmethod
+    def _stats_out(lead, n_cells):
+        stats = np.empty(lead + (_lib.NSTAT, n_cells), dtype=np.float64)
+        used = np.empty(lead + (n_cells,), dtype=np.uint64)
+        return stats, used, stats.ctypes.data_as(C.POINTER(C.c_double)), used.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    def boot_stats(self, d_sum_ptr, d_cnt_ptr, n_set, n_mat, evol_model=1, tot_sites=0, ci=0.95):
+        """the summaries of device matrices (ngd_boot_stats_device; raw addresses of [n_set][n_mat][n_pairs] sums and counts,
+        as a *_device call wrote them): -> (stats float64[n_set][5][n_pairs], used uint64[n_set][n_pairs]); stats are est,
+        mean, sd, lo, hi of every cell over the finite ones of its n_mat - 1 replicates, used their number"""
+        stats, used, sp, up = self._stats_out((int(n_set),), self.n_pairs)
+        _check(self._L.ngd_boot_stats_device(self._h, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr), int(n_set), int(n_mat),
+                                             int(tot_sites), int(evol_model), float(ci), sp, up))
+        return stats, used
+
+    def boot_stats_values(self, d_val_ptr, n_set, n_mat, n_cells, ci=0.95):
+        """the summaries of [n_set][n_mat][n_cells] float64 values in device memory as they are
+        (ngd_boot_stats_values_device): -> (stats float64[n_set][5][n_cells], used uint64[n_set][n_cells])"""
+        stats, used, sp, up = self._stats_out((int(n_set),), int(n_cells))
+        _check(self._L.ngd_boot_stats_values_device(self._h, C.c_void_p(d_val_ptr), int(n_set), int(n_mat), int(n_cells),
+                                                    float(ci), sp, up))
+        return stats, used
+
+    def run_job_stats(self, block_maps, block_size=1, evol_model=1, tot_sites=0, ci=0.95):
+        """run_job() and the summaries of its one set on the device (ngd_run_job_stats): -> (stats float64[5][n_pairs],
+        used uint64[n_pairs])"""
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        stats, used, sp, up = self._stats_out((), self.n_pairs)
+        _check(self._L.ngd_run_job_stats(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model),
+                                         float(ci), sp, up))
+        return stats, used
+
+    def run_job_groups_stats(self, block_maps, block_size=1, evol_model=1, tot_sites=0, ci=0.95):
+        """run_job(), the group reduction of its matrices and the summaries of the means, all on the device
+        (ngd_run_job_groups_stats): -> (stats float64[5][n_gp], used uint64[n_gp])"""
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        stats, used, sp, up = self._stats_out((), n_group_pairs(getattr(self, "n_groups", 0)))
+        _check(self._L.ngd_run_job_groups_stats(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model),
+                                                float(ci), sp, up))
+        return stats, used
+
+    def _windows_stats(self, fn, n_cells, lo, hi, block_maps, map_off, block_size, evol_model, tot_sites, n_rep, ci):
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
+        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        stats, used, sp, up = self._stats_out((lo.size,), n_cells)
+        _check(fn(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size), int(tot_sites), int(evol_model), float(ci), sp, up))
+        return stats, used
+
+    def run_windows_job_var_stats(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None, ci=0.95):
+        """run_windows_job_var() and the summaries of every window's set (ngd_run_windows_job_var_stats): -> (stats
+        float64[n_win][5][n_pairs], used uint64[n_win][n_pairs]); a window shorter than one block has used = 0"""
+        return self._windows_stats(self._L.ngd_run_windows_job_var_stats, self.n_pairs, lo, hi, block_maps, map_off, block_size,
+                                   evol_model, tot_sites, n_rep, ci)
+
+    def run_windows_job_var_groups_stats(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None,
+                                         ci=0.95):
+        """run_windows_job_var(), the group reduction and the summaries of every window's means
+        (ngd_run_windows_job_var_groups_stats): -> (stats float64[n_win][5][n_gp], used uint64[n_win][n_gp])"""
+        return self._windows_stats(self._L.ngd_run_windows_job_var_groups_stats, n_group_pairs(getattr(self, "n_groups", 0)), lo, hi,
+                                   block_maps, map_off, block_size, evol_model, tot_sites, n_rep, ci)
+
+    def last_boot_stats_ms(self):
+        """device time of the summary kernels in the last of these calls (ngd_last_boot_stats_ms)"""
+        v = C.c_double(0.0)
+        _check(self._L.ngd_last_boot_stats_ms(self._h, C.byref(v)))
+        return float(v.value)
+
     def run_job_keep(self, block_maps, block_size=1):
         """ngd_run_job with the matrices left in the engine; fetch_matrix(r) copies them out one at a time"""
         a = np.ascontiguousarray(block_maps, dtype=np.uint64)
@@ -653,6 +722,27 @@ def expand_groups(mean, n_groups):
     out[..., a, b] = m
     out[..., b, a] = m
     return out
+
+
+def boot_stats_max_rep():
+    """the most replicates the device's summaries serve (ngd_boot_stats_max_rep): a cell's values stay in on-chip memory"""
+    return int(_lib.load().ngd_boot_stats_max_rep())
+
+
+def boot_stats_host(values, ci=0.95):
+    """the summaries in plain host arithmetic (ngd_boot_stats_host), for callers of the *_dist forms: values
+    float64[..., n_mat, n_cells], matrix 0 the estimate and the others its replicates -> (stats float64[..., 5, n_cells] =
+    est, mean, sd, lo, hi; used uint64[..., n_cells])"""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.ndim < 2:
+        raise ValueError("values: expected [..., n_mat, n_cells]")
+    lead, (n_mat, n_cells) = v.shape[:-2], v.shape[-2:]
+    n_set = int(np.prod(lead, dtype=np.int64))
+    stats = np.empty(lead + (_lib.NSTAT, n_cells), dtype=np.float64)
+    used = np.empty(lead + (n_cells,), dtype=np.uint64)
+    _check(_lib.load().ngd_boot_stats_host(v.ctypes.data_as(C.POINTER(C.c_double)), n_set, n_mat, n_cells, float(ci),
+                                           stats.ctypes.data_as(C.POINTER(C.c_double)), used.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return stats, used
 
 
 def score_congruence(score):
