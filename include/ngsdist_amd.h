@@ -404,6 +404,9 @@ int ngd_drop_caches(ngd_engine *e);
                                  /*     through the noting plans of value 2 and fails as they do where none applies.              */
                                  /*     NGD_E_INVALID for values above 1, and for 1 on the engines that refuse NGD_OPT_EM_EXACT   */
                                  /*     (--indep_geno, an explicit kernel other than NGD_KERNEL_EM_TABLE)                         */
+#define NGD_OPT_NJ_MAX_BYTES 19    /* [0 = 2 GB] device scratch of the neighbour-joining kernel (ngd_nj_*, ngd_run_*_nj): a full n x n */
+                                 /*     matrix of doubles (rows padded to an even length) per matrix of a launch; never fewer    */
+                                 /*     than one matrix.  Any value gives the same bits                                          */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -722,6 +725,85 @@ int ngd_run_windows_job_var_groups_stats(ngd_engine *e, const uint64_t *win_lo, 
                                          uint64_t *used);
 /* device time (HIP events) of the summary kernels in the last of these calls, summed over its launches */
 int ngd_last_boot_stats_ms(const ngd_engine *e, double *ms);
+
+/* Neighbour-joining trees (added under ABI 6): one unrooted tree per matrix leaves the device -- 2n - 3 branches --
+ * instead of n (n - 1) / 2 sums and counts.  Canonical neighbour joining (Saitou & Nei 1987; Studier & Keppler 1988), stated
+ * so that a tree's bits are a function of its matrix alone, never of storage, launch, chunk or reduction order.  Every
+ * floating-point operation is a per-element formula evaluated exactly as parenthesised, in double, without contraction;
+ * the one sum whose order matters is given its order.
+ *   input      d[a][b] for the leaves 0 .. n - 1, n = n_ind >= 3, from a matrix's n_pairs cells in ngd_pair_index order;
+ *              internal nodes get the ids n, n + 1, .. in order of creation; m = the number of live nodes
+ *   at start   r_a = SUM_{b != a} d[a][b], the terms added one by one in ascending b starting from 0.0
+ *   while m > 3
+ *     for live a < b (node ids):  Q(a,b) = ((double)(m - 2) * d_ab - r_a) - r_b
+ *     join the pair (i, j), i < j, that is smallest in the total order on (Q, a, b): a tie in Q goes to the lower a,
+ *       then to the lower b
+ *     l_i = 0.5 * d_ij + (r_i - r_j) / (2.0 * (double)(m - 2)),  l_j = d_ij - l_i   (negative lengths are left as they come)
+ *     new node u; for every other live k:  d_uk = 0.5 * ((d_ik + d_jk) - d_ij),  r_k = ((r_k - d_ik) - d_jk) + d_uk
+ *     r_u = 0.5 * ((r_i + r_j) - (double)m * d_ij)   (the closed form of SUM_k d_uk: no order)
+ *   at m = 3, a < b < c, the three branches to the centre:
+ *     l_a = 0.5 * ((d_ab + d_ac) - d_bc),  l_b = 0.5 * ((d_ab + d_bc) - d_ac),  l_c = 0.5 * ((d_ac + d_bc) - d_ab)
+ * Record of a matrix: NGD_NJ_NBRANCH(n) = 2n - 3 entries of child (int32) and len (double), and one status (uint32).
+ * Join t (t < n - 3) makes node n + t: entries 2t and 2t + 1 of child are i and j, the same entries of len l_i and l_j; the
+ * last three entries are a, b, c and their lengths.  Outputs, in host memory: child[n_mat][2n - 3], len[n_mat][2n - 3],
+ * status[n_mat].
+ * A matrix with any cell that is not finite (NaN, +-inf: no shared site under --pairwise_del, the replicates of a window
+ * shorter than one block) has no tree: status 0, every child -1, every len a positive quiet NaN; otherwise status 1.  The
+ * other matrices of the call are not affected.  (Finite cells so large that a Q overflows are outside the contract: some
+ * tree is returned, its choice of pairs is not pinned.)
+ * From sums and counts a cell's value is ngd_finish()'s, operation by operation (the division and the products carry the
+ * host's bits, log is the device's).
+ * Ties at m = 4: the complementary pairs (a,b) and (c,d) of four live nodes have algebraically equal Q, so rounding picks
+ * between two records of the SAME unrooted tree -- best and second-best Q there differ by ~5e-16 relative on random data,
+ * while at every m >= 5 the smallest gap seen was 3e-5.  Device and host twin follow the same formulas and so pick alike
+ * for the same cells; values that differ in the last bits (the device's log) may pick the other record.  ngd_nj_support()
+ * counts both alike. */
+#define NGD_NJ_NBRANCH(n) (2 * (n) - 3)
+/* the most individuals the device form serves (the row sums and node ids of a matrix stay in on-chip memory); more is
+ * NGD_E_INVALID */
+uint32_t ngd_nj_max_ind(void);
+/* The contract in plain host arithmetic on val[n_mat][n_pairs]; needs no device, any n_ind >= 3; matrices are spread over
+ * host threads, which changes no bit.  NGD_E_INVALID: a null pointer, n_mat 0, n_ind < 3. */
+int ngd_nj_host(const double *val, uint64_t n_mat, uint64_t n_ind, int32_t *child, double *len, uint32_t *status);
+/* ... on the device (one workgroup per matrix, nj.hip), of [n_mat][n_pairs] values as they are, or of sums and counts in
+ * device memory as a *_device call wrote them (d_cnt is not read when tot_sites > 0); n_ind is the engine's.  The matrices
+ * go through device scratch (a full n x n matrix of doubles each) in chunks of NGD_OPT_NJ_MAX_BYTES; chunking changes no
+ * bit.  NGD_E_INVALID, before anything is launched: a null pointer, n_mat 0, n_ind < 3 or above ngd_nj_max_ind(), tot_sites
+ * with --pairwise_del, an engine that owns a share of the pairs; NGD_E_MODEL for evol_model > 2.  A refused call leaves
+ * outputs and engine as they were. */
+int ngd_nj_values_device(ngd_engine *e, const void *d_val, uint64_t n_mat, int32_t *child, double *len, uint32_t *status);
+int ngd_nj_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_mat, uint64_t tot_sites, uint64_t evol_model,
+                  int32_t *child, double *len, uint32_t *status);
+/* ngd_run_job_device (one set of n_rep + 1 matrices) / ngd_run_windows_device (one matrix per window) /
+ * ngd_run_windows_job_var_device (one set per window) into the engine's batch buffers, followed by that reduction: plans,
+ * fix-up, NGD_OPT_EM_EXACT* and refusals are the sibling's, and the trees are ngd_nj_device()'s on the sibling's output
+ * bit for bit at the same options.  n_rep = 0 is allowed: a plain run's one tree.  Outputs: child / len
+ * [n_set][n_rep + 1][2n - 3], status [n_set][n_rep + 1]; dist0, unless NULL, receives [n_set][n_pairs]: matrix 0 of every
+ * set finished by ngd_finish() on the host from its sums and counts -- the bits the _dist sibling gives. */
+int ngd_run_job_nj(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                   uint64_t tot_sites, uint64_t evol_model, int32_t *child, double *len, uint32_t *status, double *dist0);
+int ngd_run_windows_nj(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
+                       uint64_t evol_model, int32_t *child, double *len, uint32_t *status, double *dist0);
+int ngd_run_windows_job_var_nj(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                               const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                               uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, int32_t *child, double *len,
+                               uint32_t *status, double *dist0);
+/* device time (HIP events) of the tree kernels in the last of these calls, summed over its launches */
+int ngd_last_nj_ms(const ngd_engine *e, double *ms);
+/* Bootstrap support of matrix 0's tree, pure host: join t of matrix 0 defines the bipartition "leaves under node n + t |
+ * the rest"; support[t] (n - 3 entries) is the number of matrices r >= 1 with status 1 whose tree has the same
+ * bipartition, *n_used the number of those matrices.  Bipartitions are compared as leaf sets normalised to the side
+ * without leaf 0 (the two m = 4 records of one tree count alike).  Matrix 0 with status 0: every support 0.
+ * NGD_E_INVALID: a null pointer, n_mat 0, n_ind < 3, a child entry out of range in a tree with status 1. */
+int ngd_nj_support(const int32_t *child, const uint32_t *status, uint64_t n_mat, uint64_t n_ind, uint32_t *support,
+                   uint32_t *n_used);
+/* One record as a Newick line, pure host, sized like ngd_format_matrix (call with out = NULL): "(x,y,z);\n", a leaf
+ * "label:%.10f", an internal node "(x,y)" followed by its support number if support (n - 3 entries, by join) is not NULL,
+ * then ":%.10f"; children in recorded order; a tree with status 0 (child[0] < 0) is ";\n"; labels NULL (or a NULL entry):
+ * "Ind_<i>".  NGD_E_INVALID: a null pointer, n_ind < 3, an entry that names a node no earlier join made.  Returns the
+ * number of bytes (no terminator), written only if cap is large enough, or a negative NGD_E_* code. */
+int64_t ngd_nj_newick(const int32_t *child, const double *len, uint64_t n_ind, const char *const *labels, const uint32_t *support,
+                      char *out, uint64_t cap);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

@@ -92,6 +92,8 @@ EXPORTS = [
     "ngd_boot_stats_max_rep", "ngd_boot_stats_host", "ngd_boot_stats_device", "ngd_boot_stats_values_device",
     "ngd_run_job_stats", "ngd_run_windows_job_var_stats", "ngd_run_job_groups_stats", "ngd_run_windows_job_var_groups_stats",
     "ngd_last_boot_stats_ms",
+    "ngd_nj_max_ind", "ngd_nj_host", "ngd_nj_values_device", "ngd_nj_device", "ngd_run_job_nj", "ngd_run_windows_nj",
+    "ngd_run_windows_job_var_nj", "ngd_last_nj_ms", "ngd_nj_support", "ngd_nj_newick",
 ]
 
 NSTAT = 5  # NGD_BOOT_NSTAT: est, mean, sd, lo, hi
@@ -225,6 +227,19 @@ def load():
     L.ngd_run_windows_job_var_stats.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, u64, u64, C.c_double, dp, u64p]
     L.ngd_run_windows_job_var_groups_stats.argtypes = L.ngd_run_windows_job_var_stats.argtypes
     L.ngd_last_boot_stats_ms.argtypes = [vp, dp]
+    i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+    L.ngd_nj_max_ind.argtypes = []
+    L.ngd_nj_max_ind.restype = C.c_uint32
+    L.ngd_nj_host.argtypes = [dp, u64, u64, i32p, dp, u32p]
+    L.ngd_nj_values_device.argtypes = [vp, vp, u64, i32p, dp, u32p]
+    L.ngd_nj_device.argtypes = [vp, vp, vp, u64, u64, u64, i32p, dp, u32p]
+    L.ngd_run_job_nj.argtypes = [vp, u64p, C.c_uint32, u64, u64, u64, u64, i32p, dp, u32p, dp]
+    L.ngd_run_windows_nj.argtypes = [vp, u64p, u64p, u64, u64, u64, i32p, dp, u32p, dp]
+    L.ngd_run_windows_job_var_nj.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, C.c_uint32, u64, u64, u64, i32p, dp, u32p, dp]
+    L.ngd_last_nj_ms.argtypes = [vp, dp]
+    L.ngd_nj_support.argtypes = [i32p, u32p, u64, u64, u32p, u32p]
+    L.ngd_nj_newick.argtypes = [i32p, dp, u64, C.POINTER(C.c_char_p), u32p, C.c_char_p, u64]
+    L.ngd_nj_newick.restype = C.c_int64
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

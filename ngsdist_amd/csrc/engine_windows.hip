@@ -963,6 +963,27 @@ int windows_host_stats(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, ui
   }, nullptr, &bv);
 }
 
+// ... neighbour-joining trees (ngd_run_windows_nj, ngd_run_windows_job_var_nj; engine_nj.hip has checked what is the
+// trees'): the sibling's checks, then every group of windows -- whole sets: n_rep + 1 matrices per window -- from the batch
+// buffers through nj_reduce; 2 n - 3 branches per matrix leave the device, and matrix 0 of every set if dist0 asks for it
+int windows_host_nj(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
+                    const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
+                    int32_t *child, double *len, uint32_t *status, double *dist0, const char *who) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = n_rep ? windows_job_var_check(e, lo, hi, n_win, maps, maps_len, map_off, n_rep, block_size, who, st, bv)
+                     : windows_check(e, lo, hi, n_win, who))
+    return rc;
+  HIPCHK(hipSetDevice(e->device));
+  const uint64_t n_mat = (uint64_t)n_rep + 1, n_pairs = ngd_n_pairs(e->g.n_ind), nb = NGD_NJ_NBRANCH((uint64_t)e->g.n_ind);
+  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
+    if (int rc = nj_reduce(e, e->d_bsum, e->d_bcnt, false, n * n_mat, tot_sites, evol_model, child + w0 * n_mat * nb,
+                           len + w0 * n_mat * nb, status + w0 * n_mat))
+      return rc;
+    return dist0 ? nj_dist0(e, e->d_bsum, e->d_bcnt, n, n_mat, tot_sites, evol_model, dist0 + w0 * n_pairs) : NGD_OK;
+  }, nullptr, n_rep ? &bv : nullptr);
+}
+
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {
   if (!e || !info) return fail(NGD_E_INVALID, "ngd_last_windows: null argument");
   *info = e->win_info;

@@ -37,7 +37,9 @@
 //    holds the G x G table of mean distances within and between groups of every matrix, <out>.used the cells behind them;
 //    one GPU, the whole data set resident), --boot_stats [--boot_ci X] (with --n_boot_rep or --win_boot_rep: the replicates
 //    stay on the device, <out> holds the estimates and <out>.boot_mean / _sd / _lo / _hi / _used the replicates' summaries
-//    per cell; one GPU, the whole data set resident);
+//    per cell; one GPU, the whole data set resident), --nj (the neighbour-joining tree of every matrix, built on the device:
+//    <out>.nwk holds one Newick line per matrix, <out> matrix 0 of every set and, with replicates, <out>.support.nwk matrix
+//    0's tree with the number of replicate trees that share each of its branches; one GPU, the whole data set resident);
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
@@ -85,6 +87,13 @@
 #pragma weak ngd_run_windows_job_var_stats
 #pragma weak ngd_run_job_groups_stats
 #pragma weak ngd_run_windows_job_var_groups_stats
+// (--nj: a neighbour-joining tree per matrix, built on the device)
+#pragma weak ngd_nj_max_ind
+#pragma weak ngd_run_job_nj
+#pragma weak ngd_run_windows_nj
+#pragma weak ngd_run_windows_job_var_nj
+#pragma weak ngd_nj_support
+#pragma weak ngd_nj_newick
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -149,6 +158,12 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // <out>.boot_used the finite replicates behind them.  With --groups the cells are the group pairs.  Not in the reference.
   bool boot_stats = false, boot_ci_set = false;
   double boot_ci = 0.95;
+  // --nj: every matrix of the run -- the full data set and its --n_boot_rep replicates, or the windows and their
+  // --win_boot_rep replicates -- leaves the engine as its neighbour-joining tree (ngd_run_*_nj): <out>.nwk holds one Newick
+  // line per matrix in block order, <out> matrix 0 of every set (a plain run: the run without --nj) and, with replicates,
+  // <out>.support.nwk matrix 0's tree of every set with its branches' support.  Not in the reference, whose README pipes
+  // the matrices through fastme and RAxML for the same files.
+  bool nj = false;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -263,6 +278,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"groups", required_argument, nullptr, 1020},
                                  {"boot_stats", no_argument, nullptr, 1021},
                                  {"boot_ci", required_argument, nullptr, 1022},
+                                 {"nj", no_argument, nullptr, 1023},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -307,6 +323,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1020: p.in_groups = optarg; break;
       case 1021: p.boot_stats = true; break;
       case 1022: p.boot_ci_set = true; p.boot_ci = atof(optarg); break;
+      case 1023: p.nj = true; break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -357,6 +374,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.em_exact_win) fprintf(stderr, "\tem_exact_win: true\n\n");
     if (p.in_groups) fprintf(stderr, "\tgroups: %s\n\n", p.in_groups);
     if (p.boot_stats) fprintf(stderr, "\tboot_stats: true\n\tboot_ci: %f\n\n", p.boot_ci);
+    if (p.nj) fprintf(stderr, "\tnj: true\n\n");
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -428,6 +446,12 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.n_boot_rep < 1 && p.win_boot_rep < 1)
       die(__FUNCTION__, "bootstrap summaries (--boot_stats) require bootstrap replicates (--n_boot_rep or --win_boot_rep)!");
     if (p.n_gpus > 1) die(__FUNCTION__, "bootstrap summaries (--boot_stats) are computed on one GPU (--n_gpus 1)!");
+  }
+  if (p.nj) {
+    if (p.in_groups) die(__FUNCTION__, "neighbour-joining trees (--nj) cannot be combined with group means (--groups)!");
+    if (p.boot_stats) die(__FUNCTION__, "neighbour-joining trees (--nj) cannot be combined with bootstrap summaries (--boot_stats)!");
+    if (p.n_gpus > 1) die(__FUNCTION__, "neighbour-joining trees (--nj) are computed on one GPU (--n_gpus 1)!");
+    if (p.n_ind < 3) die(__FUNCTION__, "neighbour-joining trees (--nj) need three individuals or more (--n_ind)!");
   }
 }
 
@@ -1287,6 +1311,12 @@ int main(int argc, char **argv) {
     if (std::max<uint64_t>(p.n_boot_rep, p.win_boot_rep) > ngd_boot_stats_max_rep())
       die(__FUNCTION__, "too many bootstrap replicates for bootstrap summaries (--boot_stats): a cell's replicates stay in on-chip memory!");
   }
+  if (p.nj) {
+    if (!ngd_nj_max_ind || !ngd_run_job_nj || !ngd_run_windows_nj || !ngd_run_windows_job_var_nj || !ngd_nj_support || !ngd_nj_newick)
+      die(__FUNCTION__, "this build of the engine has no neighbour-joining trees (--nj)!");
+    if (p.n_ind > ngd_nj_max_ind())
+      die(__FUNCTION__, "too many individuals for neighbour-joining trees (--nj): a matrix's row sums stay in on-chip memory!");
+  }
 
   // positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149 -- except for the chromosomes
   // and coordinates of --win_size's windows
@@ -1342,9 +1372,9 @@ int main(int argc, char **argv) {
     win_bp_start.resize((size_t)n_win);
     ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, win_lo.data(), win_hi.data(), win_bp_start.data(),
                          (uint64_t)n_win);
-    if (!p.in_groups && !p.boot_stats && !ngd_run_windows_dist)  // (--groups, --boot_stats: their own entry points, checked above)
+    if (!p.in_groups && !p.boot_stats && !p.nj && !ngd_run_windows_dist)  // (--groups, --boot_stats, --nj: their own entry points, checked above)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (!p.in_groups && !p.boot_stats && p.win_boot_rep && !ngd_run_windows_job_var_dist)
+    if (!p.in_groups && !p.boot_stats && !p.nj && p.win_boot_rep && !ngd_run_windows_job_var_dist)
       die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu bp every %lu bp\n", (unsigned long)n_win, (unsigned long)B, (unsigned long)T);
   } else if (p.win) {
@@ -1355,9 +1385,9 @@ int main(int argc, char **argv) {
     win_lo.resize((size_t)n_win);
     win_hi.resize((size_t)n_win);
     ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win_lo.data(), win_hi.data(), (uint64_t)n_win);
-    if (!p.in_groups && !p.boot_stats && !ngd_run_windows_dist)  // (--groups, --boot_stats: their own entry points, checked above)
+    if (!p.in_groups && !p.boot_stats && !p.nj && !ngd_run_windows_dist)  // (--groups, --boot_stats, --nj: their own entry points, checked above)
       die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (!p.in_groups && !p.boot_stats && p.win_boot_rep && !ngd_run_windows_job_dist)
+    if (!p.in_groups && !p.boot_stats && !p.nj && p.win_boot_rep && !ngd_run_windows_job_dist)
       die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows (--win_boot_rep)!");
     if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
   }
@@ -1425,6 +1455,8 @@ int main(int argc, char **argv) {
     die(__FUNCTION__, "windows (--win_size) need the whole data set on one GPU; it does not fit the device budget!");
   if (p.boot_stats && in_parts)
     die(__FUNCTION__, "bootstrap summaries (--boot_stats) need the whole data set on one GPU; it does not fit the device budget!");
+  if (p.nj && in_parts)
+    die(__FUNCTION__, "neighbour-joining trees (--nj) need the whole data set on one GPU; it does not fit the device budget!");
   if (p.in_groups && in_parts)
     die(__FUNCTION__, "group means (--groups) need the whole data set on one GPU; it does not fit the device budget!");
 
@@ -1723,7 +1755,100 @@ int main(int argc, char **argv) {
     }
     if (fclose(wf) != 0) die(__FUNCTION__, "cannot write windows output file!");
   };
-  if (p.boot_stats) {
+  if (p.nj) {
+    // ---- neighbour-joining trees: every matrix of every set -- the run's one set, or one per window -- becomes its tree on
+    // the device (ngd_run_*_nj).  <out> takes matrix 0 of every set (a plain run: the bytes of the run without --nj),
+    // <out>.nwk one Newick line per matrix, set after set, matrix 0 first, and, with replicates, <out>.support.nwk one line
+    // per set: matrix 0's tree with the number of replicate trees that share each of its branches ----
+    const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep, n_mat = R + 1, nb = NGD_NJ_NBRANCH(p.n_ind);
+    FILE *nf = fopen((std::string(p.out) + ".nwk").c_str(), "w");
+    FILE *sf = R ? fopen((std::string(p.out) + ".support.nwk").c_str(), "w") : nullptr;
+    if (!nf || (R && !sf)) die(__FUNCTION__, "cannot open trees output file!");
+    std::vector<char> line;
+    std::vector<uint32_t> support(p.n_ind > 3 ? p.n_ind - 3 : 1);
+    uint64_t n_no_tree = 0;
+    auto write_tree = [&](FILE *f, const int32_t *c, const double *l, const uint32_t *sup) {
+      int64_t need = ngd_nj_newick(c, l, p.n_ind, label_ptr.data(), sup, line.data(), line.size());
+      if (need > (int64_t)line.size()) {
+        line.resize((size_t)need);
+        need = ngd_nj_newick(c, l, p.n_ind, label_ptr.data(), sup, line.data(), line.size());
+      }
+      if (need < 0 || fwrite(line.data(), 1, (size_t)need, f) != (size_t)need) die(__FUNCTION__, "cannot write trees output file!");
+    };
+    // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), its trees, its supports
+    auto write_set = [&](uint64_t w, const char *name, const double *d0, const int32_t *c, const double *l, const uint32_t *st) {
+      emit(w, nullptr, nullptr, nullptr, 0, d0, 0, name);
+      for (uint64_t r = 0; r < n_mat; r++) {
+        write_tree(nf, c + r * nb, l + r * nb, nullptr);
+        n_no_tree += st[r] == 0;
+      }
+      if (!R) return;
+      uint32_t used = 0;
+      if (ngd_nj_support(c, st, n_mat, p.n_ind, support.data(), &used)) die(__FUNCTION__, "cannot count the trees' support!");
+      write_tree(sf, c, l, support.data());
+    };
+    std::vector<int32_t> child;
+    std::vector<double> len, d0;
+    std::vector<uint32_t> status;
+    int rc = 0;
+    if (p.win) {
+      // --win_boot_rep: every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length
+      // share them); the replicates of a window shorter than one block are 0 / 0 and have no tree
+      const uint64_t n_win = win_lo.size();
+      std::vector<uint64_t> off(n_win), maps(1);
+      int64_t mlen = 0;
+      if (R) {
+        mlen = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0, off.data());
+        if (mlen < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
+        maps.resize((size_t)mlen + 1);
+        ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, maps.data(), (uint64_t)mlen, off.data());
+      }
+      // a group of windows per call: their records and first matrices in ~2 GB of host memory
+      const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (n_mat * nb * 12 + n_mat * 4 + n_comb * 8)));
+      for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
+        const uint64_t n = std::min(per, n_win - w0);
+        const auto t_c0 = std::chrono::steady_clock::now();
+        child.resize(n * n_mat * nb);
+        len.resize(n * n_mat * nb);
+        status.resize(n * n_mat);
+        d0.resize(n * n_comb);
+        rc = R ? ngd_run_windows_job_var_nj(eng.h, &win_lo[w0], &win_hi[w0], n, maps.data(), (uint64_t)mlen, &off[w0], (uint32_t)R,
+                                            p.boot_block_size, p.tot_sites, p.evol_model, child.data(), len.data(), status.data(), d0.data())
+               : ngd_run_windows_nj(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, child.data(), len.data(),
+                                    status.data(), d0.data());
+        if (rc) die_engine(R ? "ngd_run_windows_job_var_nj" : "ngd_run_windows_nj", rc);
+        report_fixup(eng.h, p.verbose);
+        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
+        for (uint64_t k = 0; k < n; k++) {
+          const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
+          write_set(w0 + k, name.c_str(), &d0[k * n_comb], &child[k * n_mat * nb], &len[k * n_mat * nb], &status[k * n_mat]);
+        }
+        writer.wait_idle();  // (the last block's text is written before the next group's call)
+      }
+      write_windows_file();
+    } else {
+      // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
+      const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
+      if (R && !n_blocks) die(__FUNCTION__, "neighbour-joining trees (--nj) of bootstrap replicates need at least one bootstrap block of sites!");
+      const auto t_c0 = std::chrono::steady_clock::now();
+      std::vector<uint64_t> maps(R * n_blocks + 1);
+      for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
+      child.resize(n_mat * nb);
+      len.resize(n_mat * nb);
+      status.resize(n_mat);
+      d0.resize(n_comb);
+      rc = ngd_run_job_nj(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, child.data(),
+                          len.data(), status.data(), d0.data());
+      if (rc) die_engine("ngd_run_job_nj", rc);
+      report_fixup(eng.h, p.verbose);
+      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
+      write_set(0, nullptr, d0.data(), child.data(), len.data(), status.data());
+    }
+    if (n_no_tree)
+      fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no tree (a line \";\" in %s.nwk)\n",
+              (unsigned long)n_no_tree, p.out);
+    if (fclose(nf) != 0 || (sf && fclose(sf) != 0)) die(__FUNCTION__, "cannot write trees output file!");
+  } else if (p.boot_stats) {
     // ---- bootstrap summaries: the replicates of every set -- the run's, or a window's -- stay on the device, which reduces
     // each cell to five statistics and a count (ngd_run_*_stats).  <out> takes the estimates (matrix 0 of every set: the
     // bytes of the run without replicates), <out>.boot_mean / _sd / _lo / _hi the other statistics in the same blocks and
@@ -1901,7 +2026,7 @@ int main(int argc, char **argv) {
     }
     if (fclose(uf) != 0) die(__FUNCTION__, "cannot write used output file!");
   }
-  if (p.boot_stats) {
+  if (p.boot_stats || p.nj) {
     // (written above)
   } else if (p.in_groups) {
     if (p.win) write_windows_file();  // (the windows' own file: as without --groups)

@@ -796,3 +796,213 @@ int ngd_boot_stats_host(const double *val, uint64_t n_set, uint64_t n_mat, uint6
     }
   return NGD_OK;
 }
+
+// ---- neighbour-joining trees (--nj): the contract of include/ngsdist_amd.h "Neighbour-joining trees" in plain host
+// arithmetic (no contraction: -ffp-contract=off), matrix by matrix.  The live nodes are a dense prefix of the slots, as in
+// nj.hip; the formulas do not depend on it -- Q(a,b) subtracts the row sum of the lower node id first ----
+namespace {
+void nj_one(const double *val, uint64_t n, int32_t *child, double *len, uint32_t *status, std::vector<double> &D, std::vector<double> &r,
+            std::vector<uint32_t> &id) {
+  const uint64_t n_pairs = n * (n - 1) / 2, nb = 2 * n - 3;
+  bool bad = false;
+  for (uint64_t p = 0; p < n_pairs && !bad; p++) bad = !std::isfinite(val[p]);
+  if (bad) {
+    const uint64_t nan_bits = 0x7FF8000000000000ull;
+    double nan;
+    memcpy(&nan, &nan_bits, 8);
+    for (uint64_t k = 0; k < nb; k++) { child[k] = -1; len[k] = nan; }
+    *status = 0;
+    return;
+  }
+  D.assign(n * n, 0.0);
+  r.assign(n, 0.0);
+  id.resize(n);
+  uint64_t p = 0;
+  for (uint64_t a = 0; a < n; a++) {
+    id[a] = (uint32_t)a;
+    for (uint64_t b = a + 1; b < n; b++, p++) D[a * n + b] = D[b * n + a] = val[p];
+  }
+  for (uint64_t a = 0; a < n; a++) {
+    double acc = 0.0;
+    for (uint64_t b = 0; b < n; b++)
+      if (b != a) acc += D[a * n + b];
+    r[a] = acc;
+  }
+  uint64_t m = n;
+  for (uint64_t t = 0; m > 3; t++, m--) {
+    const double mm2 = (double)(m - 2);
+    bool have = false;
+    double bq = 0.0;
+    uint32_t ba = 0, bb = 0;
+    uint64_t bs = 0, bc = 0;
+    for (uint64_t s = 0; s + 1 < m; s++)
+      for (uint64_t c = s + 1; c < m; c++) {
+        const bool lo = id[s] < id[c];
+        const uint32_t a = lo ? id[s] : id[c], b = lo ? id[c] : id[s];
+        const double q = (mm2 * D[s * n + c] - (lo ? r[s] : r[c])) - (lo ? r[c] : r[s]);
+        if (!have || q < bq || (q == bq && (a < ba || (a == ba && b < bb)))) { have = true; bq = q; ba = a; bb = b; bs = s; bc = c; }
+      }
+    const uint64_t si = id[bs] == ba ? bs : bc, sj = id[bs] == ba ? bc : bs, su = std::min(si, sj), sr = std::max(si, sj), L = m - 1;
+    const double dij = D[si * n + sj], ri = r[si], rj = r[sj];
+    const double li = 0.5 * dij + (ri - rj) / (2.0 * mm2);
+    child[2 * t] = (int32_t)ba;
+    child[2 * t + 1] = (int32_t)bb;
+    len[2 * t] = li;
+    len[2 * t + 1] = dij - li;
+    for (uint64_t k = 0; k < m; k++) {
+      if (k == si || k == sj) continue;
+      const double dik = D[si * n + k], djk = D[sj * n + k];
+      const double duk = 0.5 * ((dik + djk) - dij);
+      r[k] = ((r[k] - dik) - djk) + duk;
+      D[su * n + k] = D[k * n + su] = duk;
+    }
+    r[su] = 0.5 * ((ri + rj) - (double)m * dij);
+    id[su] = (uint32_t)(n + t);
+    if (sr != L) {  // the last live slot moves into the freed one
+      for (uint64_t k = 0; k < L; k++)
+        if (k != sr) D[sr * n + k] = D[k * n + sr] = D[L * n + k];
+      r[sr] = r[L];
+      id[sr] = id[L];
+    }
+  }
+  uint64_t s0 = 0, s1 = 1, s2 = 2;
+  if (id[s0] > id[s1]) std::swap(s0, s1);
+  if (id[s1] > id[s2]) std::swap(s1, s2);
+  if (id[s0] > id[s1]) std::swap(s0, s1);
+  const double dab = D[s0 * n + s1], dac = D[s0 * n + s2], dbc = D[s1 * n + s2];
+  child[nb - 3] = (int32_t)id[s0];
+  child[nb - 2] = (int32_t)id[s1];
+  child[nb - 1] = (int32_t)id[s2];
+  len[nb - 3] = 0.5 * ((dab + dac) - dbc);
+  len[nb - 2] = 0.5 * ((dab + dbc) - dac);
+  len[nb - 1] = 0.5 * ((dac + dbc) - dab);
+  *status = 1;
+}
+
+// the bipartitions of one record's joins as leaf sets (n bits in W words each) normalised to the side without leaf 0;
+// false: a child entry out of range
+bool nj_splits(const int32_t *child, uint64_t n, uint64_t W, std::vector<uint64_t> &sets) {
+  const uint64_t n_join = n - 3;
+  sets.assign(n_join * W, 0);
+  for (uint64_t t = 0; t < n_join; t++) {
+    uint64_t *s = &sets[t * W];
+    for (int k = 0; k < 2; k++) {
+      const int64_t c = child[2 * t + k];
+      if (c < 0 || (uint64_t)c >= n + t) return false;
+      if ((uint64_t)c < n) s[c / 64] |= 1ull << (c % 64);
+      else
+        for (uint64_t w = 0; w < W; w++) s[w] |= sets[((uint64_t)c - n) * W + w];
+    }
+  }
+  for (uint64_t t = 0; t < n_join; t++) {  // (after the unions: those need the sets as they grew)
+    uint64_t *s = &sets[t * W];
+    if (!(s[0] & 1)) continue;
+    for (uint64_t w = 0; w < W; w++) s[w] = ~s[w];
+    if (n % 64) s[W - 1] &= (1ull << (n % 64)) - 1;
+  }
+  return true;
+}
+}  // namespace
+
+int ngd_nj_host(const double *val, uint64_t n_mat, uint64_t n_ind, int32_t *child, double *len, uint32_t *status) {
+  if (!val || !child || !len || !status || !n_mat || n_ind < 3) return NGD_E_INVALID;
+  const uint64_t n_pairs = n_ind * (n_ind - 1) / 2, nb = 2 * n_ind - 3;
+  const unsigned parts = (unsigned)std::min<uint64_t>(n_mat, 1024);
+  host_pool().run(parts, [&](unsigned part) {
+    std::vector<double> D, r;
+    std::vector<uint32_t> id;
+    for (uint64_t k = part; k < n_mat; k += parts) nj_one(val + k * n_pairs, n_ind, child + k * nb, len + k * nb, status + k, D, r, id);
+  });
+  return NGD_OK;
+}
+
+int ngd_nj_support(const int32_t *child, const uint32_t *status, uint64_t n_mat, uint64_t n_ind, uint32_t *support, uint32_t *n_used) {
+  if (!child || !status || !support || !n_used || !n_mat || n_ind < 3) return NGD_E_INVALID;
+  const uint64_t n = n_ind, nb = 2 * n - 3, n_join = n - 3, W = (n + 63) / 64;
+  std::vector<uint32_t> sup(n_join, 0);
+  uint32_t used = 0;
+  if (status[0] && n_join) {
+    std::vector<uint64_t> ref, rep;
+    if (!nj_splits(child, n, W, ref)) return NGD_E_INVALID;
+    // matrix 0's bipartitions, sorted; equal ones (none in a tree of distinct splits) would count alike
+    std::vector<uint64_t> order(n_join);
+    for (uint64_t t = 0; t < n_join; t++) order[t] = t;
+    auto less = [&](const uint64_t *a, const uint64_t *b) { return std::lexicographical_compare(a, a + W, b, b + W); };
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return less(&ref[a * W], &ref[b * W]); });
+    for (uint64_t m = 1; m < n_mat; m++) {
+      if (!status[m]) continue;
+      if (!nj_splits(child + m * nb, n, W, rep)) return NGD_E_INVALID;
+      used++;
+      for (uint64_t t = 0; t < n_join; t++) {
+        const uint64_t *s = &rep[t * W];
+        auto it = std::lower_bound(order.begin(), order.end(), s, [&](uint64_t a, const uint64_t *b) { return less(&ref[a * W], b); });
+        for (; it != order.end() && std::equal(s, s + W, &ref[*it * W]); ++it) sup[*it]++;
+      }
+    }
+  } else {
+    for (uint64_t m = 1; m < n_mat; m++) used += status[m] != 0;
+  }
+  for (uint64_t t = 0; t < n_join; t++) support[t] = sup[t];
+  *n_used = used;
+  return NGD_OK;
+}
+
+int64_t ngd_nj_newick(const int32_t *child, const double *len, uint64_t n_ind, const char *const *labels, const uint32_t *support,
+                      char *out, uint64_t cap) {
+  if (!child || !len || n_ind < 3) return NGD_E_INVALID;
+  const uint64_t n = n_ind, nb = 2 * n - 3;
+  // (two walks: the first sizes, the second writes -- only into a buffer that holds the whole line)
+  const int64_t need = out ? ngd_nj_newick(child, len, n_ind, labels, support, nullptr, 0) : 0;
+  if (need < 0) return need;
+  char *const dst = out && (uint64_t)need <= cap ? out : nullptr;
+  if (out && !dst) return need;
+  uint64_t pos = 0;
+  auto put = [&](const char *s, size_t k) {
+    if (dst) memcpy(dst + pos, s, k);
+    pos += k;
+  };
+  if (child[0] < 0) {
+    put(";\n", 2);
+    return (int64_t)pos;
+  }
+  char tmp[512];
+  auto put_len = [&](double v) { put(tmp, (size_t)snprintf(tmp, sizeof tmp, ":%.10f", v)); };
+  // an entry is a node with the branch above it; (entry, phase) on a stack: no recursion down a caterpillar tree.  The node
+  // of entry e may only have been made by an earlier join than the one e belongs to: the walk ends
+  std::vector<std::pair<uint64_t, int>> stack;
+  put("(", 1);
+  for (uint64_t top = nb - 3; top < nb; top++) {
+    if (top > nb - 3) put(",", 1);
+    stack.emplace_back(top, 0);
+    while (!stack.empty()) {
+      const uint64_t e = stack.back().first;
+      const int phase = stack.back().second;
+      stack.pop_back();
+      const int64_t c = child[e];
+      const uint64_t limit = e >= nb - 3 ? n + (n - 3) : n + e / 2;  // (ids the entry may name)
+      if (c < 0 || (uint64_t)c >= limit) return NGD_E_INVALID;
+      if ((uint64_t)c < n) {
+        if (labels && labels[c]) put(labels[c], strlen(labels[c]));
+        else put(tmp, (size_t)snprintf(tmp, sizeof tmp, "Ind_%lu", (unsigned long)c));
+        put_len(len[e]);
+        continue;
+      }
+      const uint64_t t = (uint64_t)c - n;
+      if (phase == 0) {
+        put("(", 1);
+        stack.emplace_back(e, 1);
+        stack.emplace_back(2 * t, 0);
+      } else if (phase == 1) {
+        put(",", 1);
+        stack.emplace_back(e, 2);
+        stack.emplace_back(2 * t + 1, 0);
+      } else {
+        put(")", 1);
+        if (support) put(tmp, (size_t)snprintf(tmp, sizeof tmp, "%u", support[t]));
+        put_len(len[e]);
+      }
+    }
+  }
+  put(");\n", 3);
+  return (int64_t)pos;
+}

@@ -262,6 +262,14 @@ struct ngd_engine : ngd_mem {
     DevBuf<unsigned long long> d_used;
     double ms = 0;  // ngd_last_boot_stats_ms
   } bst;
+  // neighbour-joining trees (engine_nj.hip): a chunk of matrices' working copies (n x n doubles each) and their records
+  struct Nj {
+    DevBuf<double> d_work, d_len;
+    DevBuf<int32_t> d_child;
+    DevBuf<uint32_t> d_status;
+    uint64_t max_bytes = 0;  // NGD_OPT_NJ_MAX_BYTES
+    double ms = 0;           // ngd_last_nj_ms
+  } nj;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
@@ -389,6 +397,18 @@ int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cn
 int windows_host_stats(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
                        const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
                        BootCi ci, bool groups, double *stats, uint64_t *used, const char *who);
+// engine_nj.hip: the trees of [n_mat][n_pairs] device matrices -> child / len / status in host memory; d_cnt and the two
+// arguments of ngd_finish for sums and counts, `values` for cells as they are (the arguments are checked)
+int nj_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_mat, uint64_t tot_sites,
+              uint64_t evol_model, int32_t *child, double *len, uint32_t *status);
+// ... matrix 0 of n_set sets of n_mat device matrices, copied out and finished on the host: dist0 [n_set][n_pairs]
+int nj_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
+             uint64_t evol_model, double *dist0);
+// engine_windows.hip: the windowed calls through the batch buffers, every group of windows -- whole sets -- through
+// nj_reduce (n_rep == 0: the windows alone, maps are not read); dist0 may be NULL
+int windows_host_nj(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
+                    const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
+                    int32_t *child, double *len, uint32_t *status, double *dist0, const char *who);
 // engine_windows.hip: the windowed calls through the batch buffers, every group of windows reduced by groups_reduce
 // (n_rep == 0, or maps NULL with it: the windows alone)
 int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,

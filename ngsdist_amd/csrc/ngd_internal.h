@@ -438,6 +438,17 @@ int ngd_launch_boot_stats(hipStream_t st, const double *d_a, const unsigned long
                           uint32_t n_mat, uint64_t n_cells, uint64_t tot_sites, uint32_t model, double p_lo, double p_hi,
                           double *d_stats, unsigned long long *d_used);
 
+// nj.hip : a neighbour-joining tree per matrix (include/ngsdist_amd.h "Neighbour-joining trees"), one workgroup per matrix
+#define NGD_NJ_MAX_IND 4096u  // row sums (8 B) and node ids (4 B) per live slot in LDS: 48 KiB at this many
+#define NGD_NJ_THREADS 1024u  // the workgroup (DESIGN.md section 6 "Neighbour-joining trees": chosen by measurement)
+__host__ __device__ inline uint32_t ngd_nj_ld(uint32_t n_ind) { return (n_ind + 1) & ~1u; }  // doubles per row of the working matrix (even)
+// [n_mat][n_pairs] sums and counts (d_cnt is not read when tot_sites > 0) or, `values`, the cells as they are -> d_child /
+// d_len [n_mat][2 n_ind - 3], d_status [n_mat]; d_work: n_mat * n_ind * ngd_nj_ld(n_ind) doubles of scratch.  3 <= n_ind <=
+// NGD_NJ_MAX_IND, n_mat below 2^31 (grid.x), threads 256, 512 or 1024: the caller's to see to.  Returns a hipError_t.
+int ngd_launch_nj(hipStream_t st, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_mat, uint32_t n_ind,
+                  uint64_t tot_sites, uint32_t model, uint32_t threads, double *d_work, int32_t *d_child, double *d_len,
+                  uint32_t *d_status);
+
 // group_reduce.hip : group-mean distance matrices (ngd_set_groups, ngd_group_means_device, ngd_run_*_groups)
 // One work item: rows [r0, r1) of group pair (a, b) -- positions in group a's member list --, every column of group b
 #define NGD_GROUP_WG_CELLS 4096  // cells of a work item's rectangle, about: whole rows, at least one

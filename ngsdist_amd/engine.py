@@ -17,7 +17,7 @@ KERNELS = {"auto": 0, "stream": 1, "mfma": 2, "em_faithful": 3, "em_fast": 4, "e
 OPTIONS = {"boot_partials": 1, "boot_max_bytes": 2, "boot_wg": 3, "boot_unaligned": 4, "em_batch": 5,
            "em_spill": 6, "em_spill_bytes": 7, "single_image_bytes": 8, "fixup_work": 9, "stage_piece_mib": 10,
            "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "em_exact": 15, "em_exact_cap": 16,
-           "unit_skip": 17, "em_exact_win": 18,
+           "unit_skip": 17, "em_exact_win": 18, "nj_max_bytes": 19,
            "debug_forge_job": 100}
 # ngd_em_exact_entry
 EM_EXACT_ENTRY = np.dtype([("i1", np.uint32), ("i2", np.uint32), ("site", np.uint64), ("t_dev", np.uint32),
@@ -491,6 +491,67 @@ class Engine:
         _check(self._L.ngd_last_boot_stats_ms(self._h, C.byref(v)))
         return float(v.value)
 
+    # -- neighbour-joining trees: per matrix 2 n - 3 branches (child, len) and a status instead of its n_pairs cells ----
+    def _nj_out(self, lead, dist0_lead=None):
+        nb = 2 * self.n_ind - 3
+        child = np.empty(lead + (nb,), dtype=np.int32)
+        length = np.empty(lead + (nb,), dtype=np.float64)
+        status = np.empty(lead, dtype=np.uint32)
+        dist0 = None if dist0_lead is None else np.empty(dist0_lead + (self.n_pairs,), dtype=np.float64)
+        return (child, length, status, dist0, child.ctypes.data_as(C.POINTER(C.c_int32)), length.ctypes.data_as(C.POINTER(C.c_double)),
+                status.ctypes.data_as(C.POINTER(C.c_uint32)), None if dist0 is None else dist0.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def nj(self, d_sum_ptr, d_cnt_ptr, n_mat, evol_model=1, tot_sites=0):
+        """the neighbour-joining trees of device matrices (ngd_nj_device; raw addresses of [n_mat][n_pairs] sums and counts,
+        as a *_device call wrote them): -> (child int32[n_mat][2n-3], len float64[n_mat][2n-3], status uint32[n_mat]);
+        join t makes node n + t of entries 2t, 2t + 1, the last three entries meet at the centre; status 0 (child -1, len
+        NaN): a matrix with a cell that is not finite"""
+        child, length, status, _, cp, lp, sp, _ = self._nj_out((int(n_mat),))
+        _check(self._L.ngd_nj_device(self._h, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr), int(n_mat), int(tot_sites),
+                                     int(evol_model), cp, lp, sp))
+        return child, length, status
+
+    def nj_values(self, d_val_ptr, n_mat):
+        """the trees of [n_mat][n_pairs] float64 distances in device memory as they are (ngd_nj_values_device)"""
+        child, length, status, _, cp, lp, sp, _ = self._nj_out((int(n_mat),))
+        _check(self._L.ngd_nj_values_device(self._h, C.c_void_p(d_val_ptr), int(n_mat), cp, lp, sp))
+        return child, length, status
+
+    def run_job_nj(self, block_maps=None, block_size=1, evol_model=1, tot_sites=0, dist0=True):
+        """run_job() and the trees of its n_rep + 1 matrices on the device (ngd_run_job_nj): -> (child, len, status, dist0)
+        of shapes (n_rep + 1, 2n-3), (n_rep + 1, 2n-3), (n_rep + 1,), (n_pairs,); dist0 (None with dist0=False) is matrix 0
+        as run_job_dist() gives it"""
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        child, length, status, d0, cp, lp, sp, dp = self._nj_out((n_rep + 1,), () if dist0 else None)
+        _check(self._L.ngd_run_job_nj(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model), cp, lp, sp, dp))
+        return child, length, status, d0
+
+    def run_windows_nj(self, lo, hi, evol_model=1, tot_sites=0, dist0=True):
+        """run_windows() and every window's tree (ngd_run_windows_nj): -> (child (n_win, 1, 2n-3), len, status (n_win, 1),
+        dist0 (n_win, n_pairs))"""
+        lo, hi, lp_, hp = self._win_args(lo, hi)
+        child, length, status, d0, cp, lp, sp, dp = self._nj_out((lo.size, 1), (lo.size,) if dist0 else None)
+        _check(self._L.ngd_run_windows_nj(self._h, lp_, hp, lo.size, int(tot_sites), int(evol_model), cp, lp, sp, dp))
+        return child, length, status, d0
+
+    def run_windows_job_var_nj(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None, dist0=True):
+        """run_windows_job_var() and the trees of every window's set (ngd_run_windows_job_var_nj): -> (child (n_win,
+        n_rep + 1, 2n-3), len, status (n_win, n_rep + 1), dist0 (n_win, n_pairs)); the replicates of a window shorter than
+        one block have status 0"""
+        lo, hi, lp_, hp = self._win_args(lo, hi)
+        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
+        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        child, length, status, d0, cp, lp, sp, dp = self._nj_out((lo.size, n_rep + 1), (lo.size,) if dist0 else None)
+        _check(self._L.ngd_run_windows_job_var_nj(self._h, lp_, hp, lo.size, mp, n_ent, op, n_rep, int(block_size), int(tot_sites),
+                                                  int(evol_model), cp, lp, sp, dp))
+        return child, length, status, d0
+
+    def last_nj_ms(self):
+        """device time of the tree kernels in the last of these calls (ngd_last_nj_ms)"""
+        v = C.c_double(0.0)
+        _check(self._L.ngd_last_nj_ms(self._h, C.byref(v)))
+        return float(v.value)
+
     def run_job_keep(self, block_maps, block_size=1):
         """ngd_run_job with the matrices left in the engine; fetch_matrix(r) copies them out one at a time"""
         a = np.ascontiguousarray(block_maps, dtype=np.uint64)
@@ -516,7 +577,8 @@ class Engine:
         pass of the table-driven EM kernel stops where the reference does: last_em_exact(), em_exact_entries(); 2: block
         maps, multiplicities, batches and jobs are served that way too) and em_exact_cap; em_exact_win (1: while em_exact is on the windowed calls
         are served too -- run_windows* under 1 or 2, run_windows_job* under 2); unit_skip (0: the plain pass of a
-        one-image engine in congruent coordinates visits the k-groups of p0 + p1 + p2 too: plain_pass_kgroups())"""
+        one-image engine in congruent coordinates visits the k-groups of p0 + p1 + p2 too: plain_pass_kgroups());
+        nj_max_bytes (device scratch of the neighbour-joining kernel, 0 = 2 GB: the matrices a launch takes)"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self
 
@@ -743,6 +805,73 @@ def boot_stats_host(values, ci=0.95):
     _check(_lib.load().ngd_boot_stats_host(v.ctypes.data_as(C.POINTER(C.c_double)), n_set, n_mat, n_cells, float(ci),
                                            stats.ctypes.data_as(C.POINTER(C.c_double)), used.ctypes.data_as(C.POINTER(C.c_uint64))))
     return stats, used
+
+
+def nj_max_ind():
+    """the most individuals the device's neighbour joining serves (ngd_nj_max_ind)"""
+    return int(_lib.load().ngd_nj_max_ind())
+
+
+def nj_host(values, n_ind):
+    """neighbour joining in plain host arithmetic (ngd_nj_host), the device form's twin: values float64[..., n_pairs] ->
+    (child int32[..., 2n-3], len float64[..., 2n-3], status uint32[...])"""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    n_ind = int(n_ind)
+    if v.ndim < 1 or v.shape[-1] != n_ind * (n_ind - 1) // 2:
+        raise ValueError("values: expected [..., n_pairs]")
+    lead = v.shape[:-1]
+    n_mat = int(np.prod(lead, dtype=np.int64))
+    nb = max(0, 2 * n_ind - 3)
+    child = np.empty(lead + (nb,), dtype=np.int32)
+    length = np.empty(lead + (nb,), dtype=np.float64)
+    status = np.empty(lead, dtype=np.uint32)
+    _check(_lib.load().ngd_nj_host(v.ctypes.data_as(C.POINTER(C.c_double)), n_mat, n_ind, child.ctypes.data_as(C.POINTER(C.c_int32)),
+                                   length.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return child, length, status
+
+
+def nj_support(child, status, n_ind):
+    """bootstrap support of matrix 0's tree (ngd_nj_support): child int32[n_mat][2n-3], status uint32[n_mat] -> (support
+    uint32[n-3], one per join of matrix 0: the matrices r >= 1 with a tree that has the join's bipartition; n_used, the
+    matrices r >= 1 with a tree)"""
+    n_ind = int(n_ind)
+    c = np.ascontiguousarray(child, dtype=np.int32)
+    s = np.ascontiguousarray(status, dtype=np.uint32)
+    if c.ndim != 2 or c.shape != (s.size, 2 * n_ind - 3) or s.ndim != 1:
+        raise ValueError("child: expected [n_mat][2 n_ind - 3], status [n_mat]")
+    sup = np.zeros(max(0, n_ind - 3), dtype=np.uint32)
+    used = C.c_uint32(0)
+    keep = sup if sup.size else np.zeros(1, dtype=np.uint32)
+    _check(_lib.load().ngd_nj_support(c.ctypes.data_as(C.POINTER(C.c_int32)), s.ctypes.data_as(C.POINTER(C.c_uint32)), s.size, n_ind,
+                                      keep.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(used)))
+    return sup, int(used.value)
+
+
+def nj_newick(child, length, labels, support=None):
+    """one record as a Newick line (ngd_nj_newick): "(x,y,z);\\n", leaves "label:%.10f", internal nodes "(x,y)" + their
+    support number (support uint32[n-3], by join) + ":%.10f"; ";\\n" for a record without a tree.  Returns bytes."""
+    n_ind = len(labels)
+    c = np.ascontiguousarray(child, dtype=np.int32)
+    ln = np.ascontiguousarray(length, dtype=np.float64)
+    if c.shape != (2 * n_ind - 3,) or ln.shape != c.shape:
+        raise ValueError("child, length: expected [2 n_ind - 3]")
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in labels]
+    arr = (C.c_char_p * n_ind)(*raw)
+    sp = None
+    if support is not None:
+        sup = np.ascontiguousarray(support, dtype=np.uint32)
+        if sup.shape != (n_ind - 3,):
+            raise ValueError("support: expected [n_ind - 3]")
+        keep = sup if sup.size else np.zeros(1, dtype=np.uint32)
+        sp = keep.ctypes.data_as(C.POINTER(C.c_uint32))
+    L = _lib.load()
+    args = (c.ctypes.data_as(C.POINTER(C.c_int32)), ln.ctypes.data_as(C.POINTER(C.c_double)), n_ind, arr, sp)
+    need = L.ngd_nj_newick(*args, None, 0)
+    if need < 0:
+        _check(int(need))
+    buf = C.create_string_buffer(int(need) + 1)
+    _check(min(0, int(L.ngd_nj_newick(*args, buf, int(need)))))
+    return buf.raw[:int(need)]
 
 
 def score_congruence(score):
