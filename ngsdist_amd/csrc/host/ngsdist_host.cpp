@@ -43,6 +43,12 @@
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
+//
+// Layout: options (Pars, parse_cmd_args), text helpers, the readers and the Loader; then what the run reads beside the
+// genotypes (read_labels, read_positions, make_windows: WindowList), device_fit (one device or site ranges), the matrix
+// output every mode prints through (Writer, MatrixOut::emit), the jobs the modes share (draw_window_maps, draw_job_maps,
+// format_grown, for_window_groups) and one function per output mode -- site_range_matrices, trees, bootstrap_summaries,
+// group_means, window_matrices, plain_matrices; main(), last, is the run's outline and picks one of them.
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/mman.h>
@@ -1236,14 +1242,23 @@ void Loader::finish(bool check_eof) {
   gzclose(fh);
 }
 
-int main(int argc, char **argv) {
-  Pars pars;
-  parse_cmd_args(pars, argc, argv);
-  Pars &p = pars;
+// ---------------------------------------------------------------------------
+// The run.  main(), at the end of the file, is its outline.  Before it, in this order: what the run reads besides the
+// genotypes (labels, groups, positions, the window list), whether the data set fits one device, the matrix output every
+// mode prints through, the jobs several modes share (block maps, the loop over groups of windows), and one function per
+// output mode.  The bracketed name of an error message is part of the program's output: the messages below keep the two
+// names they are known by.
+// ---------------------------------------------------------------------------
+namespace {
 
-  const uint64_t n_comb = ngd_n_pairs(p.n_ind);
-  if (p.verbose >= 1) fprintf(stderr, "==> Analysis will be run in %lu combinations\n", n_comb);
-  // ngsDist.cpp:55-65
+const char *const kMain = "main", *const kLambda = "operator()";
+
+void engine_ok(const char *call, int rc) { if (rc) die_engine(call, rc); }
+
+double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// ngsDist.cpp:55-65 (which algorithm) and :73-95 (which input format)
+void input_decisions(Pars &p) {
   if (!p.in_probs && !p.indep_geno) {
     fprintf(stderr, "==> Using faster algorithm (assuming independence of genotypes) since input are genotypes!\n");
     p.indep_geno = true;
@@ -1253,13 +1268,12 @@ int main(int argc, char **argv) {
   } else if (p.indep_geno && p.verbose >= 1) {
     fprintf(stderr, "==> Using faster algorithm (assuming independence of genotypes)!\n");
   }
-  // ngsDist.cpp:73-95
   if (strcmp(p.in_geno, "-") == 0) {
     if (p.verbose >= 1) fprintf(stderr, "==> Reading from STDIN (BINARY)\n");
     p.in_bin = true;
   } else {
     struct stat st;
-    if (stat(p.in_geno, &st) != 0) die(__FUNCTION__, "cannot check GENO file size!");
+    if (stat(p.in_geno, &st) != 0) die(kMain, "cannot check GENO file size!");
     const char *dot = strrchr(p.in_geno, '.');
     if (dot && strcmp(dot, ".gz") == 0) {
       if (p.verbose >= 1) fprintf(stderr, "==> GZIP input file (never BINARY)\n");
@@ -1269,7 +1283,7 @@ int main(int argc, char **argv) {
       p.in_bin = true;
       p.in_probs = true;
       if (p.n_sites != (uint64_t)st.st_size / sizeof(double) / p.n_ind / 3)
-        die(__FUNCTION__, "invalid/corrupt genotype input file!");
+        die(kMain, "invalid/corrupt genotype input file!");
     }
   }
   if (p.evol_model > 2) {  // gen_dist() would error() on the first pair, ngsDist.cpp:387-398
@@ -1277,163 +1291,146 @@ int main(int argc, char **argv) {
                                 "HKY85 model not yet supported", "TN93 model not yet supported"};
     die("gen_dist", msg[p.evol_model - 3]);
   }
+}
 
-  // labels, ngsDist.cpp:103-125
+// labels, ngsDist.cpp:103-125
+std::vector<std::string> read_labels(const Pars &p) {
   std::vector<std::string> labels;
   if (p.in_labels) {
     if (p.verbose >= 1) fprintf(stderr, "==> Reading labels\n");
     labels = read_lines(p.in_labels, p.in_labels_header ? 1 : 0);
-    if (labels.size() != p.n_ind) die(__FUNCTION__, "invalid LABELS file!");
-    for (auto &l : labels) {
-      size_t tab = l.find('\t');
-      if (tab != std::string::npos) l.resize(tab);
-    }
+    if (labels.size() != p.n_ind) die(kMain, "invalid LABELS file!");
+    for (auto &l : labels) l.resize(std::min(l.size(), l.find('\t')));  // (the first field)
   } else {
     for (uint64_t i = 0; i < p.n_ind; i++) labels.push_back("Ind_" + std::to_string(i));
   }
   if (p.verbose >= 4) for (auto &l : labels) fprintf(stderr, "%s\n", l.c_str());
+  return labels;
+}
 
-  // --groups: the group of every individual, in input order
-  std::vector<int32_t> group_of;
-  std::vector<std::string> group_names;
-  if (p.in_groups) {
-    if (p.verbose >= 1) fprintf(stderr, "==> Reading groups\n");
-    read_groups(p.in_groups, group_of, group_names);
-    if (group_of.size() != p.n_ind || group_names.empty()) die(__FUNCTION__, "invalid GROUPS file!");
-    if (!ngd_set_groups || !ngd_run_job_groups || !ngd_run_windows_groups || !ngd_run_windows_job_var_groups)
-      die(__FUNCTION__, "this build of the engine has no group means (--groups)!");
-    if (p.verbose >= 1) fprintf(stderr, "==> %lu groups\n", (unsigned long)group_names.size());
-  }
+// what --boot_stats and --nj need of the engine and of the job
+void check_summaries_and_trees(const Pars &p) {
   if (p.boot_stats) {
     if (!ngd_boot_stats_max_rep || !ngd_run_job_stats || !ngd_run_windows_job_var_stats || !ngd_run_job_groups_stats ||
         !ngd_run_windows_job_var_groups_stats)
-      die(__FUNCTION__, "this build of the engine has no bootstrap summaries (--boot_stats)!");
+      die(kMain, "this build of the engine has no bootstrap summaries (--boot_stats)!");
     if (std::max<uint64_t>(p.n_boot_rep, p.win_boot_rep) > ngd_boot_stats_max_rep())
-      die(__FUNCTION__, "too many bootstrap replicates for bootstrap summaries (--boot_stats): a cell's replicates stay in on-chip memory!");
+      die(kMain, "too many bootstrap replicates for bootstrap summaries (--boot_stats): a cell's replicates stay in on-chip memory!");
   }
   if (p.nj) {
     if (!ngd_nj_max_ind || !ngd_run_job_nj || !ngd_run_windows_nj || !ngd_run_windows_job_var_nj || !ngd_nj_support || !ngd_nj_newick)
-      die(__FUNCTION__, "this build of the engine has no neighbour-joining trees (--nj)!");
+      die(kMain, "this build of the engine has no neighbour-joining trees (--nj)!");
     if (p.n_ind > ngd_nj_max_ind())
-      die(__FUNCTION__, "too many individuals for neighbour-joining trees (--nj): a matrix's row sums stay in on-chip memory!");
+      die(kMain, "too many individuals for neighbour-joining trees (--nj): a matrix's row sums stay in on-chip memory!");
   }
+}
 
-  // positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149 -- except for the chromosomes
-  // and coordinates of --win_size's windows
-  std::vector<uint32_t> win_chrom;
-  std::vector<std::string> win_pos_txt;
-  std::vector<uint64_t> win_pos;  // --win_bp: the coordinates as numbers
-  std::unordered_map<uint32_t, std::string> win_chr_name;
-  if (p.in_pos) {
-    if (p.verbose >= 1) fprintf(stderr, "==> Reading positions file\n");
-    std::vector<std::string> pos = read_lines(p.in_pos, p.in_pos_header ? 1 : 0);
-    uint64_t n_fields = 0;
-    for (auto &l : pos) {
-      uint64_t n = 1 + (uint64_t)std::count(l.begin(), l.end(), '\t');
-      if (!l.empty() && l.back() == '\t') n--;  // no trailing empty field (_strtok, gen_func.cpp:305-322)
-      if (n_fields == 0) n_fields = n;
-      if (n != n_fields) die("read_split", "invalid number of fields in file!");
+// The windows of --win_size / --win_bp, and what the positions file says about the sites they hold.
+struct WindowList {
+  std::vector<uint64_t> lo, hi, bp_start;  // per window: its sites [lo, hi) and (--win_bp) its first coordinate
+  std::vector<uint32_t> chrom;             // per site: its chromosome's number (empty without a positions file)
+  std::vector<std::string> pos_txt;        // per site: its position as the file spells it
+  std::vector<uint64_t> pos;               // --win_bp: the coordinates as numbers
+  std::unordered_map<uint32_t, std::string> chr_name;
+  uint64_t size() const { return lo.size(); }
+  // as the progress lines call the window
+  std::string name(uint64_t w) const { return std::to_string(w) + " [" + std::to_string(lo[w]) + ", " + std::to_string(hi[w]) + ")"; }
+  // <out>.windows: where each window lies
+  void write_file(const std::string &path, const Pars &p) const {
+    FILE *wf = fopen(path.c_str(), "w");
+    if (!wf) die(kLambda, "cannot open windows output file!");
+    fprintf(wf, p.win_bp ? "window\tchr\tstart\tend\tfirst_site\tn_sites\twin_start\twin_end\n" : "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
+    for (uint64_t w = 0; w < size(); w++) {
+      const uint64_t l = lo[w], h = hi[w];
+      if (chrom.empty()) fprintf(wf, "%lu\t.\t%lu\t%lu\t%lu\t%lu", w, l + 1, h, l, h - l);
+      else fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu", w, chr_name.at(chrom[l]).c_str(), pos_txt[l].c_str(), pos_txt[h - 1].c_str(), l, h - l);
+      // (--win_bp, which has the positions: + the window's own coordinates, inclusive: 1 + k T and k T + B)
+      if (p.win_bp) fprintf(wf, "\t%lu\t%lu", bp_start[w], bp_start[w] + (uint64_t)p.win_bp_size - 1);
+      fputc('\n', wf);
     }
-    if (pos.size() != p.n_sites || n_fields < 2) die(__FUNCTION__, "invalid POS file!");
-    if (p.win) {  // fields 1 (chromosome) and 2 (position) of every site: the windows' chromosomes and coordinates
-      std::unordered_map<std::string, uint32_t> ids;
-      win_chrom.resize(p.n_sites);
-      win_pos_txt.resize(p.n_sites);
-      for (uint64_t s = 0; s < p.n_sites; s++) {
-        const std::string &l = pos[s];
-        const size_t t1 = l.find('\t'), t2 = l.find('\t', t1 + 1);
-        const std::string chr = l.substr(0, t1);
-        win_chrom[s] = ids.emplace(chr, (uint32_t)ids.size()).first->second;
-        win_pos_txt[s] = l.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
-        if (s == 0 || win_chrom[s] != win_chrom[s - 1]) win_chr_name.emplace(win_chrom[s], chr);
-      }
-      if (p.win_bp) {  // whole numbers from 1 (below 2^62: ngd_window_ranges_bp) that do not descend inside a chromosome
-        win_pos.resize(p.n_sites);
-        for (uint64_t s = 0; s < p.n_sites; s++) {
-          const std::string &t = win_pos_txt[s];
-          const bool digits = !t.empty() && t.size() <= 18 && t.find_first_not_of("0123456789") == std::string::npos;
-          win_pos[s] = digits ? strtoull(t.c_str(), nullptr, 10) : 0;
-          if (!win_pos[s]) die(__FUNCTION__, "invalid position in POS file: windows in base pairs (--win_bp) need whole numbers from 1!");
-          if (s && win_chrom[s] == win_chrom[s - 1] && win_pos[s] < win_pos[s - 1])
-            die(__FUNCTION__, "positions descend inside a chromosome of the POS file: windows in base pairs (--win_bp) need them in ascending order!");
-        }
-      }
-    }
+    if (fclose(wf) != 0) die(kLambda, "cannot write windows output file!");
   }
-  // the windows (--win_size / --win_step): the list the Python package makes too (host_util.cpp ngd_window_ranges)
-  std::vector<uint64_t> win_lo, win_hi, win_bp_start;
-  if (p.win_bp) {
-    const uint64_t B = (uint64_t)p.win_bp_size, T = (uint64_t)p.win_bp_step, M = (uint64_t)p.win_min_sites;
-    const int64_t n_win = ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, nullptr, nullptr, nullptr, 0);
-    if (n_win < 0) die(__FUNCTION__, "positions file not grouped by chromosome!");
-    if (n_win == 0) die(__FUNCTION__, "no window is kept (--win_min_sites larger than every window's number of sites)!");
-    win_lo.resize((size_t)n_win);
-    win_hi.resize((size_t)n_win);
-    win_bp_start.resize((size_t)n_win);
-    ngd_window_ranges_bp(win_chrom.data(), win_pos.data(), p.n_sites, B, T, M, win_lo.data(), win_hi.data(), win_bp_start.data(),
-                         (uint64_t)n_win);
-    if (!p.in_groups && !p.boot_stats && !p.nj && !ngd_run_windows_dist)  // (--groups, --boot_stats, --nj: their own entry points, checked above)
-      die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (!p.in_groups && !p.boot_stats && !p.nj && p.win_boot_rep && !ngd_run_windows_job_var_dist)
-      die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!");
-    if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu bp every %lu bp\n", (unsigned long)n_win, (unsigned long)B, (unsigned long)T);
-  } else if (p.win) {
-    const uint32_t *ids = win_chrom.empty() ? nullptr : win_chrom.data();
-    const int64_t n_win = ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, nullptr, nullptr, 0);
-    if (n_win < 0) die(__FUNCTION__, "positions file not grouped by chromosome!");
-    if (n_win == 0) die(__FUNCTION__, "no window fits the data set (--win_size larger than every chromosome)!");
-    win_lo.resize((size_t)n_win);
-    win_hi.resize((size_t)n_win);
-    ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win_lo.data(), win_hi.data(), (uint64_t)n_win);
-    if (!p.in_groups && !p.boot_stats && !p.nj && !ngd_run_windows_dist)  // (--groups, --boot_stats, --nj: their own entry points, checked above)
-      die(__FUNCTION__, "this build of the engine has no windows along the genome (--win_size)!");
-    if (!p.in_groups && !p.boot_stats && !p.nj && p.win_boot_rep && !ngd_run_windows_job_dist)
-      die(__FUNCTION__, "this build of the engine has no bootstrap replicates inside windows (--win_boot_rep)!");
-    if (p.verbose >= 1) fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
-  }
+};
 
-  g_phases.mark("args_labels");
-  // devices: --n_gpus of them, the site axis split over them
-  int n_dev = ngd_device_count();
-  if (n_dev < 1) die(__FUNCTION__, "no HIP device found (this program has no CPU path)");
-  if (p.device + (p.same_device ? 1 : p.n_gpus) > n_dev) die(__FUNCTION__, "not enough HIP devices for --device/--n_gpus");
-  bool eager_ranges = false;  // (set below once it is known whether the job goes through in site ranges)
-  auto make_engine = [&](Engine &eng, uint64_t n_sites_part, int dev_index) {
-    ngd_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.n_ind = p.n_ind;
-    cfg.n_sites = n_sites_part;
-    memcpy(cfg.score, p.score, sizeof(cfg.score));
-    cfg.pairwise_del = p.pairwise_del;
-    cfg.indep_geno = p.indep_geno;
-    cfg.device = p.same_device ? p.device : p.device + dev_index;
-    cfg.kernel = p.kernel;
-    // (the MFMA kernel on one operand image, on two, or -- 0 -- as the engine chooses; nothing to the other kernels)
-    cfg.single_image = p.single_image ? 2 : p.two_images ? 3 : 0;
-    int rc = ngd_create(&cfg, &eng.h);
-    if (rc) die_engine("ngd_create", rc);
-    // the first engine call after the load is the plain full-data pass (no bootstrap; or site ranges, whose engines always
-    // begin with it): on the EM path, where that pass is several times the load, it starts beside the load
-    // (NGD_OPT_EAGER_FULL: [measured] cfg 4 2.96 -> 2.78 s end to end; --eager 0 switches it off, --eager 2 also takes it
-    // for --indep_geno, where a 46 ms pass beside a 0.5 s load gains nothing measurable)
-    if (p.eager && (!p.indep_geno || p.eager >= 2) && (p.n_boot_rep == 0 || eager_ranges) && !p.win &&
-        (rc = ngd_set_option(eng.h, NGD_OPT_EAGER_FULL, 1)))
-      die_engine("ngd_set_option", rc);
-    if ((p.em_exact || p.em_exact_boot) && (rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT, p.em_exact_boot ? 2 : 1)))
-      die_engine("ngd_set_option", rc);
-    if (p.em_exact_win && ((rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT, p.win_boot_rep ? 2 : 1)) ||
-                           (rc = ngd_set_option(eng.h, NGD_OPT_EM_EXACT_WIN, 1))))
-      die_engine("ngd_set_option", rc);
-    if (p.stage_piece && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_PIECE_MIB, p.stage_piece))) die_engine("ngd_set_option", rc);
-    if (p.stage_ring && (rc = ngd_set_option(eng.h, NGD_OPT_STAGE_RING, p.stage_ring))) die_engine("ngd_set_option", rc);
+// positions: validated, never used (models 3-6 are unimplemented), ngsDist.cpp:133-149 -- except for the chromosomes
+// and coordinates of --win_size's windows
+void read_positions(const Pars &p, WindowList &win) {
+  if (p.verbose >= 1) fprintf(stderr, "==> Reading positions file\n");
+  std::vector<std::string> pos = read_lines(p.in_pos, p.in_pos_header ? 1 : 0);
+  uint64_t n_fields = 0;
+  for (auto &l : pos) {
+    uint64_t n = 1 + (uint64_t)std::count(l.begin(), l.end(), '\t');
+    if (!l.empty() && l.back() == '\t') n--;  // no trailing empty field (_strtok, gen_func.cpp:305-322)
+    if (n_fields == 0) n_fields = n;
+    if (n != n_fields) die("read_split", "invalid number of fields in file!");
+  }
+  if (pos.size() != p.n_sites || n_fields < 2) die(kMain, "invalid POS file!");
+  if (!p.win) return;
+  // fields 1 (chromosome) and 2 (position) of every site: the windows' chromosomes and coordinates
+  std::unordered_map<std::string, uint32_t> ids;
+  win.chrom.resize(p.n_sites);
+  win.pos_txt.resize(p.n_sites);
+  win.pos.resize(p.win_bp ? p.n_sites : 0);
+  for (uint64_t s = 0; s < p.n_sites; s++) {
+    const std::string &l = pos[s];
+    const size_t t1 = l.find('\t'), t2 = l.find('\t', t1 + 1);
+    const std::string chr = l.substr(0, t1);
+    win.chrom[s] = ids.emplace(chr, (uint32_t)ids.size()).first->second;
+    win.pos_txt[s] = l.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
+    if (s == 0 || win.chrom[s] != win.chrom[s - 1]) win.chr_name.emplace(win.chrom[s], chr);
+    if (!p.win_bp) continue;
+    // --win_bp: whole numbers from 1 (below 2^62: ngd_window_ranges_bp) that do not descend inside a chromosome
+    const std::string &t = win.pos_txt[s];
+    const bool digits = !t.empty() && t.size() <= 18 && t.find_first_not_of("0123456789") == std::string::npos;
+    win.pos[s] = digits ? strtoull(t.c_str(), nullptr, 10) : 0;
+    if (!win.pos[s]) die(kMain, "invalid position in POS file: windows in base pairs (--win_bp) need whole numbers from 1!");
+    if (s && win.chrom[s] == win.chrom[s - 1] && win.pos[s] < win.pos[s - 1])
+      die(kMain, "positions descend inside a chromosome of the POS file: windows in base pairs (--win_bp) need them in ascending order!");
+  }
+}
+
+// the windows (--win_size / --win_step, or --win_bp's in coordinates): the list the Python package makes too (host_util.cpp
+// ngd_window_ranges, ngd_window_ranges_bp), and whether the engine has the entry points the plain windowed run goes through
+void make_windows(const Pars &p, WindowList &win) {
+  const uint64_t B = (uint64_t)p.win_bp_size, T = (uint64_t)p.win_bp_step, M = (uint64_t)p.win_min_sites;
+  const uint32_t *ids = win.chrom.empty() ? nullptr : win.chrom.data();
+  // both calls: first the number of windows, then the windows
+  auto ranges = [&](uint64_t n) {
+    return p.win_bp ? ngd_window_ranges_bp(ids, win.pos.data(), p.n_sites, B, T, M, win.lo.data(), win.hi.data(), win.bp_start.data(), n)
+                    : ngd_window_ranges(ids, p.n_sites, p.win_size, p.win_step, win.lo.data(), win.hi.data(), n);
   };
+  const int64_t n_win = ranges(0);
+  if (n_win < 0) die(kMain, "positions file not grouped by chromosome!");
+  if (n_win == 0)
+    die(kMain, p.win_bp ? "no window is kept (--win_min_sites larger than every window's number of sites)!"
+                        : "no window fits the data set (--win_size larger than every chromosome)!");
+  win.lo.resize((size_t)n_win);
+  win.hi.resize((size_t)n_win);
+  if (p.win_bp) win.bp_start.resize((size_t)n_win);
+  ranges((uint64_t)n_win);
+  if (!p.in_groups && !p.boot_stats && !p.nj) {  // (--groups, --boot_stats, --nj: their own entry points, checked before)
+    if (!ngd_run_windows_dist) die(kMain, "this build of the engine has no windows along the genome (--win_size)!");
+    if (p.win_boot_rep && (p.win_bp ? !ngd_run_windows_job_var_dist : !ngd_run_windows_job_dist))
+      die(kMain, p.win_bp ? "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!"
+                          : "this build of the engine has no bootstrap replicates inside windows (--win_boot_rep)!");
+  }
+  if (p.verbose >= 1 && p.win_bp)
+    fprintf(stderr, "==> %lu windows of %lu bp every %lu bp\n", (unsigned long)n_win, (unsigned long)B, (unsigned long)T);
+  else if (p.verbose >= 1)
+    fprintf(stderr, "==> %lu windows of %lu sites every %lu sites\n", (unsigned long)n_win, p.win_size, p.win_step);
+}
 
-  // Does the data set fit ONE device?  Resident bytes per site: both operand images (one on the EM path, the
-  // individual-major copy for the streaming kernel), masks and bootstrap weights; plus slabs and results.  If it
-  // does and one device is asked for, one engine runs the whole job (ngd_run_job).  Otherwise gen_dist()'s sums are
-  // split along the SITE axis (include/ngsdist_amd.h "Site sharding"): ranges of sites, each read, held and computed
-  // by one device -- side by side on --n_gpus devices, one after the other where the devices are too small -- and
-  // the per-range (sum, cnt) are added.
+// Does the data set fit ONE device?  Resident bytes per site: both operand images (one on the EM path, the
+// individual-major copy for the streaming kernel), masks and bootstrap weights; plus slabs and results.  If it
+// does and one device is asked for, one engine runs the whole job (ngd_run_job).  Otherwise gen_dist()'s sums are
+// split along the SITE axis (include/ngsdist_amd.h "Site sharding"): ranges of sites, each read, held and computed
+// by one device -- side by side on --n_gpus devices, one after the other where the devices are too small -- and
+// the per-range (sum, cnt) are added.
+struct DeviceFit {
+  uint64_t per_site, fixed, budget;  // bytes: resident per site, needed whatever the sites, that a device may hold
+  bool in_parts;                     // the job goes through in ranges of sites
+};
+DeviceFit device_fit(const Pars &p, uint64_t n_comb, uint64_t dev_free) {
   const uint64_t n_pad = (p.n_ind + 127) / 128 * 128;
   const bool mfma_path = p.indep_geno && p.kernel != NGD_KERNEL_STREAM;
   // (one image + the fix-up pass's side array, 24 n_pad + 8 n_ind: --single_image, or the engine's own choice above 384
@@ -1444,89 +1441,128 @@ int main(int argc, char **argv) {
                             (p.pairwise_del ? p.n_ind / 8 + 1 : 0) + 40;
   const uint64_t n_t = n_pad / 128, n_slabs = std::max<uint64_t>(8, std::min<uint64_t>(256, 8192 / (n_t * (n_t + 1) / 2)));
   const uint64_t fixed = n_slabs * n_pad * n_pad * 8 + n_comb * 64 + (512ull << 20);
-  uint64_t dev_free = 0, dev_total = 0;
-  if (ngd_device_memory(p.device, &dev_free, &dev_total)) die_engine("ngd_device_memory", -1);
-  g_phases.mark("first_hip_calls");
   if (p.same_device) dev_free /= (uint64_t)p.n_gpus;  // the rehearsal's ranges share one device
   const uint64_t budget = p.max_device_bytes ? p.max_device_bytes : dev_free / 100 * 85;
-  const bool in_parts = p.n_gpus > 1 || fixed + per_site * p.n_sites > budget;
-  eager_ranges = in_parts;
-  if (p.win && in_parts)
-    die(__FUNCTION__, "windows (--win_size) need the whole data set on one GPU; it does not fit the device budget!");
-  if (p.boot_stats && in_parts)
-    die(__FUNCTION__, "bootstrap summaries (--boot_stats) need the whole data set on one GPU; it does not fit the device budget!");
-  if (p.nj && in_parts)
-    die(__FUNCTION__, "neighbour-joining trees (--nj) need the whole data set on one GPU; it does not fit the device budget!");
-  if (p.in_groups && in_parts)
-    die(__FUNCTION__, "group means (--groups) need the whole data set on one GPU; it does not fit the device budget!");
+  return {per_site, fixed, budget, p.n_gpus > 1 || fixed + per_site * p.n_sites > budget};
+}
 
-  if (p.verbose >= 2) fprintf(stderr, "==> Setting seed for random number generator\n");
-  uint32_t rng[3];
-  ngd_taus_seed(rng, p.seed);  // gsl_rng_alloc(gsl_rng_taus) + gsl_rng_set, ngsDist.cpp:179-180
+// an engine for n_sites_part sites on the run's dev_index-th device; eager_ranges: the job goes through in site ranges
+void make_engine(const Pars &p, Engine &eng, uint64_t n_sites_part, int dev_index, bool eager_ranges) {
+  ngd_config cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.n_ind = p.n_ind;
+  cfg.n_sites = n_sites_part;
+  memcpy(cfg.score, p.score, sizeof(cfg.score));
+  cfg.pairwise_del = p.pairwise_del;
+  cfg.indep_geno = p.indep_geno;
+  cfg.device = p.same_device ? p.device : p.device + dev_index;
+  cfg.kernel = p.kernel;
+  // (the MFMA kernel on one operand image, on two, or -- 0 -- as the engine chooses; nothing to the other kernels)
+  cfg.single_image = p.single_image ? 2 : p.two_images ? 3 : 0;
+  engine_ok("ngd_create", ngd_create(&cfg, &eng.h));
+  auto set = [&](int option, uint64_t value) { engine_ok("ngd_set_option", ngd_set_option(eng.h, option, value)); };
+  // the first engine call after the load is the plain full-data pass (no bootstrap; or site ranges, whose engines always
+  // begin with it): on the EM path, where that pass is several times the load, it starts beside the load
+  // (NGD_OPT_EAGER_FULL: [measured] cfg 4 2.96 -> 2.78 s end to end; --eager 0 switches it off, --eager 2 also takes it
+  // for --indep_geno, where a 46 ms pass beside a 0.5 s load gains nothing measurable)
+  if (p.eager && (!p.indep_geno || p.eager >= 2) && (p.n_boot_rep == 0 || eager_ranges) && !p.win) set(NGD_OPT_EAGER_FULL, 1);
+  if (p.em_exact || p.em_exact_boot) set(NGD_OPT_EM_EXACT, p.em_exact_boot ? 2 : 1);
+  if (p.em_exact_win) {
+    set(NGD_OPT_EM_EXACT, p.win_boot_rep ? 2 : 1);
+    set(NGD_OPT_EM_EXACT_WIN, 1);
+  }
+  if (p.stage_piece) set(NGD_OPT_STAGE_PIECE_MIB, p.stage_piece);
+  if (p.stage_ring) set(NGD_OPT_STAGE_RING, p.stage_ring);
+}
 
-  FILE *out_fh = fopen(p.out, "w");
-  if (!out_fh) die(__FUNCTION__, "cannot open output file!");
+// Text of unknown length: format(buffer, its size) returns the bytes the text takes (negative: it cannot be made) and
+// writes it if it fits; where it does not, the buffer grows to that size once and the text is formatted again.
+template <typename F>
+int64_t format_grown(std::vector<char> &buf, F format) {
+  int64_t need = format(buf.data(), buf.size());
+  if (need > (int64_t)buf.size()) {
+    buf.resize((size_t)need);
+    need = format(buf.data(), buf.size());
+  }
+  return need;
+}
 
-  double t_compute = 0, t_write = 0;
-  std::vector<double> dist(n_comb);
-  std::vector<const char *> label_ptr;
-  for (auto &l : labels) label_ptr.push_back(l.c_str());
-  // A matrix's text is written by a thread of its own while the next matrix is fetched, finished and formatted: two
-  // buffers ([measured, round 6] 101 matrices of 1000 individuals, 1.3 GB of text: 8.3 ms a matrix with the write inline).
-  std::vector<char> text_buf[2];
-  struct Writer {
-    FILE *fh = nullptr;
-    std::mutex m;
-    std::condition_variable cv;
-    const char *data = nullptr;
-    size_t len = 0;
-    bool quit = false, failed = false, busy = false;
-    std::thread th;
-    void start(FILE *f) {
-      fh = f;
-      th = std::thread([this]() {
-        std::unique_lock<std::mutex> lk(m);
-        for (;;) {
-          cv.wait(lk, [&] { return quit || data; });
-          if (!data) return;
-          const char *d = data;
-          const size_t n = len;
-          lk.unlock();
-          const bool ok = fwrite(d, 1, n, fh) == n;
-          lk.lock();
-          if (!ok) failed = true;
-          data = nullptr;
-          busy = false;
-          cv.notify_all();
-        }
-      });
-    }
-    void wait_idle() {
+// The thread that writes <out>: one piece of text at a time, in the order handed in.
+struct Writer {
+  FILE *fh = nullptr;
+  std::mutex m;
+  std::condition_variable cv;
+  const char *data = nullptr;
+  size_t len = 0;
+  bool quit = false, failed = false, busy = false;
+  std::thread th;
+  void start(FILE *f) {
+    fh = f;
+    th = std::thread([this]() {
       std::unique_lock<std::mutex> lk(m);
-      cv.wait(lk, [&] { return !busy; });
-    }
-    void submit(const char *d, size_t n) {  // (the caller has waited for the writer to be idle)
-      std::lock_guard<std::mutex> lk(m);
-      data = d; len = n; busy = true;
-      cv.notify_all();
-    }
-    bool finish() {  // everything handed in is written; false if a write failed
-      if (!th.joinable()) return true;
-      wait_idle();
-      { std::lock_guard<std::mutex> lk(m); quit = true; }
-      cv.notify_all();
-      th.join();
-      return !failed;
-    }
-  } writer;
-  writer.start(out_fh);
-  uint64_t n_emitted = 0;
+      for (;;) {
+        cv.wait(lk, [&] { return quit || data; });
+        if (!data) return;
+        const char *d = data;
+        const size_t n = len;
+        lk.unlock();
+        const bool ok = fwrite(d, 1, n, fh) == n;
+        lk.lock();
+        if (!ok) failed = true;
+        data = nullptr;
+        busy = false;
+        cv.notify_all();
+      }
+    });
+  }
+  void wait_idle() {
+    std::unique_lock<std::mutex> lk(m);
+    cv.wait(lk, [&] { return !busy; });
+  }
+  void submit(const char *d, size_t n) {  // (the caller has waited for the writer to be idle)
+    std::lock_guard<std::mutex> lk(m);
+    data = d; len = n; busy = true;
+    cv.notify_all();
+  }
+  bool finish() {  // everything handed in is written; false if a write failed
+    if (!th.joinable()) return true;
+    wait_idle();
+    { std::lock_guard<std::mutex> lk(m); quit = true; }
+    cv.notify_all();
+    th.join();
+    return !failed;
+  }
+};
 
+// <out>, the file of matrices, and what every mode that prints one goes through.  A matrix's text is written by a thread of
+// its own while the next matrix is fetched, finished and formatted: two buffers ([measured, round 6] 101 matrices of 1000
+// individuals, 1.3 GB of text: 8.3 ms a matrix with the write inline).
+struct MatrixOut {
+  const Pars &p;
+  const std::vector<std::string> &labels;
+  const uint64_t n_comb;
+  FILE *fh;
+  Writer writer;
+  std::vector<char> text_buf[2];
+  uint64_t n_emitted = 0;
+  double t_compute = 0, t_write = 0;  // the run's seconds in engine calls and ngd_finish; in formatting and handing to the writer
+  std::vector<double> dist;
+  std::vector<const char *> label_ptr;
+  MatrixOut(const Pars &pars, const std::vector<std::string> &names, uint64_t n_pairs, FILE *f)
+      : p(pars), labels(names), n_comb(n_pairs), fh(f), dist(n_pairs) {
+    for (auto &l : labels) label_ptr.push_back(l.c_str());
+    writer.start(fh);
+  }
+  // a matrix's print block, ngsDist.cpp:282-287 (join(), gen_func.cpp:479-496); rows formatted in parallel, same bytes
+  int64_t format(const double *cells, std::vector<char> &text) const {
+    if (text.empty()) text.resize(64 + p.n_ind * (p.n_ind * 16 + 64));
+    return format_grown(text, [&](char *buf, size_t cap) { return ngd_format_matrix(cells, p.n_ind, label_ptr.data(), buf, cap, p.n_threads); });
+  }
   // one matrix of the output: the reference's progress lines in its order (:218-241, :281), the tail of gen_dist
   // and the print block
-  auto emit = [&](uint64_t rep, const double *rs, const uint64_t *rc_, const uint64_t *bm, uint64_t n_blocks,
-                  const double *ready = nullptr /* the matrix's distances, finished already (beside the matrix before it) */,
-                  int ready_rc = 0, const char *window = nullptr /* --win_size: the window's name; rs, rc_ unused */) {
+  void emit(uint64_t rep, const double *rs, const uint64_t *rc_, const uint64_t *bm, uint64_t n_blocks,
+            const double *ready = nullptr /* the matrix's distances, finished already (beside the matrix before it) */,
+            int ready_rc = 0, const char *window = nullptr /* --win_size: the window's name; rs, rc_ unused */) {
     if (p.verbose >= 1) {
       if (window) fprintf(stderr, "==> Window %s ...\n", window);
       else if (rep == 0) fprintf(stderr, "==> Analyzing full dataset...\n");
@@ -1554,661 +1590,672 @@ int main(int argc, char **argv) {
       const auto t_f0 = std::chrono::steady_clock::now();
       int rc = ngd_finish(rs, rc_, n_comb, p.tot_sites, p.evol_model, dist.data());
       if (rc) die("gen_dist", "invalid evolutionary model specified!");
-      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_f0).count();
+      t_compute += since(t_f0);
       cells = dist.data();
     }
 
     if (p.verbose >= 2) fprintf(stderr, "> Printing distance matrix\n");
-    // ngsDist.cpp:282-287 (join(), gen_func.cpp:479-496); rows formatted in parallel, same bytes
     const auto t_w0 = std::chrono::steady_clock::now();
     std::vector<char> &text = text_buf[n_emitted++ & 1];  // (the writer may still be on the other one)
-    if (text.empty()) text.resize(64 + p.n_ind * (p.n_ind * 16 + 64));
-    int64_t need = ngd_format_matrix(cells, p.n_ind, label_ptr.data(), text.data(), text.size(), p.n_threads);
-    if (need > (int64_t)text.size()) {
-      text.resize((size_t)need);
-      need = ngd_format_matrix(cells, p.n_ind, label_ptr.data(), text.data(), text.size(), p.n_threads);
-    }
-    if (need < 0) die(__FUNCTION__, "cannot format the distance matrix");
+    const int64_t need = format(cells, text);
+    if (need < 0) die(kLambda, "cannot format the distance matrix");
     writer.wait_idle();  // the previous matrix is on its way out: matrices are written in order, one at a time
-    if (writer.failed) die(__FUNCTION__, "cannot write output file!");
+    if (writer.failed) die(kLambda, "cannot write output file!");
     writer.submit(text.data(), (size_t)need);
-    t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_w0).count();
-  };
-
-  // Matrices per engine call.  --indep_geno: 32 (the engine forms 32 replicates per pass over the per-block partials).
-  // EM path: the per-site EM does not depend on the replicate and ONE pass of it serves every matrix of a call (the
-  // engine spills the per-(pair, site) terms and contracts them with all the weight vectors: contract_mfma.hip), so the
-  // whole job goes in one call where its results (16 B per cell) and block maps fit a few GB of host memory.
-  uint64_t kBatch = 32;
-  if (!p.indep_geno && p.n_boot_rep + 1 > kBatch) {
-    const uint64_t by_results = (4ull << 30) / std::max<uint64_t>(1, n_comb * 16);
-    const uint64_t blocks = p.boot_block_size ? p.n_sites / p.boot_block_size : 0;
-    const uint64_t by_maps = blocks ? (2ull << 30) / (blocks * 8) : ~0ull;
-    kBatch = std::max<uint64_t>(kBatch, std::min({by_results, by_maps, (uint64_t)p.n_boot_rep + 1}));
+    t_write += since(t_w0);
   }
-  fflush(stdout);
-  if (in_parts) {
-    // ---- the site axis in ranges: side by side on the devices, one after the other where they are too small ----
-    const uint64_t B = p.boot_block_size;
-    const uint64_t n_eff = p.n_boot_rep ? p.n_sites - p.n_sites % B : 0, n_blocks = p.n_boot_rep ? n_eff / B : 0;
-    uint64_t unit = 16;  // ranges are whole 16-site groups and whole bootstrap blocks
-    if (p.n_boot_rep) { uint64_t a = 16, b = B; while (b) { uint64_t t = a % b; a = b; b = t; } unit = 16 / a * B; }
-    // lcm(16, B) can exceed the data set (a large odd block size): then no split into whole units exists, one range
-    // is the whole data set, and it only has to fit one device
-    const uint64_t whole = (p.n_sites + 15) / 16 * 16;
-    if (unit > whole) unit = whole;
-    if (budget <= fixed || (budget - fixed) / per_site < unit)
-      die(__FUNCTION__, "not even one range of sites (16 sites / one bootstrap block) fits the device");
-    const uint64_t cap = (budget - fixed) / per_site / unit * unit;  // sites one device holds
-    const uint64_t n_units = (p.n_sites + unit - 1) / unit;
-    const uint64_t G = (uint64_t)p.n_gpus;
-    const uint64_t part = std::min(cap, (n_units + G - 1) / G * unit);
-    const uint64_t n_parts = (p.n_sites + part - 1) / part;
-    if (p.verbose >= 1) {
-      if (part < (n_units + G - 1) / G * unit)
-        fprintf(stderr, "==> Data set larger than the device budget (%.1f GB): %lu ranges of up to %lu sites\n", budget / 1e9,
-                n_parts, part);
-      if (G > 1) fprintf(stderr, "==> Site axis split over %lu devices: %lu ranges of up to %lu sites\n", G, n_parts, part);
-    }
-    // every replicate's block multiplicities, drawn in the reference's order before any data is read
-    std::vector<uint32_t> mult((uint64_t)p.n_boot_rep * n_blocks, 0);
-    std::vector<uint64_t> maps_kept;
-    {
-      std::vector<uint64_t> bm(n_blocks);
-      for (uint64_t r = 0; r < p.n_boot_rep; r++) {
-        ngd_boot_block_map(rng, n_blocks, bm.data());
-        for (uint64_t b = 0; b < n_blocks; b++) mult[r * n_blocks + bm[b]]++;
-        if (p.verbose >= 5) maps_kept.insert(maps_kept.end(), bm.begin(), bm.end());
-      }
-    }
-    const uint64_t n_mat = p.n_boot_rep + 1;
-    // per device: the sums of its ranges, added in ascending range order; devices are added in device order at the
-    // end -- a fixed order of additions for given --n_gpus and budget
-    std::vector<std::vector<double>> dev_sum(G);
-    std::vector<std::vector<uint64_t>> dev_cnt(G);
-    std::vector<double> dev_secs(G, 0.0);
-    // all matrices of one range: the full data set (ngd_run), then the replicates from their block multiplicities
-    auto compute_range = [&](Engine &eng, uint64_t c0, uint64_t c1, uint64_t d) {
-      const auto t_c0 = std::chrono::steady_clock::now();
-      std::vector<double> &ts = dev_sum[d];
-      std::vector<uint64_t> &tc = dev_cnt[d];
-      if (ts.empty()) { ts.assign(n_mat * n_comb, 0.0); tc.assign(n_mat * n_comb, 0); }
-      std::vector<double> ps(std::min<uint64_t>(kBatch, n_mat) * n_comb);
-      std::vector<uint64_t> pc(ps.size());
-      int rc = ngd_run(eng.h, nullptr, 0, 0, ps.data(), pc.data());
-      if (rc) die_engine("ngd_run", rc);
+};
+
+// --win_boot_rep where every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length
+// share them): the table of maps and every window's offset into it.  Returns the table's length.
+uint64_t draw_window_maps(const Pars &p, const WindowList &win, uint64_t R, std::vector<uint64_t> &maps, std::vector<uint64_t> &off) {
+  off.resize(win.size());
+  auto draw = [&](uint64_t *table, uint64_t len) {  // both calls: first the table's length, then the table
+    return ngd_window_boot_maps(p.seed, win.lo.data(), win.hi.data(), win.size(), (uint32_t)R, p.boot_block_size, table, len, off.data());
+  };
+  const int64_t len = draw(nullptr, 0);
+  if (len < 0) die(kMain, "cannot draw the windows' block maps!");
+  maps.resize((size_t)len + 1);  // (+ 1: never a null table, even where no window holds a block)
+  draw(maps.data(), (uint64_t)len);
+  return (uint64_t)len;
+}
+
+// the maps of a whole-genome job's R replicates, drawn in the order rnd_map_data (ngsDist.cpp:416-437) would draw them
+void draw_job_maps(uint32_t rng[3], uint64_t R, uint64_t n_blocks, std::vector<uint64_t> &maps) {
+  maps.resize(R * n_blocks + 1);  // (+ 1: never a null table)
+  for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
+}
+
+// The windows go to the engine a group per call, a group being the windows whose results -- bytes_per_window each -- fit
+// ~2 GB of host memory: call(w0, n) makes the engine call for windows w0 .. w0 + n - 1, written(w0, n) prints them.
+// wait_writer: the last block's text is written before the next group's call.
+template <typename Call, typename Written>
+void for_window_groups(const Pars &p, Engine &eng, MatrixOut &out, uint64_t n_win, uint64_t bytes_per_window, bool wait_writer,
+                       Call call, Written written) {
+  const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / bytes_per_window));
+  for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
+    const uint64_t n = std::min(per, n_win - w0);
+    const auto t_c0 = std::chrono::steady_clock::now();
+    call(w0, n);
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    written(w0, n);
+    if (wait_writer) out.writer.wait_idle();
+  }
+}
+
+// ---- the site axis in ranges: side by side on the devices, one after the other where they are too small; the matrices of
+// the per-range sums added up ----
+void site_range_matrices(const Pars &p, const DeviceFit &fit, uint32_t rng[3], uint64_t batch, MatrixOut &out) {
+  const uint64_t n_comb = out.n_comb, B = p.boot_block_size;
+  const uint64_t n_eff = p.n_boot_rep ? p.n_sites - p.n_sites % B : 0, n_blocks = p.n_boot_rep ? n_eff / B : 0;
+  uint64_t unit = 16;  // ranges are whole 16-site groups and whole bootstrap blocks
+  if (p.n_boot_rep) { uint64_t a = 16, b = B; while (b) { uint64_t t = a % b; a = b; b = t; } unit = 16 / a * B; }
+  // lcm(16, B) can exceed the data set (a large odd block size): then no split into whole units exists, one range
+  // is the whole data set, and it only has to fit one device
+  const uint64_t whole = (p.n_sites + 15) / 16 * 16;
+  if (unit > whole) unit = whole;
+  if (fit.budget <= fit.fixed || (fit.budget - fit.fixed) / fit.per_site < unit)
+    die(kMain, "not even one range of sites (16 sites / one bootstrap block) fits the device");
+  const uint64_t cap = (fit.budget - fit.fixed) / fit.per_site / unit * unit;  // sites one device holds
+  const uint64_t n_units = (p.n_sites + unit - 1) / unit;
+  const uint64_t G = (uint64_t)p.n_gpus;
+  const uint64_t part = std::min(cap, (n_units + G - 1) / G * unit);
+  const uint64_t n_parts = (p.n_sites + part - 1) / part;
+  if (p.verbose >= 1) {
+    if (part < (n_units + G - 1) / G * unit)
+      fprintf(stderr, "==> Data set larger than the device budget (%.1f GB): %lu ranges of up to %lu sites\n", fit.budget / 1e9,
+              n_parts, part);
+    if (G > 1) fprintf(stderr, "==> Site axis split over %lu devices: %lu ranges of up to %lu sites\n", G, n_parts, part);
+  }
+  // every replicate's block multiplicities, drawn in the reference's order before any data is read
+  std::vector<uint32_t> mult((uint64_t)p.n_boot_rep * n_blocks, 0);
+  std::vector<uint64_t> maps_kept;
+  std::vector<uint64_t> bm(n_blocks);
+  for (uint64_t r = 0; r < p.n_boot_rep; r++) {
+    ngd_boot_block_map(rng, n_blocks, bm.data());
+    for (uint64_t b = 0; b < n_blocks; b++) mult[r * n_blocks + bm[b]]++;
+    if (p.verbose >= 5) maps_kept.insert(maps_kept.end(), bm.begin(), bm.end());
+  }
+  const uint64_t n_mat = p.n_boot_rep + 1;
+  // per device: the sums of its ranges, added in ascending range order; devices are added in device order at the
+  // end -- a fixed order of additions for given --n_gpus and budget
+  std::vector<std::vector<double>> dev_sum(G);
+  std::vector<std::vector<uint64_t>> dev_cnt(G);
+  std::vector<double> dev_secs(G, 0.0);
+  // all matrices of one range: the full data set (ngd_run), then the replicates from their block multiplicities
+  auto compute_range = [&](Engine &eng, uint64_t c0, uint64_t c1, uint64_t d) {
+    const auto t_c0 = std::chrono::steady_clock::now();
+    std::vector<double> &ts = dev_sum[d];
+    std::vector<uint64_t> &tc = dev_cnt[d];
+    if (ts.empty()) { ts.assign(n_mat * n_comb, 0.0); tc.assign(n_mat * n_comb, 0); }
+    std::vector<double> ps(std::min<uint64_t>(batch, n_mat) * n_comb);
+    std::vector<uint64_t> pc(ps.size());
+    engine_ok("ngd_run", ngd_run(eng.h, nullptr, 0, 0, ps.data(), pc.data()));
+    report_fixup(eng.h, p.verbose);
+    for (uint64_t k = 0; k < n_comb; k++) { ts[k] += ps[k]; tc[k] += pc[k]; }
+    const uint64_t blk_lo = std::min(c0, n_eff) / (B ? B : 1), blk_hi = std::min(c1, n_eff) / (B ? B : 1);
+    const uint64_t nb = blk_hi - blk_lo;  // this range's blocks (none in a range of tail sites only)
+    std::vector<uint32_t> mpart;
+    for (uint64_t r0 = 0; nb && r0 < p.n_boot_rep; r0 += batch) {
+      const uint64_t nr = std::min<uint64_t>(batch, p.n_boot_rep - r0);
+      mpart.resize(nr * nb);
+      for (uint64_t r = 0; r < nr; r++)
+        memcpy(&mpart[r * nb], &mult[(r0 + r) * n_blocks + blk_lo], nb * sizeof(uint32_t));
+      engine_ok("ngd_run_mult_batch", ngd_run_mult_batch(eng.h, mpart.data(), (uint32_t)nr, nb, B, ps.data(), pc.data()));
       report_fixup(eng.h, p.verbose);
-      for (uint64_t k = 0; k < n_comb; k++) { ts[k] += ps[k]; tc[k] += pc[k]; }
-      const uint64_t blk_lo = std::min(c0, n_eff) / (B ? B : 1), blk_hi = std::min(c1, n_eff) / (B ? B : 1);
-      const uint64_t nb = blk_hi - blk_lo;  // this range's blocks (none in a range of tail sites only)
-      std::vector<uint32_t> mpart;
-      for (uint64_t r0 = 0; nb && r0 < p.n_boot_rep; r0 += kBatch) {
-        const uint64_t nr = std::min<uint64_t>(kBatch, p.n_boot_rep - r0);
-        mpart.resize(nr * nb);
-        for (uint64_t r = 0; r < nr; r++)
-          memcpy(&mpart[r * nb], &mult[(r0 + r) * n_blocks + blk_lo], nb * sizeof(uint32_t));
-        rc = ngd_run_mult_batch(eng.h, mpart.data(), (uint32_t)nr, nb, B, ps.data(), pc.data());
-        if (rc) die_engine("ngd_run_mult_batch", rc);
-        report_fixup(eng.h, p.verbose);
-        for (uint64_t k = 0; k < nr * n_comb; k++) {
-          ts[(1 + r0) * n_comb + k] += ps[k];
-          tc[(1 + r0) * n_comb + k] += pc[k];
-        }
+      for (uint64_t k = 0; k < nr * n_comb; k++) {
+        ts[(1 + r0) * n_comb + k] += ps[k];
+        tc[(1 + r0) * n_comb + k] += pc[k];
       }
-      dev_secs[d] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-    };
-    if (p.verbose >= 1) fprintf(stderr, "==> Reading genotype data\n");
-    const auto t_l0 = std::chrono::steady_clock::now();
-    Loader L(p);
-    if (L.seekable() && G > 1) {
-      // plain binary file: every device's thread reads its own ranges (nothing is read twice, nothing is replicated)
-      // the size check of the whole file, once, with the reference's two messages (read_data.cpp:45-47, :106-109)
-      if (L.raw_size < p.n_sites * p.n_ind * 24)
-        die("read_geno", "GENO file at premature EOF. Check GENO file and number of sites!");
-      L.finish(p.n_sites * p.n_ind * 24 != L.raw_size);
-      std::vector<std::thread> th;
-      for (uint64_t d = 0; d < G; d++)
-        th.emplace_back([&, d]() {
-          for (uint64_t k = d; k < n_parts; k += G) {
-            const uint64_t c0 = k * part, c1 = std::min(p.n_sites, c0 + part);
-            Loader Ld(p, c0);
-            Engine eng;
-            make_engine(eng, c1 - c0, (int)d);
-            Ld.load(eng, c1 - c0, c1 == p.n_sites);
-            Ld.finish(false);
-            compute_range(eng, c0, c1, d);
-          }
-        });
-      for (auto &t : th) t.join();
-    } else {
-      // a stream (gz text, gz binary, stdin) is read front to back by this thread; a range is computed by its device's
-      // thread while the next range is read into the next device
-      std::vector<std::thread> busy(G);
-      for (uint64_t k = 0; k < n_parts; k++) {
-        const uint64_t d = k % G, c0 = k * part, c1 = std::min(p.n_sites, c0 + part);
-        if (busy[d].joinable()) busy[d].join();  // the device's previous range has left it
-        Engine *eng = new Engine();
-        make_engine(*eng, c1 - c0, (int)d);
-        L.load(*eng, c1 - c0, c1 == p.n_sites);
-        busy[d] = std::thread([&, eng, c0, c1, d]() {
-          compute_range(*eng, c0, c1, d);
-          delete eng;
-        });
-      }
-      for (auto &t : busy) if (t.joinable()) t.join();
-      L.finish();
     }
-    const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_l0).count();
-    double t_dev = 0;
-    for (double v : dev_secs) t_dev = std::max(t_dev, v);
-    t_compute += t_dev;
-    if (p.verbose >= 2)
-      fprintf(stderr, "> read + prepare + upload + distances of %lu ranges on %lu device(s): %.3f s (%.2f GB of prepared input "
-              "in all; slowest device's kernels and copies %.3f s)\n", n_parts, G, t_all, (double)p.n_ind * p.n_sites * 24 / 1e9,
-              t_dev);
-    std::vector<double> &tot_sum = dev_sum[0];
-    std::vector<uint64_t> &tot_cnt = dev_cnt[0];
-    if (tot_sum.empty()) { tot_sum.assign(n_mat * n_comb, 0.0); tot_cnt.assign(n_mat * n_comb, 0); }
-    // devices in ascending order for every cell, cells on --n_threads threads
-    parallel_for(p.n_threads, n_mat * n_comb, 1u << 16, [&](uint64_t lo, uint64_t hi) {
-      for (uint64_t d = 1; d < G; d++)
-        if (!dev_sum[d].empty())
-          for (uint64_t k = lo; k < hi; k++) { tot_sum[k] += dev_sum[d][k]; tot_cnt[k] += dev_cnt[d][k]; }
-    });
-    for (uint64_t rep = 0; rep < n_mat; rep++)
-      emit(rep, &tot_sum[rep * n_comb], &tot_cnt[rep * n_comb],
-           rep && !maps_kept.empty() ? &maps_kept[(rep - 1) * n_blocks] : nullptr, n_blocks);
-  } else {
-  Engine eng;
-  make_engine(eng, p.n_sites, 0);
-  g_phases.mark("create");
+    dev_secs[d] += since(t_c0);
+  };
   if (p.verbose >= 1) fprintf(stderr, "==> Reading genotype data\n");
-  const auto t_load0 = std::chrono::steady_clock::now();
-  {
-    Loader L(p);
-    L.load(eng, p.n_sites, true);
+  const auto t_l0 = std::chrono::steady_clock::now();
+  Loader L(p);
+  if (L.seekable() && G > 1) {
+    // plain binary file: every device's thread reads its own ranges (nothing is read twice, nothing is replicated)
+    // the size check of the whole file, once, with the reference's two messages (read_data.cpp:45-47, :106-109)
+    if (L.raw_size < p.n_sites * p.n_ind * 24)
+      die("read_geno", "GENO file at premature EOF. Check GENO file and number of sites!");
+    L.finish(p.n_sites * p.n_ind * 24 != L.raw_size);
+    std::vector<std::thread> th;
+    for (uint64_t d = 0; d < G; d++)
+      th.emplace_back([&, d]() {
+        for (uint64_t k = d; k < n_parts; k += G) {
+          const uint64_t c0 = k * part, c1 = std::min(p.n_sites, c0 + part);
+          Loader Ld(p, c0);
+          Engine eng;
+          make_engine(p, eng, c1 - c0, (int)d, true);
+          Ld.load(eng, c1 - c0, c1 == p.n_sites);
+          Ld.finish(false);
+          compute_range(eng, c0, c1, d);
+        }
+      });
+    for (auto &t : th) t.join();
+  } else {
+    // a stream (gz text, gz binary, stdin) is read front to back by this thread; a range is computed by its device's
+    // thread while the next range is read into the next device
+    std::vector<std::thread> busy(G);
+    for (uint64_t k = 0; k < n_parts; k++) {
+      const uint64_t d = k % G, c0 = k * part, c1 = std::min(p.n_sites, c0 + part);
+      if (busy[d].joinable()) busy[d].join();  // the device's previous range has left it
+      Engine *eng = new Engine();
+      make_engine(p, *eng, c1 - c0, (int)d, true);
+      L.load(*eng, c1 - c0, c1 == p.n_sites);
+      busy[d] = std::thread([&, eng, c0, c1, d]() {
+        compute_range(*eng, c0, c1, d);
+        delete eng;
+      });
+    }
+    for (auto &t : busy) if (t.joinable()) t.join();
     L.finish();
   }
-  const double t_load = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_load0).count();
-  g_phases.mark("load");
+  const double t_all = since(t_l0);
+  double t_dev = 0;
+  for (double v : dev_secs) t_dev = std::max(t_dev, v);
+  out.t_compute += t_dev;
   if (p.verbose >= 2)
-    fprintf(stderr, "> read + prepare + upload: %.3f s (%.2f GB of prepared input resident on the device)\n", t_load,
-            (double)p.n_ind * p.n_sites * 24 / 1e9);
+    fprintf(stderr, "> read + prepare + upload + distances of %lu ranges on %lu device(s): %.3f s (%.2f GB of prepared input "
+            "in all; slowest device's kernels and copies %.3f s)\n", n_parts, G, t_all, (double)p.n_ind * p.n_sites * 24 / 1e9,
+            t_dev);
+  std::vector<double> &tot_sum = dev_sum[0];  // (never empty: range 0 is device 0's)
+  std::vector<uint64_t> &tot_cnt = dev_cnt[0];
+  // devices in ascending order for every cell, cells on --n_threads threads
+  parallel_for(p.n_threads, n_mat * n_comb, 1u << 16, [&](uint64_t lo, uint64_t hi) {
+    for (uint64_t d = 1; d < G; d++)
+      if (!dev_sum[d].empty())
+        for (uint64_t k = lo; k < hi; k++) { tot_sum[k] += dev_sum[d][k]; tot_cnt[k] += dev_cnt[d][k]; }
+  });
+  for (uint64_t rep = 0; rep < n_mat; rep++)
+    out.emit(rep, &tot_sum[rep * n_comb], &tot_cnt[rep * n_comb],
+             rep && !maps_kept.empty() ? &maps_kept[(rep - 1) * n_blocks] : nullptr, n_blocks);
+}
 
-  // <out>.windows: where each window lies
-  auto write_windows_file = [&]() {
-    const uint64_t n_win = win_lo.size();
-    const std::string wpath = std::string(p.out) + ".windows";
-    FILE *wf = fopen(wpath.c_str(), "w");
-    if (!wf) die(__FUNCTION__, "cannot open windows output file!");
-    fprintf(wf, p.win_bp ? "window\tchr\tstart\tend\tfirst_site\tn_sites\twin_start\twin_end\n" : "window\tchr\tstart\tend\tfirst_site\tn_sites\n");
-    for (uint64_t w = 0; w < n_win; w++) {
-      const uint64_t lo = win_lo[w], hi = win_hi[w];
-      if (p.win_bp)  // (+ the window's own coordinates, inclusive: 1 + k T and k T + B)
-        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
-                win_pos_txt[hi - 1].c_str(), lo, hi - lo, win_bp_start[w], win_bp_start[w] + (uint64_t)p.win_bp_size - 1);
-      else if (win_chrom.empty())
-        fprintf(wf, "%lu\t.\t%lu\t%lu\t%lu\t%lu\n", w, lo + 1, hi, lo, hi - lo);
-      else
-        fprintf(wf, "%lu\t%s\t%s\t%s\t%lu\t%lu\n", w, win_chr_name[win_chrom[lo]].c_str(), win_pos_txt[lo].c_str(),
-                win_pos_txt[hi - 1].c_str(), lo, hi - lo);
-    }
-    if (fclose(wf) != 0) die(__FUNCTION__, "cannot write windows output file!");
+// ---- neighbour-joining trees (--nj): every matrix of every set -- the run's one set, or one per window -- becomes its tree
+// on the device (ngd_run_*_nj).  <out> takes matrix 0 of every set (a plain run: the bytes of the run without --nj),
+// <out>.nwk one Newick line per matrix, set after set, matrix 0 first, and, with replicates, <out>.support.nwk one line
+// per set: matrix 0's tree with the number of replicate trees that share each of its branches ----
+void trees(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], MatrixOut &out) {
+  const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep, n_mat = R + 1, nb = NGD_NJ_NBRANCH(p.n_ind), n_comb = out.n_comb;
+  FILE *nf = fopen((std::string(p.out) + ".nwk").c_str(), "w");
+  FILE *sf = R ? fopen((std::string(p.out) + ".support.nwk").c_str(), "w") : nullptr;
+  if (!nf || (R && !sf)) die(kMain, "cannot open trees output file!");
+  std::vector<char> line;
+  std::vector<uint32_t> support(p.n_ind > 3 ? p.n_ind - 3 : 1);
+  uint64_t n_no_tree = 0;
+  auto write_tree = [&](FILE *f, const int32_t *c, const double *l, const uint32_t *sup) {
+    const int64_t need = format_grown(line, [&](char *buf, size_t cap) { return ngd_nj_newick(c, l, p.n_ind, out.label_ptr.data(), sup, buf, cap); });
+    if (need < 0 || fwrite(line.data(), 1, (size_t)need, f) != (size_t)need) die(kLambda, "cannot write trees output file!");
   };
-  if (p.nj) {
-    // ---- neighbour-joining trees: every matrix of every set -- the run's one set, or one per window -- becomes its tree on
-    // the device (ngd_run_*_nj).  <out> takes matrix 0 of every set (a plain run: the bytes of the run without --nj),
-    // <out>.nwk one Newick line per matrix, set after set, matrix 0 first, and, with replicates, <out>.support.nwk one line
-    // per set: matrix 0's tree with the number of replicate trees that share each of its branches ----
-    const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep, n_mat = R + 1, nb = NGD_NJ_NBRANCH(p.n_ind);
-    FILE *nf = fopen((std::string(p.out) + ".nwk").c_str(), "w");
-    FILE *sf = R ? fopen((std::string(p.out) + ".support.nwk").c_str(), "w") : nullptr;
-    if (!nf || (R && !sf)) die(__FUNCTION__, "cannot open trees output file!");
-    std::vector<char> line;
-    std::vector<uint32_t> support(p.n_ind > 3 ? p.n_ind - 3 : 1);
-    uint64_t n_no_tree = 0;
-    auto write_tree = [&](FILE *f, const int32_t *c, const double *l, const uint32_t *sup) {
-      int64_t need = ngd_nj_newick(c, l, p.n_ind, label_ptr.data(), sup, line.data(), line.size());
-      if (need > (int64_t)line.size()) {
-        line.resize((size_t)need);
-        need = ngd_nj_newick(c, l, p.n_ind, label_ptr.data(), sup, line.data(), line.size());
-      }
-      if (need < 0 || fwrite(line.data(), 1, (size_t)need, f) != (size_t)need) die(__FUNCTION__, "cannot write trees output file!");
-    };
-    // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), its trees, its supports
-    auto write_set = [&](uint64_t w, const char *name, const double *d0, const int32_t *c, const double *l, const uint32_t *st) {
-      emit(w, nullptr, nullptr, nullptr, 0, d0, 0, name);
-      for (uint64_t r = 0; r < n_mat; r++) {
-        write_tree(nf, c + r * nb, l + r * nb, nullptr);
-        n_no_tree += st[r] == 0;
-      }
-      if (!R) return;
-      uint32_t used = 0;
-      if (ngd_nj_support(c, st, n_mat, p.n_ind, support.data(), &used)) die(__FUNCTION__, "cannot count the trees' support!");
-      write_tree(sf, c, l, support.data());
-    };
-    std::vector<int32_t> child;
-    std::vector<double> len, d0;
-    std::vector<uint32_t> status;
-    int rc = 0;
-    if (p.win) {
-      // --win_boot_rep: every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length
-      // share them); the replicates of a window shorter than one block are 0 / 0 and have no tree
-      const uint64_t n_win = win_lo.size();
-      std::vector<uint64_t> off(n_win), maps(1);
-      int64_t mlen = 0;
-      if (R) {
-        mlen = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0, off.data());
-        if (mlen < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
-        maps.resize((size_t)mlen + 1);
-        ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, maps.data(), (uint64_t)mlen, off.data());
-      }
-      // a group of windows per call: their records and first matrices in ~2 GB of host memory
-      const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (n_mat * nb * 12 + n_mat * 4 + n_comb * 8)));
-      for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
-        const uint64_t n = std::min(per, n_win - w0);
-        const auto t_c0 = std::chrono::steady_clock::now();
-        child.resize(n * n_mat * nb);
-        len.resize(n * n_mat * nb);
-        status.resize(n * n_mat);
-        d0.resize(n * n_comb);
-        rc = R ? ngd_run_windows_job_var_nj(eng.h, &win_lo[w0], &win_hi[w0], n, maps.data(), (uint64_t)mlen, &off[w0], (uint32_t)R,
-                                            p.boot_block_size, p.tot_sites, p.evol_model, child.data(), len.data(), status.data(), d0.data())
-               : ngd_run_windows_nj(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, child.data(), len.data(),
-                                    status.data(), d0.data());
-        if (rc) die_engine(R ? "ngd_run_windows_job_var_nj" : "ngd_run_windows_nj", rc);
-        report_fixup(eng.h, p.verbose);
-        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-        for (uint64_t k = 0; k < n; k++) {
-          const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
-          write_set(w0 + k, name.c_str(), &d0[k * n_comb], &child[k * n_mat * nb], &len[k * n_mat * nb], &status[k * n_mat]);
-        }
-        writer.wait_idle();  // (the last block's text is written before the next group's call)
-      }
-      write_windows_file();
-    } else {
-      // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
-      const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
-      if (R && !n_blocks) die(__FUNCTION__, "neighbour-joining trees (--nj) of bootstrap replicates need at least one bootstrap block of sites!");
-      const auto t_c0 = std::chrono::steady_clock::now();
-      std::vector<uint64_t> maps(R * n_blocks + 1);
-      for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
-      child.resize(n_mat * nb);
-      len.resize(n_mat * nb);
-      status.resize(n_mat);
-      d0.resize(n_comb);
-      rc = ngd_run_job_nj(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, child.data(),
-                          len.data(), status.data(), d0.data());
-      if (rc) die_engine("ngd_run_job_nj", rc);
-      report_fixup(eng.h, p.verbose);
-      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-      write_set(0, nullptr, d0.data(), child.data(), len.data(), status.data());
+  // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), its trees, its supports
+  auto write_set = [&](uint64_t w, const char *name, const double *m0, const int32_t *c, const double *l, const uint32_t *st) {
+    out.emit(w, nullptr, nullptr, nullptr, 0, m0, 0, name);
+    for (uint64_t r = 0; r < n_mat; r++) {
+      write_tree(nf, c + r * nb, l + r * nb, nullptr);
+      n_no_tree += st[r] == 0;
     }
-    if (n_no_tree)
-      fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no tree (a line \";\" in %s.nwk)\n",
-              (unsigned long)n_no_tree, p.out);
-    if (fclose(nf) != 0 || (sf && fclose(sf) != 0)) die(__FUNCTION__, "cannot write trees output file!");
-  } else if (p.boot_stats) {
-    // ---- bootstrap summaries: the replicates of every set -- the run's, or a window's -- stay on the device, which reduces
-    // each cell to five statistics and a count (ngd_run_*_stats).  <out> takes the estimates (matrix 0 of every set: the
-    // bytes of the run without replicates), <out>.boot_mean / _sd / _lo / _hi the other statistics in the same blocks and
-    // <out>.boot_used the finite replicates behind them, as integers; with --groups the blocks are G x G ----
-    int rc = 0;
-    const bool grp = p.in_groups != nullptr;
-    if (grp && (rc = ngd_set_groups(eng.h, group_of.data(), (uint32_t)group_names.size()))) die_engine("ngd_set_groups", rc);
-    const uint64_t G = group_names.size(), n_cells = grp ? G * (G + 1) / 2 : n_comb;
-    static const char *const kSuffix[NGD_BOOT_NSTAT + 1] = {"", ".boot_mean", ".boot_sd", ".boot_lo", ".boot_hi", ".boot_used"};
-    FILE *sf[NGD_BOOT_NSTAT + 1] = {out_fh};
-    for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
-      if (!(sf[k] = fopen((std::string(p.out) + kSuffix[k]).c_str(), "w"))) die(__FUNCTION__, "cannot open bootstrap summaries output file!");
-    std::vector<char> text;
-    std::string txt, cnt, skip;
-    // one set's blocks: est through emit() (pairs: the progress lines and the writer of any matrix), the rest formatted here
-    auto write_set = [&](uint64_t w, const char *name, const double *st, const uint64_t *us) {
-      if (grp) {
-        for (int k = 0; k < NGD_BOOT_NSTAT; k++) {
-          txt.clear();
-          (k ? skip : cnt).clear();
-          format_groups(group_names, st + k * n_cells, us, txt, k ? skip : cnt);
-          if (fwrite(txt.data(), 1, txt.size(), sf[k]) != txt.size()) die(__FUNCTION__, "cannot write output file!");
-        }
-      } else {
-        emit(w, nullptr, nullptr, nullptr, 0, st, 0, name);
-        if (text.empty()) text.resize(64 + p.n_ind * (p.n_ind * 16 + 64));
-        for (int k = 1; k < NGD_BOOT_NSTAT; k++) {
-          int64_t need = ngd_format_matrix(st + k * n_cells, p.n_ind, label_ptr.data(), text.data(), text.size(), p.n_threads);
-          if (need > (int64_t)text.size()) {
-            text.resize((size_t)need);
-            need = ngd_format_matrix(st + k * n_cells, p.n_ind, label_ptr.data(), text.data(), text.size(), p.n_threads);
-          }
-          if (need < 0 || fwrite(text.data(), 1, (size_t)need, sf[k]) != (size_t)need) die(__FUNCTION__, "cannot write output file!");
-        }
-        // the counts in a matrix's layout: "\n<n_ind>\n", per individual its label and n_ind cells "\t<m>" (0 on the diagonal)
-        cnt = "\n" + std::to_string(p.n_ind) + "\n";
-        for (uint64_t i = 0; i < p.n_ind; i++) {
-          cnt += labels[i];
-          for (uint64_t j = 0; j < p.n_ind; j++) {
-            const uint64_t a = std::min(i, j), b = std::max(i, j);
-            cnt += "\t" + std::to_string(i == j ? 0 : (unsigned long)us[a * p.n_ind - a * (a + 1) / 2 + (b - a - 1)]);
-          }
-          cnt += "\n";
-        }
+    if (!R) return;
+    uint32_t used = 0;
+    if (ngd_nj_support(c, st, n_mat, p.n_ind, support.data(), &used)) die(kLambda, "cannot count the trees' support!");
+    write_tree(sf, c, l, support.data());
+  };
+  std::vector<int32_t> child;
+  std::vector<double> len, d0;
+  std::vector<uint32_t> status;
+  auto resize_results = [&](uint64_t n_sets) {
+    child.resize(n_sets * n_mat * nb);
+    len.resize(n_sets * n_mat * nb);
+    status.resize(n_sets * n_mat);
+    d0.resize(n_sets * n_comb);
+  };
+  if (p.win) {
+    // a group of windows per call: their records and first matrices in ~2 GB of host memory.  --win_boot_rep: the
+    // replicates of a window shorter than one block are 0 / 0 and have no tree
+    std::vector<uint64_t> off(win.size()), maps(1);
+    const uint64_t mlen = R ? draw_window_maps(p, win, R, maps, off) : 0;
+    for_window_groups(p, eng, out, win.size(), n_mat * nb * 12 + n_mat * 4 + n_comb * 8, true,
+      [&](uint64_t w0, uint64_t n) {
+        resize_results(n);
+        const int rc = R ? ngd_run_windows_job_var_nj(eng.h, &win.lo[w0], &win.hi[w0], n, maps.data(), mlen, &off[w0], (uint32_t)R,
+                                                      p.boot_block_size, p.tot_sites, p.evol_model, child.data(), len.data(),
+                                                      status.data(), d0.data())
+                         : ngd_run_windows_nj(eng.h, &win.lo[w0], &win.hi[w0], n, p.tot_sites, p.evol_model, child.data(), len.data(),
+                                              status.data(), d0.data());
+        engine_ok(R ? "ngd_run_windows_job_var_nj" : "ngd_run_windows_nj", rc);
+      },
+      [&](uint64_t w0, uint64_t n) {
+        for (uint64_t k = 0; k < n; k++)
+          write_set(w0 + k, win.name(w0 + k).c_str(), &d0[k * n_comb], &child[k * n_mat * nb], &len[k * n_mat * nb], &status[k * n_mat]);
+      });
+    win.write_file(std::string(p.out) + ".windows", p);
+  } else {
+    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
+    const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
+    if (R && !n_blocks) die(kMain, "neighbour-joining trees (--nj) of bootstrap replicates need at least one bootstrap block of sites!");
+    const auto t_c0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> maps;
+    draw_job_maps(rng, R, n_blocks, maps);
+    resize_results(1);
+    engine_ok("ngd_run_job_nj", ngd_run_job_nj(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model,
+                                               child.data(), len.data(), status.data(), d0.data()));
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    write_set(0, nullptr, d0.data(), child.data(), len.data(), status.data());
+  }
+  if (n_no_tree)
+    fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no tree (a line \";\" in %s.nwk)\n",
+            (unsigned long)n_no_tree, p.out);
+  if (fclose(nf) != 0 || (sf && fclose(sf) != 0)) die(kMain, "cannot write trees output file!");
+}
+
+// ---- bootstrap summaries (--boot_stats): the replicates of every set -- the run's, or a window's -- stay on the device,
+// which reduces each cell to five statistics and a count (ngd_run_*_stats).  <out> takes the estimates (matrix 0 of every
+// set: the bytes of the run without replicates), <out>.boot_mean / _sd / _lo / _hi the other statistics in the same blocks
+// and <out>.boot_used the finite replicates behind them, as integers; with --groups the blocks are G x G ----
+void bootstrap_summaries(const Pars &p, Engine &eng, const WindowList &win, const std::vector<int32_t> &group_of,
+                         const std::vector<std::string> &group_names, uint32_t rng[3], MatrixOut &out) {
+  const bool grp = p.in_groups != nullptr;
+  if (grp) engine_ok("ngd_set_groups", ngd_set_groups(eng.h, group_of.data(), (uint32_t)group_names.size()));
+  const uint64_t G = group_names.size(), n_cells = grp ? G * (G + 1) / 2 : out.n_comb, n_ind = p.n_ind;
+  static const char *const kSuffix[NGD_BOOT_NSTAT + 1] = {"", ".boot_mean", ".boot_sd", ".boot_lo", ".boot_hi", ".boot_used"};
+  FILE *sf[NGD_BOOT_NSTAT + 1] = {out.fh};
+  for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
+    if (!(sf[k] = fopen((std::string(p.out) + kSuffix[k]).c_str(), "w"))) die(kMain, "cannot open bootstrap summaries output file!");
+  std::vector<char> text;
+  std::string txt, cnt, skip;
+  // one set's blocks: est through emit() (pairs: the progress lines and the writer of any matrix), the rest formatted here
+  auto write_set = [&](uint64_t w, const char *name, const double *st, const uint64_t *us) {
+    if (grp) {
+      for (int k = 0; k < NGD_BOOT_NSTAT; k++) {
+        txt.clear();
+        (k ? skip : cnt).clear();
+        format_groups(group_names, st + k * n_cells, us, txt, k ? skip : cnt);
+        if (fwrite(txt.data(), 1, txt.size(), sf[k]) != txt.size()) die(kLambda, "cannot write output file!");
       }
-      if (fwrite(cnt.data(), 1, cnt.size(), sf[NGD_BOOT_NSTAT]) != cnt.size()) die(__FUNCTION__, "cannot write output file!");
-    };
-    std::vector<double> st;
-    std::vector<uint64_t> us;
-    if (p.win) {
-      // every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length share them); a
-      // window shorter than one block has replicates of 0 / 0: no finite replicate
-      const uint64_t n_win = win_lo.size(), R = p.win_boot_rep;
-      std::vector<uint64_t> off(n_win);
-      const int64_t len = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0,
-                                               off.data());
-      if (len < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
-      std::vector<uint64_t> maps((size_t)len + 1);
-      ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, maps.data(), (uint64_t)len, off.data());
-      // a group of windows per call: their statistics in ~2 GB of host memory
-      const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * (NGD_BOOT_NSTAT + 1) * std::max<uint64_t>(1, n_cells))));
-      for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
-        const uint64_t n = std::min(per, n_win - w0);
-        const auto t_c0 = std::chrono::steady_clock::now();
+    } else {
+      out.emit(w, nullptr, nullptr, nullptr, 0, st, 0, name);
+      for (int k = 1; k < NGD_BOOT_NSTAT; k++) {
+        const int64_t need = out.format(st + k * n_cells, text);
+        if (need < 0 || fwrite(text.data(), 1, (size_t)need, sf[k]) != (size_t)need) die(kLambda, "cannot write output file!");
+      }
+      // the counts in a matrix's layout: "\n<n_ind>\n", per individual its label and n_ind cells "\t<m>" (0 on the diagonal)
+      cnt = "\n" + std::to_string(n_ind) + "\n";
+      for (uint64_t i = 0; i < n_ind; i++) {
+        cnt += out.labels[i];
+        for (uint64_t j = 0; j < n_ind; j++) {
+          const uint64_t a = std::min(i, j), b = std::max(i, j);
+          cnt += "\t" + std::to_string(i == j ? 0 : (unsigned long)us[a * n_ind - a * (a + 1) / 2 + (b - a - 1)]);
+        }
+        cnt += "\n";
+      }
+    }
+    if (fwrite(cnt.data(), 1, cnt.size(), sf[NGD_BOOT_NSTAT]) != cnt.size()) die(kLambda, "cannot write output file!");
+  };
+  std::vector<double> st;
+  std::vector<uint64_t> us, maps;
+  if (p.win) {
+    // a group of windows per call: their statistics in ~2 GB of host memory.  A window shorter than one block has
+    // replicates of 0 / 0: no finite replicate
+    const uint64_t R = p.win_boot_rep;
+    std::vector<uint64_t> off;
+    const uint64_t mlen = draw_window_maps(p, win, R, maps, off);
+    // (group pairs are written here, not by the writer thread: nothing to wait for at a group's end)
+    for_window_groups(p, eng, out, win.size(), 8 * (NGD_BOOT_NSTAT + 1) * std::max<uint64_t>(1, n_cells), !grp,
+      [&](uint64_t w0, uint64_t n) {
         st.resize(n * NGD_BOOT_NSTAT * n_cells);
         us.resize(n * n_cells);
-        rc = (grp ? ngd_run_windows_job_var_groups_stats : ngd_run_windows_job_var_stats)(
-            eng.h, &win_lo[w0], &win_hi[w0], n, maps.data(), (uint64_t)len, &off[w0], (uint32_t)R, p.boot_block_size, p.tot_sites,
-            p.evol_model, p.boot_ci, st.data(), us.data());
-        if (rc) die_engine(grp ? "ngd_run_windows_job_var_groups_stats" : "ngd_run_windows_job_var_stats", rc);
-        report_fixup(eng.h, p.verbose);
-        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-        for (uint64_t k = 0; k < n; k++) {
-          const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
-          write_set(w0 + k, name.c_str(), &st[k * NGD_BOOT_NSTAT * n_cells], &us[k * n_cells]);
-        }
-        if (!grp) writer.wait_idle();  // (the last block's text is written before the next group's call)
-      }
-      write_windows_file();
-    } else {
-      // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
-      const uint64_t R = p.n_boot_rep, n_blocks = (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size;
-      if (!n_blocks) die(__FUNCTION__, "bootstrap summaries (--boot_stats) need at least one bootstrap block of sites!");
-      const auto t_c0 = std::chrono::steady_clock::now();
-      std::vector<uint64_t> maps(R * n_blocks);
-      for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
-      st.resize(NGD_BOOT_NSTAT * n_cells);
-      us.resize(n_cells);
-      rc = (grp ? ngd_run_job_groups_stats : ngd_run_job_stats)(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites,
-                                                                 p.evol_model, p.boot_ci, st.data(), us.data());
-      if (rc) die_engine(grp ? "ngd_run_job_groups_stats" : "ngd_run_job_stats", rc);
-      report_fixup(eng.h, p.verbose);
-      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-      write_set(0, nullptr, st.data(), us.data());
-    }
-    for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
-      if (fclose(sf[k]) != 0) die(__FUNCTION__, "cannot write bootstrap summaries output file!");
-  } else if (p.in_groups) {
-    // ---- group means: every matrix of the run -- the full data set and its replicates, or the windows and theirs -- leaves
-    // the engine as its G x G table (ngd_run_*_groups): one block per matrix in <out>, in the order of the run without
-    // --groups, and the same blocks with the numbers of cells behind the means in <out>.used ----
-    int rc = ngd_set_groups(eng.h, group_of.data(), (uint32_t)group_names.size());
-    if (rc) die_engine("ngd_set_groups", rc);
-    const uint64_t G = group_names.size(), n_gp = G * (G + 1) / 2;
-    const std::string upath = std::string(p.out) + ".used";
-    FILE *uf = fopen(upath.c_str(), "w");
-    if (!uf) die(__FUNCTION__, "cannot open used output file!");
-    std::string txt, cnt;
-    auto write_blocks = [&](const double *mean, const uint64_t *used, uint64_t n_mat) {
-      const auto t_w0 = std::chrono::steady_clock::now();
-      txt.clear();
-      cnt.clear();
-      for (uint64_t m = 0; m < n_mat; m++) format_groups(group_names, mean + m * n_gp, used + m * n_gp, txt, cnt);
-      if (fwrite(txt.data(), 1, txt.size(), out_fh) != txt.size() || fwrite(cnt.data(), 1, cnt.size(), uf) != cnt.size())
-        die(__FUNCTION__, "cannot write output file!");
-      t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_w0).count();
-    };
-    std::vector<double> gmean;
-    std::vector<uint64_t> gused;
+        engine_ok(grp ? "ngd_run_windows_job_var_groups_stats" : "ngd_run_windows_job_var_stats",
+                  (grp ? ngd_run_windows_job_var_groups_stats : ngd_run_windows_job_var_stats)(
+                      eng.h, &win.lo[w0], &win.hi[w0], n, maps.data(), mlen, &off[w0], (uint32_t)R, p.boot_block_size, p.tot_sites,
+                      p.evol_model, p.boot_ci, st.data(), us.data()));
+      },
+      [&](uint64_t w0, uint64_t n) {
+        for (uint64_t k = 0; k < n; k++) write_set(w0 + k, win.name(w0 + k).c_str(), &st[k * NGD_BOOT_NSTAT * n_cells], &us[k * n_cells]);
+      });
+    win.write_file(std::string(p.out) + ".windows", p);
+  } else {
+    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
+    const uint64_t R = p.n_boot_rep, n_blocks = (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size;
+    if (!n_blocks) die(kMain, "bootstrap summaries (--boot_stats) need at least one bootstrap block of sites!");
     const auto t_c0 = std::chrono::steady_clock::now();
-    if (p.win) {
-      const uint64_t n_win = win_lo.size(), R = p.win_boot_rep, n_mat = R + 1;
-      gmean.resize(n_win * n_mat * n_gp);
-      gused.resize(n_win * n_mat * n_gp);
-      if (R) {
-        // every window draws the maps of its own cut-down run (ngd_window_boot_maps; windows of one length share them); a
-        // window shorter than one block has replicates of 0 / 0, whose means are nan
-        std::vector<uint64_t> off(n_win);
-        const int64_t len = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0,
-                                                 off.data());
-        if (len < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
-        std::vector<uint64_t> maps((size_t)len + 1);
-        ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, maps.data(), (uint64_t)len,
-                             off.data());
-        rc = ngd_run_windows_job_var_groups(eng.h, win_lo.data(), win_hi.data(), n_win, maps.data(), (uint64_t)len, off.data(), (uint32_t)R,
-                                            p.boot_block_size, p.tot_sites, p.evol_model, gmean.data(), gused.data());
-        if (rc) die_engine("ngd_run_windows_job_var_groups", rc);
-      } else {
-        rc = ngd_run_windows_groups(eng.h, win_lo.data(), win_hi.data(), n_win, p.tot_sites, p.evol_model, gmean.data(), gused.data());
-        if (rc) die_engine("ngd_run_windows_groups", rc);
-      }
-      report_fixup(eng.h, p.verbose);
-      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-      if (p.verbose >= 1) fprintf(stderr, "==> %lu windows, %lu matrices each\n", (unsigned long)n_win, (unsigned long)n_mat);
-      write_blocks(gmean.data(), gused.data(), n_win * n_mat);
-    } else {
-      // the full data set, then the replicates in batches (their maps drawn in the reference's order); a batch after the
-      // first goes through the same call and its leading full-data matrix is dropped
-      const uint64_t n_sites_b = p.n_sites - p.n_sites % p.boot_block_size, n_blocks = n_sites_b / p.boot_block_size;
-      std::vector<uint64_t> maps;
-      for (uint64_t rep = 0; rep <= p.n_boot_rep;) {
-        const auto t_b0 = std::chrono::steady_clock::now();
-        const uint64_t n_here = std::min<uint64_t>(kBatch - 1, p.n_boot_rep - (rep ? rep - 1 : 0));  // replicates of this call
-        gmean.assign((n_here + 1) * n_gp, std::nan(""));
-        gused.assign((n_here + 1) * n_gp, 0);
-        if (n_here && n_blocks) {
-          maps.resize(n_here * n_blocks);
-          for (uint64_t r = 0; r < n_here; r++) ngd_boot_block_map(rng, n_blocks, &maps[r * n_blocks]);
-        }
-        // (fewer sites than one block: the replicates visit no site, ngsDist.cpp:236 -- their means stay nan, used 0)
-        const uint32_t n_call = n_blocks ? (uint32_t)n_here : 0;
-        if (rep == 0 || n_call) {
-          rc = ngd_run_job_groups(eng.h, maps.data(), n_call, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, gmean.data(),
-                                  gused.data());
-          if (rc) die_engine("ngd_run_job_groups", rc);
-          report_fixup(eng.h, p.verbose);
-        }
-        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_b0).count();
-        if (p.verbose >= 1 && rep == 0) fprintf(stderr, "==> Analyzing full dataset...\n");
-        if (p.verbose >= 1 && n_here) fprintf(stderr, "==> Bootstrap replicates # %lu to %lu ...\n", rep ? rep : 1, (rep ? rep : 1) + n_here - 1);
-        const uint64_t skip = rep ? 1 : 0;
-        write_blocks(gmean.data() + skip * n_gp, gused.data() + skip * n_gp, n_here + 1 - skip);
-        rep = (rep ? rep : 1) + n_here;
-      }
-    }
-    if (fclose(uf) != 0) die(__FUNCTION__, "cannot write used output file!");
+    draw_job_maps(rng, R, n_blocks, maps);
+    st.resize(NGD_BOOT_NSTAT * n_cells);
+    us.resize(n_cells);
+    engine_ok(grp ? "ngd_run_job_groups_stats" : "ngd_run_job_stats",
+              (grp ? ngd_run_job_groups_stats : ngd_run_job_stats)(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites,
+                                                                   p.evol_model, p.boot_ci, st.data(), us.data()));
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    write_set(0, nullptr, st.data(), us.data());
   }
-  if (p.boot_stats || p.nj) {
-    // (written above)
-  } else if (p.in_groups) {
-    if (p.win) write_windows_file();  // (the windows' own file: as without --groups)
-  } else if (p.win) {
-    // ---- windows along the genome: one matrix per window, in window order, a group of windows per engine call (their
-    // distances in ~2 GB of host memory), each window's block formatted and written like the full data set's ----
-    const uint64_t n_win = win_lo.size();
-    // --win_boot_rep: R replicates inside every window, its R + 1 blocks printed one after the other -- the file is the
-    // concatenation of the cut-down runs' files.  Every cut-down run seeds the generator anew and the windows have one
-    // length, so ONE set of block maps, drawn from a fresh state, serves them all (ngsDist.cpp:179-180, :235-238, :416-437)
-    const uint64_t R = p.win_boot_rep, n_mat = R + 1;
-    const uint64_t wb_blocks = R && !p.win_bp ? p.win_size / p.boot_block_size : 0;
-    std::vector<uint64_t> wb_maps(R * wb_blocks);
-    // --win_bp: the windows differ in length, every one draws the maps of its own cut-down run (ngd_window_boot_maps); a
-    // window shorter than one block comes back as sum 0 and count 0, printed as 0 / 0 by the call itself
-    std::vector<uint64_t> wb_off;
-    if (R && p.win_bp) {
-      wb_off.resize(n_win);
-      const int64_t len = ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, nullptr, 0,
-                                               wb_off.data());
-      if (len < 0) die(__FUNCTION__, "cannot draw the windows' block maps!");
-      wb_maps.resize((size_t)len + 1);  // (+ 1: never a null table, even where no window holds a block)
-      ngd_window_boot_maps(p.seed, win_lo.data(), win_hi.data(), n_win, (uint32_t)R, p.boot_block_size, wb_maps.data(), (uint64_t)len,
-                           wb_off.data());
+  for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
+    if (fclose(sf[k]) != 0) die(kMain, "cannot write bootstrap summaries output file!");
+}
+
+// ---- group means (--groups): every matrix of the run -- the full data set and its replicates, or the windows and theirs --
+// leaves the engine as its G x G table (ngd_run_*_groups): one block per matrix in <out>, in the order of the run without
+// --groups, and the same blocks with the numbers of cells behind the means in <out>.used ----
+void group_means(const Pars &p, Engine &eng, const WindowList &win, const std::vector<int32_t> &group_of,
+                 const std::vector<std::string> &group_names, uint32_t rng[3], uint64_t batch, MatrixOut &out) {
+  engine_ok("ngd_set_groups", ngd_set_groups(eng.h, group_of.data(), (uint32_t)group_names.size()));
+  const uint64_t G = group_names.size(), n_gp = G * (G + 1) / 2;
+  FILE *uf = fopen((std::string(p.out) + ".used").c_str(), "w");
+  if (!uf) die(kMain, "cannot open used output file!");
+  std::string txt, cnt;
+  auto write_blocks = [&](const double *mean, const uint64_t *used, uint64_t n_mat) {
+    const auto t_w0 = std::chrono::steady_clock::now();
+    txt.clear();
+    cnt.clear();
+    for (uint64_t m = 0; m < n_mat; m++) format_groups(group_names, mean + m * n_gp, used + m * n_gp, txt, cnt);
+    if (fwrite(txt.data(), 1, txt.size(), out.fh) != txt.size() || fwrite(cnt.data(), 1, cnt.size(), uf) != cnt.size())
+      die(kLambda, "cannot write output file!");
+    out.t_write += since(t_w0);
+  };
+  std::vector<double> gmean;
+  std::vector<uint64_t> gused, maps;
+  const auto t_c0 = std::chrono::steady_clock::now();
+  if (p.win) {
+    // every window and its replicates in one call.  --win_boot_rep: every window draws the maps of its own cut-down run; a
+    // window shorter than one block has replicates of 0 / 0, whose means are nan
+    const uint64_t n_win = win.size(), R = p.win_boot_rep, n_mat = R + 1;
+    gmean.resize(n_win * n_mat * n_gp);
+    gused.resize(n_win * n_mat * n_gp);
+    if (R) {
+      std::vector<uint64_t> off;
+      const uint64_t mlen = draw_window_maps(p, win, R, maps, off);
+      engine_ok("ngd_run_windows_job_var_groups",
+                ngd_run_windows_job_var_groups(eng.h, win.lo.data(), win.hi.data(), n_win, maps.data(), mlen, off.data(), (uint32_t)R,
+                                               p.boot_block_size, p.tot_sites, p.evol_model, gmean.data(), gused.data()));
+    } else {
+      engine_ok("ngd_run_windows_groups", ngd_run_windows_groups(eng.h, win.lo.data(), win.hi.data(), n_win, p.tot_sites, p.evol_model,
+                                                                 gmean.data(), gused.data()));
     }
-    if (R && wb_blocks) {
-      uint32_t wrng[3];
-      ngd_taus_seed(wrng, p.seed);
-      for (uint64_t r = 0; r < R; r++) ngd_boot_block_map(wrng, wb_blocks, &wb_maps[r * wb_blocks]);
-    }
-    // (a window shorter than one block: the reference truncates its replicates to 0 sites and prints 0 / 0, ngsDist.cpp:236)
-    std::vector<double> wb_empty;
-    if (R && !wb_blocks) {
-      const std::vector<double> zs(n_comb, 0.0);
-      const std::vector<uint64_t> zc(n_comb, 0);
-      wb_empty.resize(n_comb);
-      if (ngd_finish(zs.data(), zc.data(), n_comb, p.tot_sites, p.evol_model, wb_empty.data()))
-        die("gen_dist", "invalid evolutionary model specified!");
-    }
-    const bool job = R && (wb_blocks || p.win_bp);
-    const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (8 * (job ? n_mat : 1) * std::max<uint64_t>(1, n_comb))));
-    std::vector<double> wd;
-    for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
-      const uint64_t n = std::min(per, n_win - w0);
-      const auto t_c0 = std::chrono::steady_clock::now();
-      wd.resize(n * (job ? n_mat : 1) * n_comb);
-      if (job && p.win_bp) {
-        const int rc = ngd_run_windows_job_var_dist(eng.h, &win_lo[w0], &win_hi[w0], n, wb_maps.data(), wb_maps.size() - 1, &wb_off[w0],
-                                                    (uint32_t)R, p.boot_block_size, p.tot_sites, p.evol_model, wd.data());
-        if (rc) die_engine("ngd_run_windows_job_var_dist", rc);
-      } else if (job) {
-        const int rc = ngd_run_windows_job_dist(eng.h, &win_lo[w0], &win_hi[w0], n, wb_maps.data(), (uint32_t)R, wb_blocks,
-                                                p.boot_block_size, p.tot_sites, p.evol_model, wd.data());
-        if (rc) die_engine("ngd_run_windows_job_dist", rc);
-      } else {
-        const int rc = ngd_run_windows_dist(eng.h, &win_lo[w0], &win_hi[w0], n, p.tot_sites, p.evol_model, wd.data());
-        if (rc) die_engine("ngd_run_windows_dist", rc);
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    if (p.verbose >= 1) fprintf(stderr, "==> %lu windows, %lu matrices each\n", (unsigned long)n_win, (unsigned long)n_mat);
+    write_blocks(gmean.data(), gused.data(), n_win * n_mat);
+  } else {
+    // the full data set, then the replicates in batches (their maps drawn in the reference's order); a batch after the
+    // first goes through the same call and its leading full-data matrix is dropped
+    const uint64_t n_sites_b = p.n_sites - p.n_sites % p.boot_block_size, n_blocks = n_sites_b / p.boot_block_size;
+    for (uint64_t rep = 0; rep <= p.n_boot_rep;) {
+      const auto t_b0 = std::chrono::steady_clock::now();
+      const uint64_t n_here = std::min<uint64_t>(batch - 1, p.n_boot_rep - (rep ? rep - 1 : 0));  // replicates of this call
+      gmean.assign((n_here + 1) * n_gp, std::nan(""));
+      gused.assign((n_here + 1) * n_gp, 0);
+      if (n_here && n_blocks) draw_job_maps(rng, n_here, n_blocks, maps);
+      // (fewer sites than one block: the replicates visit no site, ngsDist.cpp:236 -- their means stay nan, used 0)
+      const uint32_t n_call = n_blocks ? (uint32_t)n_here : 0;
+      if (rep == 0 || n_call) {
+        engine_ok("ngd_run_job_groups", ngd_run_job_groups(eng.h, maps.data(), n_call, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model,
+                                                           gmean.data(), gused.data()));
+        report_fixup(eng.h, p.verbose);
       }
-      report_fixup(eng.h, p.verbose);
+      out.t_compute += since(t_b0);
+      if (p.verbose >= 1 && rep == 0) fprintf(stderr, "==> Analyzing full dataset...\n");
+      if (p.verbose >= 1 && n_here) fprintf(stderr, "==> Bootstrap replicates # %lu to %lu ...\n", rep ? rep : 1, (rep ? rep : 1) + n_here - 1);
+      const uint64_t skip = rep ? 1 : 0;
+      write_blocks(gmean.data() + skip * n_gp, gused.data() + skip * n_gp, n_here + 1 - skip);
+      rep = (rep ? rep : 1) + n_here;
+    }
+  }
+  if (fclose(uf) != 0) die(kMain, "cannot write used output file!");
+  if (p.win) win.write_file(std::string(p.out) + ".windows", p);  // (the windows' own file: as without --groups)
+}
+
+// ---- windows along the genome: one matrix per window, in window order, a group of windows per engine call (their
+// distances in ~2 GB of host memory), each window's block formatted and written like the full data set's ----
+void window_matrices(const Pars &p, Engine &eng, const WindowList &win, MatrixOut &out) {
+  const uint64_t n_comb = out.n_comb;
+  // --win_boot_rep: R replicates inside every window, its R + 1 blocks printed one after the other -- the file is the
+  // concatenation of the cut-down runs' files.  Every cut-down run seeds the generator anew and the windows have one
+  // length, so ONE set of block maps, drawn from a fresh state, serves them all (ngsDist.cpp:179-180, :235-238, :416-437)
+  const uint64_t R = p.win_boot_rep, n_mat = R + 1;
+  const uint64_t wb_blocks = R && !p.win_bp ? p.win_size / p.boot_block_size : 0;
+  std::vector<uint64_t> wb_maps, wb_off;
+  uint64_t wb_len = 0;
+  // --win_bp: the windows differ in length, every one draws the maps of its own cut-down run; a window shorter than one
+  // block comes back as sum 0 and count 0, printed as 0 / 0 by the call itself
+  if (R && p.win_bp) wb_len = draw_window_maps(p, win, R, wb_maps, wb_off);
+  if (R && wb_blocks) {
+    uint32_t wrng[3];
+    ngd_taus_seed(wrng, p.seed);
+    draw_job_maps(wrng, R, wb_blocks, wb_maps);
+  }
+  // (a window shorter than one block: the reference truncates its replicates to 0 sites and prints 0 / 0, ngsDist.cpp:236)
+  std::vector<double> wb_empty;
+  if (R && !wb_blocks) {
+    const std::vector<double> zs(n_comb, 0.0);
+    const std::vector<uint64_t> zc(n_comb, 0);
+    wb_empty.resize(n_comb);
+    if (ngd_finish(zs.data(), zc.data(), n_comb, p.tot_sites, p.evol_model, wb_empty.data()))
+      die("gen_dist", "invalid evolutionary model specified!");
+  }
+  const bool job = R && (wb_blocks || p.win_bp);
+  const uint64_t n_each = job ? n_mat : 1;  // matrices the engine returns per window
+  std::vector<double> wd;
+  for_window_groups(p, eng, out, win.size(), 8 * n_each * std::max<uint64_t>(1, n_comb), true,
+    [&](uint64_t w0, uint64_t n) {
+      wd.resize(n * n_each * n_comb);
+      const uint64_t *lo = &win.lo[w0], *hi = &win.hi[w0];
+      if (job && p.win_bp)
+        engine_ok("ngd_run_windows_job_var_dist",
+                  ngd_run_windows_job_var_dist(eng.h, lo, hi, n, wb_maps.data(), wb_len, &wb_off[w0], (uint32_t)R, p.boot_block_size,
+                                               p.tot_sites, p.evol_model, wd.data()));
+      else if (job)
+        engine_ok("ngd_run_windows_job_dist", ngd_run_windows_job_dist(eng.h, lo, hi, n, wb_maps.data(), (uint32_t)R, wb_blocks,
+                                                                       p.boot_block_size, p.tot_sites, p.evol_model, wd.data()));
+      else
+        engine_ok("ngd_run_windows_dist", ngd_run_windows_dist(eng.h, lo, hi, n, p.tot_sites, p.evol_model, wd.data()));
+    },
+    [&](uint64_t w0, uint64_t n) {
       ngd_windows_info wi;
       if (p.verbose >= 2 && ngd_last_windows && ngd_last_windows(eng.h, &wi) == NGD_OK)  // the plan the engine took
         fprintf(stderr, "> windows %lu to %lu: %lu segments in %lu batches of one pass each, %lu windows by a pass of their own (%.2f ms)\n",
                 (unsigned long)w0, (unsigned long)(w0 + n - 1), (unsigned long)wi.segments, (unsigned long)wi.batches,
                 (unsigned long)wi.windows_by_pass, wi.ms);
-      t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
       for (uint64_t k = 0; k < n; k++) {
-        const std::string name = std::to_string(w0 + k) + " [" + std::to_string(win_lo[w0 + k]) + ", " + std::to_string(win_hi[w0 + k]) + ")";
-        emit(w0 + k, nullptr, nullptr, nullptr, 0, &wd[k * (job ? n_mat : 1) * n_comb], 0, name.c_str());
+        const std::string name = win.name(w0 + k);
+        out.emit(w0 + k, nullptr, nullptr, nullptr, 0, &wd[k * n_each * n_comb], 0, name.c_str());
         for (uint64_t r = 1; r <= R; r++) {
           const std::string rname = name + ", bootstrap replicate # " + std::to_string(r);
-          emit(w0 + k, nullptr, nullptr, nullptr, 0, job ? &wd[(k * n_mat + r) * n_comb] : wb_empty.data(), 0, rname.c_str());
+          out.emit(w0 + k, nullptr, nullptr, nullptr, 0, job ? &wd[(k * n_mat + r) * n_comb] : wb_empty.data(), 0, rname.c_str());
         }
       }
-      writer.wait_idle();  // (the last block's text is written before the next group's call)
+    });
+  win.write_file(std::string(p.out) + ".windows", p);
+}
+
+// ---- the plain run: the full data set and its replicates ----
+// One batch of matrices: the full data alone (ngd_run), or the full-data matrix plus the first replicates (ngd_run_job,
+// which lets the engine share work between them), or replicates only (ngd_run_batch).  True: the batch's matrices stay
+// in the engine and come to the host one at a time, as they are printed (ngd_fetch_matrix): the host holds two n_pairs-long
+// buffers, not a batch of them ([measured] 1000 individuals, 101 matrices: the 0.8 GB of zero-filled result vectors and
+// their page faults cost 1.5 s, three times the engine's whole job).  False: they are in sum, cnt.
+bool run_batch(const Pars &p, Engine &eng, uint64_t n_comb, const uint64_t *maps, uint32_t n_rep, bool with_full, uint64_t n_blocks,
+               std::vector<double> &sum, std::vector<uint64_t> &cnt) {
+  if (!n_rep || n_blocks == 0) {
+    // the full data alone (with_full, no replicates); or fewer sites than one bootstrap block: the reference truncates the
+    // replicates to 0 sites (ngsDist.cpp:236), visits none and prints 0/0; the full data set is still a plain run
+    const uint64_t n_mat = n_rep + (with_full ? 1 : 0);
+    sum.assign(n_mat * n_comb, 0.0);
+    cnt.assign(n_mat * n_comb, 0);
+    if (with_full) {
+      engine_ok("ngd_run", ngd_run(eng.h, nullptr, 0, 0, sum.data(), cnt.data()));
+      report_fixup(eng.h, p.verbose);
     }
-    write_windows_file();
-  } else {
-  // Matrices go to the engine in batches: the first batch is the full-data matrix plus the first replicates
-  // (ngd_run_job, which lets the engine share work between them), later ones replicates only (ngd_run_batch).
-  // The block maps of a batch are drawn up front, in the order rnd_map_data (ngsDist.cpp:416-437) would draw
-  // them -- nothing else consumes the generator.
+    return false;
+  }
+  if (with_full) engine_ok("ngd_run_job", ngd_run_job(eng.h, maps, n_rep, n_blocks, p.boot_block_size, nullptr, nullptr));
+  else engine_ok("ngd_run_batch", ngd_run_batch(eng.h, maps, n_rep, n_blocks, p.boot_block_size, nullptr, nullptr));
+  report_fixup(eng.h, p.verbose);
+  return true;
+}
+
+// A batch's matrices come out of the engine one at a time -- and matrix r + 1 is fetched and finished (ngd_fetch_matrix,
+// ngd_finish) by a thread of its own while matrix r is formatted and handed to the writer: two sets of buffers
+struct Pre {
+  std::vector<double> sum, dist;
+  std::vector<uint64_t> cnt;
+  int rc_fetch = 0, rc_finish = 0;
+  std::string err;
+  std::thread th;
+};
+// prints the n_in_batch matrices the engine holds, the run's matrices rep, rep + 1, ...; bm_of(r): matrix r's block map
+template <typename MapOf>
+void emit_fetched(const Pars &p, Engine &eng, MatrixOut &out, uint64_t rep, uint64_t n_in_batch, uint64_t n_blocks, MapOf bm_of) {
+  const uint64_t n_comb = out.n_comb;
+  Pre pre[2];
+  auto start = [&](uint64_t r) {
+    Pre &q = pre[r & 1];
+    q.sum.resize(n_comb); q.dist.resize(n_comb); q.cnt.resize(n_comb);
+    q.th = std::thread([&q, r, &eng, &p, n_comb]() {
+      q.rc_fetch = ngd_fetch_matrix(eng.h, (uint32_t)r, q.sum.data(), q.cnt.data());
+      if (q.rc_fetch) { q.err = ngd_last_error(); return; }  // (the message is the fetching thread's)
+      q.rc_finish = ngd_finish(q.sum.data(), q.cnt.data(), n_comb, p.tot_sites, p.evol_model, q.dist.data());
+    });
+  };
+  start(0);
+  for (uint64_t r = 0; r < n_in_batch; r++) {
+    Pre &q = pre[r & 1];
+    const auto t_g0 = std::chrono::steady_clock::now();
+    q.th.join();
+    out.t_compute += since(t_g0);
+    if (q.rc_fetch) die("ngd_fetch_matrix", (std::string("engine error ") + std::to_string(q.rc_fetch) + ": " + q.err).c_str());
+    if (r + 1 < n_in_batch) start(r + 1);
+    out.emit(rep + r, q.sum.data(), q.cnt.data(), bm_of(r), n_blocks, q.dist.data(), q.rc_finish);
+  }
+}
+
+// Matrices go to the engine in batches: the first batch is the full-data matrix plus the first replicates, later ones
+// replicates only (run_batch).  The block maps of a batch are drawn up front, in the order rnd_map_data
+// (ngsDist.cpp:416-437) would draw them -- nothing else consumes the generator.
+void plain_matrices(const Pars &p, Engine &eng, uint32_t rng[3], uint64_t batch, MatrixOut &out) {
+  const uint64_t n_comb = out.n_comb;
   std::vector<double> sum;
   std::vector<uint64_t> cnt, block_maps;
   uint64_t n_sites = p.n_sites;
-
-  // A batch's matrices stay in the engine and come to the host one at a time, as they are printed (ngd_fetch_matrix):
-  // the host holds two n_pairs-long buffers, not a batch of them ([measured] 1000 individuals, 101 matrices: the 0.8 GB
-  // of zero-filled result vectors and their page faults cost 1.5 s, three times the engine's whole job).
-  bool in_engine = false;  // this batch's matrices are fetched from the engine
-  auto run_all = [&](const uint64_t *maps, uint32_t n_rep, bool with_full, uint64_t n_blocks) {
-    in_engine = false;
-    if (n_rep && n_blocks == 0) {
-      // fewer sites than one bootstrap block: the reference truncates the replicates to 0 sites (ngsDist.cpp:236),
-      // visits none and prints 0/0; the full data set is still a plain run
-      const uint64_t n_mat = n_rep + (with_full ? 1 : 0);
-      sum.assign(n_mat * n_comb, 0.0);
-      cnt.assign(n_mat * n_comb, 0);
-      if (with_full) {
-        int rc = ngd_run(eng.h, nullptr, 0, 0, sum.data(), cnt.data());
-        if (rc) die_engine("ngd_run", rc);
-        report_fixup(eng.h, p.verbose);
-      }
-      return;
-    }
-    sum.resize(n_comb);
-    cnt.resize(n_comb);
-    if (!n_rep) {  // the full data alone
-      int rc = ngd_run(eng.h, nullptr, 0, 0, sum.data(), cnt.data());
-      if (rc) die_engine("ngd_run", rc);
-      report_fixup(eng.h, p.verbose);
-      return;
-    }
-    int rc = with_full ? ngd_run_job(eng.h, maps, n_rep, n_blocks, p.boot_block_size, nullptr, nullptr)
-                       : ngd_run_batch(eng.h, maps, n_rep, n_blocks, p.boot_block_size, nullptr, nullptr);
-    if (rc) die_engine(with_full ? "ngd_run_job" : "ngd_run_batch", rc);
-    report_fixup(eng.h, p.verbose);
-    in_engine = true;
-  };
-
   for (uint64_t rep = 0; rep <= p.n_boot_rep;) {
     const auto t_c0 = std::chrono::steady_clock::now();
     const bool with_full = rep == 0;
-    const uint64_t n_in_batch = std::min<uint64_t>(kBatch, p.n_boot_rep - rep + 1);  // matrices of this batch
+    const uint64_t n_in_batch = std::min<uint64_t>(batch, p.n_boot_rep - rep + 1);  // matrices of this batch
     const uint64_t n_boot_here = n_in_batch - (with_full ? 1 : 0);
     uint64_t n_blocks = 0;
     if (n_boot_here) {  // ngsDist.cpp:235-238
       n_sites -= n_sites % p.boot_block_size;
       n_blocks = n_sites / p.boot_block_size;
-      block_maps.resize(n_boot_here * n_blocks);
-      for (uint64_t r = 0; r < n_boot_here; r++) ngd_boot_block_map(rng, n_blocks, &block_maps[r * n_blocks]);
+      draw_job_maps(rng, n_boot_here, n_blocks, block_maps);
     }
-    run_all(block_maps.data(), (uint32_t)n_boot_here, with_full, n_blocks);
-    t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-    if (in_engine) {
-      // a batch's matrices come out of the engine one at a time -- and matrix r + 1 is fetched and finished (ngd_fetch_matrix,
-      // ngd_finish) by a thread of its own while matrix r is formatted and handed to the writer: two sets of buffers
-      struct Pre {
-        std::vector<double> sum, dist;
-        std::vector<uint64_t> cnt;
-        int rc_fetch = 0, rc_finish = 0;
-        std::string err;
-        std::thread th;
-      } pre[2];
-      auto start = [&](uint64_t r) {
-        Pre &q = pre[r & 1];
-        q.sum.resize(n_comb); q.dist.resize(n_comb); q.cnt.resize(n_comb);
-        q.th = std::thread([&q, r, &eng, &p, n_comb]() {
-          q.rc_fetch = ngd_fetch_matrix(eng.h, (uint32_t)r, q.sum.data(), q.cnt.data());
-          if (q.rc_fetch) { q.err = ngd_last_error(); return; }  // (the message is the fetching thread's)
-          q.rc_finish = ngd_finish(q.sum.data(), q.cnt.data(), n_comb, p.tot_sites, p.evol_model, q.dist.data());
-        });
-      };
-      start(0);
-      for (uint64_t r = 0; r < n_in_batch; r++, rep++) {
-        Pre &q = pre[r & 1];
-        const auto t_g0 = std::chrono::steady_clock::now();
-        q.th.join();
-        t_compute += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_g0).count();
-        if (q.rc_fetch) die("ngd_fetch_matrix", (std::string("engine error ") + std::to_string(q.rc_fetch) + ": " + q.err).c_str());
-        if (r + 1 < n_in_batch) start(r + 1);
-        emit(rep, q.sum.data(), q.cnt.data(), rep > 0 ? &block_maps[(r - (with_full ? 1 : 0)) * n_blocks] : nullptr, n_blocks,
-             q.dist.data(), q.rc_finish);
-      }
-    } else {
-      for (uint64_t r = 0; r < n_in_batch; r++, rep++)
-        emit(rep, &sum[r * n_comb], &cnt[r * n_comb], rep > 0 ? &block_maps[(r - (with_full ? 1 : 0)) * n_blocks] : nullptr, n_blocks);
+    const bool in_engine = run_batch(p, eng, n_comb, block_maps.data(), (uint32_t)n_boot_here, with_full, n_blocks, sum, cnt);
+    out.t_compute += since(t_c0);
+    auto bm_of = [&](uint64_t r) { return rep + r > 0 ? &block_maps[(r - (with_full ? 1 : 0)) * n_blocks] : nullptr; };
+    if (in_engine) emit_fetched(p, eng, out, rep, n_in_batch, n_blocks, bm_of);
+    else for (uint64_t r = 0; r < n_in_batch; r++) out.emit(rep + r, &sum[r * n_comb], &cnt[r * n_comb], bm_of(r), n_blocks);
+    rep += n_in_batch;
+  }
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  Pars p;
+  parse_cmd_args(p, argc, argv);
+  const uint64_t n_comb = ngd_n_pairs(p.n_ind);
+  if (p.verbose >= 1) fprintf(stderr, "==> Analysis will be run in %lu combinations\n", n_comb);
+  input_decisions(p);
+
+  const std::vector<std::string> labels = read_labels(p);
+  // --groups: the group of every individual, in input order
+  std::vector<int32_t> group_of;
+  std::vector<std::string> group_names;
+  if (p.in_groups) {
+    if (p.verbose >= 1) fprintf(stderr, "==> Reading groups\n");
+    read_groups(p.in_groups, group_of, group_names);
+    if (group_of.size() != p.n_ind || group_names.empty()) die(__FUNCTION__, "invalid GROUPS file!");
+    if (!ngd_set_groups || !ngd_run_job_groups || !ngd_run_windows_groups || !ngd_run_windows_job_var_groups)
+      die(__FUNCTION__, "this build of the engine has no group means (--groups)!");
+    if (p.verbose >= 1) fprintf(stderr, "==> %lu groups\n", (unsigned long)group_names.size());
+  }
+  check_summaries_and_trees(p);
+  WindowList win;
+  if (p.in_pos) read_positions(p, win);
+  if (p.win) make_windows(p, win);
+  g_phases.mark("args_labels");
+
+  // devices: --n_gpus of them, the site axis split over them
+  const int n_dev = ngd_device_count();
+  if (n_dev < 1) die(__FUNCTION__, "no HIP device found (this program has no CPU path)");
+  if (p.device + (p.same_device ? 1 : p.n_gpus) > n_dev) die(__FUNCTION__, "not enough HIP devices for --device/--n_gpus");
+  uint64_t dev_free = 0, dev_total = 0;
+  if (ngd_device_memory(p.device, &dev_free, &dev_total)) die_engine("ngd_device_memory", -1);
+  g_phases.mark("first_hip_calls");
+  const DeviceFit fit = device_fit(p, n_comb, dev_free);
+  const struct { bool on; const char *what; } one_gpu[] = {{p.win, "windows (--win_size)"},
+                                                           {p.boot_stats, "bootstrap summaries (--boot_stats)"},
+                                                           {p.nj, "neighbour-joining trees (--nj)"},
+                                                           {p.in_groups != nullptr, "group means (--groups)"}};
+  for (auto &m : one_gpu)
+    if (m.on && fit.in_parts)
+      die(__FUNCTION__, (std::string(m.what) + " need the whole data set on one GPU; it does not fit the device budget!").c_str());
+
+  if (p.verbose >= 2) fprintf(stderr, "==> Setting seed for random number generator\n");
+  uint32_t rng[3];
+  ngd_taus_seed(rng, p.seed);  // gsl_rng_alloc(gsl_rng_taus) + gsl_rng_set, ngsDist.cpp:179-180
+
+  FILE *out_fh = fopen(p.out, "w");
+  if (!out_fh) die(__FUNCTION__, "cannot open output file!");
+  MatrixOut out(p, labels, n_comb, out_fh);
+  // Matrices per engine call.  --indep_geno: 32 (the engine forms 32 replicates per pass over the per-block partials).
+  // EM path: the per-site EM does not depend on the replicate and ONE pass of it serves every matrix of a call (the
+  // engine spills the per-(pair, site) terms and contracts them with all the weight vectors: contract_mfma.hip), so the
+  // whole job goes in one call where its results (16 B per cell) and block maps fit a few GB of host memory.
+  uint64_t batch = 32;
+  if (!p.indep_geno && p.n_boot_rep + 1 > batch) {
+    const uint64_t by_results = (4ull << 30) / std::max<uint64_t>(1, n_comb * 16);
+    const uint64_t blocks = p.boot_block_size ? p.n_sites / p.boot_block_size : 0;
+    const uint64_t by_maps = blocks ? (2ull << 30) / (blocks * 8) : ~0ull;
+    batch = std::max<uint64_t>(batch, std::min({by_results, by_maps, (uint64_t)p.n_boot_rep + 1}));
+  }
+  fflush(stdout);
+
+  // exactly one mode writes the run's matrices
+  if (fit.in_parts) {
+    site_range_matrices(p, fit, rng, batch, out);
+  } else {
+    Engine eng;  // (the scope of the run's one engine: gone, or left to the exit, before the "destroy" mark)
+    make_engine(p, eng, p.n_sites, 0, false);
+    g_phases.mark("create");
+    if (p.verbose >= 1) fprintf(stderr, "==> Reading genotype data\n");
+    const auto t_load0 = std::chrono::steady_clock::now();
+    {
+      Loader L(p);
+      L.load(eng, p.n_sites, true);
+      L.finish();
     }
-  }
-  }
-  g_phases.mark("matrices");
-  eng.leave_to_exit = true;
+    const double t_load = since(t_load0);
+    g_phases.mark("load");
+    if (p.verbose >= 2)
+      fprintf(stderr, "> read + prepare + upload: %.3f s (%.2f GB of prepared input resident on the device)\n", t_load,
+              (double)p.n_ind * p.n_sites * 24 / 1e9);
+    if (p.nj) trees(p, eng, win, rng, out);
+    else if (p.boot_stats) bootstrap_summaries(p, eng, win, group_of, group_names, rng, out);
+    else if (p.in_groups) group_means(p, eng, win, group_of, group_names, rng, batch, out);
+    else if (p.win) window_matrices(p, eng, win, out);
+    else plain_matrices(p, eng, rng, batch, out);
+    g_phases.mark("matrices");
+    eng.leave_to_exit = true;
   }
   g_phases.mark("destroy");
-  if (!writer.finish()) die(__FUNCTION__, "cannot write output file!");
+  if (!out.writer.finish()) die(__FUNCTION__, "cannot write output file!");
   g_phases.mark("write_tail");
   fclose(out_fh);
-  if (p.verbose >= 2)
-    fprintf(stderr, "> distances: %.3f s for %lu matri%s of %lu pairs; formatting + writing them: %.3f s\n", t_compute,
-            p.n_boot_rep + 1, p.n_boot_rep ? "ces" : "x", n_comb, t_write);
   if (p.verbose >= 2) {
-    g_phases.add("of_matrices_distances", t_compute);
-    g_phases.add("of_matrices_format_write", t_write);
+    fprintf(stderr, "> distances: %.3f s for %lu matri%s of %lu pairs; formatting + writing them: %.3f s\n", out.t_compute,
+            p.n_boot_rep + 1, p.n_boot_rep ? "ces" : "x", n_comb, out.t_write);
+    g_phases.add("of_matrices_distances", out.t_compute);
+    g_phases.add("of_matrices_format_write", out.t_write);
     g_phases.print();
   }
   if ((p.em_exact || p.em_exact_boot || p.em_exact_win) && p.verbose >= 1)
