@@ -1,10 +1,15 @@
 // engine_boot_stats.hip -- bootstrap summaries per cell: the reduction over the replicates of a set (boot_stats.hip) of device
-// matrices, and the run forms that end a job's tail on the device -- the sibling *_device call into the engine's batch
-// buffers, then that reduction (after the group reduction, in the _groups forms); 5 doubles and a count per cell cross the
-// link instead of n_rep + 1 sums and counts.
+// matrices, and that reduction as a tail (ngd_engine.h) behind the job driver and the window driver (after the group
+// reduction, in the _groups forms): the run forms, where 5 doubles and a count per cell cross the link instead of n_rep + 1
+// sums and counts.
 #include "ngd_engine.h"
 
 uint32_t ngd_boot_stats_max_rep(void) { return NGD_BOOT_MAX_MAT - 1; }
+
+// the two ranks' fractions of the interval
+struct BootCi {
+  double p_lo, p_hi;
+};
 
 // what every call that summarises refuses, before anything is launched; the interval's two ranks' fractions on the way
 static int boot_refuse(const ngd_engine *e, const void *stats, const void *used, uint64_t n_mat, double ci, uint64_t tot_sites,
@@ -18,11 +23,7 @@ static int boot_refuse(const ngd_engine *e, const void *stats, const void *used,
     return fail(NGD_E_INVALID, w + ": more than " + std::to_string(ngd_boot_stats_max_rep()) +
                                    " replicates (a cell's values stay in on-chip memory: ngd_boot_stats_max_rep)");
   if (groups && !e->grp.n_groups) return fail(NGD_E_INVALID, w + ": no grouping set (ngd_set_groups)");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, w + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, w + ": evolutionary model not supported (ngsDist.cpp:398-399)");
-  if (e->cfg.shard_world > 1)
-    return fail(NGD_E_INVALID, w + ": an engine that owns a share of the pairs holds part of every matrix: no summaries");
+  if (int rc = finish_refuse(e, tot_sites, evol_model, w, "no summaries")) return rc;
   out.p_lo = (1.0 - ci) / 2.0;
   out.p_hi = 1.0 - out.p_lo;
   return NGD_OK;
@@ -31,7 +32,9 @@ static int boot_refuse(const ngd_engine *e, const void *stats, const void *used,
 // The sets in chunks whose results stay small (~256 MB) and whose launches fit grid.x; a set's bits do not depend on the
 // chunk it falls into.  Events 0 and 1 time each chunk's kernel (bst.ms: the entry points start it at 0, a windowed call
 // adds up its groups of windows).
-int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
+// [n_set][n_mat][n_cells] device matrices -> stats / used in host memory; d_cnt and the two arguments of ngd_finish for sums
+// and counts, `values` for cells as they are (the arguments are checked)
+static int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
                 uint64_t n_cells, uint64_t tot_sites, uint64_t evol_model, BootCi ci, double *stats, uint64_t *used) {
   auto &b = e->bst;
   if (!n_cells) return NGD_OK;
@@ -80,20 +83,26 @@ int ngd_boot_stats_values_device(ngd_engine *e, const void *d_val, uint64_t n_se
   return boot_reduce(e, (const double *)d_val, nullptr, true, n_set, n_mat, n_cells, 0, 0, c, stats, used);
 }
 
-// ngd_run_job_device into the batch buffers, where the matrices stay (ngd_fetch_matrix), then the set's summaries
+// the tail of the run forms: every set's summaries into stats / used [.][5][n_cells] / [.][n_cells] -- of its cells, or
+// (groups) of its group means: the group reduction first, its means kept on the device, n_cells = n_gp
+static Tail stats_tail(ngd_engine *e, bool groups, uint64_t tot_sites, uint64_t evol_model, BootCi ci, double *stats, uint64_t *used) {
+  return [=](uint64_t set0, uint64_t n_set, uint64_t n_mat) {
+    const uint64_t n_cells = groups ? e->grp.n_gp : ngd_n_pairs(e->g.n_ind);
+    double *s = stats + set0 * NGD_BOOT_NSTAT * n_cells;
+    uint64_t *u = used + set0 * n_cells;
+    if (!groups) return boot_reduce(e, e->d_bsum, e->d_bcnt, false, n_set, n_mat, n_cells, tot_sites, evol_model, ci, s, u);
+    if (int rc = groups_reduce(e, e->d_bsum, e->d_bcnt, n_set * n_mat, tot_sites, evol_model, nullptr, nullptr)) return rc;
+    return boot_reduce(e, e->grp.d_keep_mean, nullptr, true, n_set, n_mat, n_cells, 0, 0, ci, s, u);
+  };
+}
+
 static int job_stats(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                      uint64_t tot_sites, uint64_t evol_model, double ci, bool groups, double *stats, uint64_t *used, const char *who) {
   BootCi c{};
   if (int rc = boot_refuse(e, stats, used, (uint64_t)n_rep + 1, ci, tot_sites, evol_model, groups, who, c)) return rc;
   if (!block_maps) return fail(NGD_E_INVALID, std::string(who) + ": null argument");
-  e->bst.ms = e->grp.ms = 0;
-  const uint64_t n_mat = (uint64_t)n_rep + 1;
-  if (int rc = batch_buffers(e, n_rep + 1)) return rc;
-  if (int rc = run_impl(e, block_maps, nullptr, n_rep, true, n_blocks, block_size, e->d_bsum, e->d_bcnt)) return rc;
-  e->n_batch_valid = n_rep + 1;
-  if (!groups) return boot_reduce(e, e->d_bsum, e->d_bcnt, false, 1, n_mat, ngd_n_pairs(e->g.n_ind), tot_sites, evol_model, c, stats, used);
-  if (int rc = groups_reduce_keep(e, e->d_bsum, e->d_bcnt, n_mat, tot_sites, evol_model)) return rc;
-  return boot_reduce(e, e->grp.d_keep_mean, nullptr, true, 1, n_mat, e->grp.n_gp, 0, 0, c, stats, used);
+  e->bst.ms = e->grp.ms = 0;  // (both, in either job form)
+  return job_tail(e, block_maps, n_rep, n_blocks, block_size, stats_tail(e, groups, tot_sites, evol_model, c, stats, used));
 }
 
 int ngd_run_job_stats(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
@@ -106,29 +115,30 @@ int ngd_run_job_groups_stats(ngd_engine *e, const uint64_t *block_maps, uint32_t
   return job_stats(e, block_maps, n_rep, n_blocks, block_size, tot_sites, evol_model, ci, true, stats, used, "ngd_run_job_groups_stats");
 }
 
+// the windowed forms (n_rep == 0 has been refused: always a job's check)
+static int windows_stats(ngd_engine *e, const WinJobArgs &a, uint64_t tot_sites, uint64_t evol_model, double ci, bool groups,
+                         double *stats, uint64_t *used, const char *who) {
+  BootCi c{};
+  if (int rc = boot_refuse(e, stats, used, (uint64_t)a.n_rep + 1, ci, tot_sites, evol_model, groups, who, c)) return rc;
+  e->bst.ms = 0;
+  if (groups) e->grp.ms = 0;
+  return windows_tail(e, a, true, who, stats_tail(e, groups, tot_sites, evol_model, c, stats, used));
+}
+
 int ngd_run_windows_job_var_stats(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                                   const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
                                   uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double ci, double *stats,
                                   uint64_t *used) {
-  BootCi c{};
-  if (int rc = boot_refuse(e, stats, used, (uint64_t)n_rep + 1, ci, tot_sites, evol_model, false, "ngd_run_windows_job_var_stats", c))
-    return rc;
-  e->bst.ms = 0;
-  return windows_host_stats(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size, tot_sites, evol_model, c, false,
-                            stats, used, "ngd_run_windows_job_var_stats");
+  return windows_stats(e, WinJobArgs{win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size}, tot_sites, evol_model,
+                       ci, false, stats, used, "ngd_run_windows_job_var_stats");
 }
 
 int ngd_run_windows_job_var_groups_stats(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                                          const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
                                          uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double ci, double *stats,
                                          uint64_t *used) {
-  BootCi c{};
-  if (int rc = boot_refuse(e, stats, used, (uint64_t)n_rep + 1, ci, tot_sites, evol_model, true,
-                           "ngd_run_windows_job_var_groups_stats", c))
-    return rc;
-  e->bst.ms = e->grp.ms = 0;
-  return windows_host_stats(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size, tot_sites, evol_model, c, true,
-                            stats, used, "ngd_run_windows_job_var_groups_stats");
+  return windows_stats(e, WinJobArgs{win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size}, tot_sites, evol_model,
+                       ci, true, stats, used, "ngd_run_windows_job_var_groups_stats");
 }
 
 int ngd_last_boot_stats_ms(const ngd_engine *e, double *ms) {

@@ -1,6 +1,6 @@
 // engine_groups.hip -- group-mean distance matrices: the engine's grouping (ngd_set_groups), the reduction of device matrices
-// to per-group-pair means (group_reduce.hip) and the run forms that end a call's tail on the device -- the sibling
-// *_device call into the engine's batch buffers, then that reduction; n_gp means and counts per matrix cross the link.
+// to per-group-pair means (group_reduce.hip), and that reduction as a tail (ngd_engine.h) behind the job driver and the
+// window driver: the run forms, where n_gp means and counts per matrix cross the link instead of n_pairs sums and counts.
 #include "ngd_engine.h"
 
 // what every call that reduces refuses, before anything is launched
@@ -9,12 +9,7 @@ static int groups_refuse(const ngd_engine *e, const void *mean, uint64_t tot_sit
   if (!e) return fail(NGD_E_INVALID, w + ": null engine");
   if (!mean) return fail(NGD_E_INVALID, w + ": null output");
   if (!e->grp.n_groups) return fail(NGD_E_INVALID, w + ": no grouping set (ngd_set_groups)");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, w + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, w + ": evolutionary model not supported (ngsDist.cpp:398-399)");
-  if (e->cfg.shard_world > 1)
-    return fail(NGD_E_INVALID, w + ": an engine that owns a share of the pairs holds part of every matrix: no group means");
-  return NGD_OK;
+  return finish_refuse(e, tot_sites, evol_model, w, "no group means");
 }
 
 static void groups_clear(ngd_engine *e) {
@@ -88,10 +83,12 @@ int ngd_set_groups(ngd_engine *e, const int32_t *group_of, uint32_t n_groups) {
 // The matrices in chunks whose partial results and outputs stay small (2^22 entries each) and whose launches fit grid.x; a
 // matrix's bits do not depend on the chunk it falls into.  Events 0 and 1 time each chunk's kernels (grp.ms: the entry
 // points start it at 0, a windowed call adds up its groups of windows).
-// keep: the chunks' results go one after the other into grp.d_keep_mean / d_keep_used and stay there, nothing is copied.
-static int groups_reduce_impl(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
-                              uint64_t evol_model, double *mean, uint64_t *used, bool keep) {
+// mean == NULL: the chunks' results go one after the other into grp.d_keep_mean / d_keep_used and stay there, nothing is
+// copied (the summaries of the means read them: engine_boot_stats.hip).
+int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
+                  uint64_t evol_model, double *mean, uint64_t *used) {
   auto &g = e->grp;
+  const bool keep = !mean;
   const uint64_t per_mat = std::max<uint64_t>(std::max<uint64_t>(1, g.n_work), g.n_gp);
   const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n_mat, (1ull << 22) / per_mat));
   int rc = g.d_part_sum.ensure(e, chunk * std::max<uint64_t>(1, g.n_work));
@@ -121,16 +118,6 @@ static int groups_reduce_impl(ngd_engine *e, const double *d_sum, const unsigned
   return NGD_OK;
 }
 
-int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
-                  uint64_t evol_model, double *mean, uint64_t *used) {
-  return groups_reduce_impl(e, d_sum, d_cnt, n_mat, tot_sites, evol_model, mean, used, false);
-}
-
-int groups_reduce_keep(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
-                       uint64_t evol_model) {
-  return groups_reduce_impl(e, d_sum, d_cnt, n_mat, tot_sites, evol_model, nullptr, nullptr, true);
-}
-
 int ngd_group_means_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_mat, uint64_t tot_sites,
                            uint64_t evol_model, double *mean, uint64_t *used) {
   if (int rc = groups_refuse(e, mean, tot_sites, evol_model, "ngd_group_means_device")) return rc;
@@ -140,33 +127,41 @@ int ngd_group_means_device(ngd_engine *e, const void *d_sum, const void *d_cnt, 
   return groups_reduce(e, (const double *)d_sum, (const unsigned long long *)d_cnt, n_mat, tot_sites, evol_model, mean, used);
 }
 
+// the tail of the run forms: n_gp means and counts per matrix cross the link, set after set into mean / used [.][n_mat][n_gp]
+static Tail groups_tail(ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, double *mean, uint64_t *used) {
+  return [=](uint64_t set0, uint64_t n_set, uint64_t n_mat) {
+    const uint64_t at = set0 * n_mat * e->grp.n_gp;
+    return groups_reduce(e, e->d_bsum, e->d_bcnt, n_set * n_mat, tot_sites, evol_model, mean + at, used ? used + at : nullptr);
+  };
+}
+
 int ngd_run_job_groups(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                        uint64_t tot_sites, uint64_t evol_model, double *mean, uint64_t *used) {
   if (int rc = groups_refuse(e, mean, tot_sites, evol_model, "ngd_run_job_groups")) return rc;
   if (n_rep && !block_maps) return fail(NGD_E_INVALID, "ngd_run_job_groups: null argument");
   e->grp.ms = 0;
-  // (ngd_run_job_device into the batch buffers, where the matrices stay: ngd_fetch_matrix)
-  if (int rc = batch_buffers(e, n_rep + 1)) return rc;
-  if (int rc = run_impl(e, block_maps, nullptr, n_rep, n_rep != 0, n_blocks, block_size, e->d_bsum, e->d_bcnt)) return rc;
-  e->n_batch_valid = n_rep + 1;
-  return groups_reduce(e, e->d_bsum, e->d_bcnt, (uint64_t)n_rep + 1, tot_sites, evol_model, mean, used);
+  return job_tail(e, block_maps, n_rep, n_blocks, block_size, groups_tail(e, tot_sites, evol_model, mean, used));
+}
+
+// the windowed forms: `a` as ngd_run_windows_job_var's, or the windows alone (n_rep 0)
+static int windows_groups(ngd_engine *e, const WinJobArgs &a, uint64_t tot_sites, uint64_t evol_model, double *mean, uint64_t *used,
+                          const char *who) {
+  if (int rc = groups_refuse(e, mean, tot_sites, evol_model, who)) return rc;
+  e->grp.ms = 0;
+  return windows_tail(e, a, false, who, groups_tail(e, tot_sites, evol_model, mean, used));
 }
 
 int ngd_run_windows_groups(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
                            uint64_t evol_model, double *mean, uint64_t *used) {
-  if (int rc = groups_refuse(e, mean, tot_sites, evol_model, "ngd_run_windows_groups")) return rc;
-  e->grp.ms = 0;
-  return windows_host_groups(e, win_lo, win_hi, n_win, nullptr, 0, nullptr, 0, 0, tot_sites, evol_model, mean, used,
-                             "ngd_run_windows_groups");
+  return windows_groups(e, WinJobArgs{win_lo, win_hi, n_win, nullptr, 0, nullptr, 0, 0}, tot_sites, evol_model, mean, used,
+                        "ngd_run_windows_groups");
 }
 
 int ngd_run_windows_job_var_groups(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                                    const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
                                    uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *mean, uint64_t *used) {
-  if (int rc = groups_refuse(e, mean, tot_sites, evol_model, "ngd_run_windows_job_var_groups")) return rc;
-  e->grp.ms = 0;
-  return windows_host_groups(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size, tot_sites, evol_model, mean,
-                             used, "ngd_run_windows_job_var_groups");
+  return windows_groups(e, WinJobArgs{win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size}, tot_sites, evol_model,
+                        mean, used, "ngd_run_windows_job_var_groups");
 }
 
 int ngd_last_groups_ms(const ngd_engine *e, double *ms) {

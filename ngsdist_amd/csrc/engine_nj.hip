@@ -1,6 +1,6 @@
-// engine_nj.hip -- neighbour-joining trees: the tree of every device matrix (nj.hip, one workgroup per matrix), and the run
-// forms that end a job's tail on the device -- the sibling *_device call into the engine's batch buffers, then that
-// reduction; 2 n - 3 branches per matrix cross the link instead of n (n - 1) / 2 sums and counts.
+// engine_nj.hip -- neighbour-joining trees: the tree of every device matrix (nj.hip, one workgroup per matrix), and that
+// reduction as a tail (ngd_engine.h) behind the job driver and the window driver: the run forms, where 2 n - 3 branches per
+// matrix cross the link instead of n (n - 1) / 2 sums and counts.
 #include "ngd_engine.h"
 
 #include <cstdlib>
@@ -26,18 +26,15 @@ static int nj_refuse(const ngd_engine *e, const void *child, const void *len, co
   if (e->g.n_ind > ngd_nj_max_ind())
     return fail(NGD_E_INVALID, w + ": more than " + std::to_string(ngd_nj_max_ind()) +
                                    " individuals (a matrix's row sums stay in on-chip memory: ngd_nj_max_ind)");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, w + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, w + ": evolutionary model not supported (ngsDist.cpp:398-399)");
-  if (e->cfg.shard_world > 1)
-    return fail(NGD_E_INVALID, w + ": an engine that owns a share of the pairs holds part of every matrix: no trees");
-  return NGD_OK;
+  return finish_refuse(e, tot_sites, evol_model, w, "no trees");
 }
 
 // The matrices in chunks whose working copies (n rows of n doubles each, rows padded to an even length) fit
 // NGD_OPT_NJ_MAX_BYTES, one matrix at least; a tree's bits do not depend on the chunk it falls into.  Events 0 and 1 time
 // each chunk's kernel (nj.ms: the entry points start it at 0, a windowed call adds up its groups of windows).
-int nj_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_mat, uint64_t tot_sites,
+// [n_mat][n_pairs] device matrices -> child / len / status in host memory; d_cnt and the two arguments of ngd_finish for sums
+// and counts, `values` for cells as they are (the arguments are checked)
+static int nj_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_mat, uint64_t tot_sites,
               uint64_t evol_model, int32_t *child, double *len, uint32_t *status) {
   auto &j = e->nj;
   const uint64_t n = e->g.n_ind, n_pairs = ngd_n_pairs(n), nb = NGD_NJ_NBRANCH(n);
@@ -73,7 +70,7 @@ int nj_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt,
 }
 
 // matrix 0 of every set: its sums and counts copied out, the tail of gen_dist() on the host (ngd_finish's bits)
-int nj_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
+static int nj_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
              uint64_t evol_model, double *dist0) {
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
   std::vector<double> h_sum(n_set * n_pairs);
@@ -110,36 +107,47 @@ int ngd_nj_values_device(ngd_engine *e, const void *d_val, uint64_t n_mat, int32
   return nj_reduce(e, (const double *)d_val, nullptr, true, n_mat, 0, 0, child, len, status);
 }
 
-// ngd_run_job_device into the batch buffers, where the matrices stay (ngd_fetch_matrix), then the set's trees
+// the tail of the run forms: 2 n - 3 branches per matrix cross the link, set after set into child / len [.][n_mat][2 n - 3]
+// and status [.][n_mat] -- and matrix 0 of every set into dist0 [.][n_pairs], if that is asked for
+static Tail nj_tail(ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, int32_t *child, double *len, uint32_t *status,
+                    double *dist0) {
+  return [=](uint64_t set0, uint64_t n_set, uint64_t n_mat) {
+    const uint64_t n = e->g.n_ind, nb = NGD_NJ_NBRANCH(n), m0 = set0 * n_mat;
+    if (int rc = nj_reduce(e, e->d_bsum, e->d_bcnt, false, n_set * n_mat, tot_sites, evol_model, child + m0 * nb, len + m0 * nb,
+                           status + m0))
+      return rc;
+    return dist0 ? nj_dist0(e, e->d_bsum, e->d_bcnt, n_set, n_mat, tot_sites, evol_model, dist0 + set0 * ngd_n_pairs(n)) : NGD_OK;
+  };
+}
+
 int ngd_run_job_nj(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
                    uint64_t tot_sites, uint64_t evol_model, int32_t *child, double *len, uint32_t *status, double *dist0) {
   if (int rc = nj_refuse(e, child, len, status, tot_sites, evol_model, "ngd_run_job_nj")) return rc;
   if (n_rep && !block_maps) return fail(NGD_E_INVALID, "ngd_run_job_nj: null argument");
   e->nj.ms = 0;
-  const uint64_t n_mat = (uint64_t)n_rep + 1;
-  if (int rc = batch_buffers(e, n_rep + 1)) return rc;
-  if (int rc = run_impl(e, block_maps, nullptr, n_rep, n_rep != 0, n_blocks, block_size, e->d_bsum, e->d_bcnt)) return rc;
-  e->n_batch_valid = n_rep + 1;
-  if (int rc = nj_reduce(e, e->d_bsum, e->d_bcnt, false, n_mat, tot_sites, evol_model, child, len, status)) return rc;
-  return dist0 ? nj_dist0(e, e->d_bsum, e->d_bcnt, 1, n_mat, tot_sites, evol_model, dist0) : NGD_OK;
+  return job_tail(e, block_maps, n_rep, n_blocks, block_size, nj_tail(e, tot_sites, evol_model, child, len, status, dist0));
+}
+
+// the windowed forms: `a` as ngd_run_windows_job_var's, or the windows alone (n_rep 0)
+static int windows_nj(ngd_engine *e, const WinJobArgs &a, uint64_t tot_sites, uint64_t evol_model, int32_t *child, double *len,
+                      uint32_t *status, double *dist0, const char *who) {
+  if (int rc = nj_refuse(e, child, len, status, tot_sites, evol_model, who)) return rc;
+  e->nj.ms = 0;
+  return windows_tail(e, a, false, who, nj_tail(e, tot_sites, evol_model, child, len, status, dist0));
 }
 
 int ngd_run_windows_nj(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
                        uint64_t evol_model, int32_t *child, double *len, uint32_t *status, double *dist0) {
-  if (int rc = nj_refuse(e, child, len, status, tot_sites, evol_model, "ngd_run_windows_nj")) return rc;
-  e->nj.ms = 0;
-  return windows_host_nj(e, win_lo, win_hi, n_win, nullptr, 0, nullptr, 0, 0, tot_sites, evol_model, child, len, status, dist0,
-                         "ngd_run_windows_nj");
+  return windows_nj(e, WinJobArgs{win_lo, win_hi, n_win, nullptr, 0, nullptr, 0, 0}, tot_sites, evol_model, child, len, status, dist0,
+                    "ngd_run_windows_nj");
 }
 
 int ngd_run_windows_job_var_nj(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                                const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
                                uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, int32_t *child, double *len,
                                uint32_t *status, double *dist0) {
-  if (int rc = nj_refuse(e, child, len, status, tot_sites, evol_model, "ngd_run_windows_job_var_nj")) return rc;
-  e->nj.ms = 0;
-  return windows_host_nj(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size, tot_sites, evol_model, child, len,
-                         status, dist0, "ngd_run_windows_job_var_nj");
+  return windows_nj(e, WinJobArgs{win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size}, tot_sites, evol_model,
+                    child, len, status, dist0, "ngd_run_windows_job_var_nj");
 }
 
 int ngd_last_nj_ms(const ngd_engine *e, double *ms) {

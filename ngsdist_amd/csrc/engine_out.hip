@@ -1,5 +1,6 @@
 // engine_out.hip -- results on their way out: the streamer of the *_dist calls (chunks leave the device while later
-// matrices are still being reduced, the host's threads finish each as it lands) and the host-pointer forms.
+// matrices are still being reduced, the host's threads finish each as it lands), the host-pointer forms, the job driver of
+// the tails and what every call that finishes matrices refuses.
 #include "ngd_engine.h"
 
 // ---- a job's matrices leaving the device while later ones are still being reduced (ngd_run_job_dist) ----
@@ -169,6 +170,24 @@ int run_to_host(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult,
   return copy_out(e, n_batch ? n_batch : 1, d_sum, d_cnt, sum, cnt);
 }
 
+// the job driver of the tails (ngd_engine.h): ngd_run_job_device into the batch buffers, where the matrices stay
+// (ngd_fetch_matrix), then the tail on that one set
+int job_tail(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, const Tail &tail) {
+  if (int rc = batch_buffers(e, n_rep + 1)) return rc;
+  if (int rc = run_impl(e, block_maps, nullptr, n_rep, n_rep != 0, n_blocks, block_size, e->d_bsum, e->d_bcnt)) return rc;
+  e->n_batch_valid = n_rep + 1;
+  return tail(0, 1, (uint64_t)n_rep + 1);
+}
+
+int finish_refuse(const ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, const std::string &who, const char *no_what) {
+  if (tot_sites && e->cfg.pairwise_del)
+    return fail(NGD_E_INVALID, who + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
+  if (evol_model > 2) return fail(NGD_E_MODEL, who + ": evolutionary model not supported (ngsDist.cpp:398-399)");
+  if (no_what && e->cfg.shard_world > 1)
+    return fail(NGD_E_INVALID, who + ": an engine that owns a share of the pairs holds part of every matrix: " + no_what);
+  return NGD_OK;
+}
+
 // A whole job AND the tail of gen_dist() (ngsDist.cpp:372-401) in one call: the sums (and, --pairwise_del, the counts) leave
 // the device chunk by chunk on a stream of their own into pinned memory of the engine's while -- in the per-block-partials
 // plan -- later groups of replicates are still being reduced, and the host's threads turn each chunk into distances as it
@@ -176,9 +195,7 @@ int run_to_host(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult,
 int run_dist(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, uint32_t n_rep, bool lead_full,
              uint64_t n_blocks, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who) {
   if (!e || !dist) return fail(NGD_E_INVALID, std::string(who) + ": null argument");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, std::string(who) + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, std::string(who) + ": evolutionary model not supported (ngsDist.cpp:398-399)");
+  if (int rc = finish_refuse(e, tot_sites, evol_model, who, nullptr)) return rc;
   if (e->cfg.shard_world > 1)
     return fail(NGD_E_INVALID, std::string(who) + ": an engine that owns a share of the pairs holds part of every matrix -- put the "
                                "shares together first (ngd_run_job_device + the ranks' exchange), then ngd_finish()");

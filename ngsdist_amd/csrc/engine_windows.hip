@@ -1,6 +1,6 @@
-// engine_windows.hip -- the windowed calls: their two plans, the fix-up of a batch of windows, the host-memory forms; and the
-// jobs that draw bootstrap replicates inside every window.
-#include <functional>
+// engine_windows.hip -- the windowed calls: their two plans, the fix-up of a batch of windows, the host-memory forms -- groups
+// of windows through the batch buffers, a tail after each: the window driver of the tails --; and the jobs that draw
+// bootstrap replicates inside every window.
 #include <map>
 #include <numeric>
 
@@ -704,13 +704,21 @@ static int windows_device(ngd_engine *e, const uint64_t *lo, const uint64_t *hi,
   return windows_impl(e, lo, hi, n_win, (double *)d_sum, (unsigned long long *)d_cnt, bt, bv);
 }
 
-// the host-memory forms: windows in groups whose results fit ~2 GB of the engine's batch buffers; fn(first, count) takes
-// each group's results out of d_bsum / d_bcnt
+// the budget of a group of windows in the engine's batch buffers
+// (tests only, NGD_ENABLE_TEST_HOOKS=1: NGD_TEST_WIN_GROUP_BYTES is the budget instead, so that a small call spans groups)
+static uint64_t windows_group_bytes() {
+  const char *hook = getenv("NGD_ENABLE_TEST_HOOKS");
+  const char *bytes = hook && atoi(hook) ? getenv("NGD_TEST_WIN_GROUP_BYTES") : nullptr;
+  return bytes ? strtoull(bytes, nullptr, 10) : 2ull << 30;
+}
+
+// the host-memory forms: windows in groups whose results fit ~2 GB of the engine's batch buffers; the tail (ngd_engine.h)
+// takes each group's results out of d_bsum / d_bcnt -- a window is a set
 // (a job, bt or bv != NULL: n_rep + 1 matrices per window, at least one window per group)
 static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win,
-                           const std::function<int(uint64_t, uint64_t)> &fn, const WinBoot *bt, const WinBootVar *bv) {
+                           const Tail &tail, const WinBoot *bt, const WinBootVar *bv) {
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind), n_mat = bv ? (uint64_t)bv->n_rep + 1 : bt ? (uint64_t)bt->n_rep + 1 : 1;
-  const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / (16 * n_mat * std::max<uint64_t>(1, n_pairs))));
+  const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, windows_group_bytes() / (16 * n_mat * std::max<uint64_t>(1, n_pairs))));
   e->win_info = ngd_windows_info{};
   e->fix_info = ngd_fixup_info{};
   if (e->opt_em_exact_win) em_exact_call_begin(e);
@@ -720,49 +728,53 @@ static int windows_chunked(ngd_engine *e, const uint64_t *lo, const uint64_t *hi
     const uint64_t n = std::min(per, n_win - w0);
     const WinBootVar from = bv ? bv->from(w0) : WinBootVar{};
     if ((rc = windows_impl(e, lo + w0, hi + w0, n, e->d_bsum, e->d_bcnt, bt, bv ? &from : nullptr))) return rc;
-    if ((rc = fn(w0, n))) return rc;
+    if ((rc = tail(w0, n, n_mat))) return rc;
   }
   e->n_batch_valid = 0;
   return NGD_OK;
 }
 
-// ... sums and counts (either may be NULL), bt == NULL: the windows alone
-static int windows_host(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt, double *sum,
-                        uint64_t *cnt, const WinBootVar *bv = nullptr) {
-  HIPCHK(hipSetDevice(e->device));
-  const uint32_t n_mat = bv ? bv->n_rep + 1 : bt ? bt->n_rep + 1 : 1;
-  const uint64_t per_win = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
-  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
-    int rc = copy_out(e, (uint32_t)(n * n_mat), e->d_bsum, e->d_bcnt, sum ? sum + w0 * per_win : nullptr,
-                      cnt ? cnt + w0 * per_win : nullptr);
+// ... the copy tail: sums and counts (either may be NULL)
+static Tail copy_tail(ngd_engine *e, double *sum, uint64_t *cnt) {
+  return [=](uint64_t set0, uint64_t n_set, uint64_t n_mat) {
+    const uint64_t at = set0 * n_mat * ngd_n_pairs(e->g.n_ind);
+    int rc = copy_out(e, (uint32_t)(n_set * n_mat), e->d_bsum, e->d_bcnt, sum ? sum + at : nullptr, cnt ? cnt + at : nullptr);
     e->n_batch_valid = 0;
     return rc;
-  }, bt, bv);
+  };
 }
 
-// ... distances: the tail of gen_dist() on every matrix
-static int windows_host_dist(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt,
-                             uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who,
-                             const WinBootVar *bv = nullptr) {
-  const std::string w(who);
-  if (!dist) return fail(NGD_E_INVALID, w + ": null argument");
-  if (tot_sites && e->cfg.pairwise_del)
-    return fail(NGD_E_INVALID, w + ": a total number of sites cannot go with pairwise deletion (parse_args.cpp:209-210)");
-  if (evol_model > 2) return fail(NGD_E_MODEL, w + ": evolutionary model not supported (ngsDist.cpp:398-399)");
-  HIPCHK(hipSetDevice(e->device));
-  const uint32_t n_mat = bv ? bv->n_rep + 1 : bt ? bt->n_rep + 1 : 1;
-  const uint64_t per_win = (uint64_t)n_mat * ngd_n_pairs(e->g.n_ind);
-  std::vector<double> h_sum;
-  std::vector<uint64_t> h_cnt;
-  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
-    h_sum.resize(n * per_win);
-    h_cnt.resize(n * per_win);
-    int rc = copy_out(e, (uint32_t)(n * n_mat), e->d_bsum, e->d_bcnt, h_sum.data(), h_cnt.data());
+// ... the distance tail: the tail of gen_dist() on every matrix (its host copies serve group after group), and what it refuses
+static Tail dist_tail(ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, double *dist) {
+  return [=, h_sum = std::vector<double>(), h_cnt = std::vector<uint64_t>()](uint64_t set0, uint64_t n_set, uint64_t n_mat) mutable {
+    const uint64_t per_set = n_mat * ngd_n_pairs(e->g.n_ind);
+    h_sum.resize(n_set * per_set);
+    h_cnt.resize(n_set * per_set);
+    int rc = copy_out(e, (uint32_t)(n_set * n_mat), e->d_bsum, e->d_bcnt, h_sum.data(), h_cnt.data());
     e->n_batch_valid = 0;
     if (rc) return rc;
     // (the tail of gen_dist() on the host, the host's libm: ngd_finish's bits)
-    return ngd_finish(h_sum.data(), h_cnt.data(), n * per_win, tot_sites, evol_model, dist + w0 * per_win);
-  }, bt, bv);
+    return ngd_finish(h_sum.data(), h_cnt.data(), n_set * per_set, tot_sites, evol_model, dist + set0 * per_set);
+  };
+}
+
+static int dist_refuse(const ngd_engine *e, const double *dist, uint64_t tot_sites, uint64_t evol_model, const char *who) {
+  if (!dist) return fail(NGD_E_INVALID, std::string(who) + ": null argument");
+  return finish_refuse(e, tot_sites, evol_model, who, nullptr);  // (the windows' check has refused a share of the pairs)
+}
+
+// the windows alone and the jobs of one window length (bt != NULL), checked: sums and counts, or distances
+static int windows_host(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt, double *sum,
+                        uint64_t *cnt) {
+  HIPCHK(hipSetDevice(e->device));
+  return windows_chunked(e, lo, hi, n_win, copy_tail(e, sum, cnt), bt, nullptr);
+}
+
+static int windows_host_dist(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const WinBoot *bt,
+                             uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who) {
+  if (int rc = dist_refuse(e, dist, tot_sites, evol_model, who)) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  return windows_chunked(e, lo, hi, n_win, dist_tail(e, tot_sites, evol_model, dist), bt, nullptr);
 }
 
 int ngd_run_windows_device(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, void *d_sum,
@@ -900,88 +912,36 @@ int ngd_run_windows_job_var_device(ngd_engine *e, const uint64_t *win_lo, const 
   return windows_device(e, win_lo, win_hi, n_win, nullptr, d_sum, d_cnt, "ngd_run_windows_job_var_device", &bv);
 }
 
+// the window driver of the tails (ngd_engine.h): the arguments checked -- as a job's, or with n_rep == 0 and no job_form as
+// ngd_run_windows' --, then what `refuse` refuses, then every group of windows from the batch buffers through the tail
+int windows_tail(ngd_engine *e, const WinJobArgs &a, bool job_form, const char *who, const Tail &tail,
+                 const std::function<int()> &refuse) {
+  WinVarStore st;
+  WinBootVar bv{};
+  if (int rc = a.n_rep || job_form
+                   ? windows_job_var_check(e, a.lo, a.hi, a.n_win, a.maps, a.maps_len, a.map_off, a.n_rep, a.block_size, who, st, bv)
+                   : windows_check(e, a.lo, a.hi, a.n_win, who))
+    return rc;
+  if (refuse)
+    if (int rc = refuse()) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  return windows_chunked(e, a.lo, a.hi, a.n_win, tail, nullptr, a.n_rep ? &bv : nullptr);
+}
+
 int ngd_run_windows_job_var(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, const uint64_t *block_maps,
                             uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, double *sum,
                             uint64_t *cnt) {
-  WinVarStore st;
-  WinBootVar bv{};
-  if (int rc = windows_job_var_check(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size,
-                                     "ngd_run_windows_job_var", st, bv))
-    return rc;
-  if (!n_rep) return ngd_run_windows(e, win_lo, win_hi, n_win, sum, cnt);
-  return windows_host(e, win_lo, win_hi, n_win, nullptr, sum, cnt, &bv);
+  return windows_tail(e, WinJobArgs{win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size}, true,
+                      "ngd_run_windows_job_var", copy_tail(e, sum, cnt));
 }
 
 int ngd_run_windows_job_var_dist(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
                                  const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
                                  uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *dist) {
-  WinVarStore st;
-  WinBootVar bv{};
-  if (int rc = windows_job_var_check(e, win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size,
-                                     "ngd_run_windows_job_var_dist", st, bv))
-    return rc;
-  if (!n_rep) return ngd_run_windows_dist(e, win_lo, win_hi, n_win, tot_sites, evol_model, dist);
-  return windows_host_dist(e, win_lo, win_hi, n_win, nullptr, tot_sites, evol_model, dist, "ngd_run_windows_job_var_dist", &bv);
-}
-
-// ... group means (ngd_run_windows_groups, ngd_run_windows_job_var_groups; engine_groups.hip has checked what is the
-// grouping's): the sibling's checks, then every group of windows from the batch buffers through the group reduction --
-// n_gp means and counts per matrix leave the device instead of n_pairs sums and counts
-int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
-                        const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
-                        double *mean, uint64_t *used, const char *who) {
-  WinVarStore st;
-  WinBootVar bv{};
-  if (int rc = n_rep ? windows_job_var_check(e, lo, hi, n_win, maps, maps_len, map_off, n_rep, block_size, who, st, bv)
-                     : windows_check(e, lo, hi, n_win, who))
-    return rc;
-  HIPCHK(hipSetDevice(e->device));
-  const uint64_t n_mat = (uint64_t)n_rep + 1, n_gp = e->grp.n_gp;
-  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
-    return groups_reduce(e, e->d_bsum, e->d_bcnt, n * n_mat, tot_sites, evol_model, mean + w0 * n_mat * n_gp,
-                         used ? used + w0 * n_mat * n_gp : nullptr);
-  }, nullptr, n_rep ? &bv : nullptr);
-}
-
-// ... bootstrap summaries (ngd_run_windows_job_var_stats, ngd_run_windows_job_var_groups_stats; engine_boot_stats.hip has
-// checked what is the summaries'): the sibling's checks, then every group of windows -- whole sets: n_rep + 1 matrices per
-// window -- from the batch buffers through boot_reduce; 5 doubles and a count per cell leave the device
-int windows_host_stats(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
-                       const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
-                       BootCi ci, bool groups, double *stats, uint64_t *used, const char *who) {
-  WinVarStore st;
-  WinBootVar bv{};
-  if (int rc = windows_job_var_check(e, lo, hi, n_win, maps, maps_len, map_off, n_rep, block_size, who, st, bv)) return rc;
-  HIPCHK(hipSetDevice(e->device));
-  const uint64_t n_mat = (uint64_t)n_rep + 1, n_cells = groups ? e->grp.n_gp : ngd_n_pairs(e->g.n_ind);
-  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
-    double *s = stats + w0 * NGD_BOOT_NSTAT * n_cells;
-    uint64_t *u = used + w0 * n_cells;
-    if (!groups) return boot_reduce(e, e->d_bsum, e->d_bcnt, false, n, n_mat, n_cells, tot_sites, evol_model, ci, s, u);
-    if (int rc = groups_reduce_keep(e, e->d_bsum, e->d_bcnt, n * n_mat, tot_sites, evol_model)) return rc;
-    return boot_reduce(e, e->grp.d_keep_mean, nullptr, true, n, n_mat, n_cells, 0, 0, ci, s, u);
-  }, nullptr, &bv);
-}
-
-// ... neighbour-joining trees (ngd_run_windows_nj, ngd_run_windows_job_var_nj; engine_nj.hip has checked what is the
-// trees'): the sibling's checks, then every group of windows -- whole sets: n_rep + 1 matrices per window -- from the batch
-// buffers through nj_reduce; 2 n - 3 branches per matrix leave the device, and matrix 0 of every set if dist0 asks for it
-int windows_host_nj(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
-                    const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
-                    int32_t *child, double *len, uint32_t *status, double *dist0, const char *who) {
-  WinVarStore st;
-  WinBootVar bv{};
-  if (int rc = n_rep ? windows_job_var_check(e, lo, hi, n_win, maps, maps_len, map_off, n_rep, block_size, who, st, bv)
-                     : windows_check(e, lo, hi, n_win, who))
-    return rc;
-  HIPCHK(hipSetDevice(e->device));
-  const uint64_t n_mat = (uint64_t)n_rep + 1, n_pairs = ngd_n_pairs(e->g.n_ind), nb = NGD_NJ_NBRANCH((uint64_t)e->g.n_ind);
-  return windows_chunked(e, lo, hi, n_win, [&](uint64_t w0, uint64_t n) {
-    if (int rc = nj_reduce(e, e->d_bsum, e->d_bcnt, false, n * n_mat, tot_sites, evol_model, child + w0 * n_mat * nb,
-                           len + w0 * n_mat * nb, status + w0 * n_mat))
-      return rc;
-    return dist0 ? nj_dist0(e, e->d_bsum, e->d_bcnt, n, n_mat, tot_sites, evol_model, dist0 + w0 * n_pairs) : NGD_OK;
-  }, nullptr, n_rep ? &bv : nullptr);
+  // (n_rep == 0 is ngd_run_windows_dist, in the words of the distances' refusals too)
+  const char *who = "ngd_run_windows_job_var_dist", *who_dist = n_rep ? who : "ngd_run_windows_dist";
+  return windows_tail(e, WinJobArgs{win_lo, win_hi, n_win, block_maps, maps_len, map_off, n_rep, block_size}, true, who,
+                      dist_tail(e, tot_sites, evol_model, dist), [&] { return dist_refuse(e, dist, tot_sites, evol_model, who_dist); });
 }
 
 int ngd_last_windows(const ngd_engine *e, ngd_windows_info *info) {

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -252,7 +253,7 @@ struct ngd_engine : ngd_mem {
     DevBuf<ngd_group_work> d_work;
     DevBuf<double> d_part_sum, d_mean;
     DevBuf<unsigned long long> d_part_cnt, d_used;
-    DevBuf<double> d_keep_mean;              // the means of a call's every matrix, kept for the summaries (groups_reduce_keep)
+    DevBuf<double> d_keep_mean;              // the means of a call's every matrix, kept for the summaries (groups_reduce, mean == NULL)
     DevBuf<unsigned long long> d_keep_used;
     double ms = 0;  // ngd_last_groups_ms
   } grp;
@@ -379,39 +380,37 @@ int run_to_host(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult,
                 uint64_t n_blocks, uint64_t block_size, uint32_t n_batch, double *sum, uint64_t *cnt);
 int run_dist(ngd_engine *e, const uint64_t *block_maps, const uint32_t *mult, uint32_t n_rep, bool lead_full,
              uint64_t n_blocks, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, double *dist, const char *who);
-// engine_groups.hip: [n_mat][n_pairs] device matrices -> mean / used [n_mat][n_gp] in host memory (the arguments are checked)
+// what every call that finishes matrices refuses (tot_sites with pairwise deletion, an unknown model, an engine that owns
+// a share of the pairs); no_what ends the last one's message -- NULL where the caller has words of its own for such an
+// engine, or the check of its windows has refused it already
+int finish_refuse(const ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, const std::string &who, const char *no_what);
+
+// ---- tails: what a call does on the device with the matrices it has just left in the batch buffers ----
+// A tail takes the matrices standing in d_bsum / d_bcnt as [n_set][n_mat][n_pairs] -- a job's one set, the sets of a group
+// of windows -- where set0 is the first of them among the call's sets: the tail owns its outputs and their offsets.  Each
+// unit builds its own from a call's outputs and parameters (engine_groups.hip, engine_boot_stats.hip, engine_nj.hip; the
+// copy and the distances in engine_windows.hip) and hands it to one of the two drivers; everything is checked before.
+using Tail = std::function<int(uint64_t set0, uint64_t n_set, uint64_t n_mat)>;
+// engine_out.hip: ngd_run_job_device into the batch buffers, where the matrices stay (ngd_fetch_matrix), then tail(0, 1,
+// n_rep + 1); n_rep == 0: the full-data matrix alone, the maps are not read
+int job_tail(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size, const Tail &tail);
+// engine_windows.hip: the arguments of ngd_run_windows_job_var (n_rep == 0: of ngd_run_windows, the rest is not read) ...
+struct WinJobArgs {
+  const uint64_t *lo, *hi;
+  uint64_t n_win;
+  const uint64_t *maps;
+  uint64_t maps_len;
+  const uint64_t *map_off;
+  uint32_t n_rep;
+  uint64_t block_size;
+};
+// ... checked -- as a job's (that check refuses under NGD_OPT_EM_EXACT), or with n_rep == 0 as ngd_run_windows' unless the
+// call is a job form whatever its n_rep (job_form) -- then what `refuse` refuses (if given: the tail's own, where the call's
+// order of refusals puts them after the windows'), then the windows in groups through the batch buffers, the tail after each
+int windows_tail(ngd_engine *e, const WinJobArgs &a, bool job_form, const char *who, const Tail &tail,
+                 const std::function<int()> &refuse = nullptr);
+// engine_groups.hip: [n_mat][n_pairs] device matrices -> mean / used [n_mat][n_gp] in host memory; mean == NULL: they stay
+// on the device instead, grp.d_keep_mean / d_keep_used [n_mat][n_gp], for the summaries (the arguments are checked)
 int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
                   uint64_t evol_model, double *mean, uint64_t *used);
-// ... the same reduction with the means left in device memory: grp.d_keep_mean / d_keep_used [n_mat][n_gp]
-int groups_reduce_keep(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
-                       uint64_t evol_model);
-// engine_boot_stats.hip: the summaries of [n_set][n_mat][n_cells] device matrices -> stats / used in host memory; d_cnt and
-// the two arguments of ngd_finish for sums and counts, `values` for cells as they are (the arguments are checked)
-struct BootCi {
-  double p_lo, p_hi;
-};
-int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
-                uint64_t n_cells, uint64_t tot_sites, uint64_t evol_model, BootCi ci, double *stats, uint64_t *used);
-// engine_windows.hip: ngd_run_windows_job_var_device through the batch buffers, every group of windows -- whole sets --
-// summarised by boot_reduce; groups: the group reduction first, the means' summaries (n_cells = n_gp)
-int windows_host_stats(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
-                       const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
-                       BootCi ci, bool groups, double *stats, uint64_t *used, const char *who);
-// engine_nj.hip: the trees of [n_mat][n_pairs] device matrices -> child / len / status in host memory; d_cnt and the two
-// arguments of ngd_finish for sums and counts, `values` for cells as they are (the arguments are checked)
-int nj_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_mat, uint64_t tot_sites,
-              uint64_t evol_model, int32_t *child, double *len, uint32_t *status);
-// ... matrix 0 of n_set sets of n_mat device matrices, copied out and finished on the host: dist0 [n_set][n_pairs]
-int nj_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
-             uint64_t evol_model, double *dist0);
-// engine_windows.hip: the windowed calls through the batch buffers, every group of windows -- whole sets -- through
-// nj_reduce (n_rep == 0: the windows alone, maps are not read); dist0 may be NULL
-int windows_host_nj(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
-                    const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
-                    int32_t *child, double *len, uint32_t *status, double *dist0, const char *who);
-// engine_windows.hip: the windowed calls through the batch buffers, every group of windows reduced by groups_reduce
-// (n_rep == 0, or maps NULL with it: the windows alone)
-int windows_host_groups(ngd_engine *e, const uint64_t *lo, const uint64_t *hi, uint64_t n_win, const uint64_t *maps, uint64_t maps_len,
-                        const uint64_t *map_off, uint32_t n_rep, uint64_t block_size, uint64_t tot_sites, uint64_t evol_model,
-                        double *mean, uint64_t *used, const char *who);
 #pragma GCC visibility pop

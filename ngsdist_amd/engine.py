@@ -315,28 +315,21 @@ class Engine:
         not given; any other layout must name it); -> (sum, cnt) of shape (n_win, n_rep + 1, n_pairs), a
         window shorter than one block with replicates of sum 0 and count 0; with device pointers
         (ngd_run_windows_job_var_device) the results go there and None is returned"""
-        lo, hi, lp, hp = self._win_args(lo, hi)
-        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
-        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        n_win, n_rep, args, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
         if d_sum_ptr is not None:
-            _check(self._L.ngd_run_windows_job_var_device(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size),
-                                                          C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr)))
+            _check(self._L.ngd_run_windows_job_var_device(*args, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr)))
             return None
-        s = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.float64)
-        c = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.uint64)
-        _check(self._L.ngd_run_windows_job_var(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size),
-                                               s.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_uint64))))
+        s = np.empty((n_win, n_rep + 1, self.n_pairs), dtype=np.float64)
+        c = np.empty((n_win, n_rep + 1, self.n_pairs), dtype=np.uint64)
+        _check(self._L.ngd_run_windows_job_var(*args, s.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_uint64))))
         return s, c
 
     def run_windows_job_var_dist(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None):
         """the job and the tail of gen_dist() on every matrix (ngd_run_windows_job_var_dist): float64 (n_win, n_rep + 1,
         n_pairs); the replicates of a window shorter than one block are ngd_finish's 0 / 0"""
-        lo, hi, lp, hp = self._win_args(lo, hi)
-        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
-        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
-        d = np.empty((lo.size, n_rep + 1, self.n_pairs), dtype=np.float64)
-        _check(self._L.ngd_run_windows_job_var_dist(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size),
-                                                    int(tot_sites), int(evol_model), d.ctypes.data_as(C.POINTER(C.c_double))))
+        n_win, n_rep, args, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
+        d = np.empty((n_win, n_rep + 1, self.n_pairs), dtype=np.float64)
+        _check(self._L.ngd_run_windows_job_var_dist(*args, int(tot_sites), int(evol_model), d.ctypes.data_as(C.POINTER(C.c_double))))
         return d
 
     @staticmethod
@@ -351,6 +344,14 @@ class Engine:
         above = off[has][off[has] > off[w]]
         end = int(above.min()) if above.size else int(n_ent)
         return (end - int(off[w])) // int(nb[w])
+
+    def _var_job(self, lo, hi, block_maps, map_off, block_size, n_rep):
+        """what every ngd_run_windows_job_var* call starts with -> (n_win, n_rep, the call's leading arguments up to
+        block_size, the arrays behind their pointers: to be kept alive until the call is over)"""
+        lo, hi, lp, hp = self._win_args(lo, hi)
+        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
+        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
+        return lo.size, n_rep, (self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size)), (lo, hi) + keep
 
     def windows_info(self):
         """what the last windowed call did (ngd_last_windows): segments, slab_bytes, batches, band_launches,
@@ -408,12 +409,9 @@ class Engine:
     def run_windows_job_var_groups(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None):
         """run_windows_job_var() and the group reduction of every matrix (ngd_run_windows_job_var_groups): -> (mean, used) of
         shape (n_win, n_rep + 1, n_gp)"""
-        lo, hi, lp, hp = self._win_args(lo, hi)
-        keep, mp_, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
-        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
-        mean, used, mp, up = self._group_out(lo.size, n_rep + 1)
-        _check(self._L.ngd_run_windows_job_var_groups(self._h, lp, hp, lo.size, mp_, n_ent, op, n_rep, int(block_size),
-                                                      int(tot_sites), int(evol_model), mp, up))
+        n_win, n_rep, args, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
+        mean, used, mp, up = self._group_out(n_win, n_rep + 1)
+        _check(self._L.ngd_run_windows_job_var_groups(*args, int(tot_sites), int(evol_model), mp, up))
         return mean, used
 
     def groups_ms(self):
@@ -465,11 +463,9 @@ class Engine:
         return stats, used
 
     def _windows_stats(self, fn, n_cells, lo, hi, block_maps, map_off, block_size, evol_model, tot_sites, n_rep, ci):
-        lo, hi, lp, hp = self._win_args(lo, hi)
-        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
-        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
-        stats, used, sp, up = self._stats_out((lo.size,), n_cells)
-        _check(fn(self._h, lp, hp, lo.size, mp, n_ent, op, n_rep, int(block_size), int(tot_sites), int(evol_model), float(ci), sp, up))
+        n_win, n_rep, args, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
+        stats, used, sp, up = self._stats_out((n_win,), n_cells)
+        _check(fn(*args, int(tot_sites), int(evol_model), float(ci), sp, up))
         return stats, used
 
     def run_windows_job_var_stats(self, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None, ci=0.95):
@@ -538,12 +534,9 @@ class Engine:
         """run_windows_job_var() and the trees of every window's set (ngd_run_windows_job_var_nj): -> (child (n_win,
         n_rep + 1, 2n-3), len, status (n_win, n_rep + 1), dist0 (n_win, n_pairs)); the replicates of a window shorter than
         one block have status 0"""
-        lo, hi, lp_, hp = self._win_args(lo, hi)
-        keep, mp, op, n_ent = self._var_maps(block_maps, map_off, lo.size)
-        n_rep = self._var_n_rep(lo, hi, keep[1], n_ent, block_size) if n_rep is None else int(n_rep)
-        child, length, status, d0, cp, lp, sp, dp = self._nj_out((lo.size, n_rep + 1), (lo.size,) if dist0 else None)
-        _check(self._L.ngd_run_windows_job_var_nj(self._h, lp_, hp, lo.size, mp, n_ent, op, n_rep, int(block_size), int(tot_sites),
-                                                  int(evol_model), cp, lp, sp, dp))
+        n_win, n_rep, args, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
+        child, length, status, d0, cp, lp, sp, dp = self._nj_out((n_win, n_rep + 1), (n_win,) if dist0 else None)
+        _check(self._L.ngd_run_windows_job_var_nj(*args, int(tot_sites), int(evol_model), cp, lp, sp, dp))
         return child, length, status, d0
 
     def last_nj_ms(self):
