@@ -262,18 +262,19 @@ def test_the_per_window_plan(pdel):
 
 def test_another_kernel_shape():
     """variant = 1 .. 4 (4 wavefronts x 16 rows, rows only; 12 steps per round; shape 0 scanned row by row): each its own
-    instantiation of the noting slice-table form"""
+    instantiation of the noting slice-table form, without and with --pairwise_del"""
     lo, hi = STEP
-    So, Co = win_oracle(False, lo, hi)
-    keys0 = entry_keys(run_windows(False, lo, hi, 1, SLAB)[2])
-    for variant in (1, 2, 3, 4):
-        S0 = run_windows(False, lo, hi, 0, SLAB, variant=variant)[0]
-        S, Cn, ent, info, _ = run_windows(False, lo, hi, 1, SLAB, variant=variant)
-        assert np.array_equal(Cn, Co) and within(S, So) and missed(S0, So) > 0, variant
-        check_list(ent, info)
-        quiet = quiet_cells(ent, lo, hi)
-        assert np.array_equal(S[quiet].view(np.uint64), S0[quiet].view(np.uint64)), variant
-        assert entry_keys(ent) == keys0, variant  # the list does not depend on the shape
+    for pdel in (False, True):
+        So, Co = win_oracle(pdel, lo, hi)
+        keys0 = entry_keys(run_windows(pdel, lo, hi, 1, SLAB)[2])
+        for variant in (1, 2, 3, 4):
+            S0 = run_windows(pdel, lo, hi, 0, SLAB, variant=variant)[0]
+            S, Cn, ent, info, _ = run_windows(pdel, lo, hi, 1, SLAB, variant=variant)
+            assert np.array_equal(Cn, Co) and within(S, So) and missed(S0, So) > 0, (pdel, variant)
+            check_list(ent, info)
+            quiet = quiet_cells(ent, lo, hi)
+            assert np.array_equal(S[quiet].view(np.uint64), S0[quiet].view(np.uint64)), (pdel, variant)
+            assert entry_keys(ent) == keys0, (pdel, variant)  # the list does not depend on the shape
 
 
 def test_engines_of_32_individuals_or_fewer():
