@@ -407,6 +407,9 @@ int ngd_drop_caches(ngd_engine *e);
 #define NGD_OPT_NJ_MAX_BYTES 19    /* [0 = 2 GB] device scratch of the neighbour-joining kernel (ngd_nj_*, ngd_run_*_nj): a full n x n */
                                  /*     matrix of doubles (rows padded to an even length) per matrix of a launch; never fewer    */
                                  /*     than one matrix.  Any value gives the same bits                                          */
+#define NGD_OPT_MDS_MAX_BYTES 20   /* [0 = 2 GB] device scratch of the classical-MDS kernel (ngd_mds_*, ngd_run_*_mds): per matrix of a */
+                                 /*     launch a full n x n matrix of doubles (rows padded to an even length) and 4 K rows     */
+                                 /*     more; never fewer than one matrix.  Any value gives the same bits                        */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -804,6 +807,74 @@ int ngd_nj_support(const int32_t *child, const uint32_t *status, uint64_t n_mat,
  * number of bytes (no terminator), written only if cap is large enough, or a negative NGD_E_* code. */
 int64_t ngd_nj_newick(const int32_t *child, const double *len, uint64_t n_ind, const char *const *labels, const uint32_t *support,
                       char *out, uint64_t cap);
+
+/* Classical MDS (added under ABI 6): the principal coordinates (Torgerson / Gower: R's cmdscale) of every matrix, computed where the matrix lies: K (n + 1) + 2
+ * numbers per matrix cross the link instead of n (n - 1) / 2 sums and counts.
+ *   input      d_ab for the individuals 0 .. n - 1, n = n_ind >= 3, from a matrix's n_pairs cells in ngd_pair_index order,
+ *              d_aa = 0
+ *   centred    A_ab = -0.5 * d_ab^2;  B = A - rowmean - colmean + grandmean   (symmetric, B 1 = 0)
+ *   outputs    eig[K]     the K algebraically largest eigenvalues of B, in descending order
+ *              vec[K][n]  a unit eigenvector for each; the component of largest magnitude is positive, the lowest index
+ *                         wins an exact tie
+ *              tot[2]     { the sum of all n eigenvalues, the sum of the positive ones }
+ *              status     uint32
+ *   1 <= K <= min(n - 1, ngd_mds_max_dim()).  Coordinates are vec[k][i] * sqrt(max(eig[k], 0)): ngd_mds_coords().
+ * Outputs, in host memory: eig[n_mat][K], vec[n_mat][K][n], tot[n_mat][2], status[n_mat].
+ * A matrix with any cell that is not finite (NaN, +-inf) has status 0 and every eigenvalue, vector entry and total a
+ * positive quiet NaN; the other matrices of the call are not affected.  Every finite matrix has status 1, whatever its
+ * spectrum: all cells zero (every eigenvalue 0, the vectors the first K unit vectors), all cells equal (one eigenvalue of
+ * multiplicity n - 1: some orthonormal basis of its space), a matrix that is not Euclidean (negative eigenvalues; they
+ * count in tot[0] alone).  (Cells whose squares overflow, |d| above about 1e150, are outside the contract.)
+ * Method: a direct one, so that accuracy does not depend on the gaps between eigenvalues -- Householder tridiagonalisation,
+ * all n eigenvalues of the tridiagonal matrix by bisection on Sturm counts, the top K vectors by inverse iteration from a
+ * fixed start vector with modified Gram-Schmidt against the vectors before them (a repeated eigenvalue gets a perturbed
+ * shift), the reflectors applied in reverse.  With S = max |eigenvalue|: eigenvalues and residuals |B v - eig v|_2 within
+ * 1e-9 S, totals within 1e-9 of the sum of |eigenvalue|, |V V^T - I| <= 1e-9; a vector whose eigenvalue lies 1e-3 S or more
+ * from every other one agrees with any other solver's to 1 - 1e-9 in the dot product (inside a cluster only the space is
+ * determined).
+ * From sums and counts a cell's value is ngd_finish()'s, operation by operation (the division and the products carry the
+ * host's bits, log is the device's).
+ * Determinism: a matrix's output bits are a function of its cells and K alone, never of its position in the call, the chunk
+ * or what else the launch holds (no atomics, fixed reduction trees).  Device and host twin follow the same method but need
+ * not agree bit for bit (their sums run in different orders), and the environment variable NGD_MDS_WG (256, 512 or 1024:
+ * the workgroup, for measurement) changes the device's trees and so may change bits. */
+/* the most individuals the device form serves (the tridiagonal matrix stays in on-chip memory) and the most dimensions K;
+ * more is NGD_E_INVALID */
+uint32_t ngd_mds_max_ind(void);
+uint32_t ngd_mds_max_dim(void);
+/* The contract in plain host arithmetic on val[n_mat][n_pairs]; needs no device, any n_ind >= 3; matrices are spread over
+ * host threads, which changes no bit.  NGD_E_INVALID: a null pointer, n_mat 0, n_ind < 3, K = 0, K > n_ind - 1 or above
+ * ngd_mds_max_dim(). */
+int ngd_mds_host(const double *val, uint64_t n_mat, uint64_t n_ind, uint32_t K, double *eig, double *vec, double *tot,
+                 uint32_t *status);
+/* coords[n_mat][n_ind][K] = vec[k][i] * sqrt(max(eig[k], 0)), pure host (NaN where eig is NaN).  NGD_E_INVALID as above. */
+int ngd_mds_coords(const double *eig, const double *vec, uint64_t n_mat, uint64_t n_ind, uint32_t K, double *coords);
+/* ... on the device (one workgroup per matrix, mds.hip), of [n_mat][n_pairs] values as they are, or of sums and counts in
+ * device memory as a *_device call wrote them (d_cnt is not read when tot_sites > 0); n_ind is the engine's.  The matrices
+ * go through device scratch in chunks of NGD_OPT_MDS_MAX_BYTES; chunking changes no bit.  NGD_E_INVALID, before anything
+ * is launched: a null pointer, n_mat 0, n_ind < 3 or above ngd_mds_max_ind(), K = 0, K > n_ind - 1 or above
+ * ngd_mds_max_dim(), tot_sites with --pairwise_del, an engine that owns a share of the pairs; NGD_E_MODEL for evol_model
+ * > 2.  A refused call leaves outputs and engine as they were. */
+int ngd_mds_values_device(ngd_engine *e, const void *d_val, uint64_t n_mat, uint32_t K, double *eig, double *vec, double *tot,
+                          uint32_t *status);
+int ngd_mds_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_mat, uint64_t tot_sites, uint64_t evol_model,
+                   uint32_t K, double *eig, double *vec, double *tot, uint32_t *status);
+/* ngd_run_job_device / ngd_run_windows_device / ngd_run_windows_job_var_device into the engine's batch buffers, followed by
+ * that reduction: plans, fix-up, NGD_OPT_EM_EXACT* and refusals are the sibling's, and the outputs are ngd_mds_device()'s
+ * on the sibling's output bit for bit at the same options.  n_rep = 0 is allowed.  Outputs: eig [n_set][n_rep + 1][K], vec
+ * [n_set][n_rep + 1][K][n], tot [n_set][n_rep + 1][2], status [n_set][n_rep + 1]; dist0, unless NULL, receives
+ * [n_set][n_pairs]: matrix 0 of every set finished by ngd_finish() on the host -- the bits the _dist sibling gives. */
+int ngd_run_job_mds(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                    uint64_t tot_sites, uint64_t evol_model, uint32_t K, double *eig, double *vec, double *tot, uint32_t *status,
+                    double *dist0);
+int ngd_run_windows_mds(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
+                        uint64_t evol_model, uint32_t K, double *eig, double *vec, double *tot, uint32_t *status, double *dist0);
+int ngd_run_windows_job_var_mds(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, uint32_t K, double *eig, double *vec,
+                                double *tot, uint32_t *status, double *dist0);
+/* device time (HIP events) of the MDS kernels in the last of these calls, summed over its launches */
+int ngd_last_mds_ms(const ngd_engine *e, double *ms);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

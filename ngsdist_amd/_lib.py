@@ -94,6 +94,8 @@ EXPORTS = [
     "ngd_last_boot_stats_ms",
     "ngd_nj_max_ind", "ngd_nj_host", "ngd_nj_values_device", "ngd_nj_device", "ngd_run_job_nj", "ngd_run_windows_nj",
     "ngd_run_windows_job_var_nj", "ngd_last_nj_ms", "ngd_nj_support", "ngd_nj_newick",
+    "ngd_mds_max_ind", "ngd_mds_max_dim", "ngd_mds_host", "ngd_mds_coords", "ngd_mds_values_device", "ngd_mds_device",
+    "ngd_run_job_mds", "ngd_run_windows_mds", "ngd_run_windows_job_var_mds", "ngd_last_mds_ms",
 ]
 
 NSTAT = 5  # NGD_BOOT_NSTAT: est, mean, sd, lo, hi
@@ -240,6 +242,19 @@ def load():
     L.ngd_nj_support.argtypes = [i32p, u32p, u64, u64, u32p, u32p]
     L.ngd_nj_newick.argtypes = [i32p, dp, u64, C.POINTER(C.c_char_p), u32p, C.c_char_p, u64]
     L.ngd_nj_newick.restype = C.c_int64
+    u32 = C.c_uint32
+    L.ngd_mds_max_ind.argtypes = []
+    L.ngd_mds_max_ind.restype = u32
+    L.ngd_mds_max_dim.argtypes = []
+    L.ngd_mds_max_dim.restype = u32
+    L.ngd_mds_host.argtypes = [dp, u64, u64, u32, dp, dp, dp, u32p]
+    L.ngd_mds_coords.argtypes = [dp, dp, u64, u64, u32, dp]
+    L.ngd_mds_values_device.argtypes = [vp, vp, u64, u32, dp, dp, dp, u32p]
+    L.ngd_mds_device.argtypes = [vp, vp, vp, u64, u64, u64, u32, dp, dp, dp, u32p]
+    L.ngd_run_job_mds.argtypes = [vp, u64p, u32, u64, u64, u64, u64, u32, dp, dp, dp, u32p, dp]
+    L.ngd_run_windows_mds.argtypes = [vp, u64p, u64p, u64, u64, u64, u32, dp, dp, dp, u32p, dp]
+    L.ngd_run_windows_job_var_mds.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, u32, u64, u64, u64, u32, dp, dp, dp, u32p, dp]
+    L.ngd_last_mds_ms.argtypes = [vp, dp]
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

@@ -70,8 +70,8 @@ static int nj_reduce(ngd_engine *e, const double *d_a, const unsigned long long 
 }
 
 // matrix 0 of every set: its sums and counts copied out, the tail of gen_dist() on the host (ngd_finish's bits)
-static int nj_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
-             uint64_t evol_model, double *dist0) {
+int tail_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
+               uint64_t evol_model, double *dist0) {
   const uint64_t n_pairs = ngd_n_pairs(e->g.n_ind);
   std::vector<double> h_sum(n_set * n_pairs);
   std::vector<uint64_t> h_cnt(n_set * n_pairs);
@@ -116,7 +116,7 @@ static Tail nj_tail(ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, int3
     if (int rc = nj_reduce(e, e->d_bsum, e->d_bcnt, false, n_set * n_mat, tot_sites, evol_model, child + m0 * nb, len + m0 * nb,
                            status + m0))
       return rc;
-    return dist0 ? nj_dist0(e, e->d_bsum, e->d_bcnt, n_set, n_mat, tot_sites, evol_model, dist0 + set0 * ngd_n_pairs(n)) : NGD_OK;
+    return dist0 ? tail_dist0(e, e->d_bsum, e->d_bcnt, n_set, n_mat, tot_sites, evol_model, dist0 + set0 * ngd_n_pairs(n)) : NGD_OK;
   };
 }
 

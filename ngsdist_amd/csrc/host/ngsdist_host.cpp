@@ -39,7 +39,12 @@
 //    stay on the device, <out> holds the estimates and <out>.boot_mean / _sd / _lo / _hi / _used the replicates' summaries
 //    per cell; one GPU, the whole data set resident), --nj (the neighbour-joining tree of every matrix, built on the device:
 //    <out>.nwk holds one Newick line per matrix, <out> matrix 0 of every set and, with replicates, <out>.support.nwk matrix
-//    0's tree with the number of replicate trees that share each of its branches; one GPU, the whole data set resident);
+//    0's tree with the number of replicate trees that share each of its branches; one GPU, the whole data set resident),
+//    --mds K (classical MDS / principal coordinates of every matrix, computed on the device: <out>.mds holds one block per
+//    matrix -- a line "eig" with the K largest eigenvalues of the double-centred matrix, a line "total" with the sum of all
+//    eigenvalues and of the positive ones, a line per individual with its label and K coordinates, an empty line; fields
+//    are separated by tabs and every number is printed as "%.10e", "nan" throughout for a matrix with a cell that is not
+//    finite --, <out> matrix 0 of every set; one GPU, the whole data set resident);
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
@@ -47,7 +52,7 @@
 // Layout: options (Pars, parse_cmd_args), text helpers, the readers and the Loader; then what the run reads beside the
 // genotypes (read_labels, read_positions, make_windows: WindowList), device_fit (one device or site ranges), the matrix
 // output every mode prints through (Writer, MatrixOut::emit), the jobs the modes share (draw_window_maps, draw_job_maps,
-// format_grown, for_window_groups) and one function per output mode -- site_range_matrices, trees, bootstrap_summaries,
+// format_grown, for_window_groups) and one function per output mode -- site_range_matrices, trees, coordinates, bootstrap_summaries,
 // group_means, window_matrices, plain_matrices; main(), last, is the run's outline and picks one of them.
 #include <fcntl.h>
 #include <getopt.h>
@@ -100,6 +105,12 @@
 #pragma weak ngd_run_windows_job_var_nj
 #pragma weak ngd_nj_support
 #pragma weak ngd_nj_newick
+// (--mds: the principal coordinates of every matrix, computed on the device; ngd_mds_max_dim and ngd_mds_coords are
+// host_util.cpp's and always there)
+#pragma weak ngd_mds_max_ind
+#pragma weak ngd_run_job_mds
+#pragma weak ngd_run_windows_mds
+#pragma weak ngd_run_windows_job_var_mds
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -170,6 +181,13 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // <out>.support.nwk matrix 0's tree of every set with its branches' support.  Not in the reference, whose README pipes
   // the matrices through fastme and RAxML for the same files.
   bool nj = false;
+  // --mds K: every matrix of the run -- as for --nj -- leaves the engine as the top K eigenpairs of its double-centred form
+  // and the two sums of its eigenvalues (ngd_run_*_mds): <out>.mds holds one block per matrix in block order -- "eig" and
+  // its K eigenvalues, "total" and the two sums, a line per individual with its K coordinates vec * sqrt(max(eig, 0)), an
+  // empty line; tabs between fields, numbers as "%.10e" --, <out> matrix 0 of every set (a plain run: the run without
+  // --mds).  Not in the reference, whose users run R's cmdscale on <out>.
+  bool mds = false;
+  uint64_t mds_dim = 0;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -285,6 +303,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"boot_stats", no_argument, nullptr, 1021},
                                  {"boot_ci", required_argument, nullptr, 1022},
                                  {"nj", no_argument, nullptr, 1023},
+                                 {"mds", required_argument, nullptr, 1024},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -330,6 +349,13 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       case 1021: p.boot_stats = true; break;
       case 1022: p.boot_ci_set = true; p.boot_ci = atof(optarg); break;
       case 1023: p.nj = true; break;
+      case 1024: {
+        char *end = nullptr;
+        p.mds = true;
+        p.mds_dim = strtoull(optarg, &end, 10);
+        if (end == optarg || *end || optarg[0] == '-') die(__FUNCTION__, "the number of dimensions (--mds K) must be a whole number!");
+        break;
+      }
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -381,6 +407,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.in_groups) fprintf(stderr, "\tgroups: %s\n\n", p.in_groups);
     if (p.boot_stats) fprintf(stderr, "\tboot_stats: true\n\tboot_ci: %f\n\n", p.boot_ci);
     if (p.nj) fprintf(stderr, "\tnj: true\n\n");
+    if (p.mds) fprintf(stderr, "\tmds: %lu\n\n", (unsigned long)p.mds_dim);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -458,6 +485,15 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.boot_stats) die(__FUNCTION__, "neighbour-joining trees (--nj) cannot be combined with bootstrap summaries (--boot_stats)!");
     if (p.n_gpus > 1) die(__FUNCTION__, "neighbour-joining trees (--nj) are computed on one GPU (--n_gpus 1)!");
     if (p.n_ind < 3) die(__FUNCTION__, "neighbour-joining trees (--nj) need three individuals or more (--n_ind)!");
+  }
+  if (p.mds) {
+    if (p.in_groups) die(__FUNCTION__, "classical MDS (--mds) cannot be combined with group means (--groups)!");
+    if (p.boot_stats) die(__FUNCTION__, "classical MDS (--mds) cannot be combined with bootstrap summaries (--boot_stats)!");
+    if (p.nj) die(__FUNCTION__, "classical MDS (--mds) cannot be combined with neighbour-joining trees (--nj)!");
+    if (p.n_gpus > 1) die(__FUNCTION__, "classical MDS (--mds) is computed on one GPU (--n_gpus 1)!");
+    if (p.n_ind < 3) die(__FUNCTION__, "classical MDS (--mds) needs three individuals or more (--n_ind)!");
+    if (p.mds_dim < 1 || p.mds_dim > p.n_ind - 1 || p.mds_dim > ngd_mds_max_dim())
+      die(__FUNCTION__, ("the number of dimensions (--mds K) must lie between 1 and min(n_ind - 1, " + std::to_string(ngd_mds_max_dim()) + ")!").c_str());
   }
 }
 
@@ -1308,7 +1344,7 @@ std::vector<std::string> read_labels(const Pars &p) {
   return labels;
 }
 
-// what --boot_stats and --nj need of the engine and of the job
+// what --boot_stats, --nj and --mds need of the engine and of the job
 void check_summaries_and_trees(const Pars &p) {
   if (p.boot_stats) {
     if (!ngd_boot_stats_max_rep || !ngd_run_job_stats || !ngd_run_windows_job_var_stats || !ngd_run_job_groups_stats ||
@@ -1322,6 +1358,12 @@ void check_summaries_and_trees(const Pars &p) {
       die(kMain, "this build of the engine has no neighbour-joining trees (--nj)!");
     if (p.n_ind > ngd_nj_max_ind())
       die(kMain, "too many individuals for neighbour-joining trees (--nj): a matrix's row sums stay in on-chip memory!");
+  }
+  if (p.mds) {
+    if (!ngd_mds_max_ind || !ngd_run_job_mds || !ngd_run_windows_mds || !ngd_run_windows_job_var_mds)
+      die(kMain, "this build of the engine has no classical MDS (--mds)!");
+    if (p.n_ind > ngd_mds_max_ind())
+      die(kMain, "too many individuals for classical MDS (--mds): a matrix's tridiagonal form stays in on-chip memory!");
   }
 }
 
@@ -1408,7 +1450,7 @@ void make_windows(const Pars &p, WindowList &win) {
   win.hi.resize((size_t)n_win);
   if (p.win_bp) win.bp_start.resize((size_t)n_win);
   ranges((uint64_t)n_win);
-  if (!p.in_groups && !p.boot_stats && !p.nj) {  // (--groups, --boot_stats, --nj: their own entry points, checked before)
+  if (!p.in_groups && !p.boot_stats && !p.nj && !p.mds) {  // (--groups, --boot_stats, --nj, --mds: their own entry points, checked before)
     if (!ngd_run_windows_dist) die(kMain, "this build of the engine has no windows along the genome (--win_size)!");
     if (p.win_boot_rep && (p.win_bp ? !ngd_run_windows_job_var_dist : !ngd_run_windows_job_dist))
       die(kMain, p.win_bp ? "this build of the engine has no bootstrap replicates inside windows of unequal length (--win_bp with --win_boot_rep)!"
@@ -1850,6 +1892,87 @@ void trees(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], M
   if (fclose(nf) != 0 || (sf && fclose(sf) != 0)) die(kMain, "cannot write trees output file!");
 }
 
+// ---- classical MDS (--mds K): every matrix of every set -- the run's one set, or one per window -- becomes the top K
+// eigenpairs of its double-centred form on the device (ngd_run_*_mds).  <out> takes matrix 0 of every set (a plain run: the
+// bytes of the run without --mds), <out>.mds one block per matrix, set after set, matrix 0 first: "eig" and the K
+// eigenvalues, "total" and the sum of all eigenvalues and of the positive ones, a line per individual with its label and K
+// coordinates, an empty line; tabs between fields, every number as "%.10e" ----
+void coordinates(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], MatrixOut &out) {
+  const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep, n_mat = R + 1, n = p.n_ind, n_comb = out.n_comb;
+  const uint32_t K = (uint32_t)p.mds_dim;
+  FILE *mf = fopen((std::string(p.out) + ".mds").c_str(), "w");
+  if (!mf) die(kMain, "cannot open coordinates output file!");
+  std::vector<double> xy(n * K);
+  uint64_t n_bad = 0;
+  // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), then its matrices' blocks
+  auto write_set = [&](uint64_t w, const char *name, const double *m0, const double *eig, const double *vec, const double *tot,
+                       const uint32_t *st) {
+    out.emit(w, nullptr, nullptr, nullptr, 0, m0, 0, name);
+    for (uint64_t r = 0; r < n_mat; r++) {
+      const double *e = eig + r * K;
+      if (ngd_mds_coords(e, vec + r * K * n, 1, n, K, xy.data())) die(kLambda, "cannot derive the coordinates!");
+      n_bad += st[r] == 0;
+      bool ok = fputs("eig", mf) >= 0;
+      for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(mf, "\t%.10e", e[k]) > 0;
+      ok = ok && fprintf(mf, "\ntotal\t%.10e\t%.10e\n", tot[2 * r], tot[2 * r + 1]) > 0;
+      for (uint64_t i = 0; i < n; i++) {
+        ok = ok && fputs(out.label_ptr[i], mf) >= 0;
+        for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(mf, "\t%.10e", xy[i * K + k]) > 0;
+        ok = ok && fputc('\n', mf) != EOF;
+      }
+      if (!ok || fputc('\n', mf) == EOF) die(kLambda, "cannot write coordinates output file!");
+    }
+  };
+  std::vector<double> eig, vec, tot, d0;
+  std::vector<uint32_t> status;
+  auto resize_results = [&](uint64_t n_sets) {
+    eig.resize(n_sets * n_mat * K);
+    vec.resize(n_sets * n_mat * K * n);
+    tot.resize(n_sets * n_mat * 2);
+    status.resize(n_sets * n_mat);
+    d0.resize(n_sets * n_comb);
+  };
+  if (p.win) {
+    // a group of windows per call: their outputs and first matrices in ~2 GB of host memory.  --win_boot_rep: the
+    // replicates of a window shorter than one block are 0 / 0 and have no coordinates
+    std::vector<uint64_t> off(win.size()), maps(1);
+    const uint64_t mlen = R ? draw_window_maps(p, win, R, maps, off) : 0;
+    for_window_groups(p, eng, out, win.size(), n_mat * (K * (n + 1) + 2) * 8 + n_mat * 4 + n_comb * 8, true,
+      [&](uint64_t w0, uint64_t nw) {
+        resize_results(nw);
+        const int rc = R ? ngd_run_windows_job_var_mds(eng.h, &win.lo[w0], &win.hi[w0], nw, maps.data(), mlen, &off[w0], (uint32_t)R,
+                                                       p.boot_block_size, p.tot_sites, p.evol_model, K, eig.data(), vec.data(),
+                                                       tot.data(), status.data(), d0.data())
+                         : ngd_run_windows_mds(eng.h, &win.lo[w0], &win.hi[w0], nw, p.tot_sites, p.evol_model, K, eig.data(), vec.data(),
+                                               tot.data(), status.data(), d0.data());
+        engine_ok(R ? "ngd_run_windows_job_var_mds" : "ngd_run_windows_mds", rc);
+      },
+      [&](uint64_t w0, uint64_t nw) {
+        for (uint64_t k = 0; k < nw; k++)
+          write_set(w0 + k, win.name(w0 + k).c_str(), &d0[k * n_comb], &eig[k * n_mat * K], &vec[k * n_mat * K * n], &tot[k * n_mat * 2],
+                    &status[k * n_mat]);
+      });
+    win.write_file(std::string(p.out) + ".windows", p);
+  } else {
+    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
+    const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
+    if (R && !n_blocks) die(kMain, "classical MDS (--mds) of bootstrap replicates needs at least one bootstrap block of sites!");
+    const auto t_c0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> maps;
+    draw_job_maps(rng, R, n_blocks, maps);
+    resize_results(1);
+    engine_ok("ngd_run_job_mds", ngd_run_job_mds(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, K,
+                                                 eig.data(), vec.data(), tot.data(), status.data(), d0.data()));
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    write_set(0, nullptr, d0.data(), eig.data(), vec.data(), tot.data(), status.data());
+  }
+  if (n_bad)
+    fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no coordinates (\"nan\" throughout their blocks in %s.mds)\n",
+            (unsigned long)n_bad, p.out);
+  if (fclose(mf) != 0) die(kMain, "cannot write coordinates output file!");
+}
+
 // ---- bootstrap summaries (--boot_stats): the replicates of every set -- the run's, or a window's -- stay on the device,
 // which reduces each cell to five statistics and a count (ngd_run_*_stats).  <out> takes the estimates (matrix 0 of every
 // set: the bytes of the run without replicates), <out>.boot_mean / _sd / _lo / _hi the other statistics in the same blocks
@@ -2195,6 +2318,7 @@ int main(int argc, char **argv) {
   const struct { bool on; const char *what; } one_gpu[] = {{p.win, "windows (--win_size)"},
                                                            {p.boot_stats, "bootstrap summaries (--boot_stats)"},
                                                            {p.nj, "neighbour-joining trees (--nj)"},
+                                                           {p.mds, "classical MDS (--mds)"},
                                                            {p.in_groups != nullptr, "group means (--groups)"}};
   for (auto &m : one_gpu)
     if (m.on && fit.in_parts)
@@ -2240,6 +2364,7 @@ int main(int argc, char **argv) {
       fprintf(stderr, "> read + prepare + upload: %.3f s (%.2f GB of prepared input resident on the device)\n", t_load,
               (double)p.n_ind * p.n_sites * 24 / 1e9);
     if (p.nj) trees(p, eng, win, rng, out);
+    else if (p.mds) coordinates(p, eng, win, rng, out);
     else if (p.boot_stats) bootstrap_summaries(p, eng, win, group_of, group_names, rng, out);
     else if (p.in_groups) group_means(p, eng, win, group_of, group_names, rng, batch, out);
     else if (p.win) window_matrices(p, eng, win, out);

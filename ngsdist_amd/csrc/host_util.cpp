@@ -1006,3 +1006,250 @@ int64_t ngd_nj_newick(const int32_t *child, const double *len, uint64_t n_ind, c
   put(");\n", 3);
   return (int64_t)pos;
 }
+
+// ---- classical MDS (--mds): the contract of include/ngsdist_amd.h "Classical MDS" in plain host arithmetic, matrix by
+// matrix, by the method of mds.hip: the double-centred matrix, Householder tridiagonalisation (the reflectors stay in the
+// rows they eliminate), every eigenvalue of the tridiagonal matrix by bisection on Sturm counts, the top K vectors by
+// inverse iteration with modified Gram-Schmidt, and the reflectors applied in reverse ----
+namespace {
+const uint32_t kMdsMaxDim = 16;  // ngd_mds_max_dim()
+const int kMdsIter = 3;          // solves per vector
+const double kMdsEps = 2.220446049250313e-16, kMdsPivMin = 1e-290;
+
+struct MdsWork {
+  std::vector<double> S, d, e, e2, lam, w, u0, u1, u2, z;
+};
+
+// the start vector of inverse iteration: a fixed function of (component, vector), uniform in (-1, 1), never 0
+inline double mds_start(uint32_t i, uint32_t k) {
+  uint32_t h = (i + 1) * 2654435761u ^ (k + 1) * 2246822519u;
+  h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
+  return ((double)(h >> 8) + 0.5) * (1.0 / 8388608.0) - 1.0;
+}
+
+// eigenvalues of the (scaled) tridiagonal matrix below x
+inline uint64_t mds_count(const double *d, const double *e2, uint64_t n, double x) {
+  double q = d[0] - x;
+  if (std::fabs(q) < kMdsPivMin) q = -kMdsPivMin;
+  uint64_t c = q < 0;
+  for (uint64_t i = 1; i < n; i++) {
+    q = (d[i] - x) - e2[i - 1] / q;
+    if (std::fabs(q) < kMdsPivMin) q = -kMdsPivMin;
+    c += q < 0;
+  }
+  return c;
+}
+
+inline double mds_piv(double x, double floor_) { return std::fabs(x) < floor_ ? (std::signbit(x) ? -floor_ : floor_) : x; }
+
+// z <- (T - sh I)^-1 z: LU with partial pivoting, the forward substitution beside it; pivots below `floor_` are raised to it
+void mds_solve(const double *d, const double *e, uint64_t n, double sh, double floor_, double *u0, double *u1, double *u2, double *z) {
+  double a = d[0] - sh, b = e[0], x = z[0];
+  for (uint64_t i = 0; i + 1 < n; i++) {
+    const double sub = e[i], dn = d[i + 1] - sh, un = i + 2 < n ? e[i + 1] : 0.0, zn = z[i + 1];
+    if (std::fabs(a) >= std::fabs(sub)) {
+      const double l = a != 0 ? sub / a : 0.0;
+      u0[i] = a; u1[i] = b; u2[i] = 0.0;
+      z[i] = x;
+      a = dn - l * b; b = un; x = zn - l * x;
+    } else {
+      const double l = a / sub;
+      u0[i] = sub; u1[i] = dn; u2[i] = un;
+      z[i] = zn;
+      a = b - l * dn; b = -(l * un); x = x - l * zn;
+    }
+  }
+  u0[n - 1] = a;
+  z[n - 1] = x / mds_piv(a, floor_);
+  z[n - 2] = (z[n - 2] - u1[n - 2] * z[n - 1]) / mds_piv(u0[n - 2], floor_);
+  for (uint64_t i = n - 2; i-- > 0;) z[i] = ((z[i] - u1[i] * z[i + 1]) - u2[i] * z[i + 2]) / mds_piv(u0[i], floor_);
+}
+
+void mds_one(const double *val, uint64_t n, uint32_t K, double *eig, double *vec, double *tot, uint32_t *status, MdsWork &W) {
+  const uint64_t n_pairs = n * (n - 1) / 2;
+  bool bad = false;
+  for (uint64_t p = 0; p < n_pairs && !bad; p++) bad = !std::isfinite(val[p]);
+  if (bad) {
+    const uint64_t nan_bits = 0x7FF8000000000000ull;
+    double nan;
+    memcpy(&nan, &nan_bits, 8);
+    for (uint64_t k = 0; k < K; k++) eig[k] = nan;
+    for (uint64_t k = 0; k < K * n; k++) vec[k] = nan;
+    tot[0] = tot[1] = nan;
+    *status = 0;
+    return;
+  }
+  *status = 1;
+  W.S.assign(n * n, 0.0);
+  for (auto *v : {&W.d, &W.e, &W.e2, &W.lam, &W.w, &W.u0, &W.u1, &W.u2}) v->assign(n, 0.0);
+  W.z.assign((uint64_t)K * n, 0.0);
+  double *S = W.S.data(), *d = W.d.data(), *e = W.e.data(), *e2 = W.e2.data(), *lam = W.lam.data(), *w = W.w.data(), *Z = W.z.data();
+  // A = -0.5 d^2, centred: B_ab = (A_ab - (mean_a + mean_b)) + grand (symmetric bit for bit)
+  for (uint64_t a = 0, p = 0; a + 1 < n; a++)
+    for (uint64_t b = a + 1; b < n; b++, p++) S[a * n + b] = S[b * n + a] = -0.5 * (val[p] * val[p]);
+  double grand = 0.0;
+  for (uint64_t a = 0; a < n; a++) {
+    double acc = 0.0;
+    for (uint64_t b = 0; b < n; b++) acc += S[b * n + a];
+    w[a] = acc / (double)n;
+  }
+  for (uint64_t a = 0; a < n; a++) grand += w[a];
+  grand /= (double)n;
+  for (uint64_t a = 0; a < n; a++)
+    for (uint64_t b = 0; b < n; b++) S[a * n + b] = (S[a * n + b] - (w[a] + w[b])) + grand;
+  // T = Q^T B Q: step k eliminates row / column k beyond k + 1; row k keeps tau (at k) and v (beyond, v[k + 1] = 1)
+  for (uint64_t k = 0; k + 2 < n; k++) {
+    double *x = S + k * n;
+    const double alpha = x[k + 1];
+    double ss = 0.0;
+    for (uint64_t c = k + 2; c < n; c++) ss += x[c] * x[c];
+    d[k] = x[k];
+    if (!(ss > 0.0)) {  // nothing to eliminate: H = I
+      e[k] = alpha;
+      x[k] = 0.0;
+      x[k + 1] = 1.0;
+      for (uint64_t c = k + 2; c < n; c++) x[c] = 0.0;
+      continue;
+    }
+    const double beta = -std::copysign(std::sqrt(alpha * alpha + ss), alpha), tau = (beta - alpha) / beta, sc = 1.0 / (alpha - beta);
+    e[k] = beta;
+    x[k] = tau;
+    x[k + 1] = 1.0;
+    for (uint64_t c = k + 2; c < n; c++) x[c] *= sc;
+    double pv = 0.0;
+    for (uint64_t r = k + 1; r < n; r++) {
+      const double *row = S + r * n;
+      double acc = 0.0;
+      for (uint64_t c = k + 1; c < n; c++) acc += row[c] * x[c];
+      w[r] = tau * acc;
+      pv += w[r] * x[r];
+    }
+    const double half = -0.5 * tau * pv;
+    for (uint64_t r = k + 1; r < n; r++) w[r] += half * x[r];
+    for (uint64_t r = k + 1; r < n; r++) {
+      double *row = S + r * n;
+      const double xr = x[r], wr = w[r];
+      for (uint64_t c = k + 1; c < n; c++) row[c] -= xr * w[c] + wr * x[c];
+    }
+  }
+  d[n - 2] = S[(n - 2) * n + (n - 2)];
+  e[n - 2] = S[(n - 2) * n + (n - 1)];
+  d[n - 1] = S[(n - 1) * n + (n - 1)];
+  e[n - 1] = 0.0;
+  double tnorm = 0.0;
+  for (uint64_t i = 0; i < n; i++) tnorm = std::max(tnorm, std::fabs(d[i]) + (i ? std::fabs(e[i - 1]) : 0.0) + std::fabs(e[i]));
+  if (!(tnorm > 0.0) || !std::isfinite(tnorm)) {  // T = 0: a matrix without variation (or cells beyond the contract)
+    const double v = tnorm > 0.0 ? tnorm - tnorm : 0.0;  // (NaN where T overflowed)
+    for (uint64_t k = 0; k < K; k++) {
+      eig[k] = v;
+      for (uint64_t i = 0; i < n; i++) vec[k * n + i] = i == k ? 1.0 + v : v;
+    }
+    tot[0] = tot[1] = v;
+    return;
+  }
+  // T scaled by a power of two into [1, 2): exact, and the floors below are then absolute
+  const int ex = std::ilogb(tnorm);
+  for (uint64_t i = 0; i < n; i++) {
+    d[i] = std::scalbn(d[i], -ex);
+    e[i] = std::scalbn(e[i], -ex);
+    e2[i] = e[i] * e[i];
+  }
+  for (uint64_t j = 0; j < n; j++) {  // eigenvalue j in ascending order: the least x with count(x) > j
+    double lo = -2.5, hi = 2.5;
+    for (int it = 0; it < 64; it++) {
+      const double mid = lo + 0.5 * (hi - lo);
+      if (!(mid > lo) || !(mid < hi) || hi - lo < 1e-17) break;
+      if (mds_count(d, e2, n, mid) > j) hi = mid;
+      else lo = mid;
+    }
+    lam[j] = lo + 0.5 * (hi - lo);
+  }
+  double sum = 0.0, pos = 0.0;
+  for (uint64_t j = 0; j < n; j++) {
+    const double l = std::scalbn(lam[j], ex);
+    sum += l;
+    if (l > 0.0) pos += l;
+  }
+  tot[0] = sum;
+  tot[1] = pos;
+  // the top K vectors of T
+  const double floor_ = kMdsEps, pert = 10.0 * kMdsEps * 2.0;
+  double sh[kMdsMaxDim];
+  for (uint32_t k = 0; k < K; k++) {
+    eig[k] = std::scalbn(lam[n - 1 - k], ex);
+    sh[k] = lam[n - 1 - k];
+    if (k && sh[k - 1] - sh[k] < pert) sh[k] = sh[k - 1] - pert;
+    for (uint64_t i = 0; i < n; i++) Z[k * n + i] = mds_start((uint32_t)i, k);
+  }
+  auto orthonormalise = [&](uint32_t k) {
+    double *z = Z + k * n;
+    double big = 0.0;
+    for (uint64_t i = 0; i < n; i++) big = std::max(big, std::fabs(z[i]));
+    if (big > 0.0 && std::isfinite(big)) for (uint64_t i = 0; i < n; i++) z[i] /= big;
+    for (int pass = 0; pass < 2; pass++)
+      for (uint32_t j = 0; j < k; j++) {
+        const double *y = Z + j * n;
+        double dot = 0.0;
+        for (uint64_t i = 0; i < n; i++) dot += z[i] * y[i];
+        for (uint64_t i = 0; i < n; i++) z[i] -= dot * y[i];
+      }
+    double ss = 0.0;
+    for (uint64_t i = 0; i < n; i++) ss += z[i] * z[i];
+    const double nrm = std::sqrt(ss);
+    if (nrm > 0.0) for (uint64_t i = 0; i < n; i++) z[i] /= nrm;
+  };
+  for (int it = 0; it < kMdsIter; it++)
+    for (uint32_t k = 0; k < K; k++) {
+      mds_solve(d, e, n, sh[k], floor_, W.u0.data(), W.u1.data(), W.u2.data(), Z + k * n);
+      orthonormalise(k);
+    }
+  // back through the reflectors, normalised, the component of largest magnitude positive (the lowest index on a tie)
+  for (uint64_t k = n - 2; k-- > 0;) {
+    const double *x = S + k * n;
+    const double tau = x[k];
+    if (tau == 0.0) continue;
+    for (uint32_t v = 0; v < K; v++) {
+      double *z = Z + v * n, dot = 0.0;
+      for (uint64_t c = k + 1; c < n; c++) dot += x[c] * z[c];
+      const double f = tau * dot;
+      for (uint64_t c = k + 1; c < n; c++) z[c] -= f * x[c];
+    }
+  }
+  for (uint32_t v = 0; v < K; v++) {
+    double *z = Z + v * n, ss = 0.0, big = -1.0;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; i++) ss += z[i] * z[i];
+    const double nrm = std::sqrt(ss);
+    for (uint64_t i = 0; i < n; i++) {
+      if (nrm > 0.0) z[i] /= nrm;
+      if (std::fabs(z[i]) > big) { big = std::fabs(z[i]); at = i; }
+    }
+    const bool flip = z[at] < 0.0;
+    for (uint64_t i = 0; i < n; i++) vec[v * n + i] = flip ? -z[i] : z[i];
+  }
+}
+}  // namespace
+
+uint32_t ngd_mds_max_dim(void) { return kMdsMaxDim; }
+
+int ngd_mds_host(const double *val, uint64_t n_mat, uint64_t n_ind, uint32_t K, double *eig, double *vec, double *tot, uint32_t *status) {
+  if (!val || !eig || !vec || !tot || !status || !n_mat || n_ind < 3 || !K || K > n_ind - 1 || K > kMdsMaxDim) return NGD_E_INVALID;
+  const uint64_t n_pairs = n_ind * (n_ind - 1) / 2;
+  const unsigned parts = (unsigned)std::min<uint64_t>(n_mat, 1024);
+  host_pool().run(parts, [&](unsigned part) {
+    MdsWork W;
+    for (uint64_t m = part; m < n_mat; m += parts)
+      mds_one(val + m * n_pairs, n_ind, K, eig + m * K, vec + m * K * n_ind, tot + m * 2, status + m, W);
+  });
+  return NGD_OK;
+}
+
+int ngd_mds_coords(const double *eig, const double *vec, uint64_t n_mat, uint64_t n_ind, uint32_t K, double *coords) {
+  if (!eig || !vec || !coords || !n_mat || n_ind < 3 || !K || K > n_ind - 1 || K > kMdsMaxDim) return NGD_E_INVALID;
+  for (uint64_t m = 0; m < n_mat; m++)
+    for (uint32_t k = 0; k < K; k++) {
+      const double l = eig[m * K + k], s = l > 0.0 ? std::sqrt(l) : l - l;  // (0 for an eigenvalue <= 0, NaN for NaN)
+      for (uint64_t i = 0; i < n_ind; i++) coords[(m * n_ind + i) * K + k] = vec[(m * K + k) * n_ind + i] * s;
+    }
+  return NGD_OK;
+}

@@ -271,6 +271,13 @@ struct ngd_engine : ngd_mem {
     uint64_t max_bytes = 0;  // NGD_OPT_NJ_MAX_BYTES
     double ms = 0;           // ngd_last_nj_ms
   } nj;
+  // classical MDS (engine_mds.hip): a chunk of matrices' working copies, their vectors' scratch and their outputs
+  struct Mds {
+    DevBuf<double> d_work, d_aux, d_eig, d_vec, d_tot;
+    DevBuf<uint32_t> d_status;
+    uint64_t max_bytes = 0;  // NGD_OPT_MDS_MAX_BYTES
+    double ms = 0;           // ngd_last_mds_ms
+  } mds;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
@@ -388,7 +395,7 @@ int finish_refuse(const ngd_engine *e, uint64_t tot_sites, uint64_t evol_model, 
 // ---- tails: what a call does on the device with the matrices it has just left in the batch buffers ----
 // A tail takes the matrices standing in d_bsum / d_bcnt as [n_set][n_mat][n_pairs] -- a job's one set, the sets of a group
 // of windows -- where set0 is the first of them among the call's sets: the tail owns its outputs and their offsets.  Each
-// unit builds its own from a call's outputs and parameters (engine_groups.hip, engine_boot_stats.hip, engine_nj.hip; the
+// unit builds its own from a call's outputs and parameters (engine_groups.hip, engine_boot_stats.hip, engine_nj.hip, engine_mds.hip; the
 // copy and the distances in engine_windows.hip) and hands it to one of the two drivers; everything is checked before.
 using Tail = std::function<int(uint64_t set0, uint64_t n_set, uint64_t n_mat)>;
 // engine_out.hip: ngd_run_job_device into the batch buffers, where the matrices stay (ngd_fetch_matrix), then tail(0, 1,
@@ -413,4 +420,8 @@ int windows_tail(ngd_engine *e, const WinJobArgs &a, bool job_form, const char *
 // on the device instead, grp.d_keep_mean / d_keep_used [n_mat][n_gp], for the summaries (the arguments are checked)
 int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
                   uint64_t evol_model, double *mean, uint64_t *used);
+// engine_nj.hip: matrix 0 of each of the n_set sets of [n_set][n_mat][n_pairs] sums and counts, finished on the host into
+// dist0 [n_set][n_pairs] (ngd_finish's bits: what the tails that keep their matrices on the device hand out beside them)
+int tail_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,
+               uint64_t evol_model, double *dist0);
 #pragma GCC visibility pop

@@ -449,6 +449,19 @@ int ngd_launch_nj(hipStream_t st, const double *d_a, const unsigned long long *d
                   uint64_t tot_sites, uint32_t model, uint32_t threads, double *d_work, int32_t *d_child, double *d_len,
                   uint32_t *d_status);
 
+// mds.hip : classical MDS per matrix (include/ngsdist_amd.h "Classical MDS"), one workgroup per matrix
+#define NGD_MDS_MAX_IND 4096u  // d, e, v, w (8 B each) per row in LDS: 128 KiB at this many
+#define NGD_MDS_MAX_DIM 16u    // K: a wave per vector in the back-transform of a 1024-thread workgroup
+#define NGD_MDS_THREADS 1024u  // the workgroup
+#define NGD_MDS_AUX_ROWS 4u    // per vector: z and the three rows of U, ngd_nj_ld(n_ind) doubles each
+// [n_mat][n_pairs] sums and counts (d_cnt is not read when tot_sites > 0) or, `values`, the cells as they are -> d_eig
+// [n_mat][K], d_vec [n_mat][K][n_ind], d_tot [n_mat][2], d_status [n_mat]; scratch: d_work n_mat * n_ind * ngd_nj_ld(n_ind)
+// doubles, d_aux n_mat * NGD_MDS_AUX_ROWS * K * ngd_nj_ld(n_ind).  3 <= n_ind <= NGD_MDS_MAX_IND, 1 <= K <= min(n_ind - 1,
+// NGD_MDS_MAX_DIM), n_mat below 2^31 (grid.x), threads 256, 512 or 1024: the caller's to see to.  Returns a hipError_t.
+int ngd_launch_mds(hipStream_t st, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_mat, uint32_t n_ind,
+                   uint64_t tot_sites, uint32_t model, uint32_t K, uint32_t threads, double *d_work, double *d_aux, double *d_eig,
+                   double *d_vec, double *d_tot, uint32_t *d_status);
+
 // group_reduce.hip : group-mean distance matrices (ngd_set_groups, ngd_group_means_device, ngd_run_*_groups)
 // One work item: rows [r0, r1) of group pair (a, b) -- positions in group a's member list --, every column of group b
 #define NGD_GROUP_WG_CELLS 4096  // cells of a work item's rectangle, about: whole rows, at least one

@@ -17,7 +17,7 @@ KERNELS = {"auto": 0, "stream": 1, "mfma": 2, "em_faithful": 3, "em_fast": 4, "e
 OPTIONS = {"boot_partials": 1, "boot_max_bytes": 2, "boot_wg": 3, "boot_unaligned": 4, "em_batch": 5,
            "em_spill": 6, "em_spill_bytes": 7, "single_image_bytes": 8, "fixup_work": 9, "stage_piece_mib": 10,
            "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "em_exact": 15, "em_exact_cap": 16,
-           "unit_skip": 17, "em_exact_win": 18, "nj_max_bytes": 19,
+           "unit_skip": 17, "em_exact_win": 18, "nj_max_bytes": 19, "mds_max_bytes": 20,
            "debug_forge_job": 100}
 # ngd_em_exact_entry
 EM_EXACT_ENTRY = np.dtype([("i1", np.uint32), ("i2", np.uint32), ("site", np.uint64), ("t_dev", np.uint32),
@@ -545,6 +545,67 @@ class Engine:
         _check(self._L.ngd_last_nj_ms(self._h, C.byref(v)))
         return float(v.value)
 
+    # -- classical MDS: per matrix its top K eigenpairs, the two sums of its eigenvalues and a status ----
+    def _mds_out(self, lead, K, dist0_lead=None):
+        K = int(K)
+        eig = np.empty(lead + (K,), dtype=np.float64)
+        vec = np.empty(lead + (K, self.n_ind), dtype=np.float64)
+        tot = np.empty(lead + (2,), dtype=np.float64)
+        status = np.empty(lead, dtype=np.uint32)
+        dist0 = None if dist0_lead is None else np.empty(dist0_lead + (self.n_pairs,), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        return ((eig, vec, tot, status, dist0),
+                (K, eig.ctypes.data_as(dp), vec.ctypes.data_as(dp), tot.ctypes.data_as(dp), status.ctypes.data_as(C.POINTER(C.c_uint32))),
+                None if dist0 is None else dist0.ctypes.data_as(dp))
+
+    def mds(self, d_sum_ptr, d_cnt_ptr, n_mat, K, evol_model=1, tot_sites=0):
+        """classical MDS of device matrices (ngd_mds_device; raw addresses of [n_mat][n_pairs] sums and counts, as a
+        *_device call wrote them): -> (eig float64[n_mat][K], the largest eigenvalues of the double-centred matrix in
+        descending order; vec float64[n_mat][K][n], their unit vectors; tot float64[n_mat][2], the sum of all eigenvalues
+        and of the positive ones; status uint32[n_mat]); status 0 (everything NaN): a matrix with a cell that is not finite"""
+        out, args, _ = self._mds_out((int(n_mat),), K)
+        _check(self._L.ngd_mds_device(self._h, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr), int(n_mat), int(tot_sites),
+                                      int(evol_model), *args))
+        return out[:4]
+
+    def mds_values(self, d_val_ptr, n_mat, K):
+        """the same of [n_mat][n_pairs] float64 distances in device memory as they are (ngd_mds_values_device)"""
+        out, args, _ = self._mds_out((int(n_mat),), K)
+        _check(self._L.ngd_mds_values_device(self._h, C.c_void_p(d_val_ptr), int(n_mat), *args))
+        return out[:4]
+
+    def run_job_mds(self, K, block_maps=None, block_size=1, evol_model=1, tot_sites=0, dist0=True):
+        """run_job() and the MDS of its n_rep + 1 matrices on the device (ngd_run_job_mds): -> (eig (n_rep + 1, K), vec
+        (n_rep + 1, K, n), tot (n_rep + 1, 2), status (n_rep + 1,), dist0 (n_pairs,)); dist0 (None with dist0=False) is
+        matrix 0 as run_job_dist() gives it"""
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        out, args, dp = self._mds_out((n_rep + 1,), K, () if dist0 else None)
+        _check(self._L.ngd_run_job_mds(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model), *args, dp))
+        return out
+
+    def run_windows_mds(self, K, lo, hi, evol_model=1, tot_sites=0, dist0=True):
+        """run_windows() and every window's MDS (ngd_run_windows_mds): -> (eig (n_win, 1, K), vec (n_win, 1, K, n), tot
+        (n_win, 1, 2), status (n_win, 1), dist0 (n_win, n_pairs))"""
+        lo, hi, lp_, hp = self._win_args(lo, hi)
+        out, args, dp = self._mds_out((lo.size, 1), K, (lo.size,) if dist0 else None)
+        _check(self._L.ngd_run_windows_mds(self._h, lp_, hp, lo.size, int(tot_sites), int(evol_model), *args, dp))
+        return out
+
+    def run_windows_job_var_mds(self, K, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None, dist0=True):
+        """run_windows_job_var() and the MDS of every window's set (ngd_run_windows_job_var_mds): -> (eig (n_win, n_rep + 1,
+        K), vec, tot, status (n_win, n_rep + 1), dist0 (n_win, n_pairs)); the replicates of a window shorter than one block
+        have status 0"""
+        n_win, n_rep, wargs, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
+        out, args, dp = self._mds_out((n_win, n_rep + 1), K, (n_win,) if dist0 else None)
+        _check(self._L.ngd_run_windows_job_var_mds(*wargs, int(tot_sites), int(evol_model), *args, dp))
+        return out
+
+    def last_mds_ms(self):
+        """device time of the MDS kernels in the last of these calls (ngd_last_mds_ms)"""
+        v = C.c_double(0.0)
+        _check(self._L.ngd_last_mds_ms(self._h, C.byref(v)))
+        return float(v.value)
+
     def run_job_keep(self, block_maps, block_size=1):
         """ngd_run_job with the matrices left in the engine; fetch_matrix(r) copies them out one at a time"""
         a = np.ascontiguousarray(block_maps, dtype=np.uint64)
@@ -571,7 +632,8 @@ class Engine:
         maps, multiplicities, batches and jobs are served that way too) and em_exact_cap; em_exact_win (1: while em_exact is on the windowed calls
         are served too -- run_windows* under 1 or 2, run_windows_job* under 2); unit_skip (0: the plain pass of a
         one-image engine in congruent coordinates visits the k-groups of p0 + p1 + p2 too: plain_pass_kgroups());
-        nj_max_bytes (device scratch of the neighbour-joining kernel, 0 = 2 GB: the matrices a launch takes)"""
+        nj_max_bytes (device scratch of the neighbour-joining kernel, 0 = 2 GB: the matrices a launch takes);
+        mds_max_bytes (the same for the classical-MDS kernel)"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self
 
@@ -865,6 +927,51 @@ def nj_newick(child, length, labels, support=None):
     buf = C.create_string_buffer(int(need) + 1)
     _check(min(0, int(L.ngd_nj_newick(*args, buf, int(need)))))
     return buf.raw[:int(need)]
+
+
+def mds_max_ind():
+    """the most individuals the device's classical MDS serves (ngd_mds_max_ind)"""
+    return int(_lib.load().ngd_mds_max_ind())
+
+
+def mds_max_dim():
+    """the most dimensions K of classical MDS, device and host (ngd_mds_max_dim)"""
+    return int(_lib.load().ngd_mds_max_dim())
+
+
+def mds_host(values, n_ind, K):
+    """classical MDS in plain host arithmetic (ngd_mds_host), the device form's twin: values float64[..., n_pairs] ->
+    (eig float64[..., K], vec float64[..., K, n], tot float64[..., 2], status uint32[...])"""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    n_ind, K = int(n_ind), int(K)
+    if v.ndim < 1 or v.shape[-1] != n_ind * (n_ind - 1) // 2:
+        raise ValueError("values: expected [..., n_pairs]")
+    lead = v.shape[:-1]
+    n_mat = int(np.prod(lead, dtype=np.int64))
+    Kc = max(K, 0)
+    eig = np.empty(lead + (Kc,), dtype=np.float64)
+    vec = np.empty(lead + (Kc, n_ind), dtype=np.float64)
+    tot = np.empty(lead + (2,), dtype=np.float64)
+    status = np.empty(lead, dtype=np.uint32)
+    dp = C.POINTER(C.c_double)
+    _check(_lib.load().ngd_mds_host(v.ctypes.data_as(dp), n_mat, n_ind, Kc, eig.ctypes.data_as(dp), vec.ctypes.data_as(dp),
+                                    tot.ctypes.data_as(dp), status.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return eig, vec, tot, status
+
+
+def mds_coords(eig, vec):
+    """the coordinates of eigenpairs (ngd_mds_coords): eig float64[..., K], vec float64[..., K, n] -> float64[..., n, K],
+    vec[k][i] * sqrt(max(eig[k], 0))"""
+    e = np.ascontiguousarray(eig, dtype=np.float64)
+    v = np.ascontiguousarray(vec, dtype=np.float64)
+    if v.ndim < 2 or e.shape != v.shape[:-1]:
+        raise ValueError("eig, vec: expected [..., K] and [..., K, n]")
+    lead, K, n = v.shape[:-2], v.shape[-2], v.shape[-1]
+    out = np.empty(lead + (n, K), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    _check(_lib.load().ngd_mds_coords(e.ctypes.data_as(dp), v.ctypes.data_as(dp), int(np.prod(lead, dtype=np.int64)), n, K,
+                                      out.ctypes.data_as(dp)))
+    return out
 
 
 def score_congruence(score):
