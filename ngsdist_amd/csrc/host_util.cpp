@@ -1009,7 +1009,7 @@ int64_t ngd_nj_newick(const int32_t *child, const double *len, uint64_t n_ind, c
 
 // ---- classical MDS (--mds): the contract of include/ngsdist_amd.h "Classical MDS" in plain host arithmetic, matrix by
 // matrix, by the method of mds.hip: the double-centred matrix, Householder tridiagonalisation (the reflectors stay in the
-// rows they eliminate), every eigenvalue of the tridiagonal matrix by bisection on Sturm counts, the top K vectors by
+// rows they eliminate; each one's norm from its row scaled by a power of two, a negligible row tail left alone), every eigenvalue of the tridiagonal matrix by bisection on Sturm counts, the top K vectors by
 // inverse iteration with modified Gram-Schmidt, and the reflectors applied in reverse ----
 namespace {
 const uint32_t kMdsMaxDim = 16;  // ngd_mds_max_dim()
@@ -1097,22 +1097,39 @@ void mds_one(const double *val, uint64_t n, uint32_t K, double *eig, double *vec
   grand /= (double)n;
   for (uint64_t a = 0; a < n; a++)
     for (uint64_t b = 0; b < n; b++) S[a * n + b] = (S[a * n + b] - (w[a] + w[b])) + grand;
+  // a row tail of the trailing block no larger than eps^2 max|B| counts as eliminated (a perturbation of B far below the
+  // method's own eps max|B|): the residue of a matrix of few distinct rows shrinks by about eps a step, and followed to the
+  // end of the normal range its bits would depend on how far away that end is -- on the scale of the cells
+  double bnorm = 0.0;
+  for (uint64_t i = 0; i < n * n; i++) bnorm = std::fmax(bnorm, std::fabs(S[i]));
+  const double negl = bnorm * kMdsEps * kMdsEps;
   // T = Q^T B Q: step k eliminates row / column k beyond k + 1; row k keeps tau (at k) and v (beyond, v[k + 1] = 1)
   for (uint64_t k = 0; k + 2 < n; k++) {
     double *x = S + k * n;
     const double alpha = x[k + 1];
-    double ss = 0.0;
-    for (uint64_t c = k + 2; c < n; c++) ss += x[c] * x[c];
+    double big = 0.0;
+    for (uint64_t c = k + 2; c < n; c++) big = std::fmax(big, std::fabs(x[c]));
     d[k] = x[k];
-    if (!(ss > 0.0)) {  // nothing to eliminate: H = I
+    if (!(big > negl)) {  // nothing to eliminate: H = I
       e[k] = alpha;
       x[k] = 0.0;
       x[k + 1] = 1.0;
       for (uint64_t c = k + 2; c < n; c++) x[c] = 0.0;
       continue;
     }
-    const double beta = -std::copysign(std::sqrt(alpha * alpha + ss), alpha), tau = (beta - alpha) / beta, sc = 1.0 / (alpha - beta);
-    e[k] = beta;
+    // the norm from the row scaled by a power of two to a largest magnitude in [1, 2) (exact; LAPACK dlarfg's remedy): the
+    // squares of a row near 1e-154 and below -- the rounding residue of a matrix of few distinct rows gets there -- would
+    // leave the normal range, and tau with them 2 / v^T v
+    big = std::fmax(big, std::fabs(alpha));
+    const int ex = std::isfinite(big) ? std::ilogb(big) : 0;
+    const double as = std::scalbn(alpha, -ex);
+    double ss = 0.0;
+    for (uint64_t c = k + 2; c < n; c++) {
+      x[c] = std::scalbn(x[c], -ex);
+      ss += x[c] * x[c];
+    }
+    const double beta = -std::copysign(std::sqrt(as * as + ss), as), tau = (beta - as) / beta, sc = 1.0 / (as - beta);
+    e[k] = std::scalbn(beta, ex);
     x[k] = tau;
     x[k + 1] = 1.0;
     for (uint64_t c = k + 2; c < n; c++) x[c] *= sc;

@@ -8,9 +8,13 @@
 // the tridiagonal matrix (d, e), the current reflector v and the vector w of the rank-2 update live in LDS, 32 bytes a row.
 //   fill        both triangles of A = -0.5 d^2 from the pairs (the cells as they are, or finished by group_cell); a cell
 //               that is not finite ends the matrix (status 0).  Column means, one thread per column; centred in place
-//   tridiagonal n - 2 Householder steps on the trailing block, each: the reflector of row k (its norm by the workgroup's
-//               tree) -- it stays in row k, tau on the diagonal --, p = tau S v with a wave per row and lanes along it,
-//               w = p - (tau/2)(p.v) v, then S -= v w^T + w v^T on both triangles (so that every row stays contiguous)
+//   tridiagonal n - 2 Householder steps on the trailing block, each: the reflector of row k -- the workgroup's maximum of
+//               the row's tail first: a tail no larger than eps^2 max|B| is left alone (H = I), any other is scaled by a
+//               power of two to a largest magnitude in [1, 2) before its norm is taken by the workgroup's tree (LAPACK
+//               dlarfg's remedy: no square leaves the normal range, whatever the scale of the cells, so tau = 2 / v^T v
+//               to rounding and H is orthogonal) -- it stays in row k, tau on the diagonal --, p = tau S v with a wave per
+//               row and lanes along it, w = p - (tau/2)(p.v) v, then S -= v w^T + w v^T on both triangles (so that every
+//               row stays contiguous)
 //   eigenvalues all n of T, scaled by a power of two into [1, 2), by bisection on Sturm counts, one thread per eigenvalue
 //   vectors     the top K of T by inverse iteration: a lane per vector solves (T - shift)x = x by LU with partial pivoting
 //               (its factors in device scratch), wave 0 then orthonormalises the vectors in order; three rounds
@@ -150,11 +154,19 @@ __global__ __launch_bounds__(NGD_MDS_THREADS) void k_mds(const double *__restric
     part += acc;
   }
   const double grand = mds_wg_sum(part, slot_a, lane, wave, n_waves) / (double)n;  // (its barrier publishes w)
+  double bmax = 0.0;
   for (uint32_t a = wave; a < n; a += n_waves) {
     const double wa = w[a];
-    for (uint32_t b = lane; b < n; b += 64) S[(uint64_t)a * ld + b] = (S[(uint64_t)a * ld + b] - (wa + w[b])) + grand;
+    for (uint32_t b = lane; b < n; b += 64) {
+      const double x = (S[(uint64_t)a * ld + b] - (wa + w[b])) + grand;
+      S[(uint64_t)a * ld + b] = x;
+      bmax = fmax(bmax, fabs(x));
+    }
   }
-  __syncthreads();
+  // a row tail no larger than eps^2 max|B| counts as eliminated (a perturbation far below the method's own eps max|B|): the
+  // residue of a matrix of few distinct rows shrinks by about eps a step, and followed to the end of the normal range its
+  // bits would depend on the scale of the cells.  (The maximum's barrier ends the reads of w)
+  const double negl = mds_wg_max(bmax, slot_b, lane, wave, n_waves) * (MDS_EPS * MDS_EPS);
   for (uint32_t a = tid; a < n; a += nt) w[a] = 0.0;
   __syncthreads();
 
@@ -162,25 +174,33 @@ __global__ __launch_bounds__(NGD_MDS_THREADS) void k_mds(const double *__restric
   for (uint32_t k = 0; k + 2 < n; k++) {
     double *rowk = S + (uint64_t)k * ld;
     // the reflector: H = I - tau v v^T, v[k + 1] = 1, H x = beta e_1
-    double ss = 0.0;
-    for (uint32_t c = k + 2 + tid; c < n; c += nt) {
-      const double x = rowk[c];
-      ss += x * x;
-    }
+    double big = 0.0;
+    for (uint32_t c = k + 2 + tid; c < n; c += nt) big = fmax(big, fabs(rowk[c]));
     const double alpha = rowk[k + 1], dk = rowk[k];
-    ss = mds_wg_sum(ss, slot_a, lane, wave, n_waves);
-    if (!(ss > 0.0)) {  // nothing to eliminate (the whole workgroup alike): H = I
+    big = mds_wg_max(big, slot_b, lane, wave, n_waves);
+    if (!(big > negl)) {  // nothing to eliminate (the whole workgroup alike): H = I
       if (!tid) { d[k] = dk; e[k] = alpha; rowk[k] = 0.0; }
-      __syncthreads();  // (the next step's sum takes the same slots)
+      __syncthreads();  // (the next step's maximum takes the same slots)
       continue;
     }
-    const double beta = -copysign(sqrt(alpha * alpha + ss), alpha), tau = (beta - alpha) / beta, sc = 1.0 / (alpha - beta);
+    // the norm from the row scaled by a power of two to a largest magnitude in [1, 2) (exact; LAPACK dlarfg's remedy): the
+    // squares of a row near 1e-154 and below would leave the normal range, and tau with them 2 / v^T v
+    big = fmax(big, fabs(alpha));
+    const int ex = isfinite(big) ? ilogb(big) : 0;
+    const double as = scalbn(alpha, -ex);
+    double ss = 0.0;
+    for (uint32_t c = k + 2 + tid; c < n; c += nt) {
+      const double x = scalbn(rowk[c], -ex);
+      ss += x * x;
+    }
+    ss = mds_wg_sum(ss, slot_a, lane, wave, n_waves);
+    const double beta = -copysign(sqrt(as * as + ss), as), tau = (beta - as) / beta, sc = 1.0 / (as - beta);
     for (uint32_t c = k + 1 + tid; c < n; c += nt) {
-      const double vv = c == k + 1 ? 1.0 : rowk[c] * sc;
+      const double vv = c == k + 1 ? 1.0 : scalbn(rowk[c], -ex) * sc;
       v[c] = vv;
       rowk[c] = vv;
     }
-    if (!tid) { d[k] = dk; e[k] = beta; rowk[k] = tau; v[k] = 0.0; w[k] = 0.0; }
+    if (!tid) { d[k] = dk; e[k] = scalbn(beta, ex); rowk[k] = tau; v[k] = 0.0; w[k] = 0.0; }
     __syncthreads();
     // p = tau S v: a wave per row of the trailing block, two columns per lane and load, MDS_LOADS loads issued before the
     // first is used.  No load is conditional: a pair of columns past the row is clamped to its last pair and masked; the

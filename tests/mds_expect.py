@@ -70,6 +70,53 @@ def few(n):
     return v
 
 
+def pairs_of(P):
+    """the Euclidean distances of the rows of P [n][dim], in pair order; a dimension at a time, so that two equal rows are
+    exactly 0 apart and, in one dimension, a distance is |x_a - x_b| with no rounding beyond the subtraction's"""
+    n = P.shape[0]
+    d2 = np.zeros((n, n))
+    for j in range(P.shape[1]):
+        d2 += (P[:, j, None] - P[None, :, j]) ** 2
+    return np.sqrt(d2)[np.triu_indices(n, 1)]
+
+
+DUP = {"halves": 0, "quarter": 1, "site": 2, "sites": 3, "protos": 4, "exact": 5}  # the matrices of duplicates(n)
+N_DUP = len(DUP)
+
+
+def duplicates(n, seed=0):
+    """six matrices of points with few distinct rows (a window with one or two variable sites, clones): B has rank 1 to 3
+    and the eigenvalue 0 about n times over.  Two groups n/2 | n/2 at +-0.5; n/4 at 1 and the rest at 0; one site of
+    genotypes 0/1/2 at random; two such sites; three prototype points in the plane, individual i taking prototype i mod 3;
+    the points (1, -1, 0, ..., 0), whose B is [[1, -1], [-1, 1]] in a corner of zeros -- at n a power of two every cell of
+    it is exact, it is tridiagonal as it stands and its spectrum is {2, 0, ...}"""
+    rng = np.random.default_rng(4000 + 31 * seed + n)
+    x = np.zeros((N_DUP, n, 2))
+    x[DUP["halves"], :, 0] = np.where(np.arange(n) < n // 2, 0.5, -0.5)
+    x[DUP["quarter"], :n // 4, 0] = 1.0
+    x[DUP["site"], :, 0] = rng.integers(0, 3, size=n)
+    x[DUP["sites"]] = rng.integers(0, 3, size=(n, 2))
+    x[DUP["protos"]] = rng.normal(size=(3, 2))[np.arange(n) % 3]
+    x[DUP["exact"], 0, 0], x[DUP["exact"], 1, 0] = 1.0, -1.0
+    return np.stack([pairs_of(P) for P in x])
+
+
+GAPS = [1e-4, 1e-7, 1e-10, 1e-13, 0.0]
+
+
+def planted_spectrum(gap):
+    return np.array([1.0 + gap, 1.0, 0.25, 0.25 * (1.0 - gap)])
+
+
+def near_degenerate(n, gap, seed=0):
+    """the distances of the points Q diag(sqrt(s)): Q four orthonormal columns orthogonal to the ones vector (QR of a
+    centred Gaussian n x 4), s = planted_spectrum(gap) -- B = Q diag(s) Q^T, so its eigenvalues are s and n - 4 zeros by
+    construction: two pairs `gap` apart, relatively, which the shift rule and Gram-Schmidt have to hold apart"""
+    G = np.random.default_rng(5000 + 31 * seed + n).normal(size=(n, 4))
+    Q = np.linalg.qr(G - G.mean(axis=0))[0]
+    return pairs_of(Q * np.sqrt(planted_spectrum(gap)))
+
+
 _spectra = {}
 
 
@@ -119,6 +166,29 @@ def check_matrix(v, n, K, eig, vec, tot, sign=True, require_gaps=False):
     for name, x in fig.items():
         assert x <= 1, "%s: %.3g of its bound" % (name, x)
     return fig
+
+
+def check_subspace(v, n, vec, idx):
+    """the vectors `idx` of a matrix span what numpy's do: 1 - (the smallest singular value of vec[idx] U[idx]^T), in units
+    of TOL.  Holds where the eigenvalues `idx` lie, by numpy alone, GAP * S or more from all others (asserted here),
+    however close they lie to each other"""
+    B, lam, U = spectrum(v, n)
+    S = np.abs(lam).max()
+    idx = list(idx)
+    away = np.abs(np.delete(lam, idx)[None, :] - lam[idx][:, None]).min()
+    assert away >= GAP * S, "eigenvalues %s lie %.3g S from the rest" % (idx, away / S)
+    x = (1 - np.linalg.svd(vec[idx] @ U[idx].T, compute_uv=False).min()) / TOL
+    assert x <= 1, "subspace %s: %.3g of its bound" % (idx, x)
+    return x
+
+
+def check_planted_spectrum(v, n, gap, eig):
+    """the top four eigenvalues of near_degenerate(n, gap) against the planted ones, in units of TOL * S"""
+    s = planted_spectrum(gap)
+    assert len(eig) >= 4
+    x = np.abs(eig[:4] - s).max() / (TOL * s[0])
+    assert x <= 1, "planted eigenvalues: %.3g of the bound" % x
+    return x
 
 
 def check_bad(eig, vec, tot, status):
