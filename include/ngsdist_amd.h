@@ -875,6 +875,67 @@ int ngd_run_windows_job_var_mds(ngd_engine *e, const uint64_t *win_lo, const uin
                                 double *tot, uint32_t *status, double *dist0);
 /* device time (HIP events) of the MDS kernels in the last of these calls, summed over its launches */
 int ngd_last_mds_ms(const ngd_engine *e, double *ms);
+/* Alignment of bootstrap replicates (added under ABI 6): an MDS solution is defined up to an orthogonal transformation --
+ * signs are arbitrary, axes of close eigenvalues rotate into each other from replicate to replicate -- so the replicates
+ * of a set are rotated onto its matrix 0 (orthogonal Procrustes) before anything is averaged over them.
+ * A set is n_mat = n_rep + 1 matrices with their outputs eig[K], vec[K][n], status; X_r[i][k] = vec_r[k][i] *
+ * sqrt(max(eig_r[k], 0)), stored [K][n] (axis by axis).
+ *   No translation step: B 1 = 0, so every column of X with a non-zero eigenvalue is centred already, up to rounding.
+ *   No scaling step: the spread of the replicates is the quantity being estimated.
+ *   for every replicate r >= 1 with status 1, where matrix 0 has status 1 too:
+ *     M = X_r^T X_0   (K x K)
+ *     Q = U V^T for M = U S V^T, the orthogonal polar factor of M; reflections are allowed (signs are arbitrary)
+ *     Y_r = X_r Q,   fit_r = |Y_r - X_0|_F^2   (not normalised)
+ *   Y_0 = X_0, fit_0 = 0.
+ *   A replicate with status 0, and every matrix of a set whose matrix 0 has status 0, has Y and fit a positive quiet NaN:
+ *   the summaries leave it out and count it as left out, as ngd_boot_stats_* treat every cell that is not finite.
+ * Where M is singular (a zero column of coordinates from eig <= 0, all-zero matrices, K above the rank) Q is not unique,
+ * and only this is pinned: |Q Q^T - I| <= 1e-9; fit_r within 1e-9 (|X_r|^2 + |X_0|^2) of |X_r|^2 + |X_0|^2 - 2 SUM sigma;
+ * bits that are a function of (X_r, X_0, K) alone.  Where sigma_min(M) >= 1e-3 sigma_max(M), Y_r agrees with any other
+ * solver's to 1e-9 max(|X_0|, |X_r|) (the polar factor moves by 2 |dM| / (sigma_{K-1} + sigma_K): three orders of margin
+ * at rounding level).
+ * Method: the K^2 sums of M as fixed trees; M scaled by a power of two to a largest magnitude in [1, 2) (so that scaling
+ * both configurations by a power of two scales Y and fit exactly); a one-sided (Hestenes) Jacobi on its columns in the
+ * cyclic order (0,1), (0,2), .., (K-2,K-1), at most 64 sweeps, a pair left alone when |g| <= eps sqrt(a b) or when either
+ * column's squared norm is no more than 1e-24 of the largest at the sweep's start; the columns that end no longer than
+ * 1e-12 of the longest are replaced: e_0, e_1, .. in order, each orthogonalised twice against the finished columns, the
+ * first whose residual exceeds 0.5 / sqrt(K) taken.  Device and host twin follow the same method and agree to the
+ * tolerances above, not bit for bit (their sums run in different orders).
+ * Summary of a set: the cells [K][n] of Y followed by the [K] eigenvalues of the same matrices, n_cells = K (n + 1); the
+ * value at position 0 is matrix 0's, positions 1 .. n_rep the replicates' (the eigenvalues of a matrix left out are NaN
+ * too); summarised by the definitions of "Bootstrap summaries" bit for bit: stats [NGD_BOOT_NSTAT][n_cells]; used is the
+ * number of replicates that went in. */
+/* The contract in plain host arithmetic, of eig [n_set][n_mat][K], vec [n_set][n_mat][K][n_ind] and status
+ * [n_set][n_mat] (NULL: every matrix has status 1) as the calls above give them: aligned [n_set][n_mat][K][n_ind], fit
+ * [n_set][n_mat].  NGD_E_INVALID: a null pointer, n_set or n_mat 0, n_ind < 3, K = 0, K > n_ind - 1 or above
+ * ngd_mds_max_dim(). */
+int ngd_mds_align_host(const double *eig, const double *vec, const uint32_t *status, uint64_t n_set, uint64_t n_mat, uint64_t n_ind,
+                       uint32_t K, double *aligned, double *fit);
+/* The alignment alone, on the device (one workgroup per matrix, mds_align.hip), of coordinates as they are: d_coords
+ * [n_set][n_mat][K][n] float64 in device memory (read only); status [n_set][n_mat] in HOST memory, NULL: every matrix has
+ * status 1; n_ind is the engine's.  Outputs in host memory as above.  NGD_E_INVALID, before anything is launched: a null
+ * pointer, n_set or n_mat 0, n_set * n_mat of 2^31 and more, n_ind < 3, K = 0, K > n_ind - 1 or above ngd_mds_max_dim(). */
+int ngd_mds_align_values_device(ngd_engine *e, const void *d_coords, const uint32_t *status, uint64_t n_set, uint64_t n_mat,
+                                uint32_t K, double *aligned, double *fit);
+/* ngd_run_job_mds / ngd_run_windows_job_var_mds, then the alignment of every set and its summary, all on the device: K (n
+ * + 1) + 2 numbers of matrix 0, 5 K (n + 1) statistics and n_rep + 1 fits per set cross the link, whatever n_rep.  Plans,
+ * fix-up, options and refusals are the _mds sibling's, then those of the summaries: n_rep 0, ci outside (0, 1), n_rep above
+ * ngd_boot_stats_max_rep(); a refused call leaves outputs and engine as they were.  Outputs: eig0 [n_set][K], vec0
+ * [n_set][K][n], tot0 [n_set][2] -- matrix 0's, the _mds sibling's bit for bit --, status [n_set][n_rep + 1], stats
+ * [n_set][NGD_BOOT_NSTAT][K (n + 1)], used [n_set] (the replicates that went in), fit [n_set][n_rep + 1]; aligned, unless
+ * NULL, receives [n_set][n_rep + 1][K][n]; dist0, unless NULL, [n_set][n_pairs] as in the sibling.  aligned and fit are
+ * ngd_mds_align_values_device()'s on the sibling's coordinates, stats ngd_boot_stats_values_device()'s on the aligned
+ * cells and the eigenvalues, bit for bit. */
+int ngd_run_job_mds_align(ngd_engine *e, const uint64_t *block_maps, uint32_t n_rep, uint64_t n_blocks, uint64_t block_size,
+                          uint64_t tot_sites, uint64_t evol_model, uint32_t K, double ci, double *eig0, double *vec0, double *tot0,
+                          uint32_t *status, double *stats, uint64_t *used, double *fit, double *aligned, double *dist0);
+int ngd_run_windows_job_var_mds_align(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win,
+                                      const uint64_t *block_maps, uint64_t maps_len, const uint64_t *map_off, uint32_t n_rep,
+                                      uint64_t block_size, uint64_t tot_sites, uint64_t evol_model, uint32_t K, double ci,
+                                      double *eig0, double *vec0, double *tot0, uint32_t *status, double *stats, uint64_t *used,
+                                      double *fit, double *aligned, double *dist0);
+/* device time (HIP events) of the two alignment kernels in the last of these calls, summed over its launches */
+int ngd_last_mds_align_ms(const ngd_engine *e, double *ms);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

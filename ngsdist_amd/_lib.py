@@ -96,6 +96,8 @@ EXPORTS = [
     "ngd_run_windows_job_var_nj", "ngd_last_nj_ms", "ngd_nj_support", "ngd_nj_newick",
     "ngd_mds_max_ind", "ngd_mds_max_dim", "ngd_mds_host", "ngd_mds_coords", "ngd_mds_values_device", "ngd_mds_device",
     "ngd_run_job_mds", "ngd_run_windows_mds", "ngd_run_windows_job_var_mds", "ngd_last_mds_ms",
+    "ngd_mds_align_host", "ngd_mds_align_values_device", "ngd_run_job_mds_align", "ngd_run_windows_job_var_mds_align",
+    "ngd_last_mds_align_ms",
 ]
 
 NSTAT = 5  # NGD_BOOT_NSTAT: est, mean, sd, lo, hi
@@ -255,6 +257,12 @@ def load():
     L.ngd_run_windows_mds.argtypes = [vp, u64p, u64p, u64, u64, u64, u32, dp, dp, dp, u32p, dp]
     L.ngd_run_windows_job_var_mds.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, u32, u64, u64, u64, u32, dp, dp, dp, u32p, dp]
     L.ngd_last_mds_ms.argtypes = [vp, dp]
+    L.ngd_mds_align_host.argtypes = [dp, dp, u32p, u64, u64, u64, u32, dp, dp]
+    L.ngd_mds_align_values_device.argtypes = [vp, vp, u32p, u64, u64, u32, dp, dp]
+    L.ngd_run_job_mds_align.argtypes = [vp, u64p, u32, u64, u64, u64, u64, u32, C.c_double, dp, dp, dp, u32p, dp, u64p, dp, dp, dp]
+    L.ngd_run_windows_job_var_mds_align.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, u32, u64, u64, u64, u32, C.c_double,
+                                                    dp, dp, dp, u32p, dp, u64p, dp, dp, dp]
+    L.ngd_last_mds_align_ms.argtypes = [vp, dp]
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

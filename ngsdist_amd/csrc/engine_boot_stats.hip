@@ -6,14 +6,9 @@
 
 uint32_t ngd_boot_stats_max_rep(void) { return NGD_BOOT_MAX_MAT - 1; }
 
-// the two ranks' fractions of the interval
-struct BootCi {
-  double p_lo, p_hi;
-};
-
 // what every call that summarises refuses, before anything is launched; the interval's two ranks' fractions on the way
-static int boot_refuse(const ngd_engine *e, const void *stats, const void *used, uint64_t n_mat, double ci, uint64_t tot_sites,
-                       uint64_t evol_model, bool groups, const char *who, BootCi &out) {
+int boot_refuse(const ngd_engine *e, const void *stats, const void *used, uint64_t n_mat, double ci, uint64_t tot_sites,
+                uint64_t evol_model, bool groups, const char *who, BootCi &out) {
   const std::string w(who);
   if (!e) return fail(NGD_E_INVALID, w + ": null engine");
   if (!stats || !used) return fail(NGD_E_INVALID, w + ": null output");
@@ -34,7 +29,7 @@ static int boot_refuse(const ngd_engine *e, const void *stats, const void *used,
 // adds up its groups of windows).
 // [n_set][n_mat][n_cells] device matrices -> stats / used in host memory; d_cnt and the two arguments of ngd_finish for sums
 // and counts, `values` for cells as they are (the arguments are checked)
-static int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
+int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
                 uint64_t n_cells, uint64_t tot_sites, uint64_t evol_model, BootCi ci, double *stats, uint64_t *used) {
   auto &b = e->bst;
   if (!n_cells) return NGD_OK;

@@ -44,7 +44,11 @@
 //    matrix -- a line "eig" with the K largest eigenvalues of the double-centred matrix, a line "total" with the sum of all
 //    eigenvalues and of the positive ones, a line per individual with its label and K coordinates, an empty line; fields
 //    are separated by tabs and every number is printed as "%.10e", "nan" throughout for a matrix with a cell that is not
-//    finite --, <out> matrix 0 of every set; one GPU, the whole data set resident);
+//    finite --, <out> matrix 0 of every set; one GPU, the whole data set resident), --mds_align [--mds_ci X] (with --mds K and
+//    --n_boot_rep or --win_boot_rep: the replicates' coordinates are rotated onto matrix 0's on the device and summarised
+//    there: <out>.mds holds matrix 0 of every set alone, <out>.mds_mean / _sd / _lo / _hi the replicates' statistics in the
+//    same blocks without the "total" line, <out>.mds_fit per set the replicates that went in and every replicate's squared
+//    distance from matrix 0 after the rotation);
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
@@ -52,7 +56,7 @@
 // Layout: options (Pars, parse_cmd_args), text helpers, the readers and the Loader; then what the run reads beside the
 // genotypes (read_labels, read_positions, make_windows: WindowList), device_fit (one device or site ranges), the matrix
 // output every mode prints through (Writer, MatrixOut::emit), the jobs the modes share (draw_window_maps, draw_job_maps,
-// format_grown, for_window_groups) and one function per output mode -- site_range_matrices, trees, coordinates, bootstrap_summaries,
+// format_grown, for_window_groups) and one function per output mode -- site_range_matrices, trees, coordinates, aligned_coordinates, bootstrap_summaries,
 // group_means, window_matrices, plain_matrices; main(), last, is the run's outline and picks one of them.
 #include <fcntl.h>
 #include <getopt.h>
@@ -111,6 +115,8 @@
 #pragma weak ngd_run_job_mds
 #pragma weak ngd_run_windows_mds
 #pragma weak ngd_run_windows_job_var_mds
+#pragma weak ngd_run_job_mds_align  // (--mds_align)
+#pragma weak ngd_run_windows_job_var_mds_align
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -188,6 +194,12 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // --mds).  Not in the reference, whose users run R's cmdscale on <out>.
   bool mds = false;
   uint64_t mds_dim = 0;
+  // --mds_align [--mds_ci X]: with --mds K and replicates, the replicates' coordinates are rotated onto matrix 0's
+  // (orthogonal Procrustes) and summarised on the device (ngd_run_*_mds_align): <out>.mds holds matrix 0 of every set,
+  // <out>.mds_mean / _sd / _lo / _hi the statistics of the aligned coordinates and of the eigenvalues, <out>.mds_fit per set
+  // the replicates that went in and their fits.  Not in the reference, whose users run vegan::procrustes in a loop.
+  bool mds_align = false, mds_ci_set = false;
+  double mds_ci = 0.95;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -304,6 +316,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"boot_ci", required_argument, nullptr, 1022},
                                  {"nj", no_argument, nullptr, 1023},
                                  {"mds", required_argument, nullptr, 1024},
+                                 {"mds_align", no_argument, nullptr, 1025},
+                                 {"mds_ci", required_argument, nullptr, 1026},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -356,6 +370,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
         if (end == optarg || *end || optarg[0] == '-') die(__FUNCTION__, "the number of dimensions (--mds K) must be a whole number!");
         break;
       }
+      case 1025: p.mds_align = true; break;
+      case 1026: p.mds_ci_set = true; p.mds_ci = atof(optarg); break;
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -408,6 +424,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.boot_stats) fprintf(stderr, "\tboot_stats: true\n\tboot_ci: %f\n\n", p.boot_ci);
     if (p.nj) fprintf(stderr, "\tnj: true\n\n");
     if (p.mds) fprintf(stderr, "\tmds: %lu\n\n", (unsigned long)p.mds_dim);
+    if (p.mds_align) fprintf(stderr, "\tmds_align: true\n\tmds_ci: %f\n\n", p.mds_ci);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -494,6 +511,13 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.n_ind < 3) die(__FUNCTION__, "classical MDS (--mds) needs three individuals or more (--n_ind)!");
     if (p.mds_dim < 1 || p.mds_dim > p.n_ind - 1 || p.mds_dim > ngd_mds_max_dim())
       die(__FUNCTION__, ("the number of dimensions (--mds K) must lie between 1 and min(n_ind - 1, " + std::to_string(ngd_mds_max_dim()) + ")!").c_str());
+  }
+  if (p.mds_ci_set && !p.mds_align) die(__FUNCTION__, "interval coverage (--mds_ci) requires aligned replicates (--mds_align)!");
+  if (p.mds_align) {
+    if (!p.mds) die(__FUNCTION__, "aligned replicates (--mds_align) require classical MDS (--mds K)!");
+    if (!(p.mds_ci > 0.0 && p.mds_ci < 1.0)) die(__FUNCTION__, "interval coverage (--mds_ci) must lie between 0 and 1!");
+    if (p.n_boot_rep < 1 && p.win_boot_rep < 1)
+      die(__FUNCTION__, "aligned replicates (--mds_align) require bootstrap replicates (--n_boot_rep or --win_boot_rep)!");
   }
 }
 
@@ -1365,6 +1389,12 @@ void check_summaries_and_trees(const Pars &p) {
     if (p.n_ind > ngd_mds_max_ind())
       die(kMain, "too many individuals for classical MDS (--mds): a matrix's tridiagonal form stays in on-chip memory!");
   }
+  if (p.mds_align) {
+    if (!ngd_boot_stats_max_rep || !ngd_run_job_mds_align || !ngd_run_windows_job_var_mds_align)
+      die(kMain, "this build of the engine has no aligned replicates (--mds_align)!");
+    if (std::max<uint64_t>(p.n_boot_rep, p.win_boot_rep) > ngd_boot_stats_max_rep())
+      die(kMain, "too many bootstrap replicates for aligned replicates (--mds_align): a cell's replicates stay in on-chip memory!");
+  }
 }
 
 // The windows of --win_size / --win_bp, and what the positions file says about the sites they hold.
@@ -1973,6 +2003,102 @@ void coordinates(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng
   if (fclose(mf) != 0) die(kMain, "cannot write coordinates output file!");
 }
 
+// ---- aligned replicates (--mds K --mds_align): the replicates of every set stay on the device, which rotates their
+// coordinates onto matrix 0's and reduces every coordinate and eigenvalue to five statistics (ngd_run_*_mds_align).  <out>
+// and <out>.mds take matrix 0 of every set (--mds' blocks); <out>.mds_mean / _sd / _lo / _hi the other statistics in the same
+// blocks -- "eig" and the statistic of the K eigenvalues, a line per individual with its label and the statistic of its K
+// aligned coordinates, an empty line; no "total" line --; <out>.mds_fit a line per set: the replicates that went in, then
+// every replicate's fit ("nan": left out) ----
+void aligned_coordinates(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], MatrixOut &out) {
+  const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep, n_mat = R + 1, n = p.n_ind, n_comb = out.n_comb;
+  const uint32_t K = (uint32_t)p.mds_dim;
+  const uint64_t n_cells = K * (n + 1);
+  static const char *const kSuffix[NGD_BOOT_NSTAT + 1] = {".mds", ".mds_mean", ".mds_sd", ".mds_lo", ".mds_hi", ".mds_fit"};
+  FILE *sf[NGD_BOOT_NSTAT + 1];
+  for (int k = 0; k <= NGD_BOOT_NSTAT; k++)
+    if (!(sf[k] = fopen((std::string(p.out) + kSuffix[k]).c_str(), "w"))) die(kMain, "cannot open coordinates output file!");
+  std::vector<double> xy(n * K);
+  uint64_t n_bad = 0;
+  // one set: matrix 0's block through emit(), then its blocks and its line of fits
+  auto write_set = [&](uint64_t w, const char *name, const double *m0, const double *eig0, const double *vec0, const double *tot0,
+                       const uint32_t *st, const double *stats, uint64_t used, const double *fit) {
+    out.emit(w, nullptr, nullptr, nullptr, 0, m0, 0, name);
+    if (ngd_mds_coords(eig0, vec0, 1, n, K, xy.data())) die(kLambda, "cannot derive the coordinates!");
+    for (uint64_t r = 0; r < n_mat; r++) n_bad += st[r] == 0;
+    for (int k = 0; k < NGD_BOOT_NSTAT; k++) {
+      FILE *f = sf[k];
+      const double *cell = stats + k * n_cells;  // [K][n] coordinates, then [K] eigenvalues
+      bool ok = fputs("eig", f) >= 0;
+      for (uint32_t d = 0; d < K; d++) ok = ok && fprintf(f, "\t%.10e", k ? cell[K * n + d] : eig0[d]) > 0;
+      ok = ok && fputc('\n', f) != EOF;
+      if (!k) ok = ok && fprintf(f, "total\t%.10e\t%.10e\n", tot0[0], tot0[1]) > 0;
+      for (uint64_t i = 0; i < n; i++) {
+        ok = ok && fputs(out.label_ptr[i], f) >= 0;
+        for (uint32_t d = 0; d < K; d++) ok = ok && fprintf(f, "\t%.10e", k ? cell[d * n + i] : xy[i * K + d]) > 0;
+        ok = ok && fputc('\n', f) != EOF;
+      }
+      if (!ok || fputc('\n', f) == EOF) die(kLambda, "cannot write coordinates output file!");
+    }
+    bool ok = fprintf(sf[NGD_BOOT_NSTAT], "%lu", (unsigned long)used) > 0;
+    for (uint64_t r = 1; r < n_mat; r++)
+      ok = ok && (std::isnan(fit[r]) ? fputs("\tnan", sf[NGD_BOOT_NSTAT]) >= 0 : fprintf(sf[NGD_BOOT_NSTAT], "\t%.10e", fit[r]) > 0);
+    if (!ok || fputc('\n', sf[NGD_BOOT_NSTAT]) == EOF) die(kLambda, "cannot write coordinates output file!");
+  };
+  std::vector<double> eig0, vec0, tot0, stats, fit, d0;
+  std::vector<uint32_t> status;
+  std::vector<uint64_t> used;
+  auto resize_results = [&](uint64_t n_sets) {
+    eig0.resize(n_sets * K);
+    vec0.resize(n_sets * K * n);
+    tot0.resize(n_sets * 2);
+    status.resize(n_sets * n_mat);
+    stats.resize(n_sets * NGD_BOOT_NSTAT * n_cells);
+    used.resize(n_sets);
+    fit.resize(n_sets * n_mat);
+    d0.resize(n_sets * n_comb);
+  };
+  if (p.win) {
+    // a group of windows per call: their outputs and first matrices in ~2 GB of host memory.  The replicates of a window
+    // shorter than one block are 0 / 0 and left out: used 0
+    std::vector<uint64_t> off(win.size()), maps(1);
+    const uint64_t mlen = draw_window_maps(p, win, R, maps, off);
+    for_window_groups(p, eng, out, win.size(), ((NGD_BOOT_NSTAT + 1) * n_cells + 3) * 8 + n_mat * 12 + n_comb * 8, true,
+      [&](uint64_t w0, uint64_t nw) {
+        resize_results(nw);
+        engine_ok("ngd_run_windows_job_var_mds_align",
+                  ngd_run_windows_job_var_mds_align(eng.h, &win.lo[w0], &win.hi[w0], nw, maps.data(), mlen, &off[w0], (uint32_t)R,
+                                                    p.boot_block_size, p.tot_sites, p.evol_model, K, p.mds_ci, eig0.data(), vec0.data(),
+                                                    tot0.data(), status.data(), stats.data(), used.data(), fit.data(), nullptr, d0.data()));
+      },
+      [&](uint64_t w0, uint64_t nw) {
+        for (uint64_t k = 0; k < nw; k++)
+          write_set(w0 + k, win.name(w0 + k).c_str(), &d0[k * n_comb], &eig0[k * K], &vec0[k * K * n], &tot0[k * 2], &status[k * n_mat],
+                    &stats[k * NGD_BOOT_NSTAT * n_cells], used[k], &fit[k * n_mat]);
+      });
+    win.write_file(std::string(p.out) + ".windows", p);
+  } else {
+    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
+    const uint64_t n_blocks = (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size;
+    if (!n_blocks) die(kMain, "aligned replicates (--mds_align) need at least one bootstrap block of sites!");
+    const auto t_c0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> maps;
+    draw_job_maps(rng, R, n_blocks, maps);
+    resize_results(1);
+    engine_ok("ngd_run_job_mds_align",
+              ngd_run_job_mds_align(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, K, p.mds_ci,
+                                    eig0.data(), vec0.data(), tot0.data(), status.data(), stats.data(), used.data(), fit.data(), nullptr,
+                                    d0.data()));
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    write_set(0, nullptr, d0.data(), eig0.data(), vec0.data(), tot0.data(), status.data(), stats.data(), used[0], fit.data());
+  }
+  if (n_bad)
+    fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no coordinates (they are left out of the summaries in %s.mds_*)\n",
+            (unsigned long)n_bad, p.out);
+  for (int k = 0; k <= NGD_BOOT_NSTAT; k++)
+    if (fclose(sf[k]) != 0) die(kMain, "cannot write coordinates output file!");
+}
+
 // ---- bootstrap summaries (--boot_stats): the replicates of every set -- the run's, or a window's -- stay on the device,
 // which reduces each cell to five statistics and a count (ngd_run_*_stats).  <out> takes the estimates (matrix 0 of every
 // set: the bytes of the run without replicates), <out>.boot_mean / _sd / _lo / _hi the other statistics in the same blocks
@@ -2364,6 +2490,7 @@ int main(int argc, char **argv) {
       fprintf(stderr, "> read + prepare + upload: %.3f s (%.2f GB of prepared input resident on the device)\n", t_load,
               (double)p.n_ind * p.n_sites * 24 / 1e9);
     if (p.nj) trees(p, eng, win, rng, out);
+    else if (p.mds_align) aligned_coordinates(p, eng, win, rng, out);
     else if (p.mds) coordinates(p, eng, win, rng, out);
     else if (p.boot_stats) bootstrap_summaries(p, eng, win, group_of, group_names, rng, out);
     else if (p.in_groups) group_means(p, eng, win, group_of, group_names, rng, batch, out);

@@ -1270,3 +1270,158 @@ int ngd_mds_coords(const double *eig, const double *vec, uint64_t n_mat, uint64_
     }
   return NGD_OK;
 }
+
+// ---- alignment of a set's MDS replicates to its matrix 0 (--mds_align): the contract of include/ngsdist_amd.h "Classical
+// MDS", alignment, in plain host arithmetic by the method of mds_align.hip: M = X_r^T X_0 from sums in ascending i, its
+// orthogonal polar factor by a one-sided Jacobi in cyclic order on M scaled by a power of two, the columns below the floor
+// completed by Gram-Schmidt of the unit vectors in order, Y = X_r Q, fit = |Y - X_0|^2 ----
+namespace {
+const int kAlignSweeps = 64;
+const double kAlignFloor = 1e-12;  // a column this far below the largest counts as zero
+
+// q [K][K] = U V^T of m [K][K] = U S V^T (row-major; K <= kMdsMaxDim)
+void align_polar(const double *m, uint32_t K, double *q) {
+  double A[kMdsMaxDim * kMdsMaxDim], V[kMdsMaxDim * kMdsMaxDim], nrm[kMdsMaxDim], w[kMdsMaxDim];
+  bool done[kMdsMaxDim];
+  double big = 0.0;
+  for (uint32_t i = 0; i < K * K; i++) big = std::max(big, std::fabs(m[i]));
+  const bool any = big > 0.0 && std::isfinite(big);
+  const int ex = any ? std::ilogb(big) : 0;
+  for (uint32_t i = 0; i < K * K; i++) {
+    A[i] = any ? std::scalbn(m[i], -ex) : 0.0;
+    V[i] = i / K == i % K ? 1.0 : 0.0;
+  }
+  for (int sweep = 0; any && sweep < kAlignSweeps; sweep++) {
+    double top = 0.0;
+    for (uint32_t j = 0; j < K; j++) {
+      double s = 0.0;
+      for (uint32_t i = 0; i < K; i++) s += A[i * K + j] * A[i * K + j];
+      top = std::max(top, s);
+    }
+    const double floor2 = (kAlignFloor * kAlignFloor) * top;
+    bool rotated = false;
+    for (uint32_t p = 0; p + 1 < K; p++)
+      for (uint32_t r = p + 1; r < K; r++) {
+        double a = 0.0, b = 0.0, g = 0.0;
+        for (uint32_t i = 0; i < K; i++) {
+          const double x = A[i * K + p], y = A[i * K + r];
+          a += x * x;
+          b += y * y;
+          g += x * y;
+        }
+        if (!(a > floor2) || !(b > floor2) || !(std::fabs(g) > kMdsEps * std::sqrt(a * b))) continue;
+        const double zeta = (b - a) / (2.0 * g), t = std::copysign(1.0, zeta) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+        for (uint32_t i = 0; i < K; i++) {
+          const double x = A[i * K + p], y = A[i * K + r], vx = V[i * K + p], vy = V[i * K + r];
+          A[i * K + p] = c * x - s * y;
+          A[i * K + r] = s * x + c * y;
+          V[i * K + p] = c * vx - s * vy;
+          V[i * K + r] = s * vx + c * vy;
+        }
+        rotated = true;
+      }
+    if (!rotated) break;
+  }
+  // U: the columns above the floor normalised (A holds U from here on) ...
+  double top = 0.0;
+  for (uint32_t j = 0; j < K; j++) {
+    double s = 0.0;
+    for (uint32_t i = 0; i < K; i++) s += A[i * K + j] * A[i * K + j];
+    nrm[j] = std::sqrt(s);
+    top = std::max(top, nrm[j]);
+  }
+  for (uint32_t j = 0; j < K; j++) {
+    done[j] = nrm[j] > kAlignFloor * top;
+    if (done[j])
+      for (uint32_t i = 0; i < K; i++) A[i * K + j] /= nrm[j];
+  }
+  // ... the others from e_0, e_1, .. in order, twice against the finished columns: the first that keeps enough of itself
+  const double keep = 0.5 / std::sqrt((double)K);
+  uint32_t next = 0;
+  for (uint32_t j = 0; j < K; j++) {
+    if (done[j]) continue;
+    for (; next < K; next++) {
+      for (uint32_t i = 0; i < K; i++) w[i] = i == next ? 1.0 : 0.0;
+      for (int pass = 0; pass < 2; pass++)
+        for (uint32_t u = 0; u < K; u++) {
+          if (!done[u]) continue;
+          double dot = 0.0;
+          for (uint32_t i = 0; i < K; i++) dot += A[i * K + u] * w[i];
+          for (uint32_t i = 0; i < K; i++) w[i] -= dot * A[i * K + u];
+        }
+      double s = 0.0;
+      for (uint32_t i = 0; i < K; i++) s += w[i] * w[i];
+      s = std::sqrt(s);
+      if (s > keep) {
+        for (uint32_t i = 0; i < K; i++) A[i * K + j] = w[i] / s;
+        break;
+      }
+    }
+    done[j] = true;
+    next++;
+  }
+  for (uint32_t a = 0; a < K; a++)
+    for (uint32_t b = 0; b < K; b++) {
+      double s = 0.0;
+      for (uint32_t j = 0; j < K; j++) s += A[a * K + j] * V[b * K + j];
+      q[a * K + b] = s;
+    }
+}
+
+// x [K][n] = vec [K][n] scaled by the roots of eig (ngd_mds_coords' formula)
+void align_coords(const double *eig, const double *vec, uint64_t n, uint32_t K, double *x) {
+  for (uint32_t k = 0; k < K; k++) {
+    const double l = eig[k], s = l > 0.0 ? std::sqrt(l) : l - l;
+    for (uint64_t i = 0; i < n; i++) x[k * n + i] = vec[k * n + i] * s;
+  }
+}
+}  // namespace
+
+int ngd_mds_align_host(const double *eig, const double *vec, const uint32_t *status, uint64_t n_set, uint64_t n_mat, uint64_t n_ind,
+                       uint32_t K, double *aligned, double *fit) {
+  if (!eig || !vec || !aligned || !fit || !n_set || !n_mat || n_ind < 3 || !K || K > n_ind - 1 || K > kMdsMaxDim) return NGD_E_INVALID;
+  const uint64_t n = n_ind, total = n_set * n_mat, nan_bits = 0x7FF8000000000000ull;
+  double nan;
+  memcpy(&nan, &nan_bits, 8);
+  const unsigned parts = (unsigned)std::min<uint64_t>(total, 1024);
+  host_pool().run(parts, [&](unsigned part) {
+    std::vector<double> x0(K * n);
+    double M[kMdsMaxDim * kMdsMaxDim], Q[kMdsMaxDim * kMdsMaxDim], xi[kMdsMaxDim];
+    for (uint64_t m = part; m < total; m += parts) {
+      const uint64_t m0 = m / n_mat * n_mat;
+      double *y = aligned + m * K * n;
+      if (status && (!status[m] || !status[m0])) {
+        for (uint64_t i = 0; i < K * n; i++) y[i] = nan;
+        fit[m] = nan;
+        continue;
+      }
+      align_coords(eig + m * K, vec + m * K * n, n, K, y);
+      if (m == m0) {
+        fit[m] = 0.0;
+        continue;
+      }
+      align_coords(eig + m0 * K, vec + m0 * K * n, n, K, x0.data());
+      for (uint32_t a = 0; a < K; a++)
+        for (uint32_t b = 0; b < K; b++) {
+          double s = 0.0;
+          for (uint64_t i = 0; i < n; i++) s += y[a * n + i] * x0[b * n + i];
+          M[a * K + b] = s;
+        }
+      align_polar(M, K, Q);
+      double f = 0.0;
+      for (uint64_t i = 0; i < n; i++) {
+        for (uint32_t a = 0; a < K; a++) xi[a] = y[a * n + i];
+        for (uint32_t b = 0; b < K; b++) {
+          double s = 0.0;
+          for (uint32_t a = 0; a < K; a++) s += xi[a] * Q[a * K + b];
+          y[b * n + i] = s;
+          const double d = s - x0[b * n + i];
+          f += d * d;
+        }
+      }
+      fit[m] = f;
+    }
+  });
+  return NGD_OK;
+}

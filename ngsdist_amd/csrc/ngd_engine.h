@@ -278,6 +278,13 @@ struct ngd_engine : ngd_mem {
     uint64_t max_bytes = 0;  // NGD_OPT_MDS_MAX_BYTES
     double ms = 0;           // ngd_last_mds_ms
   } mds;
+  // ... and the alignment of a call's replicates (engine_mds.hip): the cells of all its matrices -- coordinates [K][n], then
+  // the K eigenvalues --, their status and their fit
+  struct MdsAlign {
+    DevBuf<double> d_cells, d_fit;
+    DevBuf<uint32_t> d_status;
+    double ms = 0;  // ngd_last_mds_align_ms
+  } mal;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)
@@ -420,6 +427,18 @@ int windows_tail(ngd_engine *e, const WinJobArgs &a, bool job_form, const char *
 // on the device instead, grp.d_keep_mean / d_keep_used [n_mat][n_gp], for the summaries (the arguments are checked)
 int groups_reduce(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_mat, uint64_t tot_sites,
                   uint64_t evol_model, double *mean, uint64_t *used);
+// engine_boot_stats.hip: what every call that summarises refuses, before anything is launched (`groups`: without a grouping
+// too); the two ranks' fractions of the interval on the way
+struct BootCi {
+  double p_lo, p_hi;
+};
+int boot_refuse(const ngd_engine *e, const void *stats, const void *used, uint64_t n_mat, double ci, uint64_t tot_sites,
+                uint64_t evol_model, bool groups, const char *who, BootCi &out);
+// ... and [n_set][n_mat][n_cells] device matrices -> stats [n_set][5][n_cells] / used [n_set][n_cells] in host memory; d_cnt
+// and the two arguments of ngd_finish for sums and counts, `values` for cells as they are (the arguments are checked);
+// adds its kernels' time to bst.ms
+int boot_reduce(ngd_engine *e, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_set, uint64_t n_mat,
+                uint64_t n_cells, uint64_t tot_sites, uint64_t evol_model, BootCi ci, double *stats, uint64_t *used);
 // engine_nj.hip: matrix 0 of each of the n_set sets of [n_set][n_mat][n_pairs] sums and counts, finished on the host into
 // dist0 [n_set][n_pairs] (ngd_finish's bits: what the tails that keep their matrices on the device hand out beside them)
 int tail_dist0(ngd_engine *e, const double *d_sum, const unsigned long long *d_cnt, uint64_t n_set, uint64_t n_mat, uint64_t tot_sites,

@@ -462,6 +462,19 @@ int ngd_launch_mds(hipStream_t st, const double *d_a, const unsigned long long *
                    uint64_t tot_sites, uint32_t model, uint32_t K, uint32_t threads, double *d_work, double *d_aux, double *d_eig,
                    double *d_vec, double *d_tot, uint32_t *d_status);
 
+// mds_align.hip : a set's MDS replicates rotated onto its matrix 0 (include/ngsdist_amd.h "Classical MDS", alignment)
+#define NGD_MDS_ALIGN_THREADS 256u  // the workgroup (DESIGN.md section 3 "Alignment of the replicates")
+// a chunk's d_eig / d_vec / d_status as ngd_launch_mds wrote them -> d_cells [n_mat][K (n_ind + 1)]: per matrix the
+// coordinates [K][n_ind], then its K eigenvalues; d_status_out [n_mat].  Limits as ngd_launch_mds'.  Returns a hipError_t.
+int ngd_launch_mds_coords(hipStream_t st, const double *d_eig, const double *d_vec, const uint32_t *d_status, uint64_t n_mat,
+                          uint32_t n_ind, uint32_t K, double *d_cells, uint32_t *d_status_out);
+// d_cells [n_set][n_mat] matrices `stride` doubles apart, each [K][n_ind] coordinates and whatever follows them: every
+// replicate's coordinates rotated in place, d_fit [n_set][n_mat]; d_status [n_set][n_mat] or NULL (every matrix has status
+// 1): a matrix left out has all its `stride` doubles and its fit NaN.  n_set * n_mat below 2^31 (grid.x), stride >= K *
+// n_ind: the caller's to see to.  Returns a hipError_t.
+int ngd_launch_mds_align(hipStream_t st, double *d_cells, uint64_t stride, const uint32_t *d_status, uint64_t n_set, uint32_t n_mat,
+                         uint32_t n_ind, uint32_t K, double *d_fit);
+
 // group_reduce.hip : group-mean distance matrices (ngd_set_groups, ngd_group_means_device, ngd_run_*_groups)
 // One work item: rows [r0, r1) of group pair (a, b) -- positions in group a's member list --, every column of group b
 #define NGD_GROUP_WG_CELLS 4096  // cells of a work item's rectangle, about: whole rows, at least one

@@ -606,6 +606,65 @@ class Engine:
         _check(self._L.ngd_last_mds_ms(self._h, C.byref(v)))
         return float(v.value)
 
+    # -- the MDS replicates of a set rotated onto its matrix 0, and the summaries of the aligned cells ----
+    def mds_align_values(self, d_coords_ptr, n_set, n_mat, K, status=None):
+        """the alignment alone, of [n_set][n_mat][K][n] float64 coordinates in device memory as they are
+        (ngd_mds_align_values_device; status uint32[n_set][n_mat] on the host, None: every matrix has status 1): ->
+        (aligned float64[n_set][n_mat][K][n], fit float64[n_set][n_mat]); matrix 0 of a set stays as it is (fit 0), a matrix
+        left out is NaN"""
+        n_set, n_mat, K = int(n_set), int(n_mat), int(K)
+        aligned = np.empty((n_set, n_mat, max(K, 0), self.n_ind), dtype=np.float64)
+        fit = np.empty((n_set, n_mat), dtype=np.float64)
+        sp = None
+        if status is not None:
+            st = np.ascontiguousarray(status, dtype=np.uint32)
+            if st.size != n_set * n_mat:
+                raise ValueError("status: expected [n_set][n_mat]")
+            sp = st.ctypes.data_as(C.POINTER(C.c_uint32))
+        dp = C.POINTER(C.c_double)
+        _check(self._L.ngd_mds_align_values_device(self._h, C.c_void_p(d_coords_ptr), sp, n_set, n_mat, K, aligned.ctypes.data_as(dp),
+                                                   fit.ctypes.data_as(dp)))
+        return aligned, fit
+
+    def _mds_align_out(self, lead, n_mat, K, aligned, dist0):
+        K, n = int(K), self.n_ind
+        nc = max(K, 0) * (n + 1)
+        out = {"eig0": np.empty(lead + (max(K, 0),)), "vec0": np.empty(lead + (max(K, 0), n)), "tot0": np.empty(lead + (2,)),
+               "status": np.empty(lead + (n_mat,), dtype=np.uint32), "stats": np.empty(lead + (_lib.NSTAT, nc)),
+               "used": np.empty(lead, dtype=np.uint64), "fit": np.empty(lead + (n_mat,)),
+               "aligned": np.empty(lead + (n_mat, max(K, 0), n)) if aligned else None,
+               "dist0": np.empty(lead + (self.n_pairs,)) if dist0 else None}
+        ptr = {np.dtype(np.float64): C.POINTER(C.c_double), np.dtype(np.uint32): C.POINTER(C.c_uint32),
+               np.dtype(np.uint64): C.POINTER(C.c_uint64)}
+        args = [None if v is None else v.ctypes.data_as(ptr[v.dtype]) for v in out.values()]
+        return out, args
+
+    def run_job_mds_align(self, K, block_maps, block_size=1, evol_model=1, tot_sites=0, ci=0.95, aligned=True, dist0=True):
+        """run_job_mds(), the replicates rotated onto matrix 0 and the summaries of the aligned cells, all on the device
+        (ngd_run_job_mds_align): -> dict of eig0 (K,), vec0 (K, n), tot0 (2,) -- matrix 0's, as run_job_mds() gives them --,
+        status (n_rep + 1,), stats (5, K (n + 1)) -- est, mean, sd, lo, hi of the cells [K][n], then of the K eigenvalues --,
+        used (the replicates that went in), fit (n_rep + 1,), aligned (n_rep + 1, K, n) or None, dist0 (n_pairs,) or None"""
+        a, ap, n_rep, n_blocks = self._job_maps(block_maps)
+        out, args = self._mds_align_out((), n_rep + 1, K, aligned, dist0)
+        _check(self._L.ngd_run_job_mds_align(self._h, ap, n_rep, n_blocks, int(block_size), int(tot_sites), int(evol_model), int(K),
+                                             float(ci), *args))
+        return out
+
+    def run_windows_job_var_mds_align(self, K, lo, hi, block_maps, map_off, block_size=1, evol_model=1, tot_sites=0, n_rep=None,
+                                      ci=0.95, aligned=True, dist0=True):
+        """the same for every window's set (ngd_run_windows_job_var_mds_align): the dict's arrays with a leading n_win; the
+        replicates of a window shorter than one block are left out (used 0, the statistics but est NaN)"""
+        n_win, n_rep, wargs, keep = self._var_job(lo, hi, block_maps, map_off, block_size, n_rep)
+        out, args = self._mds_align_out((n_win,), n_rep + 1, K, aligned, dist0)
+        _check(self._L.ngd_run_windows_job_var_mds_align(*wargs, int(tot_sites), int(evol_model), int(K), float(ci), *args))
+        return out
+
+    def last_mds_align_ms(self):
+        """device time of the two alignment kernels in the last of these calls (ngd_last_mds_align_ms)"""
+        v = C.c_double(0.0)
+        _check(self._L.ngd_last_mds_align_ms(self._h, C.byref(v)))
+        return float(v.value)
+
     def run_job_keep(self, block_maps, block_size=1):
         """ngd_run_job with the matrices left in the engine; fetch_matrix(r) copies them out one at a time"""
         a = np.ascontiguousarray(block_maps, dtype=np.uint64)
@@ -972,6 +1031,30 @@ def mds_coords(eig, vec):
     _check(_lib.load().ngd_mds_coords(e.ctypes.data_as(dp), v.ctypes.data_as(dp), int(np.prod(lead, dtype=np.int64)), n, K,
                                       out.ctypes.data_as(dp)))
     return out
+
+
+def mds_align_host(eig, vec, status=None):
+    """the replicates of every set rotated onto its matrix 0 in plain host arithmetic (ngd_mds_align_host), the device
+    form's twin: eig float64[..., n_mat, K], vec float64[..., n_mat, K, n], status uint32[..., n_mat] (None: every matrix
+    has status 1) -> (aligned float64[..., n_mat, K, n], fit float64[..., n_mat]); coordinates are vec[k][i] *
+    sqrt(max(eig[k], 0)), matrix 0 stays as it is (fit 0), a matrix left out is NaN"""
+    e = np.ascontiguousarray(eig, dtype=np.float64)
+    v = np.ascontiguousarray(vec, dtype=np.float64)
+    if v.ndim < 3 or e.shape != v.shape[:-1]:
+        raise ValueError("eig, vec: expected [..., n_mat, K] and [..., n_mat, K, n]")
+    lead, n_mat, K, n = v.shape[:-3], v.shape[-3], v.shape[-2], v.shape[-1]
+    sp = None
+    if status is not None:
+        st = np.ascontiguousarray(status, dtype=np.uint32)
+        if st.shape != lead + (n_mat,):
+            raise ValueError("status: expected [..., n_mat]")
+        sp = st.ctypes.data_as(C.POINTER(C.c_uint32))
+    aligned = np.empty(v.shape, dtype=np.float64)
+    fit = np.empty(lead + (n_mat,), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    _check(_lib.load().ngd_mds_align_host(e.ctypes.data_as(dp), v.ctypes.data_as(dp), sp, int(np.prod(lead, dtype=np.int64)), n_mat, n, K,
+                                          aligned.ctypes.data_as(dp), fit.ctypes.data_as(dp)))
+    return aligned, fit
 
 
 def score_congruence(score):
