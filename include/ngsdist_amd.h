@@ -410,6 +410,9 @@ int ngd_drop_caches(ngd_engine *e);
 #define NGD_OPT_MDS_MAX_BYTES 20   /* [0 = 2 GB] device scratch of the classical-MDS kernel (ngd_mds_*, ngd_run_*_mds): per matrix of a */
                                  /*     launch a full n x n matrix of doubles (rows padded to an even length) and 4 K rows     */
                                  /*     more; never fewer than one matrix.  Any value gives the same bits                        */
+#define NGD_OPT_WIN_CMP_MAX_BYTES 21 /* [0 = half of the free device memory at the call] device memory of the comparison of       */
+                                 /*     windows (ngd_win_cmp_*, ngd_run_windows_cmp): the operand and the partial sums, resident  */
+                                 /*     for the whole call.  A call that needs more is refused with NGD_E_INVALID.                */
 #define NGD_OPT_DEBUG_FORGE_JOB 100 /* tests only: the first block of the MFMA kernel's job list gets the shape rows | cols << 3 |  */
                                  /*     tri << 6 -- a shape the kernel's block form does not list must fail the run with      */
                                  /*     NGD_E_HIP (its sums poisoned with NaN), never return zeros                            */
@@ -936,6 +939,69 @@ int ngd_run_windows_job_var_mds_align(ngd_engine *e, const uint64_t *win_lo, con
                                       double *fit, double *aligned, double *dist0);
 /* device time (HIP events) of the two alignment kernels in the last of these calls, summed over its launches */
 int ngd_last_mds_align_ms(const ngd_engine *e, double *ms);
+
+/* Comparison of windows (added under ABI 6): the windows of a genome scan related to one another where their matrices lie --
+ * W (W + 2) numbers cross the link instead of W matrices.
+ *   input      W vectors x_w of P cells each: in the run forms a window's matrix 0, every cell finished as ngd_finish()
+ *              does (the division and the products carry the host's bits, log is the device's), P = n (n - 1) / 2; in
+ *              the values form doubles as they are, any P >= 1
+ *   per vector status[w]  1 if every cell is finite, else 0: such a vector is left out and disturbs no other
+ *              mean[w]    (SUM_c x_wc) / P by a fixed tree
+ *   per pair   gram[a][b] SUM_c (x_ac - mean[a]) (x_bc - mean[b]): a full W x W array, symmetric bit for bit
+ * Row and column of a status-0 vector are a positive quiet NaN, and so is its mean: written from the status, not produced
+ * by arithmetic.
+ * Bits: gram[a][b] is a function of the cells of a and b and of (W, P) alone -- not of the other vectors, of where a and b
+ * stand among them, of how the windows fell into groups, of the device's CU count or of any NGD_OPT_* budget.  Scaling
+ * every cell by 2^k scales mean by 2^k and gram by 4^k exactly (short of overflow and underflow).  No atomics; every sum
+ * has a fixed order: the cell axis is cut into slices of ngd_win_cmp_slice(W, P) cells, a slice's products are added in
+ * ascending k-groups of four cells on the FP64 matrix pipe, a pair's slices in ascending order.
+ * Accuracy: |gram[a][b] - exact| <= 1e-9 sqrt(exact[a][a] exact[b][b]).
+ * Derived on the host by ngd_win_cmp_finish() (plain C++, IEEE sqrt only):
+ *   cor[a][b]  gram[a][b] / sqrt(gram[a][a] gram[b][b]), the Mantel statistic of the two matrices; NaN if either diagonal is
+ *              exactly 0.  An all-zero vector and a vector of one power-of-two value give exact zeros and hence NaN; a
+ *              vector of one other repeated value is not pinned (its mean may round, and the diagonal is then a tiny
+ *              positive number or 0).
+ *   rms[a][b]  sqrt(max(0, gram[a][a] + gram[b][b] - 2 gram[a][b] + P (mean[a] - mean[b])^2) / P), the diagonal exactly 0:
+ *              the root-mean-square difference of the cells.  The contract is on rms^2: within 1e-9 of (gram[a][a] +
+ *              gram[b][b] + P (mean[a] - mean[b])^2) / P -- the RMS of two nearly identical vectors is therefore only good
+ *              to about 1e-8 of that scale's root (the difference is formed from the sums, not from the cells).  Two
+ *              vectors with the same cells have rms exactly 0.
+ *   Anything that touches a status-0 vector is NaN.
+ * Device and host twin follow the same definition but need not agree bit for bit. */
+/* the most vectors a call takes (the kernels' tile indices); more is NGD_E_INVALID */
+uint32_t ngd_win_cmp_max_vec(void);
+/* cells per slice of the cell axis at (n_vec, n_cells), a multiple of 4; 0 for n_vec 0, n_cells 0 or n_vec above the limit.
+ * Pure host arithmetic. */
+uint64_t ngd_win_cmp_slice(uint64_t n_vec, uint64_t n_cells);
+/* The contract in plain host arithmetic on values[n_vec][n_cells] (sums in slices of ngd_win_cmp_slice() cells); needs no
+ * device; vectors are spread over host threads, which changes no bit.  Outputs mean[n_vec], gram[n_vec][n_vec],
+ * status[n_vec].  NGD_E_INVALID: a null pointer, n_vec 0 or above ngd_win_cmp_max_vec(), n_cells 0. */
+int ngd_win_cmp_host(const double *values, uint64_t n_vec, uint64_t n_cells, double *mean, double *gram, uint32_t *status);
+/* cor[n_vec][n_vec] and rms[n_vec][n_vec] as defined above, pure host.  NGD_E_INVALID: a null pointer, n_vec or n_cells 0. */
+int ngd_win_cmp_finish(const double *mean, const double *gram, const uint32_t *status, uint64_t n_vec, uint64_t n_cells, double *cor,
+                       double *rms);
+/* ... on the device (win_cmp.hip), of [n_vec][n_cells] values in device memory as they are -- any n_cells >= 1, not tied to
+ * the engine's n_ind --, or of [n_vec][n_pairs] sums and counts as a *_device call wrote them (d_cnt is not read when
+ * tot_sites > 0).  Outputs in host memory.  The operand (8 bytes per cell, vectors padded to whole tile blocks) and the
+ * partial sums are resident for the call; their bytes follow from (n_vec, n_cells) and a call that exceeds
+ * NGD_OPT_WIN_CMP_MAX_BYTES is refused with NGD_E_INVALID and a message that names the bytes needed.  NGD_E_INVALID, before
+ * anything is launched: a null pointer, n_vec 0 or above ngd_win_cmp_max_vec(), n_cells 0, tot_sites with --pairwise_del, an
+ * engine that owns a share of the pairs; NGD_E_MODEL for evol_model > 2.  A refused call leaves outputs and engine as they
+ * were. */
+int ngd_win_cmp_values_device(ngd_engine *e, const void *d_val, uint64_t n_vec, uint64_t n_cells, double *mean, double *gram,
+                              uint32_t *status);
+int ngd_win_cmp_device(ngd_engine *e, const void *d_sum, const void *d_cnt, uint64_t n_vec, uint64_t tot_sites, uint64_t evol_model,
+                       double *mean, double *gram, uint32_t *status);
+/* ngd_run_windows_device into the engine's batch buffers, group of windows by group, each group's matrices packed into the
+ * operand as it stands there; then the comparison.  Plans, fix-up, NGD_OPT_EM_EXACT_WIN and the windows' refusals are
+ * ngd_run_windows' unchanged (the operand is allocated before the windows are planned, so the batches' budget sees what
+ * is left), and the outputs are ngd_win_cmp_device()'s on the sibling's output bit for bit.  dist, unless NULL, receives
+ * [n_win][n_pairs]: every window's matrix finished by ngd_finish() on the host -- ngd_run_windows_dist()'s bits. */
+int ngd_run_windows_cmp(ngd_engine *e, const uint64_t *win_lo, const uint64_t *win_hi, uint64_t n_win, uint64_t tot_sites,
+                        uint64_t evol_model, double *mean, double *gram, uint32_t *status, double *dist);
+/* device time (HIP events) of the four kernels in the last of these calls, summed over its launches: ms[4] = the vectors'
+ * statistics, the packing, the Gram pass, the sum of its partials */
+int ngd_last_win_cmp_ms(const ngd_engine *e, double ms[4]);
 
 /* The tail of gen_dist(), ngsDist.cpp:372-401, on the HOST with the host's
  * libm so that -0.0 / inf / nan cells print exactly as the reference's do:

@@ -98,6 +98,8 @@ EXPORTS = [
     "ngd_run_job_mds", "ngd_run_windows_mds", "ngd_run_windows_job_var_mds", "ngd_last_mds_ms",
     "ngd_mds_align_host", "ngd_mds_align_values_device", "ngd_run_job_mds_align", "ngd_run_windows_job_var_mds_align",
     "ngd_last_mds_align_ms",
+    "ngd_win_cmp_max_vec", "ngd_win_cmp_slice", "ngd_win_cmp_host", "ngd_win_cmp_finish", "ngd_win_cmp_values_device",
+    "ngd_win_cmp_device", "ngd_run_windows_cmp", "ngd_last_win_cmp_ms",
 ]
 
 NSTAT = 5  # NGD_BOOT_NSTAT: est, mean, sd, lo, hi
@@ -263,6 +265,16 @@ def load():
     L.ngd_run_windows_job_var_mds_align.argtypes = [vp, u64p, u64p, u64, u64p, u64, u64p, u32, u64, u64, u64, u32, C.c_double,
                                                     dp, dp, dp, u32p, dp, u64p, dp, dp, dp]
     L.ngd_last_mds_align_ms.argtypes = [vp, dp]
+    L.ngd_win_cmp_max_vec.argtypes = []
+    L.ngd_win_cmp_max_vec.restype = u32
+    L.ngd_win_cmp_slice.argtypes = [u64, u64]
+    L.ngd_win_cmp_slice.restype = u64
+    L.ngd_win_cmp_host.argtypes = [dp, u64, u64, dp, dp, u32p]
+    L.ngd_win_cmp_finish.argtypes = [dp, dp, u32p, u64, u64, dp, dp]
+    L.ngd_win_cmp_values_device.argtypes = [vp, vp, u64, u64, dp, dp, u32p]
+    L.ngd_win_cmp_device.argtypes = [vp, vp, vp, u64, u64, u64, dp, dp, u32p]
+    L.ngd_run_windows_cmp.argtypes = [vp, u64p, u64p, u64, u64, u64, dp, dp, u32p, dp]
+    L.ngd_last_win_cmp_ms.argtypes = [vp, dp]
     L.ngd_device_bytes.argtypes = [vp]
     L.ngd_device_bytes.restype = u64
     _lib = L

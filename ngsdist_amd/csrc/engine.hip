@@ -134,6 +134,7 @@ int ngd_set_option(ngd_engine *e, int option, uint64_t value) {
     case NGD_OPT_WIN_MAX_BYTES: e->opt_win_max_bytes = value; break;
     case NGD_OPT_NJ_MAX_BYTES: e->nj.max_bytes = value; break;
     case NGD_OPT_MDS_MAX_BYTES: e->mds.max_bytes = value; break;
+    case NGD_OPT_WIN_CMP_MAX_BYTES: e->wcmp.max_bytes = value; break;
     case NGD_OPT_EM_EXACT: return em_exact_set(e, value);
     case NGD_OPT_EM_EXACT_WIN: return em_exact_win_set(e, value);
     case NGD_OPT_EM_EXACT_CAP:

@@ -48,7 +48,12 @@
 //    --n_boot_rep or --win_boot_rep: the replicates' coordinates are rotated onto matrix 0's on the device and summarised
 //    there: <out>.mds holds matrix 0 of every set alone, <out>.mds_mean / _sd / _lo / _hi the replicates' statistics in the
 //    same blocks without the "total" line, <out>.mds_fit per set the replicates that went in and every replicate's squared
-//    distance from matrix 0 after the rotation);
+//    distance from matrix 0 after the rotation), --win_cmp [--win_cmp_mds K] (with --win_size or --win_bp: the windows'
+//    matrices are compared with one another on the device: <out>.win_cor holds the Mantel correlation of every pair of
+//    windows and <out>.win_rms their root-mean-square difference, one line per window of W tab-separated "%.10e", "nan"
+//    where undefined; <out>.win_cmp per window its number, mean distance, standard deviation of its distances and status;
+//    <out>.win_mds, with --win_cmp_mds K, the classical MDS of the RMS table in the block format of <out>.mds; <out> and
+//    <out>.windows are the run's without the flag);
 //  * a binary file is mapped and copied into the engine's ring of pinned buffers by --n_threads (4..16) threads, the
 //    copies to the device and the preparation kernel running behind; matrices are written by a thread of their own
 //    while the next one is formatted; --verbose 2 ends with a `> phases [s]:` line (where the run's wall time went).
@@ -57,7 +62,7 @@
 // genotypes (read_labels, read_positions, make_windows: WindowList), device_fit (one device or site ranges), the matrix
 // output every mode prints through (Writer, MatrixOut::emit), the jobs the modes share (draw_window_maps, draw_job_maps,
 // format_grown, for_window_groups) and one function per output mode -- site_range_matrices, trees, coordinates, aligned_coordinates, bootstrap_summaries,
-// group_means, window_matrices, plain_matrices; main(), last, is the run's outline and picks one of them.
+// group_means, window_matrices, compared_windows, plain_matrices; main(), last, is the run's outline and picks one of them.
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/mman.h>
@@ -117,6 +122,9 @@
 #pragma weak ngd_run_windows_job_var_mds
 #pragma weak ngd_run_job_mds_align  // (--mds_align)
 #pragma weak ngd_run_windows_job_var_mds_align
+#pragma weak ngd_run_windows_cmp  // (--win_cmp: the windows' matrices compared with one another on the device)
+#pragma weak ngd_win_cmp_finish
+#pragma weak ngd_win_cmp_max_vec
 #pragma weak ngd_last_em_exact  // (--em_exact: what the recheck noted and changed; the option itself goes through ngd_set_option)
 
 static const char *kVersion = "ngsdist_amd 0.1 (ngsDist 1.0.10 command line)";
@@ -200,6 +208,12 @@ struct Pars {  // the reference's `params`, ngsDist.hpp:11-44
   // the replicates that went in and their fits.  Not in the reference, whose users run vegan::procrustes in a loop.
   bool mds_align = false, mds_ci_set = false;
   double mds_ci = 0.95;
+  // --win_cmp: the windows of --win_size / --win_bp are compared with one another where their matrices lie
+  // (ngd_run_windows_cmp): <out>.win_cor, <out>.win_rms and <out>.win_cmp beside the run's own <out> and <out>.windows;
+  // --win_cmp_mds K: the classical MDS of the RMS table of the windows that were kept, on the host (ngd_mds_host):
+  // <out>.win_mds.  Not in the reference
+  bool win_cmp = false, win_cmp_mds = false;
+  uint64_t win_cmp_dim = 0;
 };
 
 // --verbose 2: where the wall time of a run goes, as one line of name=seconds pairs at the end of the run (stderr; the
@@ -318,6 +332,8 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
                                  {"mds", required_argument, nullptr, 1024},
                                  {"mds_align", no_argument, nullptr, 1025},
                                  {"mds_ci", required_argument, nullptr, 1026},
+                                 {"win_cmp", no_argument, nullptr, 1027},
+                                 {"win_cmp_mds", required_argument, nullptr, 1028},
                                  {nullptr, 0, nullptr, 0}};
   p.seed = (unsigned)time(nullptr);  // parse_args.cpp:35
   int c;
@@ -372,6 +388,14 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
       }
       case 1025: p.mds_align = true; break;
       case 1026: p.mds_ci_set = true; p.mds_ci = atof(optarg); break;
+      case 1027: p.win_cmp = true; break;
+      case 1028: {
+        char *end = nullptr;
+        p.win_cmp_mds = true;
+        p.win_cmp_dim = strtoull(optarg, &end, 10);
+        if (end == optarg || *end || optarg[0] == '-') die(__FUNCTION__, "the number of dimensions (--win_cmp_mds K) must be a whole number!");
+        break;
+      }
       case 1009:  // --stage piece_MiB,ring[,copy share MiB[,drop pages 0|1]]: the load pipeline's geometry (measurement)
         if (sscanf(optarg, "%u,%u,%u,%u", &p.stage_piece, &p.stage_ring, &p.stage_grain, &p.stage_drop) < 2)
           die(__FUNCTION__, "--stage takes piece_MiB,ring[,share_MiB[,drop]]");
@@ -425,6 +449,7 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (p.nj) fprintf(stderr, "\tnj: true\n\n");
     if (p.mds) fprintf(stderr, "\tmds: %lu\n\n", (unsigned long)p.mds_dim);
     if (p.mds_align) fprintf(stderr, "\tmds_align: true\n\tmds_ci: %f\n\n", p.mds_ci);
+    if (p.win_cmp) fprintf(stderr, "\twin_cmp: true\n\twin_cmp_mds: %lu\n\n", (unsigned long)p.win_cmp_dim);
   }
   if (p.verbose > 4)
     fprintf(stderr, "==> Verbose values greater than 4 for debugging purpose only. Expect large amounts of info on screen\n");
@@ -518,6 +543,19 @@ static void parse_cmd_args(Pars &p, int argc, char **argv) {
     if (!(p.mds_ci > 0.0 && p.mds_ci < 1.0)) die(__FUNCTION__, "interval coverage (--mds_ci) must lie between 0 and 1!");
     if (p.n_boot_rep < 1 && p.win_boot_rep < 1)
       die(__FUNCTION__, "aligned replicates (--mds_align) require bootstrap replicates (--n_boot_rep or --win_boot_rep)!");
+  }
+  if (p.win_cmp_mds && !p.win_cmp) die(__FUNCTION__, "the ordination of the windows (--win_cmp_mds) requires their comparison (--win_cmp)!");
+  if (p.win_cmp) {
+    if (!p.win) die(__FUNCTION__, "the comparison of windows (--win_cmp) requires windows (--win_size or --win_bp)!");
+    if (p.win_boot_rep) die(__FUNCTION__, "the comparison of windows (--win_cmp) cannot be combined with bootstrap replicates inside windows (--win_boot_rep)!");
+    if (p.in_groups) die(__FUNCTION__, "the comparison of windows (--win_cmp) cannot be combined with group means (--groups)!");
+    if (p.boot_stats) die(__FUNCTION__, "the comparison of windows (--win_cmp) cannot be combined with bootstrap summaries (--boot_stats)!");
+    if (p.nj) die(__FUNCTION__, "the comparison of windows (--win_cmp) cannot be combined with neighbour-joining trees (--nj)!");
+    if (p.mds) die(__FUNCTION__, "the comparison of windows (--win_cmp) cannot be combined with classical MDS (--mds)!");
+    if (p.n_gpus > 1) die(__FUNCTION__, "the comparison of windows (--win_cmp) is computed on one GPU (--n_gpus 1)!");
+    if (p.n_ind < 2) die(__FUNCTION__, "the comparison of windows (--win_cmp) needs two individuals or more (--n_ind)!");
+    if (p.win_cmp_mds && (p.win_cmp_dim < 1 || p.win_cmp_dim > ngd_mds_max_dim()))
+      die(__FUNCTION__, ("the number of dimensions (--win_cmp_mds K) must lie between 1 and min(windows kept - 1, " + std::to_string(ngd_mds_max_dim()) + ")!").c_str());
   }
 }
 
@@ -1395,6 +1433,8 @@ void check_summaries_and_trees(const Pars &p) {
     if (std::max<uint64_t>(p.n_boot_rep, p.win_boot_rep) > ngd_boot_stats_max_rep())
       die(kMain, "too many bootstrap replicates for aligned replicates (--mds_align): a cell's replicates stay in on-chip memory!");
   }
+  if (p.win_cmp && (!ngd_run_windows_cmp || !ngd_win_cmp_finish || !ngd_win_cmp_max_vec))
+    die(kMain, "this build of the engine has no comparison of windows (--win_cmp): not linked!");
 }
 
 // The windows of --win_size / --win_bp, and what the positions file says about the sites they hold.
@@ -2317,6 +2357,86 @@ void window_matrices(const Pars &p, Engine &eng, const WindowList &win, MatrixOu
   win.write_file(std::string(p.out) + ".windows", p);
 }
 
+// ---- the comparison of windows (--win_cmp [--win_cmp_mds K]): the windows' matrices stay on the device, which relates every
+// window to every other (ngd_run_windows_cmp: all windows in ONE call, their operand is resident there).  <out> and
+// <out>.windows are window_matrices'; <out>.win_cor / <out>.win_rms one line per window of W numbers; <out>.win_cmp per window
+// its number, mean, sd = sqrt(gram[w][w] / P) and status; <out>.win_mds the classical MDS of the RMS table of the windows that
+// were kept (ngd_mds_host), in the block format of <out>.mds with the window number as label; tabs, "%.10e" ----
+void compared_windows(const Pars &p, Engine &eng, const WindowList &win, MatrixOut &out) {
+  const uint64_t W = win.size(), n_comb = out.n_comb;
+  const uint32_t K = (uint32_t)p.win_cmp_dim;
+  if (W > ngd_win_cmp_max_vec()) die(kMain, "too many windows for their comparison (--win_cmp)!");
+  std::vector<double> mean(W), gram(W * W), cor(W * W), rms(W * W), wd(W * n_comb);
+  std::vector<uint32_t> status(W);
+  const auto t_c0 = std::chrono::steady_clock::now();
+  engine_ok("ngd_run_windows_cmp", ngd_run_windows_cmp(eng.h, win.lo.data(), win.hi.data(), W, p.tot_sites, p.evol_model, mean.data(),
+                                                       gram.data(), status.data(), wd.data()));
+  report_fixup(eng.h, p.verbose);
+  if (ngd_win_cmp_finish(mean.data(), gram.data(), status.data(), W, n_comb, cor.data(), rms.data()))
+    die(kMain, "cannot derive the windows' correlations!");
+  out.t_compute += since(t_c0);
+  for (uint64_t w = 0; w < W; w++) out.emit(w, nullptr, nullptr, nullptr, 0, &wd[w * n_comb], 0, win.name(w).c_str());
+  win.write_file(std::string(p.out) + ".windows", p);
+  auto open = [&](const char *suffix) {
+    FILE *f = fopen((std::string(p.out) + suffix).c_str(), "w");
+    if (!f) die(kLambda, "cannot open window comparison output file!");
+    return f;
+  };
+  auto close = [&](FILE *f, bool ok) {
+    if (fclose(f) != 0 || !ok) die(kLambda, "cannot write window comparison output file!");
+  };
+  auto table = [&](const char *suffix, const std::vector<double> &t) {
+    FILE *f = open(suffix);
+    bool ok = true;
+    for (uint64_t a = 0; a < W; a++)
+      for (uint64_t b = 0; b < W; b++) ok = ok && fprintf(f, "%.10e%c", t[a * W + b], b + 1 < W ? '\t' : '\n') > 0;
+    close(f, ok);
+  };
+  table(".win_cor", cor);
+  table(".win_rms", rms);
+  uint64_t n_bad = 0;
+  {
+    FILE *f = open(".win_cmp");
+    bool ok = fputs("window\tmean\tsd\tstatus\n", f) >= 0;
+    for (uint64_t w = 0; w < W; w++) {
+      n_bad += status[w] == 0;
+      ok = ok && fprintf(f, "%lu\t%.10e\t%.10e\t%u\n", (unsigned long)w, mean[w], std::sqrt(gram[w * W + w] / (double)n_comb), status[w]) > 0;
+    }
+    close(f, ok);
+  }
+  if (n_bad)
+    fprintf(stderr, "WARNING: %lu of the run's windows have a cell that is not finite and are left out of the comparison (\"nan\" throughout their lines in %s.win_*)\n",
+            (unsigned long)n_bad, p.out);
+  if (!p.win_cmp_mds) return;
+  // the RMS table of the windows that were kept, taken as an ordinary distance matrix
+  std::vector<uint64_t> kept;
+  for (uint64_t w = 0; w < W; w++)
+    if (status[w]) kept.push_back(w);
+  const uint64_t n = kept.size();
+  if (n < 3) die(kMain, "the ordination of the windows (--win_cmp_mds) needs three windows or more that were kept!");
+  if (K > n - 1)
+    die(kMain, ("the number of dimensions (--win_cmp_mds K) must lie between 1 and min(windows kept - 1, " + std::to_string(ngd_mds_max_dim()) + ")!").c_str());
+  std::vector<double> val(n * (n - 1) / 2), eig(K), vec(K * n), tot(2), xy(n * K);
+  uint32_t st = 0;
+  uint64_t at = 0;
+  for (uint64_t a = 0; a < n; a++)
+    for (uint64_t b = a + 1; b < n; b++) val[at++] = rms[kept[a] * W + kept[b]];
+  if (ngd_mds_host(val.data(), 1, n, K, eig.data(), vec.data(), tot.data(), &st) || ngd_mds_coords(eig.data(), vec.data(), 1, n, K, xy.data()))
+    die(kMain, "cannot derive the windows' coordinates!");
+  FILE *f = open(".win_mds");
+  bool ok = fputs("eig", f) >= 0;
+  for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(f, "\t%.10e", eig[k]) > 0;
+  ok = ok && fprintf(f, "\ntotal\t%.10e\t%.10e\n", tot[0], tot[1]) > 0;
+  for (uint64_t w = 0, a = 0; w < W; w++) {
+    ok = ok && fprintf(f, "%lu", (unsigned long)w) > 0;
+    for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(f, "\t%.10e", status[w] ? xy[a * K + k] : std::nan("")) > 0;
+    ok = ok && fputc('\n', f) != EOF;
+    a += status[w] != 0;
+  }
+  ok = ok && fputc('\n', f) != EOF;
+  close(f, ok);
+}
+
 // ---- the plain run: the full data set and its replicates ----
 // One batch of matrices: the full data alone (ngd_run), or the full-data matrix plus the first replicates (ngd_run_job,
 // which lets the engine share work between them), or replicates only (ngd_run_batch).  True: the batch's matrices stay
@@ -2494,6 +2614,7 @@ int main(int argc, char **argv) {
     else if (p.mds) coordinates(p, eng, win, rng, out);
     else if (p.boot_stats) bootstrap_summaries(p, eng, win, group_of, group_names, rng, out);
     else if (p.in_groups) group_means(p, eng, win, group_of, group_names, rng, batch, out);
+    else if (p.win_cmp) compared_windows(p, eng, win, out);
     else if (p.win) window_matrices(p, eng, win, out);
     else plain_matrices(p, eng, rng, batch, out);
     g_phases.mark("matrices");

@@ -12,6 +12,7 @@
 #include <string>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <thread>
 #include <unordered_set>
@@ -19,6 +20,7 @@
 
 #include "../../include/ngsdist_amd.h"
 #include "ngd_shard.h"
+#include "win_cmp_geom.h"
 
 namespace {
 // gsl_rng_taus: GSL is a third-party dependency of the reference (README.md:20,
@@ -1423,5 +1425,73 @@ int ngd_mds_align_host(const double *eig, const double *vec, const uint32_t *sta
       fit[m] = f;
     }
   });
+  return NGD_OK;
+}
+
+// ---- comparison of windows (--win_cmp): the contract of include/ngsdist_amd.h "Comparison of windows" in plain host
+// arithmetic -- sums in slices of ngd_win_cmp_slice() cells, a slice's cells in order, the slices in ascending order --, the
+// cut of the cell axis that win_cmp.hip follows too (win_cmp_geom.h), and the derived tables.
+uint32_t ngd_win_cmp_max_vec(void) { return NGD_WIN_CMP_MAX_VEC; }
+uint64_t ngd_win_cmp_slice(uint64_t n_vec, uint64_t n_cells) { return ngd_wincmp_slice(n_vec, n_cells); }
+
+namespace {
+// SUM_c f(c) over [0, P) in slices of s cells
+template <typename F>
+inline double sliced_sum(uint64_t P, uint64_t s, F f) {
+  double total = 0.0;
+  for (uint64_t c0 = 0; c0 < P; c0 += s) {
+    const uint64_t c1 = std::min(P, c0 + s);
+    double part = 0.0;
+    for (uint64_t c = c0; c < c1; c++) part += f(c);
+    total = c0 ? total + part : part;
+  }
+  return total;
+}
+}  // namespace
+
+int ngd_win_cmp_host(const double *values, uint64_t n_vec, uint64_t n_cells, double *mean, double *gram, uint32_t *status) {
+  if (!values || !mean || !gram || !status || !n_vec || !n_cells || n_vec > ngd_win_cmp_max_vec()) return NGD_E_INVALID;
+  const uint64_t W = n_vec, P = n_cells, s = ngd_win_cmp_slice(W, P);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const unsigned parts = (unsigned)std::min<uint64_t>(W, 1024);
+  std::vector<double> Z(W * P);
+  host_pool().run(parts, [&](unsigned part) {
+    for (uint64_t w = part; w < W; w += parts) {
+      const double *x = values + w * P;
+      bool ok = true;
+      for (uint64_t c = 0; c < P; c++) ok = ok && std::isfinite(x[c]);
+      status[w] = ok ? 1u : 0u;
+      mean[w] = ok ? sliced_sum(P, s, [&](uint64_t c) { return x[c]; }) / (double)P : nan;
+      for (uint64_t c = 0; c < P; c++) Z[w * P + c] = ok ? x[c] - mean[w] : 0.0;
+    }
+  });
+  host_pool().run(parts, [&](unsigned part) {
+    for (uint64_t a = part; a < W; a += parts)
+      for (uint64_t b = a; b < W; b++) {
+        const double *za = &Z[a * P], *zb = &Z[b * P];
+        const double g = status[a] && status[b] ? sliced_sum(P, s, [&](uint64_t c) { return za[c] * zb[c]; }) : nan;
+        gram[a * W + b] = gram[b * W + a] = g;
+      }
+  });
+  return NGD_OK;
+}
+
+int ngd_win_cmp_finish(const double *mean, const double *gram, const uint32_t *status, uint64_t n_vec, uint64_t n_cells, double *cor,
+                       double *rms) {
+  if (!mean || !gram || !status || !cor || !rms || !n_vec || !n_cells) return NGD_E_INVALID;
+  const uint64_t W = n_vec;
+  const double nan = std::numeric_limits<double>::quiet_NaN(), P = (double)n_cells;
+  for (uint64_t a = 0; a < W; a++)
+    for (uint64_t b = 0; b < W; b++) {
+      const uint64_t at = a * W + b;
+      if (!status[a] || !status[b]) {
+        cor[at] = rms[at] = nan;
+        continue;
+      }
+      const double gaa = gram[a * W + a], gbb = gram[b * W + b], gab = gram[at], dm = mean[a] - mean[b];
+      cor[at] = gaa == 0.0 || gbb == 0.0 ? nan : gab / std::sqrt(gaa * gbb);
+      const double q = gaa + gbb - 2 * gab + P * (dm * dm);
+      rms[at] = a == b ? 0.0 : std::sqrt((q > 0.0 ? q : 0.0) / P);
+    }
   return NGD_OK;
 }

@@ -285,6 +285,14 @@ struct ngd_engine : ngd_mem {
     DevBuf<uint32_t> d_status;
     double ms = 0;  // ngd_last_mds_align_ms
   } mal;
+  // comparison of windows (engine_win_cmp.hip): the operand Z and the partials, resident for a whole call; the call's means,
+  // status and Gram matrix on their way to the host
+  struct WinCmp {
+    DevBuf<double> Z, part, d_mean, d_gram;
+    DevBuf<uint32_t> d_status;
+    uint64_t max_bytes = 0;         // NGD_OPT_WIN_CMP_MAX_BYTES
+    double ms[4] = {0, 0, 0, 0};    // ngd_last_win_cmp_ms: stats, pack, gram, sum
+  } wcmp;
 };
 
 // what the launchers of accum_mfma.hip / accum_em_table.hip are handed of the engine (ngd_internal.h)

@@ -6,6 +6,7 @@
 #include "../../include/ngsdist_amd.h"
 #include "ngd_layout.h"
 #include "win_plan.h"
+#include "win_cmp_geom.h"
 
 #define NGD_TILE 128     // pair tile edge owned by one workgroup of the MFMA kernel
 #define NGD_IG 16        // individuals per fragment group (one MFMA operand edge)
@@ -474,6 +475,26 @@ int ngd_launch_mds_coords(hipStream_t st, const double *d_eig, const double *d_v
 // n_ind: the caller's to see to.  Returns a hipError_t.
 int ngd_launch_mds_align(hipStream_t st, double *d_cells, uint64_t stride, const uint32_t *d_status, uint64_t n_set, uint32_t n_mat,
                          uint32_t n_ind, uint32_t K, double *d_fit);
+
+// win_cmp.hip : comparison of windows (include/ngsdist_amd.h "Comparison of windows"): means, status and the centred Gram
+// matrix of n_vec vectors of n_cells cells each
+// (the geometry -- NGD_WIN_CMP_MAX_VEC, the tile block, Z's vector groups, the slice rule: win_cmp_geom.h)
+// doubles of the resident operand Z (fragment-major: k-groups of 4 cells x ngd_wincmp_groups(n_vec) groups of 16 vectors, +
+// the run-ahead k-group) and of the partials [slice][group][group][256]; both known from (n_vec, n_cells)
+uint64_t ngd_wincmp_z_doubles(uint64_t n_vec, uint64_t n_cells);
+uint64_t ngd_wincmp_part_doubles(uint64_t n_vec, uint64_t n_cells);
+// [n_vec][n_cells] sums and counts (d_cnt is not read when tot_sites > 0) or, `values`, the cells as they are: the launch's
+// vector v is vector w0 + v of the call -> d_mean / d_status [w0 + v]; then x - mean into Z, which the caller has zeroed
+// once (n_vec_call: the vectors of the whole call, which sets Z's geometry).  n_cells >= 1, n_vec_call <=
+// NGD_WIN_CMP_MAX_VEC: the caller's to see to.  Each returns a hipError_t.
+int ngd_launch_wincmp_stats(hipStream_t st, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_vec,
+                            uint64_t n_cells, uint64_t tot_sites, uint32_t model, uint64_t w0, double *d_mean, uint32_t *d_status);
+int ngd_launch_wincmp_pack(hipStream_t st, const double *d_a, const unsigned long long *d_cnt, bool values, uint64_t n_vec,
+                           uint64_t n_cells, uint64_t tot_sites, uint32_t model, uint64_t w0, uint64_t n_vec_call, const double *d_mean,
+                           const uint32_t *d_status, double *Z);
+// Z -> the partials of every (slice, tile on or above the diagonal); then gram [n_vec][n_vec] from them and d_status
+int ngd_launch_wincmp_gram(hipStream_t st, const double *Z, uint64_t n_vec, uint64_t n_cells, double *part);
+int ngd_launch_wincmp_sum(hipStream_t st, const double *part, uint64_t n_vec, uint64_t n_cells, const uint32_t *d_status, double *gram);
 
 // group_reduce.hip : group-mean distance matrices (ngd_set_groups, ngd_group_means_device, ngd_run_*_groups)
 // One work item: rows [r0, r1) of group pair (a, b) -- positions in group a's member list --, every column of group b

@@ -17,7 +17,7 @@ KERNELS = {"auto": 0, "stream": 1, "mfma": 2, "em_faithful": 3, "em_fast": 4, "e
 OPTIONS = {"boot_partials": 1, "boot_max_bytes": 2, "boot_wg": 3, "boot_unaligned": 4, "em_batch": 5,
            "em_spill": 6, "em_spill_bytes": 7, "single_image_bytes": 8, "fixup_work": 9, "stage_piece_mib": 10,
            "stage_ring": 11, "eager_full": 12, "win_plan": 13, "win_max_bytes": 14, "em_exact": 15, "em_exact_cap": 16,
-           "unit_skip": 17, "em_exact_win": 18, "nj_max_bytes": 19, "mds_max_bytes": 20,
+           "unit_skip": 17, "em_exact_win": 18, "nj_max_bytes": 19, "mds_max_bytes": 20, "win_cmp_max_bytes": 21,
            "debug_forge_job": 100}
 # ngd_em_exact_entry
 EM_EXACT_ENTRY = np.dtype([("i1", np.uint32), ("i2", np.uint32), ("site", np.uint64), ("t_dev", np.uint32),
@@ -606,6 +606,47 @@ class Engine:
         _check(self._L.ngd_last_mds_ms(self._h, C.byref(v)))
         return float(v.value)
 
+    # -- comparison of windows: per vector its mean and status, per pair of vectors the centred Gram entry ----
+    @staticmethod
+    def _win_cmp_out(W):
+        mean = np.empty(W, dtype=np.float64)
+        gram = np.empty((W, W), dtype=np.float64)
+        status = np.empty(W, dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        return (mean, gram, status), (mean.ctypes.data_as(dp), gram.ctypes.data_as(dp), status.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    def win_cmp(self, d_sum_ptr, d_cnt_ptr, n_vec, evol_model=1, tot_sites=0):
+        """the windows of device matrices compared (ngd_win_cmp_device; raw addresses of [n_vec][n_pairs] sums and counts, as
+        run_windows_device() wrote them): -> (mean float64[n_vec], gram float64[n_vec][n_vec], status uint32[n_vec]); status
+        0 (mean, row and column NaN): a matrix with a cell that is not finite.  win_cmp_finish() derives cor and rms"""
+        out, args = self._win_cmp_out(int(n_vec))
+        _check(self._L.ngd_win_cmp_device(self._h, C.c_void_p(d_sum_ptr), C.c_void_p(d_cnt_ptr), int(n_vec), int(tot_sites),
+                                          int(evol_model), *args))
+        return out
+
+    def win_cmp_values(self, d_val_ptr, n_vec, n_cells):
+        """the same of [n_vec][n_cells] float64 vectors in device memory as they are (ngd_win_cmp_values_device); n_cells is
+        free of the engine's n_ind"""
+        out, args = self._win_cmp_out(int(n_vec))
+        _check(self._L.ngd_win_cmp_values_device(self._h, C.c_void_p(d_val_ptr), int(n_vec), int(n_cells), *args))
+        return out
+
+    def run_windows_cmp(self, lo, hi, evol_model=1, tot_sites=0, dist=True):
+        """run_windows() and the comparison of its windows on the device (ngd_run_windows_cmp): -> (mean (n_win,), gram
+        (n_win, n_win), status (n_win,), dist (n_win, n_pairs)); dist (None with dist=False) is run_windows_dist()'s"""
+        lo, hi, lp_, hp = self._win_args(lo, hi)
+        out, args = self._win_cmp_out(lo.size)
+        d = np.empty((lo.size, self.n_pairs), dtype=np.float64) if dist else None
+        _check(self._L.ngd_run_windows_cmp(self._h, lp_, hp, lo.size, int(tot_sites), int(evol_model), *args,
+                                           None if d is None else d.ctypes.data_as(C.POINTER(C.c_double))))
+        return out + (d,)
+
+    def last_win_cmp_ms(self):
+        """device time of the four kernels in the last of these calls (ngd_last_win_cmp_ms): dict of stats, pack, gram, sum"""
+        v = (C.c_double * 4)()
+        _check(self._L.ngd_last_win_cmp_ms(self._h, v))
+        return dict(zip(("stats", "pack", "gram", "sum"), (float(x) for x in v)))
+
     # -- the MDS replicates of a set rotated onto its matrix 0, and the summaries of the aligned cells ----
     def mds_align_values(self, d_coords_ptr, n_set, n_mat, K, status=None):
         """the alignment alone, of [n_set][n_mat][K][n] float64 coordinates in device memory as they are
@@ -692,7 +733,8 @@ class Engine:
         are served too -- run_windows* under 1 or 2, run_windows_job* under 2); unit_skip (0: the plain pass of a
         one-image engine in congruent coordinates visits the k-groups of p0 + p1 + p2 too: plain_pass_kgroups());
         nj_max_bytes (device scratch of the neighbour-joining kernel, 0 = 2 GB: the matrices a launch takes);
-        mds_max_bytes (the same for the classical-MDS kernel)"""
+        mds_max_bytes (the same for the classical-MDS kernel); win_cmp_max_bytes (device memory of the comparison of windows,
+        0 = half of what is free at the call: a call that needs more is refused)"""
         _check(self._L.ngd_set_option(self._h, OPTIONS[name], int(value)))
         return self
 
@@ -1016,6 +1058,49 @@ def mds_host(values, n_ind, K):
     _check(_lib.load().ngd_mds_host(v.ctypes.data_as(dp), n_mat, n_ind, Kc, eig.ctypes.data_as(dp), vec.ctypes.data_as(dp),
                                     tot.ctypes.data_as(dp), status.ctypes.data_as(C.POINTER(C.c_uint32))))
     return eig, vec, tot, status
+
+
+def win_cmp_max_vec():
+    """the most vectors a comparison of windows takes (ngd_win_cmp_max_vec)"""
+    return int(_lib.load().ngd_win_cmp_max_vec())
+
+
+def win_cmp_slice(n_vec, n_cells):
+    """cells per slice of the cell axis in the comparison of n_vec vectors of n_cells cells (ngd_win_cmp_slice)"""
+    return int(_lib.load().ngd_win_cmp_slice(int(n_vec), int(n_cells)))
+
+
+def win_cmp_host(values):
+    """the comparison of windows in plain host arithmetic (ngd_win_cmp_host), the device form's twin: values
+    float64[n_vec][n_cells] -> (mean float64[n_vec], gram float64[n_vec][n_vec], status uint32[n_vec])"""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.ndim != 2:
+        raise ValueError("values: expected [n_vec][n_cells]")
+    W, P = v.shape
+    mean = np.empty(W, dtype=np.float64)
+    gram = np.empty((W, W), dtype=np.float64)
+    status = np.empty(W, dtype=np.uint32)
+    dp = C.POINTER(C.c_double)
+    _check(_lib.load().ngd_win_cmp_host(v.ctypes.data_as(dp), W, P, mean.ctypes.data_as(dp), gram.ctypes.data_as(dp),
+                                        status.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return mean, gram, status
+
+
+def win_cmp_finish(mean, gram, status, n_cells):
+    """the Mantel correlations and RMS differences of compared windows (ngd_win_cmp_finish): -> (cor float64[n_vec][n_vec],
+    rms float64[n_vec][n_vec]); NaN wherever a status-0 vector is touched, cor NaN where a diagonal of gram is exactly 0"""
+    m = np.ascontiguousarray(mean, dtype=np.float64)
+    g = np.ascontiguousarray(gram, dtype=np.float64)
+    st = np.ascontiguousarray(status, dtype=np.uint32)
+    W = m.size
+    if m.ndim != 1 or g.shape != (W, W) or st.shape != (W,):
+        raise ValueError("expected mean [n_vec], gram [n_vec][n_vec], status [n_vec]")
+    cor = np.empty((W, W), dtype=np.float64)
+    rms = np.empty((W, W), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    _check(_lib.load().ngd_win_cmp_finish(m.ctypes.data_as(dp), g.ctypes.data_as(dp), st.ctypes.data_as(C.POINTER(C.c_uint32)), W,
+                                          int(n_cells), cor.ctypes.data_as(dp), rms.ctypes.data_as(dp)))
+    return cor, rms
 
 
 def mds_coords(eig, vec):
