@@ -1740,11 +1740,15 @@ void draw_job_maps(uint32_t rng[3], uint64_t R, uint64_t n_blocks, std::vector<u
 
 // The windows go to the engine a group per call, a group being the windows whose results -- bytes_per_window each -- fit
 // ~2 GB of host memory: call(w0, n) makes the engine call for windows w0 .. w0 + n - 1, written(w0, n) prints them.
-// wait_writer: the last block's text is written before the next group's call.
+// wait_writer: the last block's text is written before the next group's call.  NGSDIST_WIN_GROUP_MAX in the environment
+// (the tests' knob; unset, empty or 0: none) lowers a group to at most that many windows.
 template <typename Call, typename Written>
 void for_window_groups(const Pars &p, Engine &eng, MatrixOut &out, uint64_t n_win, uint64_t bytes_per_window, bool wait_writer,
                        Call call, Written written) {
-  const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / bytes_per_window));
+  uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(n_win, (2ull << 30) / bytes_per_window));
+  const char *const knob = getenv("NGSDIST_WIN_GROUP_MAX");
+  const uint64_t most = knob ? strtoull(knob, nullptr, 10) : 0;
+  if (most) per = std::min(per, most);
   for (uint64_t w0 = 0; w0 < n_win; w0 += per) {
     const uint64_t n = std::min(per, n_win - w0);
     const auto t_c0 = std::chrono::steady_clock::now();
@@ -1754,6 +1758,72 @@ void for_window_groups(const Pars &p, Engine &eng, MatrixOut &out, uint64_t n_wi
     written(w0, n);
     if (wait_writer) out.writer.wait_idle();
   }
+}
+
+// What run_sets() needs of a mode whose engine calls return SETS: the run's one set -- the full data set and its replicates --
+// or one per window.
+using EngineCall = std::pair<const char *, int>;  // an entry point's name, as engine_ok prints it, and its return code
+struct SetMode {
+  const char *no_block;        // the refusal of replicates on fewer sites than one bootstrap block
+  uint64_t bytes_per_window;   // of results: what sizes a group of windows
+  bool wait_writer = true;     // a group's end waits for <out>'s writer (for_window_groups)
+  std::function<void(uint64_t n_sets)> resize;  // the result vectors, for one call
+  std::function<EngineCall(const uint64_t *maps, uint64_t n_blocks)> job;  // the whole-genome call
+  // the windowed call on n windows: the whole table of maps, the offsets of these windows
+  std::function<EngineCall(const uint64_t *lo, const uint64_t *hi, uint64_t n, const uint64_t *maps, uint64_t maps_len,
+                           const uint64_t *off)> windows;
+  std::function<void(uint64_t w, const char *name, uint64_t k)> write_set;  // set k of the call's results: the run's set w
+};
+
+// The driver of --nj, --mds, --mds_align and --boot_stats.  Without windows: the full data set and all its replicates in ONE
+// call, their maps drawn in the reference's order.  With windows: a group of them per call (for_window_groups), every window
+// with the maps of its own cut-down run (--win_boot_rep; the replicates of a window shorter than one block are 0 / 0), then
+// <out>.windows.  window_matrices, group_means, compared_windows, plain_matrices and site_range_matrices keep their own flow --
+// one arm, batches of replicates, or one call for all windows: this driver is not for them.
+void run_sets(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], MatrixOut &out, const SetMode &mode) {
+  const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep;
+  std::vector<uint64_t> maps(1);
+  if (!p.win) {
+    const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
+    if (R && !n_blocks) die(kMain, mode.no_block);
+    const auto t_c0 = std::chrono::steady_clock::now();
+    draw_job_maps(rng, R, n_blocks, maps);
+    mode.resize(1);
+    const auto call = mode.job(maps.data(), n_blocks);
+    engine_ok(call.first, call.second);
+    report_fixup(eng.h, p.verbose);
+    out.t_compute += since(t_c0);
+    mode.write_set(0, nullptr, 0);
+    return;
+  }
+  std::vector<uint64_t> off(win.size());
+  const uint64_t maps_len = R ? draw_window_maps(p, win, R, maps, off) : 0;
+  for_window_groups(p, eng, out, win.size(), mode.bytes_per_window, mode.wait_writer,
+    [&](uint64_t w0, uint64_t n) {
+      mode.resize(n);
+      const auto call = mode.windows(&win.lo[w0], &win.hi[w0], n, maps.data(), maps_len, &off[w0]);
+      engine_ok(call.first, call.second);
+    },
+    [&](uint64_t w0, uint64_t n) {
+      for (uint64_t k = 0; k < n; k++) mode.write_set(w0 + k, win.name(w0 + k).c_str(), k);
+    });
+  win.write_file(std::string(p.out) + ".windows", p);
+}
+
+// One block of <out>.mds and its kin: "eig" and the K eigenvalues, "total" and tot[0], tot[1] (tot null: no such line), a line
+// per row with its label -- label(f, i) writes it and says whether it could -- and the K numbers at(i, k), an empty line; tabs
+// between fields, every number as "%.10e".  False: a write failed.
+template <typename Label, typename At>
+bool write_mds_block(FILE *f, const double *eig, uint32_t K, const double *tot, uint64_t n, Label label, At at) {
+  auto numbers = [&](auto value) {  // the K numbers of a line and its end
+    bool ok = true;
+    for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(f, "\t%.10e", value(k)) > 0;
+    return ok && fputc('\n', f) != EOF;
+  };
+  bool ok = fputs("eig", f) >= 0 && numbers([&](uint32_t k) { return eig[k]; });
+  if (tot) ok = ok && fprintf(f, "total\t%.10e\t%.10e\n", tot[0], tot[1]) > 0;
+  for (uint64_t i = 0; i < n; i++) ok = ok && label(f, i) && numbers([&](uint32_t k) { return at(i, k); });
+  return ok && fputc('\n', f) != EOF;
 }
 
 // ---- the site axis in ranges: side by side on the devices, one after the other where they are too small; the matrices of
@@ -1901,9 +1971,37 @@ void trees(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], M
     const int64_t need = format_grown(line, [&](char *buf, size_t cap) { return ngd_nj_newick(c, l, p.n_ind, out.label_ptr.data(), sup, buf, cap); });
     if (need < 0 || fwrite(line.data(), 1, (size_t)need, f) != (size_t)need) die(kLambda, "cannot write trees output file!");
   };
+  std::vector<int32_t> child;
+  std::vector<double> len, d0;
+  std::vector<uint32_t> status;
+  SetMode mode;
+  mode.no_block = "neighbour-joining trees (--nj) of bootstrap replicates need at least one bootstrap block of sites!";
+  mode.bytes_per_window = n_mat * nb * 12 + n_mat * 4 + n_comb * 8;  // (a window's records and first matrix)
+  mode.resize = [&](uint64_t n_sets) {
+    child.resize(n_sets * n_mat * nb);
+    len.resize(n_sets * n_mat * nb);
+    status.resize(n_sets * n_mat);
+    d0.resize(n_sets * n_comb);
+  };
+  mode.job = [&](const uint64_t *maps, uint64_t n_blocks) -> EngineCall {
+    return {"ngd_run_job_nj", ngd_run_job_nj(eng.h, maps, (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, child.data(),
+                                             len.data(), status.data(), d0.data())};
+  };
+  // (--win_boot_rep: the replicates of a window shorter than one block have no tree)
+  mode.windows = [&](const uint64_t *lo, const uint64_t *hi, uint64_t n, const uint64_t *maps, uint64_t maps_len,
+                     const uint64_t *off) -> EngineCall {
+    if (!R)
+      return {"ngd_run_windows_nj", ngd_run_windows_nj(eng.h, lo, hi, n, p.tot_sites, p.evol_model, child.data(), len.data(), status.data(),
+                                                       d0.data())};
+    return {"ngd_run_windows_job_var_nj", ngd_run_windows_job_var_nj(eng.h, lo, hi, n, maps, maps_len, off, (uint32_t)R, p.boot_block_size, p.tot_sites,
+                                                                     p.evol_model, child.data(), len.data(), status.data(), d0.data())};
+  };
   // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), its trees, its supports
-  auto write_set = [&](uint64_t w, const char *name, const double *m0, const int32_t *c, const double *l, const uint32_t *st) {
-    out.emit(w, nullptr, nullptr, nullptr, 0, m0, 0, name);
+  mode.write_set = [&](uint64_t w, const char *name, uint64_t k) {
+    const int32_t *c = &child[k * n_mat * nb];
+    const double *l = &len[k * n_mat * nb];
+    const uint32_t *st = &status[k * n_mat];
+    out.emit(w, nullptr, nullptr, nullptr, 0, &d0[k * n_comb], 0, name);
     for (uint64_t r = 0; r < n_mat; r++) {
       write_tree(nf, c + r * nb, l + r * nb, nullptr);
       n_no_tree += st[r] == 0;
@@ -1913,49 +2011,7 @@ void trees(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng[3], M
     if (ngd_nj_support(c, st, n_mat, p.n_ind, support.data(), &used)) die(kLambda, "cannot count the trees' support!");
     write_tree(sf, c, l, support.data());
   };
-  std::vector<int32_t> child;
-  std::vector<double> len, d0;
-  std::vector<uint32_t> status;
-  auto resize_results = [&](uint64_t n_sets) {
-    child.resize(n_sets * n_mat * nb);
-    len.resize(n_sets * n_mat * nb);
-    status.resize(n_sets * n_mat);
-    d0.resize(n_sets * n_comb);
-  };
-  if (p.win) {
-    // a group of windows per call: their records and first matrices in ~2 GB of host memory.  --win_boot_rep: the
-    // replicates of a window shorter than one block are 0 / 0 and have no tree
-    std::vector<uint64_t> off(win.size()), maps(1);
-    const uint64_t mlen = R ? draw_window_maps(p, win, R, maps, off) : 0;
-    for_window_groups(p, eng, out, win.size(), n_mat * nb * 12 + n_mat * 4 + n_comb * 8, true,
-      [&](uint64_t w0, uint64_t n) {
-        resize_results(n);
-        const int rc = R ? ngd_run_windows_job_var_nj(eng.h, &win.lo[w0], &win.hi[w0], n, maps.data(), mlen, &off[w0], (uint32_t)R,
-                                                      p.boot_block_size, p.tot_sites, p.evol_model, child.data(), len.data(),
-                                                      status.data(), d0.data())
-                         : ngd_run_windows_nj(eng.h, &win.lo[w0], &win.hi[w0], n, p.tot_sites, p.evol_model, child.data(), len.data(),
-                                              status.data(), d0.data());
-        engine_ok(R ? "ngd_run_windows_job_var_nj" : "ngd_run_windows_nj", rc);
-      },
-      [&](uint64_t w0, uint64_t n) {
-        for (uint64_t k = 0; k < n; k++)
-          write_set(w0 + k, win.name(w0 + k).c_str(), &d0[k * n_comb], &child[k * n_mat * nb], &len[k * n_mat * nb], &status[k * n_mat]);
-      });
-    win.write_file(std::string(p.out) + ".windows", p);
-  } else {
-    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
-    const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
-    if (R && !n_blocks) die(kMain, "neighbour-joining trees (--nj) of bootstrap replicates need at least one bootstrap block of sites!");
-    const auto t_c0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> maps;
-    draw_job_maps(rng, R, n_blocks, maps);
-    resize_results(1);
-    engine_ok("ngd_run_job_nj", ngd_run_job_nj(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model,
-                                               child.data(), len.data(), status.data(), d0.data()));
-    report_fixup(eng.h, p.verbose);
-    out.t_compute += since(t_c0);
-    write_set(0, nullptr, d0.data(), child.data(), len.data(), status.data());
-  }
+  run_sets(p, eng, win, rng, out, mode);
   if (n_no_tree)
     fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no tree (a line \";\" in %s.nwk)\n",
             (unsigned long)n_no_tree, p.out);
@@ -1974,69 +2030,43 @@ void coordinates(const Pars &p, Engine &eng, const WindowList &win, uint32_t rng
   if (!mf) die(kMain, "cannot open coordinates output file!");
   std::vector<double> xy(n * K);
   uint64_t n_bad = 0;
-  // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), then its matrices' blocks
-  auto write_set = [&](uint64_t w, const char *name, const double *m0, const double *eig, const double *vec, const double *tot,
-                       const uint32_t *st) {
-    out.emit(w, nullptr, nullptr, nullptr, 0, m0, 0, name);
-    for (uint64_t r = 0; r < n_mat; r++) {
-      const double *e = eig + r * K;
-      if (ngd_mds_coords(e, vec + r * K * n, 1, n, K, xy.data())) die(kLambda, "cannot derive the coordinates!");
-      n_bad += st[r] == 0;
-      bool ok = fputs("eig", mf) >= 0;
-      for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(mf, "\t%.10e", e[k]) > 0;
-      ok = ok && fprintf(mf, "\ntotal\t%.10e\t%.10e\n", tot[2 * r], tot[2 * r + 1]) > 0;
-      for (uint64_t i = 0; i < n; i++) {
-        ok = ok && fputs(out.label_ptr[i], mf) >= 0;
-        for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(mf, "\t%.10e", xy[i * K + k]) > 0;
-        ok = ok && fputc('\n', mf) != EOF;
-      }
-      if (!ok || fputc('\n', mf) == EOF) die(kLambda, "cannot write coordinates output file!");
-    }
-  };
   std::vector<double> eig, vec, tot, d0;
   std::vector<uint32_t> status;
-  auto resize_results = [&](uint64_t n_sets) {
+  SetMode mode;
+  mode.no_block = "classical MDS (--mds) of bootstrap replicates needs at least one bootstrap block of sites!";
+  mode.bytes_per_window = n_mat * (K * (n + 1) + 2) * 8 + n_mat * 4 + n_comb * 8;  // (a window's outputs and first matrix)
+  mode.resize = [&](uint64_t n_sets) {
     eig.resize(n_sets * n_mat * K);
     vec.resize(n_sets * n_mat * K * n);
     tot.resize(n_sets * n_mat * 2);
     status.resize(n_sets * n_mat);
     d0.resize(n_sets * n_comb);
   };
-  if (p.win) {
-    // a group of windows per call: their outputs and first matrices in ~2 GB of host memory.  --win_boot_rep: the
-    // replicates of a window shorter than one block are 0 / 0 and have no coordinates
-    std::vector<uint64_t> off(win.size()), maps(1);
-    const uint64_t mlen = R ? draw_window_maps(p, win, R, maps, off) : 0;
-    for_window_groups(p, eng, out, win.size(), n_mat * (K * (n + 1) + 2) * 8 + n_mat * 4 + n_comb * 8, true,
-      [&](uint64_t w0, uint64_t nw) {
-        resize_results(nw);
-        const int rc = R ? ngd_run_windows_job_var_mds(eng.h, &win.lo[w0], &win.hi[w0], nw, maps.data(), mlen, &off[w0], (uint32_t)R,
-                                                       p.boot_block_size, p.tot_sites, p.evol_model, K, eig.data(), vec.data(),
-                                                       tot.data(), status.data(), d0.data())
-                         : ngd_run_windows_mds(eng.h, &win.lo[w0], &win.hi[w0], nw, p.tot_sites, p.evol_model, K, eig.data(), vec.data(),
-                                               tot.data(), status.data(), d0.data());
-        engine_ok(R ? "ngd_run_windows_job_var_mds" : "ngd_run_windows_mds", rc);
-      },
-      [&](uint64_t w0, uint64_t nw) {
-        for (uint64_t k = 0; k < nw; k++)
-          write_set(w0 + k, win.name(w0 + k).c_str(), &d0[k * n_comb], &eig[k * n_mat * K], &vec[k * n_mat * K * n], &tot[k * n_mat * 2],
-                    &status[k * n_mat]);
-      });
-    win.write_file(std::string(p.out) + ".windows", p);
-  } else {
-    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
-    const uint64_t n_blocks = R ? (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size : 0;
-    if (R && !n_blocks) die(kMain, "classical MDS (--mds) of bootstrap replicates needs at least one bootstrap block of sites!");
-    const auto t_c0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> maps;
-    draw_job_maps(rng, R, n_blocks, maps);
-    resize_results(1);
-    engine_ok("ngd_run_job_mds", ngd_run_job_mds(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, K,
-                                                 eig.data(), vec.data(), tot.data(), status.data(), d0.data()));
-    report_fixup(eng.h, p.verbose);
-    out.t_compute += since(t_c0);
-    write_set(0, nullptr, d0.data(), eig.data(), vec.data(), tot.data(), status.data());
-  }
+  mode.job = [&](const uint64_t *maps, uint64_t n_blocks) -> EngineCall {
+    return {"ngd_run_job_mds", ngd_run_job_mds(eng.h, maps, (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, K, eig.data(),
+                                               vec.data(), tot.data(), status.data(), d0.data())};
+  };
+  // (--win_boot_rep: the replicates of a window shorter than one block have no coordinates)
+  mode.windows = [&](const uint64_t *lo, const uint64_t *hi, uint64_t nw, const uint64_t *maps, uint64_t maps_len,
+                     const uint64_t *off) -> EngineCall {
+    if (!R)
+      return {"ngd_run_windows_mds", ngd_run_windows_mds(eng.h, lo, hi, nw, p.tot_sites, p.evol_model, K, eig.data(), vec.data(), tot.data(),
+                                                         status.data(), d0.data())};
+    return {"ngd_run_windows_job_var_mds", ngd_run_windows_job_var_mds(eng.h, lo, hi, nw, maps, maps_len, off, (uint32_t)R, p.boot_block_size, p.tot_sites,
+                                                                       p.evol_model, K, eig.data(), vec.data(), tot.data(), status.data(), d0.data())};
+  };
+  // one set: matrix 0's block through emit() (the progress lines and the writer of any matrix), then its matrices' blocks
+  mode.write_set = [&](uint64_t w, const char *name, uint64_t k) {
+    out.emit(w, nullptr, nullptr, nullptr, 0, &d0[k * n_comb], 0, name);
+    for (uint64_t m = k * n_mat; m < (k + 1) * n_mat; m++) {
+      if (ngd_mds_coords(&eig[m * K], &vec[m * K * n], 1, n, K, xy.data())) die(kLambda, "cannot derive the coordinates!");
+      n_bad += status[m] == 0;
+      if (!write_mds_block(mf, &eig[m * K], K, &tot[m * 2], n, [&](FILE *f, uint64_t i) { return fputs(out.label_ptr[i], f) >= 0; },
+                           [&](uint64_t i, uint32_t d) { return xy[i * K + d]; }))
+        die(kLambda, "cannot write coordinates output file!");
+    }
+  };
+  run_sets(p, eng, win, rng, out, mode);
   if (n_bad)
     fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no coordinates (\"nan\" throughout their blocks in %s.mds)\n",
             (unsigned long)n_bad, p.out);
@@ -2059,35 +2089,13 @@ void aligned_coordinates(const Pars &p, Engine &eng, const WindowList &win, uint
     if (!(sf[k] = fopen((std::string(p.out) + kSuffix[k]).c_str(), "w"))) die(kMain, "cannot open coordinates output file!");
   std::vector<double> xy(n * K);
   uint64_t n_bad = 0;
-  // one set: matrix 0's block through emit(), then its blocks and its line of fits
-  auto write_set = [&](uint64_t w, const char *name, const double *m0, const double *eig0, const double *vec0, const double *tot0,
-                       const uint32_t *st, const double *stats, uint64_t used, const double *fit) {
-    out.emit(w, nullptr, nullptr, nullptr, 0, m0, 0, name);
-    if (ngd_mds_coords(eig0, vec0, 1, n, K, xy.data())) die(kLambda, "cannot derive the coordinates!");
-    for (uint64_t r = 0; r < n_mat; r++) n_bad += st[r] == 0;
-    for (int k = 0; k < NGD_BOOT_NSTAT; k++) {
-      FILE *f = sf[k];
-      const double *cell = stats + k * n_cells;  // [K][n] coordinates, then [K] eigenvalues
-      bool ok = fputs("eig", f) >= 0;
-      for (uint32_t d = 0; d < K; d++) ok = ok && fprintf(f, "\t%.10e", k ? cell[K * n + d] : eig0[d]) > 0;
-      ok = ok && fputc('\n', f) != EOF;
-      if (!k) ok = ok && fprintf(f, "total\t%.10e\t%.10e\n", tot0[0], tot0[1]) > 0;
-      for (uint64_t i = 0; i < n; i++) {
-        ok = ok && fputs(out.label_ptr[i], f) >= 0;
-        for (uint32_t d = 0; d < K; d++) ok = ok && fprintf(f, "\t%.10e", k ? cell[d * n + i] : xy[i * K + d]) > 0;
-        ok = ok && fputc('\n', f) != EOF;
-      }
-      if (!ok || fputc('\n', f) == EOF) die(kLambda, "cannot write coordinates output file!");
-    }
-    bool ok = fprintf(sf[NGD_BOOT_NSTAT], "%lu", (unsigned long)used) > 0;
-    for (uint64_t r = 1; r < n_mat; r++)
-      ok = ok && (std::isnan(fit[r]) ? fputs("\tnan", sf[NGD_BOOT_NSTAT]) >= 0 : fprintf(sf[NGD_BOOT_NSTAT], "\t%.10e", fit[r]) > 0);
-    if (!ok || fputc('\n', sf[NGD_BOOT_NSTAT]) == EOF) die(kLambda, "cannot write coordinates output file!");
-  };
   std::vector<double> eig0, vec0, tot0, stats, fit, d0;
   std::vector<uint32_t> status;
   std::vector<uint64_t> used;
-  auto resize_results = [&](uint64_t n_sets) {
+  SetMode mode;
+  mode.no_block = "aligned replicates (--mds_align) need at least one bootstrap block of sites!";
+  mode.bytes_per_window = ((NGD_BOOT_NSTAT + 1) * n_cells + 3) * 8 + n_mat * 12 + n_comb * 8;  // (a window's outputs and first matrix)
+  mode.resize = [&](uint64_t n_sets) {
     eig0.resize(n_sets * K);
     vec0.resize(n_sets * K * n);
     tot0.resize(n_sets * 2);
@@ -2097,41 +2105,40 @@ void aligned_coordinates(const Pars &p, Engine &eng, const WindowList &win, uint
     fit.resize(n_sets * n_mat);
     d0.resize(n_sets * n_comb);
   };
-  if (p.win) {
-    // a group of windows per call: their outputs and first matrices in ~2 GB of host memory.  The replicates of a window
-    // shorter than one block are 0 / 0 and left out: used 0
-    std::vector<uint64_t> off(win.size()), maps(1);
-    const uint64_t mlen = draw_window_maps(p, win, R, maps, off);
-    for_window_groups(p, eng, out, win.size(), ((NGD_BOOT_NSTAT + 1) * n_cells + 3) * 8 + n_mat * 12 + n_comb * 8, true,
-      [&](uint64_t w0, uint64_t nw) {
-        resize_results(nw);
-        engine_ok("ngd_run_windows_job_var_mds_align",
-                  ngd_run_windows_job_var_mds_align(eng.h, &win.lo[w0], &win.hi[w0], nw, maps.data(), mlen, &off[w0], (uint32_t)R,
-                                                    p.boot_block_size, p.tot_sites, p.evol_model, K, p.mds_ci, eig0.data(), vec0.data(),
-                                                    tot0.data(), status.data(), stats.data(), used.data(), fit.data(), nullptr, d0.data()));
-      },
-      [&](uint64_t w0, uint64_t nw) {
-        for (uint64_t k = 0; k < nw; k++)
-          write_set(w0 + k, win.name(w0 + k).c_str(), &d0[k * n_comb], &eig0[k * K], &vec0[k * K * n], &tot0[k * 2], &status[k * n_mat],
-                    &stats[k * NGD_BOOT_NSTAT * n_cells], used[k], &fit[k * n_mat]);
-      });
-    win.write_file(std::string(p.out) + ".windows", p);
-  } else {
-    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
-    const uint64_t n_blocks = (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size;
-    if (!n_blocks) die(kMain, "aligned replicates (--mds_align) need at least one bootstrap block of sites!");
-    const auto t_c0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> maps;
-    draw_job_maps(rng, R, n_blocks, maps);
-    resize_results(1);
-    engine_ok("ngd_run_job_mds_align",
-              ngd_run_job_mds_align(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, K, p.mds_ci,
-                                    eig0.data(), vec0.data(), tot0.data(), status.data(), stats.data(), used.data(), fit.data(), nullptr,
-                                    d0.data()));
-    report_fixup(eng.h, p.verbose);
-    out.t_compute += since(t_c0);
-    write_set(0, nullptr, d0.data(), eig0.data(), vec0.data(), tot0.data(), status.data(), stats.data(), used[0], fit.data());
-  }
+  mode.job = [&](const uint64_t *maps, uint64_t n_blocks) -> EngineCall {
+    return {"ngd_run_job_mds_align",
+            ngd_run_job_mds_align(eng.h, maps, (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model, K, p.mds_ci, eig0.data(),
+                                  vec0.data(), tot0.data(), status.data(), stats.data(), used.data(), fit.data(), nullptr, d0.data())};
+  };
+  // (the replicates of a window shorter than one block are left out: used 0)
+  mode.windows = [&](const uint64_t *lo, const uint64_t *hi, uint64_t nw, const uint64_t *maps, uint64_t maps_len,
+                     const uint64_t *off) -> EngineCall {
+    return {"ngd_run_windows_job_var_mds_align",
+            ngd_run_windows_job_var_mds_align(eng.h, lo, hi, nw, maps, maps_len, off, (uint32_t)R, p.boot_block_size, p.tot_sites, p.evol_model, K,
+                                              p.mds_ci, eig0.data(), vec0.data(), tot0.data(), status.data(), stats.data(), used.data(),
+                                              fit.data(), nullptr, d0.data())};
+  };
+  // one set: matrix 0's block through emit(), then its blocks and its line of fits
+  mode.write_set = [&](uint64_t w, const char *name, uint64_t k) {
+    out.emit(w, nullptr, nullptr, nullptr, 0, &d0[k * n_comb], 0, name);
+    if (ngd_mds_coords(&eig0[k * K], &vec0[k * K * n], 1, n, K, xy.data())) die(kLambda, "cannot derive the coordinates!");
+    for (uint64_t r = 0; r < n_mat; r++) n_bad += status[k * n_mat + r] == 0;
+    auto label = [&](FILE *f, uint64_t i) { return fputs(out.label_ptr[i], f) >= 0; };
+    // matrix 0's own coordinates [n][K]; of the other statistics the cells [K][n], then their [K] eigenvalues
+    bool ok = write_mds_block(sf[0], &eig0[k * K], K, &tot0[k * 2], n, label, [&](uint64_t i, uint32_t d) { return xy[i * K + d]; });
+    for (int s = 1; s < NGD_BOOT_NSTAT; s++) {
+      const double *cell = &stats[(k * NGD_BOOT_NSTAT + s) * n_cells];
+      ok = ok && write_mds_block(sf[s], cell + K * n, K, nullptr, n, label, [&](uint64_t i, uint32_t d) { return cell[d * n + i]; });
+    }
+    FILE *ff = sf[NGD_BOOT_NSTAT];
+    ok = ok && fprintf(ff, "%lu", (unsigned long)used[k]) > 0;
+    for (uint64_t r = 1; r < n_mat; r++) {
+      const double v = fit[k * n_mat + r];
+      ok = ok && (std::isnan(v) ? fputs("\tnan", ff) >= 0 : fprintf(ff, "\t%.10e", v) > 0);
+    }
+    if (!ok || fputc('\n', ff) == EOF) die(kLambda, "cannot write coordinates output file!");
+  };
+  run_sets(p, eng, win, rng, out, mode);
   if (n_bad)
     fprintf(stderr, "WARNING: %lu of the run's matrices have a cell that is not finite and no coordinates (they are left out of the summaries in %s.mds_*)\n",
             (unsigned long)n_bad, p.out);
@@ -2154,8 +2161,33 @@ void bootstrap_summaries(const Pars &p, Engine &eng, const WindowList &win, cons
     if (!(sf[k] = fopen((std::string(p.out) + kSuffix[k]).c_str(), "w"))) die(kMain, "cannot open bootstrap summaries output file!");
   std::vector<char> text;
   std::string txt, cnt, skip;
+  const uint64_t R = p.win ? p.win_boot_rep : p.n_boot_rep;
+  std::vector<double> stats;
+  std::vector<uint64_t> used;
+  SetMode mode;
+  mode.no_block = "bootstrap summaries (--boot_stats) need at least one bootstrap block of sites!";
+  mode.bytes_per_window = 8 * (NGD_BOOT_NSTAT + 1) * std::max<uint64_t>(1, n_cells);  // (a window's statistics)
+  mode.wait_writer = !grp;  // (group pairs are written here, not by the writer thread: nothing to wait for at a group's end)
+  mode.resize = [&](uint64_t n_sets) {
+    stats.resize(n_sets * NGD_BOOT_NSTAT * n_cells);
+    used.resize(n_sets * n_cells);
+  };
+  mode.job = [&](const uint64_t *maps, uint64_t n_blocks) -> EngineCall {
+    return {grp ? "ngd_run_job_groups_stats" : "ngd_run_job_stats",
+            (grp ? ngd_run_job_groups_stats : ngd_run_job_stats)(eng.h, maps, (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites, p.evol_model,
+                                                                 p.boot_ci, stats.data(), used.data())};
+  };
+  // (a window shorter than one block has replicates of 0 / 0: no finite replicate)
+  mode.windows = [&](const uint64_t *lo, const uint64_t *hi, uint64_t n, const uint64_t *maps, uint64_t maps_len,
+                     const uint64_t *off) -> EngineCall {
+    return {grp ? "ngd_run_windows_job_var_groups_stats" : "ngd_run_windows_job_var_stats",
+            (grp ? ngd_run_windows_job_var_groups_stats : ngd_run_windows_job_var_stats)(
+                eng.h, lo, hi, n, maps, maps_len, off, (uint32_t)R, p.boot_block_size, p.tot_sites, p.evol_model, p.boot_ci, stats.data(), used.data())};
+  };
   // one set's blocks: est through emit() (pairs: the progress lines and the writer of any matrix), the rest formatted here
-  auto write_set = [&](uint64_t w, const char *name, const double *st, const uint64_t *us) {
+  mode.write_set = [&](uint64_t w, const char *name, uint64_t set) {
+    const double *st = stats.data() + set * NGD_BOOT_NSTAT * n_cells;
+    const uint64_t *us = used.data() + set * n_cells;
     if (grp) {
       for (int k = 0; k < NGD_BOOT_NSTAT; k++) {
         txt.clear();
@@ -2182,43 +2214,7 @@ void bootstrap_summaries(const Pars &p, Engine &eng, const WindowList &win, cons
     }
     if (fwrite(cnt.data(), 1, cnt.size(), sf[NGD_BOOT_NSTAT]) != cnt.size()) die(kLambda, "cannot write output file!");
   };
-  std::vector<double> st;
-  std::vector<uint64_t> us, maps;
-  if (p.win) {
-    // a group of windows per call: their statistics in ~2 GB of host memory.  A window shorter than one block has
-    // replicates of 0 / 0: no finite replicate
-    const uint64_t R = p.win_boot_rep;
-    std::vector<uint64_t> off;
-    const uint64_t mlen = draw_window_maps(p, win, R, maps, off);
-    // (group pairs are written here, not by the writer thread: nothing to wait for at a group's end)
-    for_window_groups(p, eng, out, win.size(), 8 * (NGD_BOOT_NSTAT + 1) * std::max<uint64_t>(1, n_cells), !grp,
-      [&](uint64_t w0, uint64_t n) {
-        st.resize(n * NGD_BOOT_NSTAT * n_cells);
-        us.resize(n * n_cells);
-        engine_ok(grp ? "ngd_run_windows_job_var_groups_stats" : "ngd_run_windows_job_var_stats",
-                  (grp ? ngd_run_windows_job_var_groups_stats : ngd_run_windows_job_var_stats)(
-                      eng.h, &win.lo[w0], &win.hi[w0], n, maps.data(), mlen, &off[w0], (uint32_t)R, p.boot_block_size, p.tot_sites,
-                      p.evol_model, p.boot_ci, st.data(), us.data()));
-      },
-      [&](uint64_t w0, uint64_t n) {
-        for (uint64_t k = 0; k < n; k++) write_set(w0 + k, win.name(w0 + k).c_str(), &st[k * NGD_BOOT_NSTAT * n_cells], &us[k * n_cells]);
-      });
-    win.write_file(std::string(p.out) + ".windows", p);
-  } else {
-    // the full data set and all its replicates in ONE call, their maps drawn in the reference's order
-    const uint64_t R = p.n_boot_rep, n_blocks = (p.n_sites - p.n_sites % p.boot_block_size) / p.boot_block_size;
-    if (!n_blocks) die(kMain, "bootstrap summaries (--boot_stats) need at least one bootstrap block of sites!");
-    const auto t_c0 = std::chrono::steady_clock::now();
-    draw_job_maps(rng, R, n_blocks, maps);
-    st.resize(NGD_BOOT_NSTAT * n_cells);
-    us.resize(n_cells);
-    engine_ok(grp ? "ngd_run_job_groups_stats" : "ngd_run_job_stats",
-              (grp ? ngd_run_job_groups_stats : ngd_run_job_stats)(eng.h, maps.data(), (uint32_t)R, n_blocks, p.boot_block_size, p.tot_sites,
-                                                                   p.evol_model, p.boot_ci, st.data(), us.data()));
-    report_fixup(eng.h, p.verbose);
-    out.t_compute += since(t_c0);
-    write_set(0, nullptr, st.data(), us.data());
-  }
+  run_sets(p, eng, win, rng, out, mode);
   for (int k = 1; k <= NGD_BOOT_NSTAT; k++)
     if (fclose(sf[k]) != 0) die(kMain, "cannot write bootstrap summaries output file!");
 }
@@ -2409,9 +2405,11 @@ void compared_windows(const Pars &p, Engine &eng, const WindowList &win, MatrixO
             (unsigned long)n_bad, p.out);
   if (!p.win_cmp_mds) return;
   // the RMS table of the windows that were kept, taken as an ordinary distance matrix
-  std::vector<uint64_t> kept;
-  for (uint64_t w = 0; w < W; w++)
+  std::vector<uint64_t> kept, row(W);  // (row[w]: where window w stands among them)
+  for (uint64_t w = 0; w < W; w++) {
+    row[w] = kept.size();
     if (status[w]) kept.push_back(w);
+  }
   const uint64_t n = kept.size();
   if (n < 3) die(kMain, "the ordination of the windows (--win_cmp_mds) needs three windows or more that were kept!");
   if (K > n - 1)
@@ -2424,17 +2422,9 @@ void compared_windows(const Pars &p, Engine &eng, const WindowList &win, MatrixO
   if (ngd_mds_host(val.data(), 1, n, K, eig.data(), vec.data(), tot.data(), &st) || ngd_mds_coords(eig.data(), vec.data(), 1, n, K, xy.data()))
     die(kMain, "cannot derive the windows' coordinates!");
   FILE *f = open(".win_mds");
-  bool ok = fputs("eig", f) >= 0;
-  for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(f, "\t%.10e", eig[k]) > 0;
-  ok = ok && fprintf(f, "\ntotal\t%.10e\t%.10e\n", tot[0], tot[1]) > 0;
-  for (uint64_t w = 0, a = 0; w < W; w++) {
-    ok = ok && fprintf(f, "%lu", (unsigned long)w) > 0;
-    for (uint32_t k = 0; k < K; k++) ok = ok && fprintf(f, "\t%.10e", status[w] ? xy[a * K + k] : std::nan("")) > 0;
-    ok = ok && fputc('\n', f) != EOF;
-    a += status[w] != 0;
-  }
-  ok = ok && fputc('\n', f) != EOF;
-  close(f, ok);
+  // (a row per window of the run, "nan" throughout for one that was not kept)
+  close(f, write_mds_block(f, eig.data(), K, tot.data(), W, [](FILE *g, uint64_t w) { return fprintf(g, "%lu", (unsigned long)w) > 0; },
+                           [&](uint64_t w, uint32_t k) { return status[w] ? xy[row[w] * K + k] : std::nan(""); }));
 }
 
 // ---- the plain run: the full data set and its replicates ----

@@ -1,7 +1,9 @@
 """--mds end to end through the C++ host (ngsdist_amd/bin/ngsDist) on a 12 x 400 text file: <out>.mds parses to the values
 the Python run form gives on the same data, seed and block size -- eigenvalues, totals and mds_coords of the vectors, at the
 printed precision ("%.10e": 11 significant digits) --, set after set, matrix 0 first; <out> of a plain run is the run without
---mds, and with replicates or windows matrix 0 of every set; the refused flag combinations exit non-zero with a message."""
+--mds, and with replicates or windows matrix 0 of every set; the refused flag combinations exit non-zero with a message.
+Under NGSDIST_WIN_GROUP_MAX=3 the host sends 7 windows to the engine in calls of 3, 3 and 1: the files are those of the Python
+calls on the same three groups of windows, one after the other."""
 import gzip
 import os
 import subprocess
@@ -14,12 +16,14 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "ngsdist_amd", "bin", "ngsDist")
 N_IND, N_SITES, Q, SEED, K = 12, 400, 10, 5, 3  # (evol_model: the host's default, 1)
+GROUPS = (slice(0, 3), slice(3, 6), slice(6, 7))  # 7 windows under NGSDIST_WIN_GROUP_MAX=3
 LABELS = ["Ind_%d" % i for i in range(N_IND)]
 
 
-def run_cli(tmp_path, args, name, ok=True):
+def run_cli(tmp_path, args, name, ok=True, group_max=0):
     out = str(tmp_path / name)
-    r = subprocess.run([BIN] + [str(a) for a in args] + ["--out", out, "--verbose", "0"], capture_output=True, timeout=600)
+    r = subprocess.run([BIN] + [str(a) for a in args] + ["--out", out, "--verbose", "0"], capture_output=True, timeout=600,
+                       env=dict(os.environ, NGSDIST_WIN_GROUP_MAX=str(group_max)))
     assert (r.returncode == 0) == ok, r.stderr.decode()
     return out if ok else r.stderr.decode()
 
@@ -125,6 +129,67 @@ def test_windows_in_base_pairs_with_replicates(tmp_path, data):
     with N.Engine(N_IND, N_SITES, indep_geno=False) as e:
         e.upload_ind_major(p).commit()
         eig, vec, tot, status, _ = e.run_windows_job_var_mds(K, lo, hi, maps, off, Q, evol_model=1, n_rep=R)
+    check_file(out + ".mds", eig, vec, tot, status)
+
+
+@pytest.mark.parametrize("R", [0, 8], ids=["plain", "replicates"])
+def test_windows_in_several_engine_calls(tmp_path, data, R):
+    """The host's window w0 + k is set k of its call: one Python call per group on that group's windows (the whole table of
+    maps, the group's offsets), concatenated.  (Not the ungrouped run's bytes: a call cuts its slices by the boundaries of its
+    own windows, DESIGN.md "The budget does not change the replicates' bits".)"""
+    import ngsdist_amd as N
+    path, pos, p = data
+    base = ["--geno", path, "--probs", "--n_ind", N_IND, "--n_sites", N_SITES, "--win_size", 100, "--win_step", 50]
+    boot = ["--win_boot_rep", R, "--boot_block_size", Q, "--seed", SEED] if R else []
+    plain = run_cli(tmp_path, base, "plain.dist")
+    out = run_cli(tmp_path, base + boot + ["--mds", K], "mds.dist", group_max=3)
+    assert read(out + ".windows") == read(plain + ".windows")
+    lo, hi = N.window_ranges(N_SITES, 100, 50)
+    assert len(lo) == 7
+    with N.Engine(N_IND, N_SITES, indep_geno=False) as e:
+        e.upload_ind_major(p).commit()
+        if R:
+            maps, off = N.window_boot_maps(SEED, lo, hi, R, Q)
+            parts = [e.run_windows_job_var_mds(K, lo[g], hi[g], maps, off[g], Q, evol_model=1, n_rep=R) for g in GROUPS]
+        else:
+            parts = [e.run_windows_mds(K, lo[g], hi[g], evol_model=1) for g in GROUPS]
+    eig, vec, tot, status, d0 = (np.concatenate(x) for x in zip(*parts))
+    assert read(out) == b"".join(N.format_matrix(d, LABELS) for d in d0)
+    check_file(out + ".mds", eig, vec, tot, status)
+
+
+def unequal_windows(d):
+    """windows in base pairs of several lengths over the 400 sites, none shorter than a block, after writing their positions
+    file into d: -> (the host's arguments, lo, hi, the groups of windows under NGSDIST_WIN_GROUP_MAX=3).  Windows of one length
+    share their maps, so only here does a group's offset into the table of maps differ from the first group's."""
+    import ngsdist_amd as N
+    coords = np.cumsum(np.where(np.arange(N_SITES) < 150, 5, 20))
+    path = str(d / "uneven.tsv")
+    with open(path, "w") as fh:
+        fh.write("".join("chrSIM\t%d\n" % x for x in coords))
+    lo, hi, _ = N.window_ranges_bp(coords, 1000, 700, min_sites=Q)
+    assert len(lo) >= 7 and len(set((hi - lo).tolist())) >= 3 and (hi - lo).min() >= Q
+    groups = [slice(k, min(k + 3, len(lo))) for k in range(0, len(lo), 3)]
+    return ["--pos", path, "--win_bp", 1000, "--win_bp_step", 700, "--win_min_sites", Q], lo, hi, groups
+
+
+def test_unequal_windows_in_several_engine_calls(tmp_path, data):
+    """test_windows_in_several_engine_calls where every group has map offsets of its own"""
+    import ngsdist_amd as N
+    path, pos, p = data
+    R = 8
+    shape, lo, hi, groups = unequal_windows(tmp_path)
+    base = ["--geno", path, "--probs", "--n_ind", N_IND, "--n_sites", N_SITES] + shape
+    plain = run_cli(tmp_path, base, "plain.dist")
+    out = run_cli(tmp_path, base + ["--win_boot_rep", R, "--boot_block_size", Q, "--seed", SEED, "--mds", K], "mds.dist", group_max=3)
+    assert read(out + ".windows") == read(plain + ".windows")
+    maps, off = N.window_boot_maps(SEED, lo, hi, R, Q)
+    assert all(off[g].tolist() != off[groups[0]].tolist() for g in groups[1:])
+    with N.Engine(N_IND, N_SITES, indep_geno=False) as e:
+        e.upload_ind_major(p).commit()
+        parts = [e.run_windows_job_var_mds(K, lo[g], hi[g], maps, off[g], Q, evol_model=1, n_rep=R) for g in groups]
+    eig, vec, tot, status, d0 = (np.concatenate(x) for x in zip(*parts))
+    assert read(out) == b"".join(N.format_matrix(d, LABELS) for d in d0)
     check_file(out + ".mds", eig, vec, tot, status)
 
 

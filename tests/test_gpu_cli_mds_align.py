@@ -2,13 +2,14 @@
 and with --win_size .. --win_boot_rep 5: <out> and <out>.mds -- matrix 0 of every set -- are byte for byte those of the run
 without --mds_align (its matrix 0 blocks); <out>.mds_mean / _sd / _lo / _hi and <out>.mds_fit parse to the values the Python
 door gives on the same data, seed and block size, at the printed precision ("%.10e"); the refused flag combinations exit
-non-zero with a message."""
+non-zero with a message.  Under NGSDIST_WIN_GROUP_MAX=3 the host sends the 7 windows to the engine in calls of 3, 3 and 1: the
+files are those of the Python calls on the same three groups of windows, one after the other."""
 import os
 
 import numpy as np
 import pytest
 
-from test_gpu_cli_mds import LABELS, N_IND, N_SITES, Q, SEED, data, read, run_cli  # noqa: F401 (data: a fixture)
+from test_gpu_cli_mds import GROUPS, LABELS, N_IND, N_SITES, Q, SEED, data, read, run_cli, unequal_windows  # noqa: F401 (data: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +17,9 @@ K, R, CI = 2, 5, 0.9
 STATS = (".mds_mean", ".mds_sd", ".mds_lo", ".mds_hi")
 
 
-def check_files(out, plain_mds, res):
-    """the files of an aligned run against the Python door's dict (a leading axis of sets) and the .mds of the run without
-    --mds_align"""
+def check_files(out, plain_mds, res, R=R):
+    """the files of an aligned run of R replicates against the Python door's dict (a leading axis of sets) and the .mds of the
+    run without --mds_align"""
     n_set = res["eig0"].shape[0]
     theirs = read(plain_mds).decode()[:-2].split("\n\n")
     assert len(theirs) == n_set * (R + 1)
@@ -75,6 +76,55 @@ def test_replicates_inside_windows(tmp_path, data):
         res = e.run_windows_job_var_mds_align(K, lo, hi, maps, off, Q, evol_model=1, n_rep=R)
     assert res["used"].tolist() == [R] * 7
     check_files(out, plain + ".mds", res)
+
+
+def test_replicates_inside_windows_in_several_engine_calls(tmp_path, data):
+    """The host's window w0 + k is set k of its call: one Python call per group on that group's windows (the whole table of
+    maps, the group's offsets), concatenated; <out> and <out>.mds are the run's without --mds_align in the same groups.  (Not
+    the ungrouped run's bytes: a call cuts its slices by the boundaries of its own windows, DESIGN.md "The budget does not
+    change the replicates' bits".)"""
+    import ngsdist_amd as N
+    path, pos, p = data
+    R8 = 8
+    shape = ["--geno", path, "--probs", "--n_ind", N_IND, "--n_sites", N_SITES, "--win_size", 100, "--win_step", 50]
+    base = shape + ["--win_boot_rep", R8, "--boot_block_size", Q, "--seed", SEED, "--mds", K]
+    ungrouped = run_cli(tmp_path, shape, "plain.dist")
+    plain = run_cli(tmp_path, base, "mds.dist", group_max=3)
+    out = run_cli(tmp_path, base + ["--mds_align"], "align.dist", group_max=3)
+    assert read(out) == read(plain) and read(out + ".windows") == read(ungrouped + ".windows")
+    lo, hi = N.window_ranges(N_SITES, 100, 50)
+    assert len(lo) == 7
+    maps, off = N.window_boot_maps(SEED, lo, hi, R8, Q)
+    with N.Engine(N_IND, N_SITES, indep_geno=False) as e:
+        e.upload_ind_major(p).commit()
+        parts = [e.run_windows_job_var_mds_align(K, lo[g], hi[g], maps, off[g], Q, evol_model=1, n_rep=R8) for g in GROUPS]
+    res = {k: None if parts[0][k] is None else np.concatenate([q[k] for q in parts]) for k in parts[0]}
+    assert res["used"].tolist() == [R8] * 7
+    assert read(out) == b"".join(N.format_matrix(d, LABELS) for d in res["dist0"])
+    check_files(out, plain + ".mds", res, R8)
+
+
+def test_unequal_windows_in_several_engine_calls(tmp_path, data):
+    """the test above where every group has map offsets of its own (windows in base pairs of several lengths)"""
+    import ngsdist_amd as N
+    path, pos, p = data
+    R8 = 8
+    shape, lo, hi, groups = unequal_windows(tmp_path)
+    shape = ["--geno", path, "--probs", "--n_ind", N_IND, "--n_sites", N_SITES] + shape
+    base = shape + ["--win_boot_rep", R8, "--boot_block_size", Q, "--seed", SEED, "--mds", K]
+    ungrouped = run_cli(tmp_path, shape, "plain.dist")
+    plain = run_cli(tmp_path, base, "mds.dist", group_max=3)
+    out = run_cli(tmp_path, base + ["--mds_align"], "align.dist", group_max=3)
+    assert read(out) == read(plain) and read(out + ".windows") == read(ungrouped + ".windows")
+    maps, off = N.window_boot_maps(SEED, lo, hi, R8, Q)
+    assert all(off[g].tolist() != off[groups[0]].tolist() for g in groups[1:])
+    with N.Engine(N_IND, N_SITES, indep_geno=False) as e:
+        e.upload_ind_major(p).commit()
+        parts = [e.run_windows_job_var_mds_align(K, lo[g], hi[g], maps, off[g], Q, evol_model=1, n_rep=R8) for g in groups]
+    res = {k: None if parts[0][k] is None else np.concatenate([q[k] for q in parts]) for k in parts[0]}
+    assert res["used"].tolist() == [R8] * len(lo)
+    assert read(out) == b"".join(N.format_matrix(d, LABELS) for d in res["dist0"])
+    check_files(out, plain + ".mds", res, R8)
 
 
 def test_refused_flag_combinations(tmp_path, data):

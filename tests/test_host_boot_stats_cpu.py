@@ -1,7 +1,8 @@
 """The host's --boot_stats path under AddressSanitizer + UBSan on the CPU: the stand-alone binary of
 test_host_sanitize_cpu.py, linked against the stub engine plus tests/host_sanitize/stub_boot_stats.cpp (and stub_groups.cpp)
 -- the summaries' entry points with no compute behind them.  Checked: no sanitizer report, the files of a run and the
-shapes of their blocks, and every refusal by its message and exit status 255.  (What the numbers are is the GPU suite's
+shapes of their blocks -- also where NGSDIST_WIN_GROUP_MAX cuts 7 windows of unequal length into engine calls of 3, 3 and 1 --,
+and every refusal by its message and exit status 255.  (What the numbers are is the GPU suite's
 business: tests/test_gpu_cli_boot_stats.py.)"""
 import os
 import subprocess
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 from test_host_groups_cpu import build
+from test_host_nj_cpu import GROUP_MAX, same_shapes, seven_windows
 
 EXTS = ("", ".boot_mean", ".boot_sd", ".boot_lo", ".boot_hi", ".boot_used")
 
@@ -25,13 +27,13 @@ def san_bin_plain(tmp_path_factory):
     return build(str(tmp_path_factory.mktemp("san0") / "ngsDist_plain"), ["stub_engine.cpp"])
 
 
-def run(binary, tmp_path, args, ok=True, verbose=1):
+def run(binary, tmp_path, args, ok=True, verbose=1, group_max=0):
     out = str(tmp_path / "o.dist")
     for ext in EXTS + (".windows", ".used"):
         if os.path.exists(out + ext):
             os.remove(out + ext)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
-               NGD_STUB_GROUP_PAIRS="6")
+               NGD_STUB_GROUP_PAIRS="6", NGSDIST_WIN_GROUP_MAX=str(group_max))
     r = subprocess.run([binary] + [str(a) for a in args] + ["--out", out, "--verbose", str(verbose)], capture_output=True, env=env,
                        timeout=300)
     err = r.stderr.decode(errors="replace")
@@ -66,18 +68,29 @@ def data(tmp_path_factory):
 def test_the_six_files_of_a_run(san_bin, tmp_path, data):
     gl, groups, n_ind, n_sites = data
     base = ["--geno", gl, "--probs", "--n_ind", n_ind, "--n_sites", n_sites, "--boot_stats"]
-    for extra, n_set in ((["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1),
-                         (["--n_boot_rep", 70, "--boot_block_size", 7, "--indep_geno", "--boot_ci", 0.5], 1),
-                         (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5),
-                         (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7], 3)):
+    bp = seven_windows(tmp_path)  # (7 windows, the sixth shorter than a block)
+    ungrouped = {}
+    # (arguments, sets, windows per engine call at the most: 0 = all)
+    for extra, n_set, group_max in ((["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 0),
+                                    (["--n_boot_rep", 70, "--boot_block_size", 7, "--indep_geno", "--boot_ci", 0.5], 1, 0),
+                                    (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 0),
+                                    (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7], 3, 0),
+                                    (["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3] + bp, 7, 0),
+                                    (["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3] + bp, 7, GROUP_MAX)):
         for grp in (False, True):
-            files, err = run(san_bin, tmp_path, base + extra + (["--groups", groups] if grp else []))
+            files, err = run(san_bin, tmp_path, base + extra + (["--groups", groups] if grp else []), group_max=group_max)
+            windows = open(str(tmp_path / "o.dist.windows")).read() if os.path.exists(str(tmp_path / "o.dist.windows")) else None
+            if group_max:
+                same_shapes(files, ungrouped[grp][0])
+                assert windows == ungrouped[grp][1]
+            ungrouped[grp] = files, windows
             n = 3 if grp else n_ind
             assert [n_blocks_of(files[ext], n) for ext in EXTS] == [n_set] * 6, (extra, grp)
-            R = extra[1] if "--n_boot_rep" in extra else extra[5]
+            R = extra[extra.index("--n_boot_rep" if "--n_boot_rep" in extra else "--win_boot_rep") + 1]
             cells = [c for l in files[".boot_used"].split("\n") if "\t" in l for c in l.split("\t")[1:]]
             assert set(cells) <= {"0", str(R)} and str(R) in cells
-            assert os.path.exists(str(tmp_path / "o.dist.windows")) == ("--win_size" in extra)
+            assert (windows is not None) == ("--win_size" in extra or "--win_bp" in extra)
+            assert windows is None or len(windows.split("\n")) == n_set + 2
             assert "\tboot_stats: true\n\tboot_ci: %f\n" % (0.5 if "--boot_ci" in extra else 0.95) in err
     # the echo of the arguments has the two lines only with the flag
     out = str(tmp_path / "plain.dist")

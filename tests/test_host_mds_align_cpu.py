@@ -2,8 +2,8 @@
 test_host_sanitize_cpu.py, linked against the stub engine plus tests/host_sanitize/stub_mds.cpp, stub_boot_stats.cpp and
 stub_mds_align.cpp -- the aligned entry points with no device behind them (their outputs are the host twins' on made-up
 distances, so ngd_mds_align_host runs under the sanitizers too).  Checked: no sanitizer report, the files of each run form
-and the shape of their blocks, that <out> and matrix 0's blocks are the bytes of the run without the flag, and every
-refusal by its message and exit status 255.  (What the numbers are is the GPU suite's business:
+and the shape of their blocks -- also where NGSDIST_WIN_GROUP_MAX cuts 7 windows of unequal length into engine calls of 3, 3
+and 1 --, that <out> and matrix 0's blocks are the bytes of the run without the flag, and every refusal by its message and exit status 255.  (What the numbers are is the GPU suite's business:
 tests/test_gpu_cli_mds_align.py.)"""
 import os
 import subprocess
@@ -13,6 +13,7 @@ import pytest
 
 from test_host_groups_cpu import build
 from test_host_mds_cpu import mds_blocks, n_blocks_of
+from test_host_nj_cpu import GROUP_MAX, same_shapes, seven_windows
 
 EXTS = ("", ".mds", ".mds_mean", ".mds_sd", ".mds_lo", ".mds_hi", ".mds_fit", ".windows")
 STATS = (".mds_mean", ".mds_sd", ".mds_lo", ".mds_hi")
@@ -30,12 +31,13 @@ def san_bin_mds(tmp_path_factory):
     return build(str(tmp_path_factory.mktemp("san0") / "ngsDist_mds"), ["stub_engine.cpp", "stub_mds.cpp", "stub_boot_stats.cpp"])
 
 
-def run(binary, tmp_path, args, ok=True, verbose=1):
+def run(binary, tmp_path, args, ok=True, verbose=1, group_max=0):
     out = str(tmp_path / "o.dist")
     for ext in EXTS:
         if os.path.exists(out + ext):
             os.remove(out + ext)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
+               NGSDIST_WIN_GROUP_MAX=str(group_max))
     r = subprocess.run([binary] + [str(a) for a in args] + ["--out", out, "--verbose", str(verbose)], capture_output=True, env=env,
                        timeout=300)
     err = r.stderr.decode(errors="replace")
@@ -88,14 +90,21 @@ def test_the_files_of_each_run_form(san_bin, tmp_path, data):
     gl, labels, n_ind, n_sites = data
     K = 3
     base = ["--geno", gl, "--probs", "--n_ind", n_ind, "--n_sites", n_sites, "--mds", K]
-    # (arguments, sets, replicates, windows shorter than a block)
-    for extra, n_set, R, short in ((["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 3, 0),
-                                   (["--n_boot_rep", 40, "--boot_block_size", 7, "--indep_geno", "--labels", labels, "--seed", 9], 1, 40, 0),
-                                   (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 2, 0),
-                                   (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 4], 3, 2, 3)):
-        plain, _ = run(san_bin, tmp_path, base + extra)
+    bp = seven_windows(tmp_path) + ["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3]
+    ungrouped = None
+    # (arguments, sets, replicates, windows shorter than a block, windows per engine call at the most: 0 = all)
+    for extra, n_set, R, short, group_max in ((["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 3, 0, 0),
+                                              (["--n_boot_rep", 40, "--boot_block_size", 7, "--indep_geno", "--labels", labels, "--seed", 9], 1, 40, 0, 0),
+                                              (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 2, 0, 0),
+                                              (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 4], 3, 2, 3, 0),
+                                              (bp, 7, 2, 1, 0),
+                                              (bp, 7, 2, 1, GROUP_MAX)):
+        plain, _ = run(san_bin, tmp_path, base + extra, group_max=group_max)  # (the stubs' numbers follow the grouping)
         ci = ["--mds_ci", 0.8] if R == 40 else []
-        files, err = run(san_bin, tmp_path, base + extra + ["--mds_align"] + ci)
+        files, err = run(san_bin, tmp_path, base + extra + ["--mds_align"] + ci, group_max=group_max)
+        if group_max:
+            same_shapes(files, ungrouped)
+        ungrouped = files
         # <out>, and matrix 0 of every set in <out>.mds, are the bytes of the run without the flag
         assert files[""] == plain[""] and n_blocks_of(files[""], n_ind) == n_set
         assert files[".windows"] == plain[".windows"]

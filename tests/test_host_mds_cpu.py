@@ -1,8 +1,8 @@
 """The host's --mds path under AddressSanitizer + UBSan on the CPU: the stand-alone binary of test_host_sanitize_cpu.py,
 linked against the stub engine plus tests/host_sanitize/stub_mds.cpp -- the MDS entry points with no device behind them
 (their outputs are ngd_mds_host's on made-up distances, so the host twin runs under the sanitizers too).  Checked: no
-sanitizer report, the files of each run form and the shape of their blocks, and every refusal by its message and exit
-status 255.  (What the coordinates are is the GPU suite's business: tests/test_gpu_cli_mds.py.)"""
+sanitizer report, the files of each run form and the shape of their blocks -- also where NGSDIST_WIN_GROUP_MAX cuts 7 windows
+of unequal length into engine calls of 3, 3 and 1 --, and every refusal by its message and exit status 255.  (What the coordinates are is the GPU suite's business: tests/test_gpu_cli_mds.py.)"""
 import os
 import subprocess
 
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from test_host_groups_cpu import build
+from test_host_nj_cpu import GROUP_MAX, same_shapes, seven_windows
 
 EXTS = ("", ".mds", ".windows")
 
@@ -25,12 +26,13 @@ def san_bin_plain(tmp_path_factory):
     return build(str(tmp_path_factory.mktemp("san0") / "ngsDist_plain"), ["stub_engine.cpp"])
 
 
-def run(binary, tmp_path, args, ok=True, verbose=1):
+def run(binary, tmp_path, args, ok=True, verbose=1, group_max=0):
     out = str(tmp_path / "o.dist")
     for ext in EXTS:
         if os.path.exists(out + ext):
             os.remove(out + ext)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
+               NGSDIST_WIN_GROUP_MAX=str(group_max))
     r = subprocess.run([binary] + [str(a) for a in args] + ["--out", out, "--verbose", str(verbose)], capture_output=True, env=env,
                        timeout=300)
     err = r.stderr.decode(errors="replace")
@@ -76,15 +78,24 @@ def test_the_files_of_each_run_form(san_bin, tmp_path, data):
     gl, labels, n_ind, n_sites = data
     K = 3
     base = ["--geno", gl, "--probs", "--n_ind", n_ind, "--n_sites", n_sites, "--mds", K]
-    # (arguments, sets, replicates, windows shorter than a block)
-    for extra, n_set, R, short in (([], 1, 0, 0),
-                                   (["--labels", labels], 1, 0, 0),
-                                   (["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 3, 0),
-                                   (["--n_boot_rep", 40, "--boot_block_size", 7, "--indep_geno"], 1, 40, 0),
-                                   (["--win_size", 40, "--win_step", 20], 5, 0, 0),
-                                   (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 2, 0),
-                                   (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7], 3, 2, 3)):
-        files, err = run(san_bin, tmp_path, base + extra)
+    bp = seven_windows(tmp_path)
+    ungrouped = None
+    # (arguments, sets, replicates, windows shorter than a block, windows per engine call at the most: 0 = all)
+    for extra, n_set, R, short, group_max in (([], 1, 0, 0, 0),
+                                              (["--labels", labels], 1, 0, 0, 0),
+                                              (["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 3, 0, 0),
+                                              (["--n_boot_rep", 40, "--boot_block_size", 7, "--indep_geno"], 1, 40, 0, 0),
+                                              (["--win_size", 40, "--win_step", 20], 5, 0, 0, 0),
+                                              (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 2, 0, 0),
+                                              (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7], 3, 2, 3, 0),
+                                              (bp, 7, 0, 0, 0),
+                                              (bp, 7, 0, 0, GROUP_MAX),
+                                              (bp + ["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 7, 2, 1, 0),
+                                              (bp + ["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 7, 2, 1, GROUP_MAX)):
+        files, err = run(san_bin, tmp_path, base + extra, group_max=group_max)
+        if group_max:
+            same_shapes(files, ungrouped)
+        ungrouped = files
         assert n_blocks_of(files[""], n_ind) == n_set, extra
         blocks = mds_blocks(files[".mds"], n_ind, K)
         assert len(blocks) == n_set * (R + 1), extra
@@ -98,7 +109,7 @@ def test_the_files_of_each_run_form(san_bin, tmp_path, data):
             assert np.all(np.diff(eig) <= 0) and tot[1] >= tot[0] and tot[1] >= eig[eig > 0].sum() * (1 - 1e-9)
             # the coordinates' squared lengths are the positive eigenvalues (unit vectors, at the printed precision)
             assert np.allclose((xy ** 2).sum(axis=0), np.maximum(eig, 0), rtol=1e-8, atol=1e-12)
-        assert (files[".windows"] is not None) == ("--win_size" in extra)
+        assert (files[".windows"] is not None) == ("--win_size" in extra or "--win_bp" in extra)
         assert "\tmds: 3\n" in err
         assert ("WARNING: %d of the run's matrices" % (short * R) in err) == (short > 0)
     # the echo of the arguments has the line only with the flag

@@ -1,8 +1,8 @@
 """The host's --nj path under AddressSanitizer + UBSan on the CPU: the stand-alone binary of test_host_sanitize_cpu.py,
 linked against the stub engine plus tests/host_sanitize/stub_nj.cpp -- the trees' entry points with no device behind them
 (their records are ngd_nj_host's on made-up distances).  Checked: no sanitizer report, the files of each run form and their
-line counts, and every refusal by its message and exit status 255.  (What the trees are is the GPU suite's business:
-tests/test_gpu_cli_nj.py.)"""
+line counts -- also where NGSDIST_WIN_GROUP_MAX cuts 7 windows of unequal length into engine calls of 3, 3 and 1 --, and every
+refusal by its message and exit status 255.  (What the trees are is the GPU suite's business: tests/test_gpu_cli_nj.py.)"""
 import os
 import subprocess
 
@@ -13,6 +13,27 @@ import nj_expect as X
 from test_host_groups_cpu import build
 
 EXTS = ("", ".nwk", ".support.nwk", ".windows")
+GROUP_MAX = 3  # NGSDIST_WIN_GROUP_MAX of the grouped runs: the 7 windows of seven_windows() in engine calls of 3, 3 and 1
+
+
+def seven_windows(d):
+    """the arguments of 7 windows in base pairs over 120 sites, after writing their positions file into d: 20, 20, 20, 20, 20,
+    3 and 17 sites -- the sixth shorter than a bootstrap block of 7"""
+    pos = [10 * s + 1 for s in range(100)] + [1001 + 10 * k for k in range(3)] + [1201 + 10 * k for k in range(17)]
+    path = str(d / "pos.tsv")
+    open(path, "w").write("".join("chr1\t%d\n" % x for x in pos))
+    return ["--pos", path, "--win_bp", 200]
+
+
+def same_shapes(files, other):
+    """the files of a run cut into groups of windows against the ungrouped run's: the same files with the same numbers of lines
+    and fields (the stubs' made-up numbers follow a window's index within its call), <out>.windows byte for byte"""
+    assert files.keys() == other.keys() and files.get(".windows") == other.get(".windows")
+    assert files[""] != other[""]  # (those numbers: the run did go to the engine in several calls)
+    for ext in files:
+        assert (files[ext] is None) == (other[ext] is None), ext
+        if files[ext] is not None:
+            assert [l.count("\t") for l in files[ext].split("\n")] == [l.count("\t") for l in other[ext].split("\n")], ext
 
 
 @pytest.fixture(scope="module")
@@ -26,12 +47,13 @@ def san_bin_plain(tmp_path_factory):
     return build(str(tmp_path_factory.mktemp("san0") / "ngsDist_plain"), ["stub_engine.cpp"])
 
 
-def run(binary, tmp_path, args, ok=True, verbose=1):
+def run(binary, tmp_path, args, ok=True, verbose=1, group_max=0):
     out = str(tmp_path / "o.dist")
     for ext in EXTS:
         if os.path.exists(out + ext):
             os.remove(out + ext)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
+               NGSDIST_WIN_GROUP_MAX=str(group_max))
     r = subprocess.run([binary] + [str(a) for a in args] + ["--out", out, "--verbose", str(verbose)], capture_output=True, env=env,
                        timeout=300)
     err = r.stderr.decode(errors="replace")
@@ -63,15 +85,24 @@ def data(tmp_path_factory):
 def test_the_files_of_each_run_form(san_bin, tmp_path, data):
     gl, labels, n_ind, n_sites = data
     base = ["--geno", gl, "--probs", "--n_ind", n_ind, "--n_sites", n_sites, "--nj"]
-    # (arguments, sets, replicates, windows shorter than a block)
-    for extra, n_set, R, short in (([], 1, 0, 0),
-                                   (["--labels", labels], 1, 0, 0),
-                                   (["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 3, 0),
-                                   (["--n_boot_rep", 40, "--boot_block_size", 7, "--indep_geno"], 1, 40, 0),
-                                   (["--win_size", 40, "--win_step", 20], 5, 0, 0),
-                                   (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 2, 0),
-                                   (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7], 3, 2, 3)):
-        files, err = run(san_bin, tmp_path, base + extra)
+    bp = seven_windows(tmp_path)
+    ungrouped = None
+    # (arguments, sets, replicates, windows shorter than a block, windows per engine call at the most: 0 = all)
+    for extra, n_set, R, short, group_max in (([], 1, 0, 0, 0),
+                                              (["--labels", labels], 1, 0, 0, 0),
+                                              (["--n_boot_rep", 3, "--boot_block_size", 10, "--seed", 5], 1, 3, 0, 0),
+                                              (["--n_boot_rep", 40, "--boot_block_size", 7, "--indep_geno"], 1, 40, 0, 0),
+                                              (["--win_size", 40, "--win_step", 20], 5, 0, 0, 0),
+                                              (["--win_size", 40, "--win_step", 20, "--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 5, 2, 0, 0),
+                                              (["--win_size", 5, "--win_step", 50, "--win_boot_rep", 2, "--boot_block_size", 7], 3, 2, 3, 0),
+                                              (bp, 7, 0, 0, 0),
+                                              (bp, 7, 0, 0, GROUP_MAX),
+                                              (bp + ["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 7, 2, 1, 0),
+                                              (bp + ["--win_boot_rep", 2, "--boot_block_size", 7, "--seed", 3], 7, 2, 1, GROUP_MAX)):
+        files, err = run(san_bin, tmp_path, base + extra, group_max=group_max)
+        if group_max:
+            same_shapes(files, ungrouped)
+        ungrouped = files
         assert n_blocks_of(files[""], n_ind) == n_set, extra
         trees = files[".nwk"].split("\n")
         assert trees[-1] == "" and len(trees) - 1 == n_set * (R + 1), extra
@@ -87,10 +118,12 @@ def test_the_files_of_each_run_form(san_bin, tmp_path, data):
             for w, t in enumerate(sup[:-1]):
                 _, nodes = X.parse_newick(t)
                 inner = [int(nm) for nm, _ in nodes if not nm.startswith(("Ind_", "name"))]
-                assert len(inner) == n_ind - 3 and all(0 <= s <= (0 if short else R) for s in inner)
+                in_short = trees[w * (R + 1) + 1] == ";"  # (a window shorter than a block: no replicate has a tree)
+                assert in_short == (short == n_set or (short == 1 and w == 5))
+                assert len(inner) == n_ind - 3 and all(0 <= s <= (0 if in_short else R) for s in inner)
         else:
             assert files[".support.nwk"] is None
-        assert (files[".windows"] is not None) == ("--win_size" in extra)
+        assert (files[".windows"] is not None) == ("--win_size" in extra or "--win_bp" in extra)
         assert "\tnj: true\n" in err
         assert ("WARNING: %d of the run's matrices" % (short * R) in err) == (short > 0)
     # the echo of the arguments has the line only with the flag
