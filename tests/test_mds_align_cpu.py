@@ -6,7 +6,18 @@ noise; where M is singular; status 0; scaling by 2^+-40; the refusals.
 Bounds: Y within 1e-9 max(|X_0|, |X_r|) of numpy's where sigma_min(M) >= 1e-3 sigma_max(M) (asserted of every planted
 replicate); fit within 1e-9 (|X_r|^2 + |X_0|^2) of |X_r|^2 + |X_0|^2 - 2 SUM sigma; |Q Q^T - I| <= 1e-9.  Every case prints
 its largest figures in units of the bound; the largest seen over this file: Y 5.3e-15 of max |X|, fit 1.5e-15 of the
-squared norms, orthogonality 1.9e-14; without noise |Y - X_0| 7.0e-16 of max |X| and fit 5.1e-31 |X_0|^2."""
+squared norms, orthogonality 1.9e-14; without noise |Y - X_0| 7.0e-16 of max |X| and fit 5.1e-31 |X_0|^2.
+
+Between those two extremes, against mpmath at 60 digits (mds_align_expect.procrustes_mp), at (n, K) = (5, 3), (17, 7), (17, 16),
+(65, 15), (65, 16) with R = 3: graded sets -- X_0's columns scaled by geomspace(1, g, K), g = 1e-1, 1e-3, 1e-5, replicates
+that differ by a generic rotation, by signs, by turns inside pairs of axes -- and clustered ones (equal scales, X_r = X_0 R_r
++ eps Gaussian, eps = 1e-6, 1e-10, 1e-14) by the same three bounds, Y included although sigma_min(M) / sigma_max(M) goes down
+to 1e-10 (every replicate's ratio is asserted by mpmath's sigma to lie within a decade of g^2); the floor band g = 1e-6,
+1e-7 (ratios about 1e-12 and 1e-14, where a column may or may not be replaced) by fit, orthogonality, finiteness and the
+same bits again, Y against nothing.  The largest seen over these cases: graded Y 1.6e-15 of max |X|, fit 2.1e-17 of the
+squared norms, orthogonality 9.9e-14; clustered Y 2.0e-15, fit 1.1e-21, orthogonality 1.1e-14; floor band fit 2.0e-12 of
+the squared norms, orthogonality 6.5e-16.  Sign flips, by bits, where no column is replaced (planted and graded
+sets): the signs of the replicates' columns change nothing, those of X_0's columns D give Y D and the same fit."""
 import ctypes as C
 import os
 import re
@@ -145,6 +156,78 @@ def test_scaling_by_a_power_of_two_scales_the_result_exactly(N, k):
             big = N.mds_align_host(eig * 4.0 ** k, vec)
             assert np.array_equal(A.bits(big[0]), A.bits(aligned * 2.0 ** k))
             assert np.array_equal(A.bits(big[1]), A.bits(fit * 4.0 ** k))
+
+
+# ---- between well separated and singular: graded and clustered spectra against mpmath -------------------------------------
+CASES = [(5, 3), (17, 7), (17, 16), (65, 15), (65, 16)]
+GRADES = [1e-1, 1e-3, 1e-5]   # sigma_min / sigma_max of M about 1e-2, 1e-6, 1e-10
+FLOOR = [1e-6, 1e-7]          # ... about 1e-12 and 1e-14: the band where a column is, or is not, replaced
+NEAR = [1e-6, 1e-10, 1e-14]
+SEED = 3
+
+
+def show_mp(who, band, worst):
+    print("%s, sigma_min/sigma_max in [%.0e, %.0e): largest figures in units of 1e-9 against mpmath: %s" %
+          (who, band[0], band[1], {k: "%.3g" % x for k, x in worst.items()}))
+
+
+@pytest.mark.parametrize("mode", A.MODES)
+@pytest.mark.parametrize("n,K", CASES)
+def test_host_twin_on_graded_sets_against_mpmath(N, n, K, mode):
+    for g in GRADES:
+        Xs, aligned, fit = align(N, A.graded(n, K, 3, g, SEED, mode))
+        show_mp("host graded %s n=%d K=%d g=%.0e" % (mode, n, K, g), A.band_of(g), A.check_set_mp(Xs, aligned, fit, A.band_of(g)))
+
+
+@pytest.mark.parametrize("n,K", CASES)
+def test_host_twin_on_clustered_sets_against_mpmath(N, n, K):
+    for eps in NEAR:
+        Xs, aligned, fit = align(N, A.clustered(n, K, 3, eps, SEED))
+        show_mp("host clustered n=%d K=%d eps=%.0e" % (n, K, eps), A.CLUSTERED_BAND,
+                A.check_set_mp(Xs, aligned, fit, A.CLUSTERED_BAND))
+
+
+@pytest.mark.parametrize("mode", A.MODES)
+@pytest.mark.parametrize("n,K", CASES)
+def test_host_twin_in_the_floor_band_keeps_what_the_contract_pins(N, n, K, mode):
+    """a column may or may not be replaced here: fit, orthogonality, finiteness and the same bits again -- Y against nothing"""
+    for g in FLOOR:
+        Xp = A.graded(n, K, 3, g, SEED, mode)
+        Xs, aligned, fit = align(N, Xp)
+        show_mp("host floor %s n=%d K=%d g=%.0e" % (mode, n, K, g), A.band_of(g),
+                A.check_set_mp(Xs, aligned, fit, A.band_of(g), y=False))
+        again = align(N, Xp)
+        assert np.array_equal(A.bits(aligned), A.bits(again[1])) and np.array_equal(A.bits(fit), A.bits(again[2]))
+
+
+def flip_cases(n, K):
+    """(name, set) where no column is replaced: a planted set and the graded ones down to sigma_min / sigma_max = 1e-10"""
+    return [("planted", A.planted(n, K, 3, seed=SEED))] + [("graded %s g=%.0e" % (mode, g), A.graded(n, K, 3, g, SEED, mode))
+                                                           for mode in A.MODES for g in GRADES]
+
+
+def flips(K, seed):
+    """K signs, not all equal (K >= 2)"""
+    d = np.random.default_rng(400 + seed).choice([-1.0, 1.0], size=K)
+    d[0], d[-1] = -1.0, 1.0
+    return d
+
+
+@pytest.mark.parametrize("n,K", CASES)
+def test_sign_flips_change_no_bit_but_the_signs(N, n, K):
+    """the signs of the replicates' columns do not matter at all; those of X_0's columns come out in Y as they went in"""
+    for name, Xp in flip_cases(n, K):
+        eig, vec = A.eigvec_of(Xp)
+        aligned, fit = N.mds_align_host(eig, vec)
+        d = flips(K, K)
+        v = vec.copy()
+        v[1:] *= d[:, None]
+        got = N.mds_align_host(eig, v)
+        assert np.array_equal(A.bits(got[0][1:]), A.bits(aligned[1:])) and np.array_equal(A.bits(got[1]), A.bits(fit)), name
+        v = vec.copy()
+        v[0] *= d[:, None]
+        got = N.mds_align_host(eig, v)
+        assert np.array_equal(A.bits(got[0]), A.bits(aligned * d[:, None])) and np.array_equal(A.bits(got[1]), A.bits(fit)), name
 
 
 def test_refusals(N):
