@@ -1489,7 +1489,9 @@ int ngd_win_cmp_finish(const double *mean, const double *gram, const uint32_t *s
         continue;
       }
       const double gaa = gram[a * W + a], gbb = gram[b * W + b], gab = gram[at], dm = mean[a] - mean[b];
-      cor[at] = gaa == 0.0 || gbb == 0.0 ? nan : gab / std::sqrt(gaa * gbb);
+      // (two diagonals near 2^-1000, or near 2^+600, leave no normal product: the roots one by one then)
+      const double prod = gaa * gbb;
+      cor[at] = gaa == 0.0 || gbb == 0.0 ? nan : gab / (std::isnormal(prod) ? std::sqrt(prod) : std::sqrt(gaa) * std::sqrt(gbb));
       const double q = gaa + gbb - 2 * gab + P * (dm * dm);
       rms[at] = a == b ? 0.0 : std::sqrt((q > 0.0 ? q : 0.0) / P);
     }

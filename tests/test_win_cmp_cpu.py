@@ -79,6 +79,19 @@ def test_the_nan_cases_of_cor():
     assert rms[1, 2] == 0.125 and rms[2, 3] == 4.125 and np.all(np.diag(rms) == 0.0)
 
 
+@pytest.mark.parametrize("k", [-500, 300])
+def test_cor_where_the_product_of_two_diagonals_leaves_the_normal_range(k):
+    # cells near 2^k: each diagonal is near 4^k and finite, their product is not -- cor is the quotient all the same
+    W, P = 9, 301
+    v, _ = X.vectors(W, P)
+    v[5], v[6] = np.ldexp(v[5], k), np.ldexp(v[6], k)
+    mean, gram, status = N().win_cmp_host(v)
+    assert np.all(np.isfinite(gram[:W - 1, :W - 1])) and gram[5, 5] > 0 and float(gram[5, 5]) * float(gram[6, 6]) in (0.0, np.inf)
+    X.check_all(v, mean, gram, status, N().win_cmp_finish, "host, cells near 2^%d" % k)
+    cor, _ = N().win_cmp_finish(mean, gram, status, P)
+    assert abs(cor[5, 5] - 1.0) <= 4 * 2.0 ** -53 and abs(cor[5, 6]) < 1.0 and cor[5, 6] == cor[6, 5]
+
+
 def test_scaling_by_a_power_of_two_is_exact():
     W, P = 9, 1031  # several slices of 256 cells
     v, _ = X.vectors(W, P)

@@ -2,7 +2,8 @@
 definition in extended precision: numpy's longdouble where that is wider than a double (x86: 64 bits of mantissa), exact
 rational arithmetic where it is not.  rms^2 comes from the cell differences themselves, never from the Gram matrix.  Also
 the input makers of test_win_cmp_cpu.py and test_gpu_win_cmp.py, and check_all, which prints every comparison's largest figure
-in units of its bound.
+in units of its bound.  For W too large for the W^2 loop (test_gpu_win_cmp_edges.py): check_pairs, the same on listed pairs
+and every diagonal entry, and screen_all, every pair against numpy's FP64 product.
 
 Bounds.  gram and rms^2 are the contract's: 1e-9 of sqrt(exact[a][a] exact[b][b]), and 1e-9 of (exact[a][a] + exact[b][b] +
 P (mean[a] - mean[b])^2) / P.  The header sets none for mean and cor; the ones here follow from those two.  mean: a sum of P
@@ -33,10 +34,13 @@ def P_of(W, slice_of):
     return Ps
 
 
-def vectors(W, P, seed=0):
+def vectors(W, P, seed=0, bad=np.nan, bad_at=None, extreme=False):
     """W vectors of P cells: a common random base plus noise of 1e-2 each, as the windows of one genome resemble each other;
     among them, as far as W allows, an exact duplicate of vector 0 (index 1), a copy of it plus noise of 1e-9 (2), an all-zero
-    vector (3), a vector of one power-of-two value (4), and with W >= 3 a vector with a cell that is not finite (the last).
+    vector (3), a vector of one power-of-two value (4), and with W >= 3 a vector with a cell that is not finite (the last):
+    the value `bad` (NaN, +inf or -inf) in cell `bad_at` (7 W mod P when not given).  extreme, with W >= 8: a vector of large
+    mean and tiny spread, 1 + 1e-8 noise (5), and one of cells near 2^-500 (6), whose products stay short of underflow.  The
+    other vectors are the same with and without the options.
     -> (values float64[W][P], dict of the special indices)"""
     r = np.random.default_rng(1000 * W + P + seed)
     base = r.random(P)
@@ -55,8 +59,12 @@ def vectors(W, P, seed=0):
         v[4] = 0.25
         at["pow2"] = 4
     if W >= 3:
-        v[W - 1, (7 * W) % P] = np.nan
+        v[W - 1, (7 * W) % P if bad_at is None else bad_at] = bad
         at["bad"] = W - 1
+    if extreme and W >= 8:  # (drawn last: the vectors above do not depend on the option)
+        v[5] = 1.0 + 1e-8 * r.standard_normal(P)
+        v[6] = np.ldexp(0.5 + r.random(P), -500)
+        at["big"], at["tiny"] = 5, 6
     return np.ascontiguousarray(v), at
 
 
@@ -95,6 +103,67 @@ def _f(x):
     return float(x)
 
 
+def _scale(ea, eb):
+    """sqrt(exact[a][a] exact[b][b]) as a double: the roots first, so that two diagonals near 2^-1000 do not underflow in the
+    product (the vector of cells near 2^-500)"""
+    return math.sqrt(_f(ea)) * math.sqrt(_f(eb))
+
+
+def _check_status(mean, gram, status, cor, rms, exp_status, what):
+    """status, the NaNs written from it (a status-0 vector: its mean, row and column the positive quiet NaN, and everything
+    derived NaN), finite numbers everywhere else, symmetry by bits"""
+    ok = exp_status == 1
+    assert np.array_equal(status, exp_status), (what, status)
+    for w in np.flatnonzero(~ok):
+        assert bits(mean[w:w + 1])[0] == NAN_BITS
+        assert np.all(bits(gram[w]) == NAN_BITS) and np.all(bits(gram[:, w]) == NAN_BITS)
+        if cor is not None:
+            assert np.all(np.isnan(cor[w])) and np.all(np.isnan(cor[:, w])) and np.all(np.isnan(rms[w])) and np.all(np.isnan(rms[:, w]))
+    assert np.all(np.isfinite(gram[np.ix_(ok, ok)])) and np.all(np.isfinite(mean[ok]))
+    assert np.array_equal(bits(gram), bits(gram.T)), what + ": gram is not symmetric bit for bit"
+    if cor is not None:
+        assert np.array_equal(bits(rms), bits(rms.T)) and np.array_equal(bits(cor), bits(cor.T))
+
+
+def _check_mean(fig, what, a, mean_a, e_mean, e_absmean):
+    err = abs(_f(mean_a - e_mean) if WIDE else _f(Fraction(float(mean_a)) - e_mean))
+    bound = TOL * _f(e_absmean)
+    assert err <= bound, (what, "mean", a, err, bound)
+    if bound > 0:
+        fig["mean"] = max(fig["mean"], err / bound)
+
+
+def _check_pair(fig, what, a, b, P, got, e_ab, e_aa, e_bb, e_dm, e_rms2):
+    """gram, rms^2 and cor of one pair, got = (gram[a][b], rms[a][b], cor[a][b]), against the exact Gram entry, the two exact
+    diagonals, the exact difference of the means and the exact mean squared cell difference"""
+    g_ab, rms_ab, cor_ab = got
+    g = np.longdouble(g_ab) if WIDE else Fraction(float(g_ab))
+    scale = _scale(e_aa, e_bb)
+    err, bound = abs(_f(g - e_ab)), TOL * scale
+    assert err <= bound, (what, "gram", a, b, err, bound)
+    if bound > 0:
+        fig["gram"] = max(fig["gram"], err / bound)
+    bound = TOL * _f((e_aa + e_bb + P * e_dm * e_dm) / P)
+    r2 = np.longdouble(rms_ab) ** 2 if WIDE else Fraction(float(rms_ab)) ** 2
+    err = abs(_f(r2 - e_rms2))
+    assert err <= bound, (what, "rms2", a, b, err, bound)
+    if bound > 0:
+        fig["rms2"] = max(fig["rms2"], err / bound)
+    if e_aa == 0 or e_bb == 0:
+        # the exact diagonal is 0 only for the vectors the header pins: all cells zero, or one power of two (and P = 1)
+        assert np.isnan(cor_ab), (what, "cor is not NaN", a, b, cor_ab)
+        assert g_ab == 0.0
+    else:
+        err = abs(float(cor_ab) - _f(e_ab) / scale)
+        assert err <= COR_TOL, (what, "cor", a, b, err)
+        fig["cor"] = max(fig["cor"], err / COR_TOL)
+
+
+def _say(what, W, P, fig):
+    print("%s W=%d P=%d: largest figures in units of their bounds: %s" % (what, W, P, {k: "%.3g" % x for k, x in fig.items()}))
+    return fig
+
+
 def check_all(values, mean, gram, status, finish, what, exp=None):
     """mean / gram / status of `values` (device or host twin) and the cor / rms that finish(mean, gram, status, P) derives
     from them, against the expectation: status, the NaNs written from it, symmetry by bits, then gram, mean, rms^2 and cor
@@ -103,49 +172,17 @@ def check_all(values, mean, gram, status, finish, what, exp=None):
     W, P = exp["W"], exp["P"]
     ok = exp["status"] == 1
     assert mean.shape == (W,) and gram.shape == (W, W) and status.shape == (W,)
-    assert np.array_equal(status, exp["status"]), (what, status)
     cor, rms = finish(mean, gram, status, P)
-    # a status-0 vector: its mean, row and column the positive quiet NaN, and everything derived NaN
-    for w in np.flatnonzero(~ok):
-        assert bits(mean[w:w + 1])[0] == NAN_BITS
-        assert np.all(bits(gram[w]) == NAN_BITS) and np.all(bits(gram[:, w]) == NAN_BITS)
-        assert np.all(np.isnan(cor[w])) and np.all(np.isnan(cor[:, w])) and np.all(np.isnan(rms[w])) and np.all(np.isnan(rms[:, w]))
-    assert np.all(np.isfinite(gram[np.ix_(ok, ok)])) and np.all(np.isfinite(mean[ok]))
-    assert np.array_equal(bits(gram), bits(gram.T)), what + ": gram is not symmetric bit for bit"
-    assert np.array_equal(bits(rms), bits(rms.T)) and np.array_equal(bits(cor), bits(cor.T))
+    _check_status(mean, gram, status, cor, rms, exp["status"], what)
     fig = {"gram": 0.0, "mean": 0.0, "rms2": 0.0, "cor": 0.0}
     E = exp["gram"]
     for a in np.flatnonzero(ok):
-        err = abs(_f(mean[a] - exp["mean"][a]) if WIDE else _f(Fraction(float(mean[a])) - exp["mean"][a]))
-        bound = TOL * _f(exp["absmean"][a])
-        assert err <= bound, (what, "mean", a, err, bound)
-        if bound > 0:
-            fig["mean"] = max(fig["mean"], err / bound)
+        _check_mean(fig, what, a, mean[a], exp["mean"][a], exp["absmean"][a])
         assert rms[a, a] == 0.0
         for b in np.flatnonzero(ok):
-            g = np.longdouble(gram[a, b]) if WIDE else Fraction(float(gram[a, b]))
-            scale = math.sqrt(_f(E[a, a]) * _f(E[b, b]))
-            err, bound = abs(_f(g - E[a, b])), TOL * scale
-            assert err <= bound, (what, "gram", a, b, err, bound)
-            if bound > 0:
-                fig["gram"] = max(fig["gram"], err / bound)
-            dm = exp["mean"][a] - exp["mean"][b]
-            bound = TOL * _f((E[a, a] + E[b, b] + P * dm * dm) / P)
-            r2 = np.longdouble(rms[a, b]) ** 2 if WIDE else Fraction(float(rms[a, b])) ** 2
-            err = abs(_f(r2 - exp["rms2"][a, b]))
-            assert err <= bound, (what, "rms2", a, b, err, bound)
-            if bound > 0:
-                fig["rms2"] = max(fig["rms2"], err / bound)
-            if E[a, a] == 0 or E[b, b] == 0:
-                # the exact diagonal is 0 only for the vectors the header pins: all cells zero, or one power of two (and P = 1)
-                assert np.isnan(cor[a, b]), (what, "cor is not NaN", a, b, cor[a, b])
-                assert gram[a, b] == 0.0
-            else:
-                err = abs(float(cor[a, b]) - _f(E[a, b]) / scale)
-                assert err <= COR_TOL, (what, "cor", a, b, err)
-                fig["cor"] = max(fig["cor"], err / COR_TOL)
-    print("%s W=%d P=%d: largest figures in units of their bounds: %s" % (what, W, P, {k: "%.3g" % x for k, x in fig.items()}))
-    return fig
+            _check_pair(fig, what, a, b, P, (gram[a, b], rms[a, b], cor[a, b]), E[a, b], E[a, a], E[b, b],
+                        exp["mean"][a] - exp["mean"][b], exp["rms2"][a, b])
+    return _say(what, W, P, fig)
 
 
 def check_twin(mean, gram, status, hmean, hgram, hstatus, exp, what):
@@ -156,10 +193,86 @@ def check_twin(mean, gram, status, hmean, hgram, hstatus, exp, what):
     for a in ok:
         assert abs(mean[a] - hmean[a]) <= 2 * TOL * _f(exp["absmean"][a])
         for b in ok:
-            bound = 2 * TOL * math.sqrt(_f(exp["gram"][a, a]) * _f(exp["gram"][b, b]))
+            bound = 2 * TOL * _scale(exp["gram"][a, a], exp["gram"][b, b])
             err = abs(gram[a, b] - hgram[a, b])
             assert err <= bound, (what, a, b, err, bound)
             if bound > 0:
                 worst = max(worst, err / bound)
     print("%s: device against host twin, gram differs by %.3g of the bound" % (what, worst))
     return worst
+
+
+def expect_rows(values):
+    """the per-vector part of the expectation, for W too large for expect()'s W^2 loop: -> dict of status, mean, absmean, the
+    diagonal of gram, and the extended-precision cells x and centred cells z that expect_pair() multiplies"""
+    v = np.asarray(values, dtype=np.float64)
+    W, P = v.shape
+    status = np.all(np.isfinite(v), axis=1).astype(np.uint32)
+    if WIDE:
+        x = np.where(status[:, None] == 1, v, 0.0).astype(np.longdouble)
+        mean = x.sum(axis=1) / np.longdouble(P)
+        z = x - mean[:, None]
+        diag = (z * z).sum(axis=1)
+        absmean = np.abs(x).sum(axis=1) / np.longdouble(P)
+    else:
+        x = [[Fraction(float(t)) if status[w] else Fraction(0) for t in v[w]] for w in range(W)]
+        mean = np.array([sum(r) / P for r in x], dtype=object)
+        z = [[t - mean[w] for t in x[w]] for w in range(W)]
+        diag = np.array([sum(t * t for t in r) for r in z], dtype=object)
+        absmean = np.array([sum(abs(t) for t in r) / P for r in x], dtype=object)
+    return {"status": status, "mean": mean, "absmean": absmean, "diag": diag, "x": x, "z": z, "W": W, "P": P}
+
+
+def expect_pair(rows, a, b):
+    """-> (exact gram[a][b], exact mean squared cell difference of a and b)"""
+    x, z, P = rows["x"], rows["z"], rows["P"]
+    if WIDE:
+        return np.sum(z[a] * z[b]), np.sum((x[a] - x[b]) ** 2) / np.longdouble(P)
+    return sum(p * q for p, q in zip(z[a], z[b])), sum((p - q) ** 2 for p, q in zip(x[a], x[b])) / P
+
+
+def check_pairs(values, mean, gram, status, finish, pairs, what, rows=None):
+    """check_all on the listed (a, b) pairs and on every diagonal entry only: the same bounds, the same printing.  The mean
+    and the diagonal of every vector are formed first, then the listed products.  A listed pair with a status-0 vector is
+    covered by the NaN check of its row and column."""
+    rows = rows or expect_rows(values)
+    W, P = rows["W"], rows["P"]
+    assert mean.shape == (W,) and gram.shape == (W, W) and status.shape == (W,)
+    cor, rms = finish(mean, gram, status, P)
+    _check_status(mean, gram, status, cor, rms, rows["status"], what)
+    fig = {"gram": 0.0, "mean": 0.0, "rms2": 0.0, "cor": 0.0}
+    ok, d, m = rows["status"] == 1, rows["diag"], rows["mean"]
+    for a in np.flatnonzero(ok):
+        _check_mean(fig, what, a, mean[a], m[a], rows["absmean"][a])
+        assert rms[a, a] == 0.0
+        _check_pair(fig, what, a, a, P, (gram[a, a], rms[a, a], cor[a, a]), d[a], d[a], d[a], m[a] - m[a], m[a] - m[a])
+    n = 0
+    for a, b in pairs:
+        if ok[a] and ok[b]:
+            e_ab, e_rms2 = expect_pair(rows, a, b)
+            _check_pair(fig, what, a, b, P, (gram[a, b], rms[a, b], cor[a, b]), e_ab, d[a], d[b], m[a] - m[b], e_rms2)
+            n += 1
+    print("%s: %d listed pairs and %d diagonal entries" % (what, n, int(ok.sum())))
+    return _say(what, W, P, fig)
+
+
+def screen_all(values, mean, gram, status, what, rows=None):
+    """every pair of status-1 vectors against numpy's FP64 product of the centred cells, within the contract's bound
+    1e-9 sqrt(d_a d_b), d the extended-precision diagonal; status, the NaN rows written from it and symmetry by bits.  A
+    screen for W too large for the W^2 loop, not the reference (check_pairs is, on the pairs it is given): the cells are
+    centred in extended precision and rounded once, and the FP64 product of P terms is within about P 2^-53 of the scale."""
+    rows = rows or expect_rows(values)
+    W = rows["W"]
+    assert mean.shape == (W,) and gram.shape == (W, W) and status.shape == (W,)
+    _check_status(mean, gram, status, None, None, rows["status"], what)
+    ok = np.flatnonzero(rows["status"] == 1)
+    zc = np.array([[_f(t) for t in rows["z"][w]] for w in ok]) if not WIDE else rows["z"][ok].astype(np.float64)
+    root = np.array([math.sqrt(_f(t)) for t in rows["diag"][ok]])
+    err = np.abs(gram[np.ix_(ok, ok)] - zc @ zc.T)
+    bound = TOL * np.outer(root, root)
+    worst = np.unravel_index(np.argmax(err - bound), err.shape)
+    assert np.all(err <= bound), (what, "gram", ok[worst[0]], ok[worst[1]], err[worst], bound[worst])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fig = float(np.max(np.where(bound > 0, err / bound, 0.0)))
+    print("%s W=%d P=%d: every pair against the FP64 product, largest difference %.3g of the bound" % (what, W, rows["P"], fig))
+    return fig
