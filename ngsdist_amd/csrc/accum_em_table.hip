@@ -57,7 +57,8 @@ struct alignas(16) em_tables {
   // the lanes that computed them to the lanes that own the pairs, and the unit's column list
   double unit_c[PACK ? 8 * 64 : 2];
   // bit i of word p: row i of the tile cannot stop at any of the steps the p-th row builder wrote this round
-  // (its own factor R_t is still >= e^tole there, and a column's is never below 1): the plain scan skips those steps
+  // (its own factor R_t is still >= e^tole there, and a column's is never below 1 -- but for a missing column's 0: the scan
+  // drops such a column's pairs itself in a site's first round): the plain scan skips those steps
   unsigned long long row_nostop[4];
   uint8_t unit_col[PACK ? 8 * 8 : 8];
   uint8_t poison[2][TS];  // RB > 1, kernel end: bit b = matrix b drew a site at which this row / column was all zero
@@ -658,6 +659,18 @@ __global__ __launch_bounds__(NW * 64, WPS) void k_accum_em_table(
             double R2[CH];
 #pragma unroll
             for (int tt = 0; tt < CH; tt++) R2[tt] = lds_b64(&L.Rc[tt * TS + lane]);
+            if constexpr (PDEL) {
+              // The verdicts assume a column's R of 1 or more.  A missing column's is 0: its pairs leave at step 1 with a term
+              // of exactly 0 (g = 0), whatever the row -- left to the verdicts such a pair would wait for its row's own stop, and
+              // a tile whose other pairs are done would take a table round for it.  So in a site's FIRST round the lanes of
+              // such columns drop their pairs here, before any row is scanned, and add nothing (acc + 0.0 is acc, bit for bit).
+              // R of step 1 is 0 only where build_round's `force` wrote it, i.e. for `miss` (step 1 is below MAX_ITER): computed,
+              // it is 3 A_2 / A_1^2 >= 1, and where A_2 underflows r_1^2 is inf and the product NaN, never 0.  Later rounds
+              // have no such pair left and are not touched; nor is a first round in which none of this wavefront's rows
+              // skips both blocks (the plain search then drops those pairs at step 1 as ever).
+              static_assert(MAX_ITER > 1, "step 1 must not be a forced stop: R == 0 there means a missing column");
+              if (t0 == 0 && (rows & ska & skb) != 0 && R2[0] == 0.0) todo = 0;
+            }
             const uint32_t go = rows & ~(ska & skb);     // rows searched in this round
             const uint32_t need_a = go & ~ska;           // ... that search their first block
             const uint32_t load = need_a & ~(go << 1);   // ... and whose predecessor is not there to fetch its thresholds
